@@ -3,6 +3,8 @@
 
     python bench.py                         # N = 1
     python bench.py --gpus N --steps K --warmup W
+    python bench.py --full                  # ... and every side measurement listed below
+    python bench.py --dump-outputs bench_outputs    # ... and the last timed step's outputs as bench_outputs/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,21 +16,24 @@ synthetic [B, T=256, d=768] fp32 image + event feature blocks that are already r
 N > 1 -- by the single RCCL all-gather of per-snippet scores (`iefvad_gather_scores`, librccl over xGMI).
 Workload: BASELINE.json config 4, B = 8192 chunks (2,097,152 snippets) IN TOTAL; rank r holds and scores chunks
 [r*B/N, (r+1)*B/N), so scaling is "strong" and `value` is the whole-job rate.  `--scaling weak` keeps
-8192 chunks per GPU instead; a default N > 1 run also measures that variant and reports it as `weak_scaling`.
-Weights are seeded synthetic tensors of the reference architecture (K=10, nu=8, StudentT).
+8192 chunks per GPU instead; a `--full` N > 1 run also measures that variant and reports it as `weak_scaling`.
+Weights are seeded synthetic tensors of the reference architecture (K=10, nu=8, StudentT); weights and input blocks
+are the same from run to run for the same arguments.
 
 Arithmetic (--compute): the default, bf16x6, is fp32-ACCURATE: every fp32 operand of a dense projection is split
 exactly into three bf16 terms and the product is accumulated in fp32 from six bf16 MFMA products (csrc/gemm_split.h);
-it is held to the fp32 parity gates (tests/test_gpu_bf16x6.py).  The same workload is timed in the same run in the
-other arithmetic modes and reported as `f32_mfma_mode` (fp32 MFMA instruction), `bf16_mode` (BASELINE configs 3 / 5:
+it is held to the fp32 parity gates (tests/test_gpu_bf16x6.py).  With --full the same workload is timed in the same run
+in the other arithmetic modes and reported as `f32_mfma_mode` (fp32 MFMA instruction), `bf16_mode` (BASELINE configs 3 / 5:
 bf16-rounded operands, fp32 accumulation and state) and `fp16x3_mode`.
 
-The JSON line also carries
+A plain run sets up, warms up, times the `--steps` steps, writes the outputs if --dump-outputs is given and prints the
+line.  Beside the headline (`value`, `ms_per_step`) the line carries, from those same timed steps,
   roofline      the dense-projection GEMM kernel (~85 % of device time).  `achieved` = ALGORITHMIC FLOPs (SURVEY.md 8d:
                 47,185,920 per snippet at K=10) of the rows one launch processes / that kernel's average launch
                 duration, timed with hipEvents on the launch stream inside the timed region; `peak` = dense MFMA peak of
                 the pipe the kernel runs on (MI355X_MICROARCH.md: bf16 2500, fp32 157.3 TFLOP/s).  For the emulated
                 modes `mfma_pipe_util` is the EXECUTED-product rate / peak (6 bf16 products per algorithmic one).
+--full adds the other arithmetic modes above, `weak_scaling` (N > 1) and, at N = 1,
   cpu_baseline  the CPU oracle (oracle/iefvad_oracle.py, torch CPU ops on the host cores) on a bounded sample of the
                 same workload, rank 0 at N=1 only.  A reported baseline, not the target.
   xd_eval, shang_msad_eval   BASELINE configs 3 and 5 (XD-Violence-sized; ShanghaiTech + MSAD sized with K = 5), bf16 projections
@@ -38,6 +43,12 @@ The JSON line also carries
   ucf_eval      BASELINE config 2 (UCF-Crime-sized synthetic set, 290 videos, ~69.5 k snippets) through harness.test:
                 the reference's per-video call pattern and the cross-video batched pattern, snippets/s wall clock
                 including H2D, |dAUC| against the CPU oracle on a bounded sample, and the oracle's own rate.
+  metric_tail   SURVEY 8f-1: iefvad_auc_ap on config 4's 2.1 M scores against sklearn on a sample.
+The --no-* options drop single blocks of a --full run.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step (rank 0's MMFMIL.forward outputs, and at
+N > 1 the gathered score vector) as DIR/<name>.npy in float32, at most DUMP_BYTES in all: an array larger than its share
+is replaced by the rows (last dimension kept whole) at a fixed, seeded, ascending choice of row indices.
 """
 import argparse
 import json
@@ -63,6 +74,8 @@ GEMM_KERNEL = {"f32": "iefvad_gemm_f32_t256_kernel",
                        "iefvad_heads_pchain_bf16_kernel (heads + fusion, persistent) + iefvad_outproj_ln_pchain_bf16_kernel (out_proj + LayerNorm, "
                        "persistent)",
                "bf16x6": "iefvad_gemm_split_n128_kernel", "fp16x3": "iefvad_gemm_split_f16_n128_kernel"}
+DUMP_BYTES = 60_000_000                                         # --dump-outputs: array data in all (+ 128 B of header per file) < 64 MB
+DUMP_SAMPLE_SEED = 0
 PRODUCTS_PER_MAC = {"f32": 1.0, "bf16": 1.0, "bf16x6": 6.0, "fp16x3": 3.0}
 DTYPE = {"f32": "f32", "bf16": "bf16",
          "bf16x6": "f32 emulated: exact 3-term bf16 split of both fp32 operands, 6 bf16 MFMA products, fp32 accumulate",
@@ -86,10 +99,16 @@ def parse(argv=None):
                         "f32 = fp32 MFMA; bf16 = bf16-rounded operands (reduced precision, BASELINE config 3)")
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                    help="nccl (= RCCL over xGMI) for real multi-GPU runs; gloo only to rehearse N>1 on a one-GPU box")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also measure the other arithmetic modes, weak scaling (N > 1), the dataset-shaped "
+                        "evaluations, the training step, the metric tail and the CPU-oracle baseline (N = 1)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float32, seeded row sample above DUMP_BYTES)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
     p.add_argument("--no-extra-modes", action="store_true",
-                   help="skip the side passes (f32_mfma_mode, bf16_mode, fp16x3_mode, weak_scaling)")
-    p.add_argument("--no-ucf-eval", action="store_true", help="skip the dataset-shaped blocks (ucf_eval, xd_eval, shang_msad_eval)")
+                   help="--full without the side passes (f32_mfma_mode, bf16_mode, fp16x3_mode, weak_scaling)")
+    p.add_argument("--no-ucf-eval", action="store_true",
+                   help="--full without the dataset-shaped blocks (ucf_eval, xd_eval, shang_msad_eval), train_step and metric_tail")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each CPU-oracle sample")
     p.add_argument("--plumbing-only", action="store_true",
                    help="launcher self-test for machines without a GPU (tests/test_bench_launcher_cpu.py): NO forward runs; "
@@ -526,6 +545,25 @@ def metric_tail_block(dev, n=8192 * T, sample=131072):
             "kernel": "iefvad_auc_ap: radix sort of (score, positives) pairs + scan + tie-group reduction (csrc/metrics.h)"}
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor, any device) as path/<name>.npy in float32 (float64 stays float64).  An array
+    whose bytes exceed its share of DUMP_BYTES keeps only the rows (last dimension whole) at a fixed seeded choice of row
+    indices, in ascending order, picked on the array's device before the copy to the host."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype in (torch.float32, torch.float64) else t.float()
+        rows = t.reshape(-1, t.shape[-1] if t.dim() > 1 else 1)
+        if rows.numel() * rows.element_size() > share:
+            keep = max(1, share // (rows.shape[1] * rows.element_size()))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows.shape[0], keep, replace=False))
+            t = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 def xd_parts():
     from iefvad_amd import harness, synth
     lengths = synth.lognormal_lengths(2, 753, 145000)
@@ -621,9 +659,10 @@ def main():
 
     def timed_run(img, ev, first, counts, steps, warmup):
         """Contract timing: `warmup` untimed steps, barrier + sync, exactly `steps` steps, sync + barrier, MAX over
-        ranks.  Returns (max seconds, per-rank seconds, stage sums, last gathered scores)."""
+        ranks.  Returns (max seconds, per-rank seconds, stage sums, last gathered scores, last step's outputs)."""
         stage = {}
         snips = [c * T for c in counts]
+        last = {}
 
         def step():
             if gpu:
@@ -633,9 +672,13 @@ def main():
                     stage[k] = stage.get(k, 0.0) + v
                 scores = out["logits"].reshape(-1)
             else:       # --plumbing-only: the global snippet indices of this rank's shard
-                scores = torch.arange(first * T, (first + counts[rank]) * T, dtype=torch.float32)
+                out = {"scores": torch.arange(first * T, (first + counts[rank]) * T, dtype=torch.float32)}
+                scores = out["scores"]
             if world > 1:
                 scores = gatherer(scores if backend == "nccl" or not gpu else scores.cpu(), snips)
+                out = dict(out, gathered_scores=scores)
+            if a.dump_outputs:
+                last["out"] = out
             return scores
 
         for _ in range(warmup):
@@ -663,21 +706,24 @@ def main():
             per_rank = allr.tolist()
         # (IEFVAD_TIMING_PROBE: tools/*_probe.sh run deliberately wrong-result probe builds for their timings only)
         assert scores.numel() == sum(snips) and (bool(torch.isfinite(scores).all()) or bool(os.environ.get("IEFVAD_TIMING_PROBE")))
-        return dt, per_rank, stage, scores
+        return dt, per_rank, stage, scores, last.get("out")
 
     first, B, counts = shard(a.chunks, a.scaling)
     img, ev = make_blocks(B)
-    dt, per_rank, stage, scores = timed_run(img, ev, first, counts, a.steps, a.warmup)
+    dt, per_rank, stage, scores, last_out = timed_run(img, ev, first, counts, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0 and last_out is not None:
+        dump_outputs(a.dump_outputs, last_out)
+    last_out = None
     total_chunks = sum(counts)
     gathered = int(scores.numel())
     in_order = bool((scores == torch.arange(total_chunks * T, dtype=torch.float32)).all()) if not gpu else None
 
     weak = None
-    if gpu and world > 1 and a.scaling == "strong" and not a.no_extra_modes:
+    if a.full and gpu and world > 1 and a.scaling == "strong" and not a.no_extra_modes:
         del img, ev, scores
         wimg, wev = make_blocks(a.chunks)
         wsteps = max(2, min(a.steps, 3))
-        wdt, wper, _, _ = timed_run(wimg, wev, rank * a.chunks, [a.chunks] * world, wsteps, 1)
+        wdt, wper, _, _, _ = timed_run(wimg, wev, rank * a.chunks, [a.chunks] * world, wsteps, 1)
         weak = {"value": world * a.chunks * T * wsteps / wdt, "unit": "snippets/s", "steps": wsteps,
                 "ms_per_step": wdt / wsteps * 1e3, "chunks_per_gpu": a.chunks,
                 "per_rank_ms_per_step": [t / wsteps * 1e3 for t in wper]}
@@ -716,12 +762,12 @@ def main():
             line["gathered_scores"] = gathered
             if weak is not None:
                 line["weak_scaling"] = weak
-        if gpu and world == 1 and not a.no_extra_modes:     # N=1 only: rank 0 must not linger at N>1
+        if a.full and gpu and world == 1 and not a.no_extra_modes:     # N=1 only: rank 0 must not linger at N>1
             for key, mode in (("f32_mfma_mode", "f32"), ("bf16_mode", "bf16"), ("fp16x3_mode", "fp16x3"), ("bf16x6_mode", "bf16x6")):
                 if mode != a.compute:
                     line[key] = extra_mode(sd, margs, dev, img, ev, a, mode)
         img = ev = None
-        if gpu and world == 1 and not a.no_ucf_eval:
+        if a.full and gpu and world == 1 and not a.no_ucf_eval:
             model = None
             torch.cuda.empty_cache()
             line["ucf_eval"] = ucf_eval(sd, margs, dev, a)
@@ -732,7 +778,7 @@ def main():
                                                    19, 5, "bf16", dev, a, batch_chunks=128, lanes=2)
             line["train_step"] = train_step_block(dev, a)
             line["metric_tail"] = metric_tail_block(dev)
-        if gpu and world == 1 and not a.no_cpu_baseline:
+        if a.full and gpu and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, a.cpu_seconds)
         print(json.dumps(line), file=json_out, flush=True)
     if gatherer is not None:

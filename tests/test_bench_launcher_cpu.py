@@ -41,6 +41,40 @@ def test_plain_shell_launch_of_two_ranks(chunks, expect):
     assert line["dist_backend"] == "gloo"
 
 
+def test_dump_outputs_of_the_last_step_from_two_ranks(tmp_path):
+    """--dump-outputs writes rank 0's step outputs (here: its fabricated shard) and the gathered vector, float32, once per run."""
+    import numpy as np
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--plumbing-only", "--steps", "2", "--warmup", "1", "--chunks", "5",
+                        "--dump-outputs", str(tmp_path / "out")], env=_env(), capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _one_json_line(r.stdout)["steps"] == 2
+    assert sorted(os.listdir(tmp_path / "out")) == ["gathered_scores.npy", "scores.npy"]
+    mine, gathered = np.load(tmp_path / "out" / "scores.npy"), np.load(tmp_path / "out" / "gathered_scores.npy")
+    assert mine.dtype == np.float32 and gathered.dtype == np.float32
+    assert np.array_equal(mine, np.arange(2 * 256, dtype=np.float32))                   # rank 0 holds chunks [0, 2) of 5
+    assert np.array_equal(gathered, np.arange(5 * 256, dtype=np.float32))
+
+
+def test_dump_outputs_samples_large_arrays_by_a_fixed_row_choice(tmp_path, monkeypatch):
+    """An array above its share of the budget keeps whole rows at seeded, ascending indices: the same rows every run, the
+    total under the budget; smaller arrays are written whole, other float dtypes as float32."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 40_000)
+    big = torch.arange(1000 * 64, dtype=torch.float32).reshape(10, 100, 64)
+    small = torch.linspace(-1, 1, 300, dtype=torch.float16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert np.array_equal(a, b) and a.dtype == np.float32 and a.shape[1] == 64 and a.nbytes <= 40_000
+    rows = a[:, 0].astype(np.int64) // 64
+    assert len(rows) == 40_000 // (64 * 4) and np.all(np.diff(rows) > 0) and rows.max() < 1000
+    assert np.array_equal(a, big.reshape(-1, 64).numpy()[rows])
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+
+
 def test_launch_under_torch_distributed_run_as_the_driver_does():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

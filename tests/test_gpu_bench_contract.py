@@ -1,6 +1,7 @@
-"""bench.py's output contract, on the GPU: ONE JSON line on stdout carrying the metric of BASELINE.json, the roofline
-block on SURVEY.md 8(d)'s algorithmic FLOPs, the CPU-oracle baseline, the side modes and the UCF-sized evaluation block.
-A reduced batch keeps this a ~30 s test; the numbers are not checked, the structure and the internal consistency are."""
+"""bench.py's output contract, on the GPU: ONE JSON line on stdout carrying the metric of BASELINE.json and the roofline
+block on SURVEY.md 8(d)'s algorithmic FLOPs; with --full also the CPU-oracle baseline, the side modes and the dataset-shaped
+evaluation blocks, without it none of them; --dump-outputs writes the last timed step's outputs, the same from run to run.
+Reduced batches keep these short tests; the numbers are not checked, the structure and the internal consistency are."""
 import json
 import math
 import os
@@ -13,10 +14,17 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+SIDE_BLOCKS = ("f32_mfma_mode", "bf16_mode", "fp16x3_mode", "cpu_baseline", "ucf_eval", "xd_eval", "shang_msad_eval", "train_step",
+               "metric_tail")
+
+
+def _env():
+    return {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+
+
 def test_default_line_structure_and_consistency():
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--chunks", "1024", "--steps", "2", "--warmup", "1",
-                        "--cpu-seconds", "2"], env=env, capture_output=True, text=True, timeout=560)
+                        "--cpu-seconds", "2", "--full"], env=_env(), capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[:2000]
@@ -67,3 +75,27 @@ def test_default_line_structure_and_consistency():
     mt = d["metric_tail"]                                                                # iefvad_auc_ap on config 4's 2.1 M scores
     assert mt["snippets"] == 8192 * 256 and mt["device_ms"] > 0 and 0 < mt["auc"] < 1 and 0 < mt["ap"] < 1
     assert mt["sklearn_sample"]["abs_auc_diff"] < 1e-12 and mt["sklearn_sample"]["abs_ap_diff"] < 1e-12
+
+
+def test_plain_line_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline of exactly --steps timed steps (and the roofline of those steps), no side block;
+    --dump-outputs writes what the timed path returned in its last step, float32, and two runs with the same arguments agree."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--chunks", "64", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:2000]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["higher_is_better"] is True
+        assert d["metric"].startswith("snippets/sec") and d["unit"] == "snippets/s" and d["dtype"].startswith("f32 emulated")
+        assert abs(d["value"] - 64 * 256 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+        assert d["roofline"]["launches_per_step"] > 0 and not any(k in d for k in SIDE_BLOCKS)
+        assert sorted(os.listdir(tmp_path / run)) == ["logits.npy", "w_e_mean.npy", "w_i_mean.npy"]
+        dumps.append({k: np.load(tmp_path / run / f"{k}.npy") for k in ("logits", "w_i_mean", "w_e_mean")})
+    a, b = dumps
+    assert a["logits"].shape == (64, 256, 1) and a["w_i_mean"].shape == (64, 256) and a["logits"].dtype == np.float32
+    assert all(np.isfinite(v).all() for v in a.values())
+    assert all(np.array_equal(a[k], b[k]) for k in a)

@@ -28,7 +28,7 @@ def main():
     p.add_argument("--threads", type=int, default=0)
     p.add_argument("--batch-chunks", type=int, default=128)
     p.add_argument("--prelude", default="none", choices=["none", "ucf", "threads"],
-                   help="what runs in the process first: bench.ucf_eval (as in a default bench run), or only torch.set_num_threads(host share)")
+                   help="what runs in the process first: bench.ucf_eval (as in a bench.py --full run), or only torch.set_num_threads(host share)")
     p.add_argument("--wire-bf16", action="store_true", help="round the fp32 rows to bf16 while staging (wire_dtype = BF16)")
     a = p.parse_args()
     wire = torch.bfloat16 if a.wire_bf16 else None
