@@ -34,7 +34,7 @@ struct GemmBProblem {
     float* C;            // [M, ldc] fp32 result, nullable
     bf16_t* Cb;          // [M, ldc] bf16 copy of the result, nullable
     const float* R;      // residual, fp32, same layout as C
-    float* C2;           // EPI_HEADS second output (fp32, [M, 768])
+    float* C2;           // EPI_HEADS second output (fp32, [M, ldc])
     // fp16x3 mode (gemm_split.h, F16 path): running max |.| words of the A tensor, of the W matrix (both read) and of the
     // result written to C (updated), nullable
     const float* amaxA;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_bf16_v1_kernel(GemmBArgs a
     bf16_t* Cb16 = P.Cb;
     int nn = ncol;
     f32x4 scale = {1.f, 1.f, 1.f, 1.f};
-    if (epi == EPI_HEADS && ncol >= IEF_D) { Cb32 = P.C2; nn = ncol - IEF_D; }
+    if (epi == EPI_HEADS && ncol >= ldc) { Cb32 = P.C2; nn = ncol - ldc; }
     if (epi == EPI_QKV && ncol < args.qcols) scale = f32x4{alpha, alpha, alpha, alpha};
 #pragma unroll
     for (int a = 0; a < 2; ++a) {                           // 32-row half a of the wave tile
@@ -285,7 +285,7 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
     bf16_t* C16 = P.Cb;
     int nn = ncol;
     f32x4 scale = {1.f, 1.f, 1.f, 1.f};
-    if (epi == EPI_HEADS && ncol >= IEF_D) { C32 = P.C2; nn = ncol - IEF_D; }
+    if (epi == EPI_HEADS && ncol >= ldc) { C32 = P.C2; nn = ncol - ldc; }
     if (epi == EPI_QKV && ncol < args.qcols) scale = f32x4{alpha, alpha, alpha, alpha};
     float vmax = 0.f;
     // bf16-only results (in_proj q|k|v and the refinement's ReLU output in the bf16 mode): a lane takes EIGHT columns of a row,

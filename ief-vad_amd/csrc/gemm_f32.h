@@ -27,7 +27,7 @@ enum GemmEpilogue {
     EPI_BIAS_RELU = 2,   // C = relu(acc + bias)                              refinement Linear -> ReLU
     EPI_BIAS_RESID = 3,  // C = acc + bias + R                                out_proj + residual (x + attn_out)
     EPI_REFINE = 4,      // C = R - alpha * (acc + bias)                      z - lambda * block(z)
-    EPI_HEADS = 5,       // n < 768: C = acc + bias ; n >= 768: C2 = acc + bias   (mu | logvar heads share A)
+    EPI_HEADS = 5,       // n < ldc: C = acc + bias ; n >= ldc: C2 = acc + bias   (mu | logvar heads share A; N = 2 ldc = 2 D)
     EPI_GATE = 6,        // C = R > 0 ? alpha * (acc + bias) : 0   (split kernel only: ReLU backward on the saved activation, train.h)
 };
 
@@ -37,7 +37,7 @@ struct GemmProblem {
     const float* bias;   // [N]
     float* C;            // [M, ldc]
     const float* R;      // residual input, [M, ldc] (same layout as C); may alias C
-    float* C2;           // second output for EPI_HEADS, [M, 768]
+    float* C2;           // second output for EPI_HEADS, [M, ldc]
 };
 
 struct GemmArgs {
@@ -85,7 +85,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& args, const GemmPr
         float* Cb = P.C;
         int nn = n;
         float scale = 1.f;
-        if (epi == EPI_HEADS && n >= IEF_D) { Cb = P.C2; nn = n - IEF_D; }
+        if (epi == EPI_HEADS && n >= ldc) { Cb = P.C2; nn = n - ldc; }
         if (epi == EPI_QKV && n < args.qcols) scale = alpha;
 #pragma unroll
         for (int a = 0; a < TM; ++a) {
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_f32_tiny_kernel(GemmArgs a
     float* Cb = P.C;
     int nn = n;
     float scale = 1.f;
-    if (epi == EPI_HEADS && n >= IEF_D) { Cb = P.C2; nn = n - IEF_D; }
+    if (epi == EPI_HEADS && n >= ldc) { Cb = P.C2; nn = n - ldc; }
     if (epi == EPI_QKV && n < args.qcols) scale = alpha;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {

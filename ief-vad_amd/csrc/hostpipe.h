@@ -82,8 +82,8 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
     }
     hipStream_t stream = (hipStream_t)stream_;
     const bool narrow = wire_dtype != in_dtype;
-    const size_t row_bytes = (size_t)IEF_D * in_elem_bytes(in_dtype);            // host rows
-    const size_t wire_row_bytes = (size_t)IEF_D * in_elem_bytes(wire_dtype);     // staging slots, copies, device input slots
+    const size_t row_bytes = (size_t)h->D * in_elem_bytes(in_dtype);            // host rows
+    const size_t wire_row_bytes = (size_t)h->D * in_elem_bytes(wire_dtype);     // staging slots, copies, device input slots
     const int want = batch_chunks > 0 ? batch_chunks : 128;
     try {
 

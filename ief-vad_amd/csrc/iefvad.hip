@@ -63,6 +63,7 @@ static int fail(const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------------
 struct iefvad_handle {
     iefvad_config cfg;
+    int D, DH;             // embed dim and head dim: 768 / 96, or 512 / 64 (iefvad_create_ex: the f32 forward only)
     int device;
     bool weights_set;
     // IEFVAD_ROWBLOCK_OFF=<mask> at iefvad_create (A/B runs and the bit-identity tests): bf16 mode takes the stage off its row-block kernel
@@ -155,32 +156,49 @@ extern "C" int iefvad_abi_version(void) { return IEFVAD_ABI_VERSION; }
 
 extern "C" const char* iefvad_last_error(void) { return g_err; }
 
-extern "C" int iefvad_create(const iefvad_config* cfg, iefvad_handle** out) {
-    if (!cfg || !out) return fail("iefvad_create: null argument");
+// The D=512 (head dim 64) forward: ViT-B/16 features, the f32 arithmetic's kernels only
+#define IEF_D512 512
+
+// iefvad_create (D = 768 only) and iefvad_create_ex (also D = 512 in the f32 arithmetic): every check before the first HIP call
+static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg, iefvad_handle** out) {
+    if (!cfg || !out) return fail("%s: null argument", who);
     *out = nullptr;
     if (cfg->abi_version != IEFVAD_ABI_VERSION)
-        return fail("iefvad_create: abi_version %d, library is %d", cfg->abi_version, IEFVAD_ABI_VERSION);
-    if (cfg->embed_dim != IEF_D || cfg->seq_len != IEF_T || cfg->num_heads != IEF_H)
+        return fail("%s: abi_version %d, library is %d", who, cfg->abi_version, IEFVAD_ABI_VERSION);
+    const bool d512 = allow_512 && cfg->embed_dim == IEF_D512;
+    if (d512) {
+        if (cfg->seq_len != IEF_T || cfg->num_heads != IEF_D512 / 64)
+            return fail("%s: D=512 is built for T=256, H=8 (head dim 64) (got T=%d H=%d)", who, cfg->seq_len, cfg->num_heads);
+        if (cfg->compute != IEFVAD_COMPUTE_F32)
+            return fail("%s: D=512 runs in the f32 arithmetic only (compute = %d; bf16, bf16x6 and fp16x3 are built for D=768)", who,
+                        cfg->compute);
+    } else if (cfg->embed_dim != IEF_D || cfg->seq_len != IEF_T || cfg->num_heads != IEF_H) {
+        if (allow_512)
+            return fail("%s: kernels are built for D=768, T=256, H=8, or D=512, T=256, H=8 in the f32 arithmetic (got D=%d T=%d H=%d)", who,
+                        cfg->embed_dim, cfg->seq_len, cfg->num_heads);
         return fail("iefvad_create: kernels are built for D=768, T=256, H=8 (got D=%d T=%d H=%d)",
                     cfg->embed_dim, cfg->seq_len, cfg->num_heads);
+    }
     if (cfg->num_layers < 1 || cfg->num_layers > IEFVAD_MAX_LAYERS)
-        return fail("iefvad_create: num_layers %d outside 1..%d", cfg->num_layers, IEFVAD_MAX_LAYERS);
+        return fail("%s: num_layers %d outside 1..%d", who, cfg->num_layers, IEFVAD_MAX_LAYERS);
     if (cfg->num_steps < 0 || cfg->num_steps > IEFVAD_MAX_STEPS)
-        return fail("iefvad_create: num_steps %d outside 0..%d", cfg->num_steps, IEFVAD_MAX_STEPS);
+        return fail("%s: num_steps %d outside 0..%d", who, cfg->num_steps, IEFVAD_MAX_STEPS);
     if (cfg->noise_model != IEFVAD_NOISE_GAUSSIAN && cfg->noise_model != IEFVAD_NOISE_STUDENT_T)
         return fail("Unsupported noise_model. Choose 'Gaussian' or 'StudentT'.");   // imf_vad.py:138
     if (cfg->compute != IEFVAD_COMPUTE_F32 && cfg->compute != IEFVAD_COMPUTE_BF16 && cfg->compute != IEFVAD_COMPUTE_BF16X6 &&
         cfg->compute != IEFVAD_COMPUTE_FP16X3)
-        return fail("iefvad_create: unknown compute mode %d", cfg->compute);
+        return fail("%s: unknown compute mode %d", who, cfg->compute);
     if (cfg->noise_model == IEFVAD_NOISE_STUDENT_T && !(cfg->nu != 0.f))
-        return fail("iefvad_create: nu must be non-zero for StudentT");
+        return fail("%s: nu must be non-zero for StudentT", who);
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) return fail("iefvad_create: no HIP device");
+    if (ndev <= 0) return fail("%s: no HIP device", who);
     iefvad_handle* h = new (std::nothrow) iefvad_handle();
-    if (!h) return fail("iefvad_create: out of host memory");
+    if (!h) return fail("%s: out of host memory", who);
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
+    h->D = d512 ? IEF_D512 : IEF_D;
+    h->DH = h->D / IEF_H;
     {
         const char* v = getenv("IEFVAD_ROWBLOCK_OFF");
         const int off = v ? atoi(v) : 0;
@@ -273,11 +291,15 @@ extern "C" int iefvad_create(const iefvad_config* cfg, iefvad_handle** out) {
     if (e == hipSuccess && cfg->compute == IEFVAD_COMPUTE_FP16X3) e = hipMalloc((void**)&h->amax_dev, amax_words(cfg->num_layers, cfg->num_steps, micro_batch(h)) * sizeof(float));
     if (e != hipSuccess) {
         delete h;
-        return fail("iefvad_create: %s", hipGetErrorString(e));
+        return fail("%s: %s", who, hipGetErrorString(e));
     }
     *out = h;
     return 0;
 }
+
+extern "C" int iefvad_create(const iefvad_config* cfg, iefvad_handle** out) { return create_impl("iefvad_create", false, cfg, out); }
+
+extern "C" int iefvad_create_ex(const iefvad_config* cfg, iefvad_handle** out) { return create_impl("iefvad_create_ex", true, cfg, out); }
 
 static void release_events(iefvad_handle* h);
 static void release_graphs(iefvad_handle* h);
@@ -321,12 +343,12 @@ static int launch_cast(const void* in0, const void* in1, float* o0, float* o1, b
     return 0;
 }
 
-template <typename T>
+template <typename T, int W>
 static int launch_cast_scaled(const void* in0, const void* in1, float* o0, float* o1, bf16_t* b0, bf16_t* b1, size_t n, const float* s0,
                               const float* s1, hipStream_t stream) {
     size_t blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(iefvad_cast_scaled_kernel<T>, dim3((unsigned)blocks, 2), dim3(256), 0, stream, (const T*)in0, (const T*)in1, o0, o1, b0, b1,
+    hipLaunchKernelGGL((iefvad_cast_scaled_kernel<T, W>), dim3((unsigned)blocks, 2), dim3(256), 0, stream, (const T*)in0, (const T*)in1, o0, o1, b0, b1,
                        n, s0, s1);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -407,7 +429,7 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     if (!h || !w) return fail("iefvad_set_weights: null argument");
     hipStream_t stream = (hipStream_t)stream_;
     const int L = h->cfg.num_layers, K = h->cfg.num_steps;
-    const size_t D = IEF_D, DD = D * D;
+    const size_t D = h->D, DD = D * D;
     // validate pointers first
     for (int m = 0; m < 2; ++m) {
         for (int l = 0; l < L; ++l)
@@ -588,15 +610,15 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     return 0;
 }
 
-// workspace, in floats per row: xin(2) + qkv(6) + att(2) + y(2) + x(2) = 14 * 768, + 1 (logits scratch).
-// mu_i, lv_i, mu_e, lv_e, z, h alias the qkv region (6 * 768), which is dead once the encoder is done.
-static const size_t kWsFloatsPerRow = 14 * IEF_D + 4;
+// workspace, in floats per row: xin(2) + qkv(6) + att(2) + y(2) + x(2) = 14 * D, + 1 (logits scratch).
+// mu_i, lv_i, mu_e, lv_e, z, h alias the qkv region (6 * D), which is dead once the encoder is done.
+static size_t ws_floats_per_row(const iefvad_handle* h) { return 14 * (size_t)h->D + 4; }
 
 extern "C" size_t iefvad_workspace_bytes(const iefvad_handle* h, int32_t B) {
     if (!h || B <= 0) return 0;
     const int mb = micro_batch(h);
     const size_t rows = (size_t)(B < mb ? B : mb) * IEF_T;
-    return rows * kWsFloatsPerRow * sizeof(float) + 256;
+    return rows * ws_floats_per_row(h) * sizeof(float) + 256;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -787,7 +809,8 @@ struct Proj {
     int qcols;
 };
 
-static int launch_proj(const Proj& p, int compute, bool use_split, int rows, hipStream_t stream, Timer& tm, int stage) {
+// D: the contraction length (the row width of A), the handle's embed dim
+static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage) {
     const bool bf16 = (compute == IEFVAD_COMPUTE_BF16);
     if (use_split) {   // one rule for every projection of a micro-batch: the 768-wide, single-problem grid fills the chip
         const bool f16 = (compute == IEFVAD_COMPUTE_FP16X3);
@@ -809,7 +832,7 @@ static int launch_proj(const Proj& p, int compute, bool use_split, int rows, hip
     if (!bf16) {
         GemmArgs g;
         memset(&g, 0, sizeof(g));
-        g.M = rows; g.N = p.N; g.K = IEF_D; g.lda = IEF_D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
+        g.M = rows; g.N = p.N; g.K = D; g.lda = D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
         for (int m = 0; m < p.nz; ++m) {
             g.p[m].A = p.A32[m]; g.p[m].W = p.W32[m]; g.p[m].bias = p.bias[m]; g.p[m].C = p.C[m]; g.p[m].R = p.R[m];
             g.p[m].C2 = p.C2[m];
@@ -957,14 +980,15 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const int L = c.num_layers, K = c.num_steps;
     const int mb = micro_batch(h);
-    const size_t D = IEF_D;
+    const size_t D = h->D;
+    const bool d512 = h->D == IEF_D512;      // iefvad_create_ex: f32 arithmetic only, so every bf16 / split branch below is 768-wide
     const float factor = (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;   // imf_vad.py:134
-    const float qscale = 1.0f / sqrtf((float)IEF_DH);
+    const float qscale = 1.0f / sqrtf((float)h->DH);
     {
         const bool enc_rows_mode = rg && rg->enc_rows > 0;       // row-compressed chunks: valid rows + one pad row each
         int rows = enc_rows_mode ? rg->enc_rows : nb * IEF_T;
         const size_t R = (size_t)nb * IEF_T;                     // region stride: the dense capacity
-        // workspace regions, in units of R*768 floats: xin 0..2 | qkv 2..8 | att 8..10 | y 10..12 | x 12..14 | logits
+        // workspace regions, in units of R*D floats: xin 0..2 | qkv 2..8 | att 8..10 | y 10..12 | x 12..14 | logits
         float* ws = (float*)workspace;
         float* xin[2] = {ws, ws + R * D};
         float* qkv[2] = {ws + 2 * R * D, ws + 5 * R * D};
@@ -1013,15 +1037,19 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
             hipEvent_t e = tm.begin(ST_CAST);
             // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
             // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
-#define RAGGED_IN(T)                                                                                                        \
+#define RAGGED_IN(T, W)                                                                                                     \
     do {                                                                                                                    \
-        hipLaunchKernelGGL(iefvad_scatter_rows_kernel<T>, dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)rg->img_rows,         \
+        hipLaunchKernelGGL((iefvad_scatter_rows_kernel<T, W>), dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)rg->img_rows, \
                            (const T*)rg->ev_rows, rg->d_chunks, rg->d_flags, xin[0], xin[1], need_xb0 ? xb[0] : (bf16_t*)nullptr, \
                            need_xb0 ? xb[1] : (bf16_t*)nullptr, enc_rows_mode ? 0 : IEF_T);                                  \
     } while (0)
-            if (in_dtype == IEFVAD_IN_F32) RAGGED_IN(float);
-            else if (in_dtype == IEFVAD_IN_F16) RAGGED_IN(__half);
-            else RAGGED_IN(__hip_bfloat16);
+            if (d512) {
+                if (in_dtype == IEFVAD_IN_F32) RAGGED_IN(float, IEF_D512);
+                else if (in_dtype == IEFVAD_IN_F16) RAGGED_IN(__half, IEF_D512);
+                else RAGGED_IN(__hip_bfloat16, IEF_D512);
+            } else if (in_dtype == IEFVAD_IN_F32) RAGGED_IN(float, IEF_D);
+            else if (in_dtype == IEFVAD_IN_F16) RAGGED_IN(__half, IEF_D);
+            else RAGGED_IN(__hip_bfloat16, IEF_D);
 #undef RAGGED_IN
             tm.end(e);
             HIP_TRY(hipGetLastError());
@@ -1034,9 +1062,12 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
             bf16_t* b1p = need_xb0 ? xb[1] : nullptr;
             const float* s0 = h->row_scale[0] ? h->row_scale[0] + row0 : nullptr;
             const float* s1 = h->row_scale[1] ? h->row_scale[1] + row0 : nullptr;
-            int rc = (in_dtype == IEFVAD_IN_F32)   ? launch_cast_scaled<float>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
-                     : (in_dtype == IEFVAD_IN_F16) ? launch_cast_scaled<__half>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
-                                                   : launch_cast_scaled<__hip_bfloat16>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream);
+            int rc = d512 ? ((in_dtype == IEFVAD_IN_F32)   ? launch_cast_scaled<float, IEF_D512>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
+                             : (in_dtype == IEFVAD_IN_F16) ? launch_cast_scaled<__half, IEF_D512>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
+                                                           : launch_cast_scaled<__hip_bfloat16, IEF_D512>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream))
+                          : ((in_dtype == IEFVAD_IN_F32)   ? launch_cast_scaled<float, IEF_D>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
+                             : (in_dtype == IEFVAD_IN_F16) ? launch_cast_scaled<__half, IEF_D>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
+                                                           : launch_cast_scaled<__hip_bfloat16, IEF_D>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream));
             tm.end(e);
             if (rc) return rc;
             cur[0] = xin[0];
@@ -1092,8 +1123,8 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
                 if (int rc = launch_inproj_chain(h, l, ipA, l == 0, qkvb, rows, stream, tm)) return rc;
             }
             memset(&p, 0, sizeof(p));
-            p.N = 3 * IEF_D; p.ldc = 3 * IEF_D; p.epi = EPI_QKV; p.qcols = IEF_D; p.nz = 2;
-            // q is pre-scaled for the softmax by log2(e)/sqrt(96): both attention kernels use exp2
+            p.N = 3 * (int)D; p.ldc = 3 * (int)D; p.epi = EPI_QKV; p.qcols = (int)D; p.nz = 2;
+            // q is pre-scaled for the softmax by log2(e)/sqrt(d_h): both attention kernels use exp2
             p.alpha = qscale * 1.4426950408889634f;
             for (int m = 0; m < 2; ++m) {
                 p.A32[m] = cur[m]; p.A16[m] = xb[m]; p.W32[m] = h->in_w[m][l]; p.W16[m] = h->in_wb[m][l]; p.Ws[m] = h->in_ws[m][l];
@@ -1103,7 +1134,7 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
                 if (bf) p.Cb[m] = qkvb[m]; else p.C[m] = qkv[m];
             }
             if (!ip_chain)
-                if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_QKV)) return rc;
+                if (int rc = launch_proj(p, c.compute, splitmb, (int)D, rows, stream, tm, ST_QKV)) return rc;
 
             hipEvent_t e = tm.begin(ST_ATT);
             if (bf) {
@@ -1137,6 +1168,10 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
                     hipLaunchKernelGGL(iefvad_attention_split_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), ATS_LDS_BYTES, stream, aa);
                 else if (splitmb)
                     hipLaunchKernelGGL(iefvad_attention_split_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), ATS_LDS_BYTES, stream, aa);
+                else if (d512 && enc_rows_mode)
+                    hipLaunchKernelGGL(iefvad_attention_f32_rows_d64_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
+                else if (d512)
+                    hipLaunchKernelGGL(iefvad_attention_f32_d64_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
                 else if (enc_rows_mode)
                     hipLaunchKernelGGL(iefvad_attention_f32_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
                 else
@@ -1158,13 +1193,13 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
             }
 
             memset(&p, 0, sizeof(p));
-            p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RESID; p.nz = 2;
+            p.N = (int)D; p.ldc = (int)D; p.epi = EPI_BIAS_RESID; p.nz = 2;
             for (int m = 0; m < 2; ++m) {
                 p.A32[m] = att[m]; p.A16[m] = attb[m]; p.W32[m] = h->out_w[m][l]; p.W16[m] = h->out_wb[m][l]; p.Ws[m] = h->out_ws[m][l];
                 p.Wh[m] = h->out_wh[m][l]; p.amaxW[m] = h->out_wa[m][l]; p.amaxA[m] = am_att(l, m);
                 p.bias[m] = h->out_b[m][l]; p.C[m] = ybuf[m]; p.R[m] = cur[m];
             }
-            if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_OUT)) return rc;
+            if (int rc = launch_proj(p, c.compute, splitmb, (int)D, rows, stream, tm, ST_OUT)) return rc;
 
             LnArgs la;
             memset(&la, 0, sizeof(la));
@@ -1179,7 +1214,8 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
                 la.amax[m] = am_x(l, m);
             }
             e = tm.begin(ST_LN);
-            hipLaunchKernelGGL(iefvad_layernorm_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
+            if (d512) hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
+            else hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
             tm.end(e);
             HIP_TRY(hipGetLastError());
             cur[0] = xbuf[0];
@@ -1210,7 +1246,8 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
                         HIP_TRY(bf ? hipMemsetAsync(attb[m] + tail0, 0, tailn * sizeof(bf16_t), stream)
                                    : hipMemsetAsync(att[m] + tail0, 0, tailn * sizeof(float), stream));
                 hipEvent_t e = tm.begin(ST_CAST);
-                hipLaunchKernelGGL(iefvad_compact_rows_kernel, dim3(nb, 2), dim3(256), 0, stream, ca);
+                if (d512) hipLaunchKernelGGL(iefvad_compact_rows_kernel<IEF_D512>, dim3(nb, 2), dim3(256), 0, stream, ca);
+                else hipLaunchKernelGGL(iefvad_compact_rows_kernel<IEF_D>, dim3(nb, 2), dim3(256), 0, stream, ca);
                 tm.end(e);
                 HIP_TRY(hipGetLastError());
                 rows = mc;
@@ -1254,13 +1291,13 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
         if (!heads_fused) {
             Proj p;
             memset(&p, 0, sizeof(p));
-            p.N = 2 * IEF_D; p.ldc = IEF_D; p.epi = EPI_HEADS; p.nz = 2;
+            p.N = 2 * (int)D; p.ldc = (int)D; p.epi = EPI_HEADS; p.nz = 2;
             for (int m = 0; m < 2; ++m) {
                 p.A32[m] = xt[m]; p.A16[m] = xtb[m]; p.W32[m] = h->head_w[m]; p.W16[m] = h->head_wb[m]; p.Ws[m] = h->head_ws[m]; p.bias[m] = h->head_b[m];
                 p.Wh[m] = h->head_wh[m]; p.amaxW[m] = h->head_wa[m]; p.amaxA[m] = am_x(L - 1, m);
             }
             p.C[0] = mu_i; p.C2[0] = lv_i; p.C[1] = mu_e; p.C2[1] = lv_e;
-            if (int rc = launch_proj(p, c.compute, tail_split, rows, stream, tm, ST_HEAD)) return rc;
+            if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_HEAD)) return rc;
         }
 
         // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
@@ -1277,7 +1314,8 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
             fa.nrows = rows; fa.factor = factor; fa.eps = c.epsilon;
             fa.z_amax = am_z(0);
             hipEvent_t e = tm.begin(ST_FUSION);
-            hipLaunchKernelGGL(iefvad_fusion_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
+            if (d512) hipLaunchKernelGGL(iefvad_fusion_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
+            else hipLaunchKernelGGL(iefvad_fusion_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
             tm.end(e);
             HIP_TRY(hipGetLastError());
         }
@@ -1289,24 +1327,28 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
         for (int k = 0; k < K && !chain; ++k) {
             Proj p;
             memset(&p, 0, sizeof(p));
-            p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RELU; p.nz = 1;
+            p.N = (int)D; p.ldc = (int)D; p.epi = EPI_BIAS_RELU; p.nz = 1;
             p.A32[0] = z; p.A16[0] = zb; p.W32[0] = h->ref_w1[k]; p.W16[0] = h->ref_w1b[k]; p.Ws[0] = h->ref_w1s[k]; p.bias[0] = h->ref_b1[k];
             p.Wh[0] = h->ref_w1h[k]; p.amaxW[0] = h->ref_w1a[k]; p.amaxA[0] = am_z(k); p.amaxC[0] = am_h(k);
             p.C[0] = bf ? nullptr : hbuf; p.Cb[0] = bf ? hb : nullptr;
-            if (int rc = launch_proj(p, c.compute, tail_split, rows, stream, tm, ST_REFINE)) return rc;
+            if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_REFINE)) return rc;
             memset(&p, 0, sizeof(p));
-            p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
+            p.N = (int)D; p.ldc = (int)D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
             p.A32[0] = hbuf; p.A16[0] = hb; p.W32[0] = h->ref_w2[k]; p.W16[0] = h->ref_w2b[k]; p.Ws[0] = h->ref_w2s[k]; p.bias[0] = h->ref_b2[k];
             p.Wh[0] = h->ref_w2h[k]; p.amaxW[0] = h->ref_w2a[k]; p.amaxA[0] = am_h(k); p.amaxC[0] = am_z(k + 1);
             p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? zb : nullptr;
-            if (int rc = launch_proj(p, c.compute, tail_split, rows, stream, tm, ST_REFINE)) return rc;
+            if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_REFINE)) return rc;
         }
 
         // 5. scorer (imf_vad.py:150)
         if (!chain) {
             hipEvent_t e = tm.begin(ST_SCORER);
-            hipLaunchKernelGGL(iefvad_scorer_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, z,
-                               h->cls_w, h->cls_b, logits, rows);
+            if (d512)
+                hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, z,
+                                   h->cls_w, h->cls_b, logits, rows);
+            else
+                hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, z,
+                                   h->cls_w, h->cls_b, logits, rows);
             tm.end(e);
             HIP_TRY(hipGetLastError());
         }
@@ -1342,7 +1384,7 @@ static int forward_impl(iefvad_handle* h, const void* img, const void* ev, int32
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = (B - b0 < mb) ? (B - b0) : mb;
         const size_t row0 = (size_t)b0 * IEF_T;
-        const size_t in_off = row0 * IEF_D * in_elem_bytes(in_dtype);
+        const size_t in_off = row0 * (size_t)h->D * in_elem_bytes(in_dtype);
         if (int rc = forward_pass(h, (const char*)img + in_off, (const char*)ev + in_off, in_dtype, nb, row0, workspace, out, nullptr,
                                   stream, tm))
             return rc;
@@ -1480,14 +1522,17 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
         long long r0 = 0;
         for (long long c0 = 0; c0 < total_chunks; c0 += mb) {
             const int nb = (int)((total_chunks - c0 < mb) ? (total_chunks - c0) : mb);
-            const void* pi = (const char*)img_rows + (size_t)r0 * IEF_D * esz;
-            const void* pe = (const char*)ev_rows + (size_t)r0 * IEF_D * esz;
-            if (in_dtype == IEFVAD_IN_F32)
-                hipLaunchKernelGGL(iefvad_nanflag_kernel<float>, dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const float*)pi, (const float*)pe, dc + c0, (int*)dflags);
-            else if (in_dtype == IEFVAD_IN_F16)
-                hipLaunchKernelGGL(iefvad_nanflag_kernel<__half>, dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const __half*)pi, (const __half*)pe, dc + c0, (int*)dflags);
-            else
-                hipLaunchKernelGGL(iefvad_nanflag_kernel<__hip_bfloat16>, dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const __hip_bfloat16*)pi, (const __hip_bfloat16*)pe, dc + c0, (int*)dflags);
+            const void* pi = (const char*)img_rows + (size_t)r0 * h->D * esz;
+            const void* pe = (const char*)ev_rows + (size_t)r0 * h->D * esz;
+#define NANFLAG(T, W) hipLaunchKernelGGL((iefvad_nanflag_kernel<T, W>), dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)pi, (const T*)pe, dc + c0, (int*)dflags)
+            if (h->D == IEF_D512) {
+                if (in_dtype == IEFVAD_IN_F32) NANFLAG(float, IEF_D512);
+                else if (in_dtype == IEFVAD_IN_F16) NANFLAG(__half, IEF_D512);
+                else NANFLAG(__hip_bfloat16, IEF_D512);
+            } else if (in_dtype == IEFVAD_IN_F32) NANFLAG(float, IEF_D);
+            else if (in_dtype == IEFVAD_IN_F16) NANFLAG(__half, IEF_D);
+            else NANFLAG(__hip_bfloat16, IEF_D);
+#undef NANFLAG
             for (int j = 0; j < nb; ++j) r0 += hc[c0 + j].valid;
         }
         tm.end(e);
@@ -1498,8 +1543,8 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
         long long vrows = 0;
         for (int j = 0; j < nb; ++j) vrows += hc[c0 + j].valid;
         RaggedPass rg;
-        rg.img_rows = (const char*)img_rows + (size_t)row0 * IEF_D * esz;
-        rg.ev_rows = (const char*)ev_rows + (size_t)row0 * IEF_D * esz;
+        rg.img_rows = (const char*)img_rows + (size_t)row0 * h->D * esz;
+        rg.ev_rows = (const char*)ev_rows + (size_t)row0 * h->D * esz;
         rg.d_chunks = dc + c0;
         rg.d_flags = dflags;
         rg.valid_rows = (int)vrows;
@@ -1579,7 +1624,7 @@ static int graph_limit(const iefvad_handle* h) {
 static int forward_graphed(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
                            size_t workspace_bytes, const iefvad_outputs* out, hipStream_t stream) {
     static_assert(sizeof(iefvad_outputs) == 10 * sizeof(float*), "iefvad_outputs is ten pointers");
-    const size_t D = IEF_D, T = IEF_T;
+    const size_t D = h->D, T = IEF_T;
     if (!h->graphs) {
         h->graphs = new (std::nothrow) GraphCache();
         if (!h->graphs) return fail("iefvad_forward: out of host memory");
@@ -2055,6 +2100,7 @@ extern "C" int iefvad_auc_ap(const float* scores, const uint8_t* gt_frames, int6
 extern "C" int iefvad_rowblock_unit(iefvad_handle* h, int32_t stage, int32_t layer, int32_t rows, const iefvad_unit_io* io, void* stream_) {
     if (!h || !io) return fail("iefvad_rowblock_unit: null argument");
     if (!h->weights_set) return fail("iefvad_rowblock_unit: weights not set");
+    if (h->D != IEF_D) return fail("iefvad_rowblock_unit: the row-block kernels are built for D=768 (this handle has D=%d)", h->D);
     if (h->cfg.compute != IEFVAD_COMPUTE_BF16) return fail("iefvad_rowblock_unit: the row-block kernels belong to compute = BF16 (got %d)", h->cfg.compute);
     if (rows <= 0 || rows % 64) return fail("iefvad_rowblock_unit: rows = %d must be a positive multiple of 64", rows);
     hipStream_t stream = (hipStream_t)stream_;

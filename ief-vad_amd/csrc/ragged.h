@@ -32,13 +32,13 @@ template <> struct RaggedLimits<__hip_bfloat16> { static __device__ float max() 
 
 // gridDim.z workgroups per (chunk, modality), each scanning every gridDim.z-th 4096-element tile (a pass of 60 - 130 chunks is
 // 120 - 260 workgroups otherwise: a few per CU, each a chain of memory latencies): any NaN among the chunk's valid elements ->
-// flags[2 video + modality] = 1
+// flags[2 video + modality] = 1.  The kernels here are templates on the row width D (768, or 512 for ViT-B/16 features).
 #define IEF_RAGGED_SLICES 4
-template <typename T>
+template <typename T, int D>
 __global__ __launch_bounds__(256) void iefvad_nanflag_kernel(const T* img, const T* ev, const RaggedChunk* chunks, int* flags) {
     const RaggedChunk c = chunks[blockIdx.x];
-    const T* src = (blockIdx.y ? ev : img) + (size_t)c.src_row * IEF_D;
-    const int n = c.valid * IEF_D;                     // a multiple of 768, hence of 4
+    const T* src = (blockIdx.y ? ev : img) + (size_t)c.src_row * D;
+    const int n = c.valid * D;                         // a multiple of D, hence of 4
     bool bad = false;
     for (int base = blockIdx.z * 4096 + threadIdx.x * 4; base < n; base += gridDim.z * 4096) {
         float v[16];                                   // four 16-byte (8-byte) loads in flight per lane
@@ -54,32 +54,33 @@ __global__ __launch_bounds__(256) void iefvad_nanflag_kernel(const T* img, const
 
 // gridDim.z workgroups per (chunk, modality), 16-row groups dealt round-robin: valid rows from the packed input (fixed up if the
 // video's flag is set), zeros behind them (nrows = 256: whole chunks; nrows = 0: row-compressed, one zero row)
-template <typename T>
+template <typename T, int D>
 __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, const T* ev, const RaggedChunk* chunks, const int* flags,
                                                                   float* out0, float* out1, __bf16* ob0, __bf16* ob1, int nrows) {
+    constexpr int NJ = D / 256;
     const RaggedChunk c = chunks[blockIdx.x];
     const int m = blockIdx.y;
-    const T* src = (m ? ev : img) + (size_t)c.src_row * IEF_D;
-    float* out = (m ? out1 : out0) + (size_t)c.enc_row * IEF_D;
+    const T* src = (m ? ev : img) + (size_t)c.src_row * D;
+    float* out = (m ? out1 : out0) + (size_t)c.enc_row * D;
     __bf16* ob = m ? ob1 : ob0;
-    if (ob) ob += (size_t)c.enc_row * IEF_D;
+    if (ob) ob += (size_t)c.enc_row * D;
     const bool fix = flags && flags[2 * c.video + m] != 0;
     const float big = RaggedLimits<T>::max();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nr = nrows ? nrows : ragged_rows(c.valid);
     // four rows of the wave per trip: all their loads are issued before the first store (a 40-row chunk is 2-3 trips of pure latency)
     for (int r0 = wave + 16 * blockIdx.z; r0 < nr; r0 += 16 * gridDim.z) {
-        f32x4 v[4][3];
+        f32x4 v[4][NJ];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int r = r0 + 4 * u;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
+            for (int j = 0; j < NJ; ++j) {
                 const int col = 4 * lane + 256 * j;
                 v[u][j] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (r < c.valid) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[u][j][e] = (float)src[(size_t)r * IEF_D + col + e];
+                    for (int e = 0; e < 4; ++e) v[u][j][e] = (float)src[(size_t)r * D + col + e];
                 }
             }
         }
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, 
             const int r = r0 + 4 * u;
             if (r >= nr) break;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) {
+            for (int j = 0; j < NJ; ++j) {
                 const int col = 4 * lane + 256 * j;
                 f32x4 w = v[u][j];
                 if (fix && r < c.valid) {
@@ -98,8 +99,8 @@ __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, 
                         w[e] = (x != x) ? 0.f : (x > big ? big : (x < -big ? -big : x));     // torch.nan_to_num(nan=0.0)
                     }
                 }
-                *(f32x4*)(out + (size_t)r * IEF_D + col) = w;
-                if (ob) *(bf16x4_t*)(ob + (size_t)r * IEF_D + col) = to_bf16x4(w);
+                *(f32x4*)(out + (size_t)r * D + col) = w;
+                if (ob) *(bf16x4_t*)(ob + (size_t)r * D + col) = to_bf16x4(w);
             }
         }
     }
@@ -113,19 +114,20 @@ struct CompactArgs {
     __bf16* xcb[2];
     const RaggedChunk* chunks;
 };
+template <int D>
 __global__ __launch_bounds__(256) void iefvad_compact_rows_kernel(CompactArgs a) {
     const RaggedChunk c = a.chunks[blockIdx.x];
     const int m = blockIdx.y;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int r = wave; r < c.valid; r += 4) {
-        const size_t s = ((size_t)c.enc_row + r) * IEF_D + 4 * lane, d = ((size_t)c.src_row + r) * IEF_D + 4 * lane;
+        const size_t s = ((size_t)c.enc_row + r) * D + 4 * lane, d = ((size_t)c.src_row + r) * D + 4 * lane;
         if (a.x[m]) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) *(f32x4*)(a.xc[m] + d + 256 * j) = *(const f32x4*)(a.x[m] + s + 256 * j);
+            for (int j = 0; j < D / 256; ++j) *(f32x4*)(a.xc[m] + d + 256 * j) = *(const f32x4*)(a.x[m] + s + 256 * j);
         }
         if (a.xb[m]) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) *(bf16x4_t*)(a.xcb[m] + d + 256 * j) = *(const bf16x4_t*)(a.xb[m] + s + 256 * j);
+            for (int j = 0; j < D / 256; ++j) *(bf16x4_t*)(a.xcb[m] + d + 256 * j) = *(const bf16x4_t*)(a.xb[m] + s + 256 * j);
         }
     }
 }

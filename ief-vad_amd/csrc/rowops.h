@@ -1,6 +1,8 @@
 // Row-wise (one wavefront per 768-wide snippet row) stages of the forward: LayerNorm, the
 // precision-weighted fusion, the scorer and the input cast.  All are HBM-bound streaming passes:
 // 16-byte coalesced loads (lane l owns columns 4l + 256 j, j = 0..2) and 64-lane shuffle reductions.
+// The kernels are templates on the row width D (768, or 512 for ViT-B/16 features: j = 0..1); the per-lane sums run over
+// j in ascending order, so the 768 instances keep the summation trees they always had, e.g. (v0 + v1) + v2.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
@@ -36,26 +38,36 @@ struct LnArgs {
 // block at two waves per SIMD), not memory bound.  ln_row and ln_rows perform the SAME operations per row in the same order, so the
 // stand-alone kernel and every fused epilogue agree bit for bit.
 __device__ __forceinline__ float ln_hsum(f32x4 t) { return (t[0] + t[1]) + (t[2] + t[3]); }
+// ((v0 + v1) + v2) ...: the lane's sum over its NJ column groups, left to right
+template <int NJ>
+__device__ __forceinline__ f32x4 row_vsum(const f32x4 (&v)[NJ]) {
+    f32x4 s = v[0];
+#pragma unroll
+    for (int j = 1; j < NJ; ++j) s = s + v[j];
+    return s;
+}
 
 // centre the row in place and return 1 / sqrt(var + eps): THE statistics of a LayerNorm row -- ln_row and the backward kernel
 // (backward.h: iefvad_layernorm_bwd_kernel recomputes instead of storing them) share these operations, so both see the same bits
-__device__ __forceinline__ float ln_center_rstd(f32x4 (&v)[3], float eps) {
-    const float mean = wave_sum(ln_hsum((v[0] + v[1]) + v[2])) * (1.0f / IEF_D);
+template <int NJ>
+__device__ __forceinline__ float ln_center_rstd(f32x4 (&v)[NJ], float eps) {
+    const float mean = wave_sum(ln_hsum(row_vsum(v))) * (1.0f / (256 * NJ));
     const f32x4 m4 = {mean, mean, mean, mean};
 #pragma unroll
-    for (int j = 0; j < 3; ++j) v[j] = v[j] - m4;
+    for (int j = 0; j < NJ; ++j) v[j] = v[j] - m4;
     f32x4 sq = v[0] * v[0];
-    sq = v[1] * v[1] + sq;
-    sq = v[2] * v[2] + sq;
-    const float var = wave_sum(ln_hsum(sq)) * (1.0f / IEF_D);
+#pragma unroll
+    for (int j = 1; j < NJ; ++j) sq = v[j] * v[j] + sq;
+    const float var = wave_sum(ln_hsum(sq)) * (1.0f / (256 * NJ));
     return 1.0f / sqrtf(var + eps);
 }
 
-__device__ __forceinline__ void ln_row(f32x4 (&v)[3], const float* g, const float* b, int lane, float eps) {
+template <int NJ>
+__device__ __forceinline__ void ln_row(f32x4 (&v)[NJ], const float* g, const float* b, int lane, float eps) {
     const float rstd = ln_center_rstd(v, eps);
     const f32x4 r4 = {rstd, rstd, rstd, rstd};
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < NJ; ++j) {
         const f32x4 gv = *(const f32x4*)(g + 4 * lane + 256 * j);
         const f32x4 bv = *(const f32x4*)(b + 4 * lane + 256 * j);
         v[j] = (v[j] * r4) * gv + bv;
@@ -101,31 +113,33 @@ __device__ __forceinline__ void ln_rows(f32x4 (&v)[R][3], const float* g, const 
     }
 }
 
+template <int D>
 __global__ __launch_bounds__(256) void iefvad_layernorm_kernel(LnArgs a) {
+    constexpr int NJ = D / 256;
     const int mod = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (row >= a.nrows) return;
-    const float* xp = a.x[mod] + (size_t)row * IEF_D + 4 * lane;
-    f32x4 v[3];
+    const float* xp = a.x[mod] + (size_t)row * D + 4 * lane;
+    f32x4 v[NJ];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) v[j] = *(const f32x4*)(xp + 256 * j);
+    for (int j = 0; j < NJ; ++j) v[j] = *(const f32x4*)(xp + 256 * j);
     ln_row(v, a.g1[mod], a.b1[mod], lane, a.eps);
     if (a.g2[mod] != nullptr) ln_row(v, a.g2[mod], a.b2[mod], lane, a.eps);
     if (a.y[mod]) {
-        float* yp = a.y[mod] + (size_t)row * IEF_D + 4 * lane;
+        float* yp = a.y[mod] + (size_t)row * D + 4 * lane;
 #pragma unroll
-        for (int j = 0; j < 3; ++j) *(f32x4*)(yp + 256 * j) = v[j];
+        for (int j = 0; j < NJ; ++j) *(f32x4*)(yp + 256 * j) = v[j];
     }
     if (a.yb[mod]) {
-        __bf16* yb = a.yb[mod] + (size_t)row * IEF_D + 4 * lane;
+        __bf16* yb = a.yb[mod] + (size_t)row * D + 4 * lane;
 #pragma unroll
-        for (int j = 0; j < 3; ++j) *(bf16x4_t*)(yb + 256 * j) = to_bf16x4(v[j]);
+        for (int j = 0; j < NJ; ++j) *(bf16x4_t*)(yb + 256 * j) = to_bf16x4(v[j]);
     }
     if (a.amax[mod]) {
         float m = 0.f;
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) m = amax_fold(m, v[j][e]);
         amax_store_part(a.amax[mod], row / IEF_T, row % IEF_T, wave_max(m), lane);
@@ -158,14 +172,15 @@ struct FusionArgs {
     float* z_amax;              // fp16x3 mode: running max |z| (nullable)
 };
 
+template <int D>
 __global__ __launch_bounds__(256) void iefvad_fusion_kernel(FusionArgs a) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (row >= a.nrows) return;
-    const size_t base = (size_t)row * IEF_D + 4 * lane;
+    const size_t base = (size_t)row * D + 4 * lane;
     float si = 0.f, se = 0.f, zm = 0.f;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < D / 256; ++j) {
         const size_t o = base + 256 * j;
         const f32x4 mi = *(const f32x4*)(a.mu_i + o), li = *(const f32x4*)(a.lv_i + o);
         const f32x4 me = *(const f32x4*)(a.mu_e + o), le = *(const f32x4*)(a.lv_e + o);
@@ -186,8 +201,8 @@ __global__ __launch_bounds__(256) void iefvad_fusion_kernel(FusionArgs a) {
     }
     if (a.z_amax) amax_store_part(a.z_amax, row / IEF_T, row % IEF_T, wave_max(zm), lane);
     if (a.n_i_mean || a.n_e_mean) {
-        si = wave_sum(si) * (1.0f / IEF_D);
-        se = wave_sum(se) * (1.0f / IEF_D);
+        si = wave_sum(si) * (1.0f / D);
+        se = wave_sum(se) * (1.0f / D);
         if (lane == 0) {
             if (a.n_i_mean) a.n_i_mean[row] = si;
             if (a.n_e_mean) a.n_e_mean[row] = se;
@@ -196,15 +211,16 @@ __global__ __launch_bounds__(256) void iefvad_fusion_kernel(FusionArgs a) {
 }
 
 // ---- scorer: logits = z . w_c + b_c  (classifier = Linear(768, 1), imf_vad.py:107,150)
+template <int D>
 __global__ __launch_bounds__(256) void iefvad_scorer_kernel(const float* z, const float* w, const float* b,
                                                              float* logits, int nrows) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
     if (row >= nrows) return;
-    const float* zp = z + (size_t)row * IEF_D + 4 * lane;
+    const float* zp = z + (size_t)row * D + 4 * lane;
     float s = 0.f;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < D / 256; ++j) {
         const f32x4 zv = *(const f32x4*)(zp + 256 * j);
         const f32x4 wv = *(const f32x4*)(w + 4 * lane + 256 * j);
 #pragma unroll
@@ -237,7 +253,7 @@ __global__ __launch_bounds__(256) void iefvad_cast_kernel(const T* in0, const T*
 // /root/reference/test2.py:71-77 `x[:, idx] = x[:, idx] * 0.01`): the product is formed in fp32 and, for fp16 / bf16 sources, rounded
 // to the source type before the widening -- torch multiplies a half tensor in fp32 and stores a half tensor, and the model then
 // widens it (imf_vad.py:41-42).  A NULL scale vector, or a scale of exactly 1, leaves the row's bits alone.
-template <typename T>
+template <typename T, int D>
 __global__ __launch_bounds__(256) void iefvad_cast_scaled_kernel(const T* in0, const T* in1, float* out0, float* out1, __bf16* ob0, __bf16* ob1,
                                                                  size_t n, const float* s0, const float* s1) {
     const T* in = blockIdx.y ? in1 : in0;
@@ -246,7 +262,7 @@ __global__ __launch_bounds__(256) void iefvad_cast_scaled_kernel(const T* in0, c
     const float* sc = blockIdx.y ? s1 : s0;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx * 4 < n; idx += (size_t)gridDim.x * blockDim.x) {
         const size_t o = idx * 4;   // n is a multiple of 4, and so is the row length: the four elements share a row
-        const float f = sc ? sc[o / IEF_D] : 1.0f;
+        const float f = sc ? sc[o / D] : 1.0f;
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {

@@ -111,6 +111,7 @@ static TrainLayout train_layout(int L, int K, int B) {
 
 extern "C" size_t iefvad_train_workspace_bytes(const iefvad_handle* h, int32_t B) {
     if (!h || B <= 0 || B > 4096) return 0;
+    if (h->D != IEF_D) { fail("iefvad_train_workspace_bytes: training is built for D=768 (this handle has D=%d)", h->D); return 0; }
     return train_layout(h->cfg.num_layers, h->cfg.num_steps, B).total * sizeof(float) + 256;
 }
 
@@ -376,6 +377,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
                                     const iefvad_train_options* opt, void* train_ws, size_t train_ws_bytes, const iefvad_outputs* out,
                                     void* stream_) {
     if (!h) return fail("iefvad_train_forward: null handle");
+    if (h->D != IEF_D) return fail("iefvad_train_forward: training is built for D=768 (this handle has D=%d)", h->D);
     const bool fused = train_attn_fused(h);
     if (int rc = train_check(h, B, train_ws, train_ws_bytes, "iefvad_train_forward")) return rc;
     if (!img || !ev || !out || !opt) return fail("iefvad_train_forward: null argument");
@@ -448,7 +450,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             p.A32[m] = xin(m, l); p.W32[m] = h->in_w[m][l]; p.Ws[m] = h->in_ws[m][l]; p.bias[m] = h->in_b[m][l];
             p.C[m] = ws + t.qkv[m][l];
         }
-        if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_QKV)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_QKV)) return rc;
 
         // bf16x6: S = q k^T -> softmax -> dropout -> Pd v in ONE launch for both modalities (attention_split.h, TRAIN: the eval kernel
         // with the sign-carrying P stored for the backward); IEFVAD_TRAIN_ATTN=unfused keeps the three launches below (A/B: read per
@@ -513,7 +515,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             p.A32[m] = ws + t.att[m][l]; p.W32[m] = h->out_w[m][l]; p.Ws[m] = h->out_ws[m][l]; p.bias[m] = h->out_b[m][l];
             p.C[m] = ws + t.s[m][l]; p.R[m] = xin(m, l);
         }
-        if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_OUT)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_OUT)) return rc;
 
         LnArgs la;
         memset(&la, 0, sizeof(la));
@@ -521,7 +523,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         for (int m = 0; m < 2; ++m) {
             la.x[m] = ws + t.s[m][l]; la.g1[m] = h->norm_w[m][l]; la.b1[m] = h->norm_b[m][l]; la.y[m] = ws + t.x[m][l + 1];
         }
-        hipLaunchKernelGGL(iefvad_layernorm_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
+        hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
         HIP_TRY(hipGetLastError());
     }
     {   // whitening LayerNorm (imf_vad.py:117,123) as a launch of its own: the backward needs its input, the last norm's output
@@ -531,7 +533,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         for (int m = 0; m < 2; ++m) {
             la.x[m] = ws + t.x[m][L]; la.g1[m] = h->whiten_w[m]; la.b1[m] = h->whiten_b[m]; la.y[m] = ws + t.E[m];
         }
-        hipLaunchKernelGGL(iefvad_layernorm_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
+        hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
         HIP_TRY(hipGetLastError());
     }
     {
@@ -542,7 +544,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             p.A32[m] = ws + t.E[m]; p.W32[m] = h->head_w[m]; p.Ws[m] = h->head_ws[m]; p.bias[m] = h->head_b[m];
             p.C[m] = rec->mu[m]; p.C2[m] = rec->lv[m];
         }
-        if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_HEAD)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_HEAD)) return rc;
     }
     {
         FusionArgs fa;
@@ -551,7 +553,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         fa.n_i = out->w_i; fa.n_e = out->w_e; fa.z = zst(0);
         fa.n_i_mean = out->w_i_mean; fa.n_e_mean = out->w_e_mean;
         fa.nrows = rows; fa.factor = factor; fa.eps = c.epsilon;
-        hipLaunchKernelGGL(iefvad_fusion_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
+        hipLaunchKernelGGL(iefvad_fusion_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
         HIP_TRY(hipGetLastError());
     }
     for (int k = 0; k < K; ++k) {
@@ -559,15 +561,15 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         memset(&p, 0, sizeof(p));
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RELU; p.nz = 1;
         p.A32[0] = zst(k); p.W32[0] = h->ref_w1[k]; p.Ws[0] = h->ref_w1s[k]; p.bias[0] = h->ref_b1[k]; p.C[0] = ws + t.hid[k];
-        if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_REFINE)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE)) return rc;
         memset(&p, 0, sizeof(p));
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
         p.A32[0] = ws + t.hid[k]; p.W32[0] = h->ref_w2[k]; p.Ws[0] = h->ref_w2s[k]; p.bias[0] = h->ref_b2[k];
         p.C[0] = zst(k + 1); p.R[0] = zst(k);
-        if (int rc = launch_proj(p, c.compute, splitmb, rows, stream, tm, ST_REFINE)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE)) return rc;
     }
     float* logits = out->logits ? out->logits : ws + t.logits;
-    hipLaunchKernelGGL(iefvad_scorer_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, rec->zK, h->cls_w, h->cls_b,
+    hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, rec->zK, h->cls_w, h->cls_b,
                        logits, rows);
     HIP_TRY(hipGetLastError());
     // (the dict entries of imf_vad.py:152-161 that are also saved tensors were written in place: TrainRecord)
@@ -578,6 +580,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
 extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes, const iefvad_output_grads* dout,
                                      const iefvad_weight_grads* dw, void* stream_) {
     if (!h) return fail("iefvad_train_backward: null handle");
+    if (h->D != IEF_D) return fail("iefvad_train_backward: training is built for D=768 (this handle has D=%d)", h->D);
     if (!dout || !dw) return fail("iefvad_train_backward: null argument");
     const TrainRecord* rec = nullptr;
     if (h->train)

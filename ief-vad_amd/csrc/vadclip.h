@@ -336,7 +336,7 @@ extern "C" int iefvad_resblock_forward(const float* x, const iefvad_resblock_wei
         LnArgs la;
         memset(&la, 0, sizeof(la));
         la.nrows = rows; la.eps = 1e-5f; la.x[0] = in; la.g1[0] = g; la.b1[0] = b; la.y[0] = o;
-        hipLaunchKernelGGL(iefvad_layernorm_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 1), dim3(256), 0, stream, la);
+        hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 1), dim3(256), 0, stream, la);
     };
     // x = x + attention(ln_1(x))   (module.py:40)
     ln(xb, w->ln_1_w, w->ln_1_b, y);

@@ -22,7 +22,7 @@ COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X6, COMPUTE_FP16X3 = 0, 1, 2, 3
 COMPUTE_CODES = {"f32": COMPUTE_F32, "bf16": COMPUTE_BF16, "bf16x6": COMPUTE_BF16X6, "fp16x3": COMPUTE_FP16X3}
 
 # every symbol include/iefvad.h declares
-SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_set_weights", "iefvad_workspace_bytes",
+SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_set_weights", "iefvad_workspace_bytes",
            "iefvad_forward", "iefvad_forward_timed", "iefvad_gemm_bias", "iefvad_split_bf16x3", "iefvad_split_bf16x3_many", "iefvad_last_error",
            "iefvad_destroy", "iefvad_comm_unique_id", "iefvad_comm_create", "iefvad_comm_nranks", "iefvad_comm_destroy",
            "iefvad_gather_scores", "iefvad_gather_plan", "iefvad_rccl_version", "iefvad_forward_videos",
@@ -127,6 +127,8 @@ def load_library() -> C.CDLL:
     lib.iefvad_abi_version.restype = C.c_int
     lib.iefvad_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
     lib.iefvad_create.restype = C.c_int
+    lib.iefvad_create_ex.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
+    lib.iefvad_create_ex.restype = C.c_int
     lib.iefvad_set_weights.argtypes = [C.c_void_p, C.POINTER(Weights), C.c_void_p]
     lib.iefvad_set_weights.restype = C.c_int
     lib.iefvad_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]

@@ -284,8 +284,10 @@ class MMFMIL(nn.Module):
                           nu=float(t.nu), epsilon=float(t.epsilon), micro_batch=int(self.micro_batch),
                           graph_chunks=int(self.graph_chunks))
         h = C.c_void_p()
+        # D = 768 keeps the original entry; other widths (D = 512, the f32 forward of ViT-B/16 features) need iefvad_create_ex
+        create = lib.iefvad_create if t.embed_dim == 768 else lib.iefvad_create_ex
         with torch.cuda.device(device):
-            rc = lib.iefvad_create(C.byref(cfg), C.byref(h))
+            rc = create(C.byref(cfg), C.byref(h))
         if rc != 0:
             raise RuntimeError("iefvad_create: " + _lib.last_error())
         self._handle, self._handle_key = h, key
@@ -509,6 +511,9 @@ class MMFMIL(nn.Module):
         it), or from `self.dropout_mask` (uint8 [2, L, B, 8, T, T], 1 = keep) when a test injects one."""
         if self.compute not in ("f32", "bf16x6"):
             raise RuntimeError("iefvad_amd.MMFMIL trains in the fp32-accurate arithmetics only: compute='f32' or 'bf16x6'")
+        if self.temporal.embed_dim != 768:
+            raise RuntimeError(f"iefvad_amd.MMFMIL trains at D=768 only (this model has D={self.temporal.embed_dim}: "
+                               "the D=512 path is the f32 evaluation forward)")
         if not (img_visual.is_cuda and ev_visual.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback "
                                "(move the inputs with .to('cuda'))")

@@ -60,9 +60,9 @@ typedef struct iefvad_handle iefvad_handle;
  * plus epsilon (always 1e-8 in the reference, :58) and visual_length T. */
 typedef struct iefvad_config {
     int32_t abi_version;   /* IEFVAD_ABI_VERSION */
-    int32_t embed_dim;     /* D, must be 768 */
+    int32_t embed_dim;     /* D: 768 (iefvad_create), or 768 / 512 (iefvad_create_ex; 512 with compute = IEFVAD_COMPUTE_F32) */
     int32_t seq_len;       /* T, must be 256 */
-    int32_t num_heads;     /* H, must be 8 (head dim 96) */
+    int32_t num_heads;     /* H, must be 8 (head dim 96 at D = 768, 64 at D = 512) */
     int32_t num_layers;    /* L, 1..IEFVAD_MAX_LAYERS */
     int32_t num_steps;     /* K, 0..IEFVAD_MAX_STEPS */
     int32_t noise_model;   /* IEFVAD_NOISE_* */
@@ -136,8 +136,14 @@ typedef struct iefvad_stage_times {
 
 int iefvad_abi_version(void);
 
-/* Build a handle on the current HIP device.  Unsupported dimensions or noise_model -> error. */
+/* Build a handle on the current HIP device.  Unsupported dimensions or noise_model -> error.  embed_dim must be 768. */
 int iefvad_create(const iefvad_config* cfg, iefvad_handle** out);
+
+/* As iefvad_create, and embed_dim may also be 512 (head dim 64) with compute = IEFVAD_COMPUTE_F32: the ViT-B/16 features of the
+ * reference's `--ds vitb_rgb` model.  Such a handle runs the evaluation forward -- iefvad_forward / _scaled / _timed, the hipGraph
+ * replay, iefvad_forward_videos and iefvad_forward_videos_host (D = 512 rows everywhere) -- and the training entries and
+ * iefvad_rowblock_unit refuse it by name.  Every check runs before the first HIP call.  For D = 768 it is iefvad_create. */
+int iefvad_create_ex(const iefvad_config* cfg, iefvad_handle** out);
 
 /* Copy/repack the weights into library-owned device memory (stream-ordered on `stream`). */
 int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, void* stream);
@@ -293,6 +299,7 @@ typedef struct iefvad_weight_grads {
     float* cls_b;
 } iefvad_weight_grads;
 
+/* Training is built for D = 768: a D = 512 handle (iefvad_create_ex) gets 0 bytes / an error that names the width. */
 size_t iefvad_train_workspace_bytes(const iefvad_handle* h, int32_t B);
 int iefvad_train_forward(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B,
                          const iefvad_train_options* opt, void* train_ws, size_t train_ws_bytes, const iefvad_outputs* out,
