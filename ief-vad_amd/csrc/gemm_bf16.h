@@ -50,7 +50,6 @@ struct GemmBArgs {
     float alpha;
     int qcols;
     int wplane;          // split kernel (gemm_split.h): bytes between the three bf16 planes of W
-    int stagger;         // ring kernels: the second resident workgroup of each CU starts `stagger` x 8128 cycles late
 };
 
 #define GEMMB_BK 64                 // bf16 elements per k-tile (128 bytes per row)
@@ -250,15 +249,8 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_bf16_v1_kernel(GemmBArgs a
 // Result stores of the ring / split kernels.  GB2_NT_STORES=1 marks them non-temporal (global_store ... nt): a launch writes
 // 0.8-4.8 GB that no workgroup of the SAME launch reads again, while the A panels and W planes its co-resident workgroups
 // share must stay in the 4 MB L2 of their XCD.
-#ifndef GB2_EPI_SLEEP
-#define GB2_EPI_SLEEP 0
-#endif
 #ifndef GB2_NT_STORES
 #define GB2_NT_STORES 1      // bf16 ring kernel +3..6 % with fp32 results, split kernels +0..1 % (profiles/r02_gemm_nt_stores.log)
-#endif
-#ifndef GB2_NT_RESID
-#define GB2_NT_RESID 0       // experiment (round 5): the epilogue's residual / gate rows as non-temporal loads: +4 % in the stand-alone
-                             // harness (a 200 MB residual buffer re-read every iteration), nothing in the forward (TRIED.md)
 #endif
 #if GB2_NT_STORES
 #define GB2_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
@@ -341,8 +333,7 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
         if (has_resid) {
 #pragma unroll
             for (int u = 0; u < 16; ++u)
-                res[u] = GB2_NT_RESID ? __builtin_nontemporal_load((const f32x4*)(P.R + (size_t)(mrow + 2 * u) * ldc + ncol))
-                                      : *(const f32x4*)(P.R + (size_t)(mrow + 2 * u) * ldc + ncol);
+                res[u] = *(const f32x4*)(P.R + (size_t)(mrow + 2 * u) * ldc + ncol);
         }
         if constexpr (MF16) {
             // 16x16 accumulator map: col = lane & 15, row = 4 (lane >> 4) + reg; this pass takes row sub-tiles 2a, 2a+1
@@ -386,9 +377,6 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) vmax = amax_fold(vmax, v[e]);
             }
-#if GB2_EPI_SLEEP
-            __builtin_amdgcn_s_sleep(GB2_EPI_SLEEP);      // experiment: spread the stores over the partner's main loop
-#endif
         }
     }
     if (amax_out)      // a wave tile lies inside one chunk; its word: (32-row band of the chunk, 128-column tile), N <= 4096
@@ -441,29 +429,6 @@ __device__ __forceinline__ void gemm_t256_body(const GemmBArgs& args, float* sme
     const int lane = t & 63, wave = t >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int i = lane & 31, h = lane >> 5;
-
-    // De-phasing.  All workgroups of a launch start together and take the same time, so chip-wide every main loop
-    // (matrix pipe busy, HBM idle) and every epilogue (128 KB of stores per workgroup: HBM saturated, matrix pipe idle)
-    // coincide.  The launch's first 512 workgroups are the two residents of each CU; the second 256 of them (dispatch
-    // order is linear in blockIdx -- an observed property used for speed only) wait about half a tile time once, and
-    // from then on one resident of a CU stores while the other multiplies.
-    if (args.stagger != 0) {
-        const int lin = blockIdx.x + gridDim.x * blockIdx.z;
-        const int n = args.stagger > 0 ? args.stagger : -args.stagger;
-        // which of the first 512 workgroups share a CU is not documented: > 0 assumes (b, b + 256), < 0 assumes consecutive
-        // workgroups of one XCD, (b, b + 8)
-        const bool late = args.stagger > 0 ? (lin >= 256 && lin < 512) : (lin < 512 && ((lin >> 3) & 1));
-        if (n >= 1000) {
-            // uniform phases: the first 512 workgroups (every initial resident) start at one of 64 evenly spaced offsets
-            // over (n - 1000) x 64 x 64 cycles, so that chip-wide the store traffic is a steady stream, not a burst per tile
-            if (lin < 512) {
-                const int ph = (lin * 29) & 63;
-                for (int w = 0; w < ph; ++w)
-                    for (int u = 0; u < n - 1000; ++u) __builtin_amdgcn_s_sleep(1);
-            }
-        } else if (late)
-            for (int w = 0; w < n; ++w) __builtin_amdgcn_s_sleep(127);
-    }
 
     // staging: thread t moves chunk (row = (t>>2) + RPJ j, slot chunk = t&3); A: j < NJA, W: j < NJW
     const int srow = t >> 2, sch = t & 3;

@@ -13,9 +13,9 @@
 //     address) so that the two lane halves (r and r + 8) use different banks;
 //   * each wave splits the fragments it reads in registers (split8 of attention_split.h: 22 VALU per 8 elements and plane set):
 //     four fragments (two 32-column tiles of A, two of B) per 16-r tile feed 2 x 2 x 6 = 24 MFMAs.
-// 128 x 128 output tile, 4 waves (2 x 2) of 64 x 64, three workgroups per CU (48 KB of LDS: three buffers x (A + B) x 8 KB; 114
-// VGPRs).  Split-K over the rows in grid.z slices; each slice writes its partial tile, the caller reduces them in index order
-// (deterministic).  The workgroups of the first column block also sum the columns of their A tiles: the bias gradient.
+// Round 4's kernel was a 128 x 128 output tile, 4 waves (2 x 2) of 64 x 64, three workgroups per CU (48 KB of LDS: three buffers x
+// (A + B) x 8 KB; 114 VGPRs); the 128 x 256 block below replaced it and it was removed (TRIED.md).  Split-K over the rows in slices;
+// each slice writes its partial tile, the caller reduces them in index order (deterministic).  The workgroups of the first column block also sum the columns of their A tiles: the bias gradient.
 #pragma once
 #include "attention_split.h"
 
@@ -40,9 +40,8 @@ struct TnArgs {
 #define TN_A_FLOATS (TN_BK * 128)                            // the A image of a k-tile: 8 KB
 #define TN_B_FLOATS(NB) (TN_BK * 64 * (NB))                  // the B image: 8 KB (NB = 2) / 16 KB (NB = 4)
 #define TN_LDS_BYTES_OF(NB) (TN_NBUF * (TN_A_FLOATS + TN_B_FLOATS(NB)) * 4)      // [buffer b: A | B]
-#define TN_LDS_BYTES TN_LDS_BYTES_OF(2)
 
-// NB = 32-column tiles of B per wave: 2 = the 128 x 128 block above (three workgroups per CU); 4 = a 128 x 256 block, 64 x 128 per wave
+// NB = 32-column tiles of B per wave (2 was the 128 x 128 block above): 4 = a 128 x 256 block, 64 x 128 per wave
 // (round 5: six fragment splits per 48 MFMAs instead of four per 24 -- the kernel is bound by the VALU issue of its splits, 7.3 VALU
 // per MFMA against the ~7 issue slots an MFMA leaves -- 72 KB of LDS, two workgroups per CU).  The row slices are RAGGED (any count):
 // the host picks as many slices as fill the chip's workgroup slots once.
@@ -171,11 +170,6 @@ __device__ __forceinline__ void gemm_split_tn_body(const TnArgs& args, float* tn
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 C[(size_t)(32 * a + (r & 3) + 8 * (r >> 2) + 4 * h) * args.ldc + 32 * b + i] = acc[a][b][r];
-}
-
-__global__ __launch_bounds__(256, TN_NBUF == 3 ? 3 : 2) void iefvad_gemm_split_tn_kernel(TnArgs args) {
-    extern __shared__ __attribute__((aligned(16))) float tn_smem[];
-    gemm_split_tn_body<2>(args, tn_smem);
 }
 
 __global__ __launch_bounds__(256, 2) void iefvad_gemm_split_tn256_kernel(TnArgs args) {

@@ -9,7 +9,7 @@
 //            registers): biases, fuse_elem (rowops.h: the fusion kernel's own operations) and the stores follow in registers,
 //            no LDS park, no partner wave.
 // Weights are read once per 64 rows (4.7 MB over the three column thirds), the same L2 -> CU stream per row as the
-// in_proj kernel's; round 2's 256 x 64 ring kernel (tools/heads_fused_bf16_v1.h) read 196 KB of A and W per k-tile barrier for the same work.
+// in_proj kernel's; round 2's 256 x 64 ring kernel (TRIED.md, round 3) read 196 KB of A and W per k-tile barrier for the same work.
 // Same products in the same k order, same epilogue arithmetic: mu, logvar, n_i, n_e and z are bit-identical to
 // the unfused path (heads GEMM + fusion kernel: IEFVAD_ROWBLOCK_OFF=4); the row sums of n_i / n_e leave as 24 partials per row (32
 // columns each) and are finished in a fixed order by iefvad_rowmean_finish_kernel.
@@ -61,13 +61,7 @@ struct HeadsChainArgs {
     int M;                   // multiple of 64
     float factor, eps;
     unsigned wave_stride;
-    unsigned long long* diag; // HC_DIAG builds only: 8 s_memtime stamps per workgroup (tools/rowblock_diag.py)
 };
-#ifdef HC_DIAG
-#define HC_STAMP(i) do { if (args.diag && t == 0) args.diag[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define HC_STAMP(i)
-#endif
 
 __global__ __launch_bounds__(512, 2) void iefvad_heads_chain_bf16_kernel(HeadsChainArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -78,7 +72,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_heads_chain_bf16_kernel(HeadsCh
     const int m = lane & 15, q = lane >> 4;
     const int c3 = blockIdx.y;
     const int m0 = blockIdx.x * HC_BM;
-    HC_STAMP(0);
 
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(args.stream + (size_t)(8 * c3 + wave) * args.wave_stride), 0, (int)args.wave_stride, 0x00020000);
     const int vlane = lane * 16;
@@ -106,7 +99,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_heads_chain_bf16_kernel(HeadsCh
     for (int j = 0; j < 4; ++j) rd[j] = m * (IEF_D * 2) + (((4 * j + q) ^ m) & 15) * 16;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     GB2_BARRIER();
-    HC_STAMP(1);
 
     // acc[phase][2 hd + tile][a]: lane (m, q) holds row 16 a + m, columns 256 c3 + 32 wave + 16 tile + 4 q .. + 3
     f32x4 acc[2][4][4];
@@ -134,7 +126,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_heads_chain_bf16_kernel(HeadsCh
         }                                                                                                   \
     }
     HC_MAIN(0)
-    HC_STAMP(2);
     // ---- swap the image: x_e.  Requested only now: a load that misses L2 ahead of the weight pieces in the wave's in-order
     // queue stalls the ring behind it for the HBM latency, and touching the rows early (one dword per 64 bytes at entry) does
     // not help: under the 110 GB/s per CU weight stream a line lives ~1 us in the XCD's 4 MB L2
@@ -145,9 +136,7 @@ __global__ __launch_bounds__(512, 2) void iefvad_heads_chain_bf16_kernel(HeadsCh
     HC_WRITE_IMAGE()
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     GB2_BARRIER();
-    HC_STAMP(3);
     HC_MAIN(1)
-    HC_STAMP(4);
 #undef HC_MAIN
 #undef HC_LOAD
 #undef HC_FETCH_IMAGE
@@ -203,7 +192,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_heads_chain_bf16_kernel(HeadsCh
             }
         }
     }
-    HC_STAMP(5);
 }
 
 // row means of the normalised weights from the kernel's partial sums: fixed order, one thread per (row, modality) -- its np =

@@ -98,9 +98,8 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
     long long max_rows = 0, max_chunks = 0, total_chunks = 0;
     for (int v = 0; v < nvideos; ++v) total_chunks += video_chunks(lengths[v]);
     const bool compressed = !h->dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
-    static const bool row_cap_off = [] { const char* v = getenv("IEFVAD_HOSTPIPE_ROWCAP"); return v && v[0] == '0'; }();
     const long long round_rows = (long long)(h->num_cus > 0 ? h->num_cus : 256) * 64;
-    const long long row_cap = (compressed && !row_cap_off) ? round_rows * ((want + 64) / 128 > 1 ? (want + 64) / 128 : 1) : (1LL << 60);
+    const long long row_cap = compressed ? round_rows * ((want + 64) / 128 > 1 ? (want + 64) / 128 : 1) : (1LL << 60);
     auto enc_rows_of = [](int n) -> long long { return (long long)(n / IEF_T) * IEF_T + (n % IEF_T ? n % IEF_T + 1 : 0); };
     {
         Batch b = {0, 0, 0, 0, 0};
@@ -257,7 +256,7 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
     for (int l = 0; l < HostPipe::kLanes && he == hipSuccess; ++l) he = hipStreamWaitEvent(p.lane[l], p.ready, 0);
     long long row0 = 0;
     Timer tm;
-    static const bool trace = [] { const char* v = getenv("IEFVAD_HOSTPIPE_TRACE"); return v && v[0] == '1'; }();
+    const bool trace = h->hostpipe_trace;
     auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_begin = trace ? now_us() : 0.0;
     for (int k = 0; k < nb && rc == 0 && he == hipSuccess; ++k) {

@@ -28,7 +28,6 @@
 #include "refine_chain_bf16.h"
 #include "outproj_ln_chain_bf16.h"
 #include "outproj_ln_pchain_bf16.h"
-#include "outproj_ln_rchain_bf16.h"
 #include "inproj_chain_bf16.h"
 #include "heads_chain_bf16.h"
 #include "heads_pchain_bf16.h"
@@ -76,8 +75,10 @@ struct iefvad_handle {
     int rowblock_min_wgs;  // bf16 mode: the row-block kernels take a projection from this many workgroups on (IEFVAD_ROWBLOCK_MIN_WGS overrides)
     bool no_inproj_chain;
     char* oproj_stream[2][IEFVAD_MAX_LAYERS];   // bf16 mode: out_proj weights in per-wave fragment order (outproj_ln_chain_bf16.h)
-    char* oproj_stream_r[2][IEFVAD_MAX_LAYERS]; // the same matrices with the output columns dealt to the waves for the in-register LayerNorm (outproj_ln_rchain_bf16.h)
     bool dense_encoder;    // IEFVAD_DENSE_ENCODER=1: whole-video passes run the encoder on whole 256-row chunks (pad rows computed), the tail on the gathered valid rows
+    bool persist;          // bf16 mode: the persistent out_proj + LayerNorm, heads + fusion and attention kernels from two blocks per CU on (IEFVAD_PERSIST=0: off)
+    bool train_attn_unfused; // IEFVAD_TRAIN_ATTN=unfused: bf16x6 train-mode attention on the three-launch path (train.h)
+    bool hostpipe_trace;   // IEFVAD_HOSTPIPE_TRACE=1: iefvad_forward_videos_host prints its per-pass timeline to stderr (hostpipe.h)
     bool no_chain;
     char* chain_stream;    // bf16 mode: the refinement weights in the chain kernel's per-wave piece order (refine_chain_bf16.h)
     float* arena;          // one allocation holding every repacked weight
@@ -199,14 +200,18 @@ static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg
     h->cfg = *cfg;
     h->D = d512 ? IEF_D512 : IEF_D;
     h->DH = h->D / IEF_H;
+    // The library's only environment switches: alternative paths that tests compare the default against, and a trace
     {
         const char* v = getenv("IEFVAD_ROWBLOCK_OFF");
         const int off = v ? atoi(v) : 0;
         h->no_inproj_chain = off & 1; h->no_ln_fusion = off & 2; h->no_heads_fusion = off & 4; h->no_chain = off & 8;
     }
-    { const char* v = getenv("IEFVAD_DENSE_ENCODER"); h->dense_encoder = v && v[0] == '1'; }
     { const char* v = getenv("IEFVAD_ROWBLOCK_MIN_WGS"); h->rowblock_min_wgs = (v && atoi(v) > 0) ? atoi(v) : 128; }      // tools/rowblock_threshold_probe.py
     { const char* v = getenv("IEFVAD_CHAIN_MIN_BLOCKS"); h->chain_min_blocks = (v && atoi(v) > 0) ? atoi(v) : 4; }         // one chunk: 4 blocks take one block time, 2K launches more
+    { const char* v = getenv("IEFVAD_PERSIST"); h->persist = !(v && v[0] == '0'); }
+    { const char* v = getenv("IEFVAD_DENSE_ENCODER"); h->dense_encoder = v && v[0] == '1'; }
+    { const char* v = getenv("IEFVAD_TRAIN_ATTN"); h->train_attn_unfused = v && v[0] == 'u'; }
+    { const char* v = getenv("IEFVAD_HOSTPIPE_TRACE"); h->hostpipe_trace = v && v[0] == '1'; }
     hipError_t e = hipGetDevice(&h->device);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)iefvad_gemm_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -233,13 +238,8 @@ static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg
         e = hipFuncSetAttribute((const void*)iefvad_outproj_ln_pchain_bf16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 OP_LDS_BYTES);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_outproj_ln_rchain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                OR_LDS_BYTES);
-    if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)iefvad_heads_pchain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 HP_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)iefvad_gemm_split_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES_OF(4));
     if (e == hipSuccess)
@@ -316,7 +316,6 @@ extern "C" void iefvad_destroy(iefvad_handle* h) {
     for (int m = 0; m < 2; ++m)
         for (int l = 0; l < IEFVAD_MAX_LAYERS; ++l) {
             if (h->oproj_stream[m][l]) (void)hipFree(h->oproj_stream[m][l]);
-            if (h->oproj_stream_r[m][l]) (void)hipFree(h->oproj_stream_r[m][l]);
             if (h->iproj_stream[m][l]) (void)hipFree(h->iproj_stream[m][l]);
         }
     if (h->arena_s) (void)hipFree(h->arena_s);
@@ -523,9 +522,6 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
                 if (!h->oproj_stream[m][l]) HIP_TRY(hipMalloc((void**)&h->oproj_stream[m][l], wstream_bytes()));
                 hipLaunchKernelGGL(iefvad_wstream_pack_kernel, dim3(256), dim3(256), 0, stream, h->out_wb[m][l], h->oproj_stream[m][l], 1);
                 HIP_TRY(hipGetLastError());
-                if (!h->oproj_stream_r[m][l]) HIP_TRY(hipMalloc((void**)&h->oproj_stream_r[m][l], wstream_bytes()));
-                hipLaunchKernelGGL(iefvad_wstream_pack_colmap_kernel, dim3(256), dim3(256), 0, stream, h->out_wb[m][l], h->oproj_stream_r[m][l]);
-                HIP_TRY(hipGetLastError());
                 if (!h->iproj_stream[m][l]) HIP_TRY(hipMalloc((void**)&h->iproj_stream[m][l], wstream_bytes(IC_NPASS)));
                 hipLaunchKernelGGL(iefvad_wstream_pack_kernel, dim3(512), dim3(256), 0, stream, h->in_wb[m][l], h->iproj_stream[m][l], IC_NPASS);
                 HIP_TRY(hipGetLastError());
@@ -682,15 +678,12 @@ static void release_events(iefvad_handle* h) {
     }
 }
 
-// A/B switch for tests and tools (IEFVAD_NO_TINY_GEMM=1): route small problems to the 64x64 kernel as before round 2
-static const bool g_force_no_tiny = [] { const char* v = getenv("IEFVAD_NO_TINY_GEMM"); return v && v[0] == '1'; }();
-// grid-size rules of the fp32 tilings (tools/f32_threshold_probe.py): IEFVAD_F32_RULES="tiny_max_blocks64,t256_min_blocks,small_max_blocks128"
-static int g_f32_rules[3] = {320, 1536, 1024};      // were {320, 256, 256} ("when the grid fills the chip") until measured: B = 48 forward 6.7 -> 5.5 ms
-static const bool g_f32_rules_read = [] {
-    const char* v = getenv("IEFVAD_F32_RULES");
-    if (v) (void)sscanf(v, "%d,%d,%d", &g_f32_rules[0], &g_f32_rules[1], &g_f32_rules[2]);
-    return true;
-}();
+// Grid-size rules of the fp32 tilings, measured over B = 1 .. 256 chunks (profiles/r03_kernel_selection_thresholds.log): the 32x32
+// kernel below 320 blocks of 64x64, the 128x256 one from 1536 blocks of 128x256 on, the 64x64 one below 1024 blocks of 128x128.
+// They were {320, 256, 256} ("when the grid fills the chip") until measured: B = 48 forward 6.7 -> 5.5 ms.
+static const int kF32TinyMaxBlocks64 = 320;
+static const int kF32T256MinBlocks = 1536;
+static const int kF32SmallMaxBlocks128 = 1024;
 
 static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm, int stage) {
     if (a.M % GEMM_BM || a.N % GEMM_BN || a.K % GEMM_BK)
@@ -707,12 +700,12 @@ static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm,
     const int blocks64 = (a.M / GEMS_BM) * (a.N / GEMS_BN) * nz;
     const bool t256_ok = (a.N % GB2_BN == 0) && (a.K % 16 == 0) && (a.K >= 32);
     const int blocks256 = t256_ok ? (a.M / GB2_BM) * (a.N / GB2_BN) * nz : 0;
-    const bool tiny = blocks64 < g_f32_rules[0] && a.K % 64 == 0 && !g_force_no_tiny;      // < 1.25 blocks of 64x64 per CU: the chain, not the chip, bounds it
+    const bool tiny = blocks64 < kF32TinyMaxBlocks64 && a.K % 64 == 0;      // < 1.25 blocks of 64x64 per CU: the chain, not the chip, bounds it
     hipEvent_t e = tm.begin(stage);
     if (tiny) {
         dim3 grid((a.M / GEMT_BM) * (a.N / GEMT_BN), 1, nz);
         hipLaunchKernelGGL(iefvad_gemm_f32_tiny_kernel, grid, dim3(256), 0, stream, a);
-    } else if (blocks256 >= g_f32_rules[1]) {
+    } else if (blocks256 >= kF32T256MinBlocks) {
         GemmBArgs b;
         memset(&b, 0, sizeof(b));
         b.M = a.M; b.N = a.N; b.K = a.K; b.lda = a.lda; b.ldc = a.ldc; b.epi = a.epi; b.alpha = a.alpha; b.qcols = a.qcols;
@@ -722,7 +715,7 @@ static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm,
         }
         dim3 grid((a.M / GB2_BM) * (a.N / GB2_BN), 1, nz);
         hipLaunchKernelGGL(iefvad_gemm_f32_t256_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, b);
-    } else if (blocks128 < g_f32_rules[2]) {
+    } else if (blocks128 < kF32SmallMaxBlocks128) {
         dim3 grid((a.M / GEMS_BM) * (a.N / GEMS_BN), 1, nz);
         hipLaunchKernelGGL(iefvad_gemm_f32_small_kernel, grid, dim3(256), 0, stream, a);
     } else {
@@ -766,11 +759,11 @@ static int launch_gemm_b(const GemmBArgs& a, int nz, hipStream_t stream, Timer& 
 // BF16X6: the split kernel (128 x 128 tiles, two workgroups per CU; tools/gemm_tune_split: +5..8 % over the 128 x 256 /
 // one-workgroup configuration, same bits) takes a micro-batch's projections from 72 workgroups of a 768-wide projection on
 // (6 chunks: measured crossover, B = 24 forward 3.55 -> 1.97 ms; it was 512 workgroups, "fills the chip", until the end of
-// round 3); smaller problems run on the fp32 kernels (launch_gemm)
+// round 3; profiles/r03_kernel_selection_thresholds.log); smaller problems run on the fp32 kernels (launch_gemm)
 static const int kSplitBN = GS_BN_OF(2);
-static int g_split_min_wgs = [] { const char* v = getenv("IEFVAD_SPLIT_MIN_WGS"); return (v && atoi(v) > 0) ? atoi(v) : 72; }();      // 6 chunks; tools/split_threshold_probe.py
+static const int kSplitMinWgs = 72;      // 6 chunks
 static bool split_eligible(int M, int N, int K, int nz) {
-    return M % GS_BM == 0 && N % kSplitBN == 0 && K % 64 == 0 && K >= 64 && (M / GS_BM) * (N / kSplitBN) * nz >= g_split_min_wgs;
+    return M % GS_BM == 0 && N % kSplitBN == 0 && K % 64 == 0 && K >= 64 && (M / GS_BM) * (N / kSplitBN) * nz >= kSplitMinWgs;
 }
 
 static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false) {
@@ -860,9 +853,6 @@ static int launch_inproj_chain(iefvad_handle* h, int l, const void* const A[2], 
     }
     // q is pre-scaled for the softmax by log2(e)/sqrt(96): both attention kernels use exp2
     ia.M = rows; ia.alpha = (1.0f / sqrtf((float)IEF_DH)) * 1.4426950408889634f; ia.wave_stride = (unsigned)wstream_wave_stride_bytes(IC_NPASS);
-#ifdef IC_DIAG
-    { static unsigned long long* dg = [] { const char* v = getenv("IEFVAD_IC_DIAG_PTR"); return v ? (unsigned long long*)strtoull(v, nullptr, 0) : nullptr; }(); ia.diag = dg; }
-#endif
     hipEvent_t e = tm.begin(ST_QKV);
     if (a_fp32) hipLaunchKernelGGL(iefvad_inproj_chain_f32in_kernel, dim3(rows / IC_BM, 2), dim3(512), IC_LDS_BYTES, stream, ia);
     else hipLaunchKernelGGL(iefvad_inproj_chain_bf16_kernel, dim3(rows / IC_BM, 2), dim3(512), IC_LDS_BYTES, stream, ia);
@@ -885,24 +875,12 @@ static int launch_outproj_ln_chain(iefvad_handle* h, int l, bool whiten, const b
         q.yb = yb[m];
     }
     oa.M = rows; oa.eps = 1e-5f; oa.wave_stride = (unsigned)wstream_wave_stride_bytes();
-    { static const int st = [] { const char* v = getenv("IEFVAD_OL_STAGGER"); return v ? atoi(v) : 0; }(); oa.stagger = st; }
-#ifdef OC_DIAG
-    { static unsigned long long* dg = [] { const char* v = getenv("IEFVAD_OC_DIAG_PTR"); return v ? (unsigned long long*)strtoull(v, nullptr, 0) : nullptr; }(); oa.diag = dg; }
-#endif
     // From two blocks per workgroup on: the persistent kernel, one workgroup per CU, the next block's image fetched during the LayerNorm
     // epilogue (outproj_ln_pchain_bf16.h; same bits); IEFVAD_PERSIST=0 keeps the one-block-per-workgroup kernels (A/B).
-    // IEFVAD_OUTLN=r (opt-in, round 5's experiment): the LayerNorm in the accumulator registers (outproj_ln_rchain_bf16.h: its own weight
-    // streams, any number of blocks per workgroup; bit-identical; epilogue 30 k -> 13 k cycles per block, but its 32 - 64-byte row pieces
-    // cost more in memory waits than the park-through-LDS epilogue costs in barriers: 19.8 vs 16.7 ms per step, TRIED.md)
-    static const bool rchain = [] { const char* v = getenv("IEFVAD_OUTLN"); return v && v[0] == 'r'; }();
-    static const bool persist = [] { const char* v = getenv("IEFVAD_PERSIST"); return !(v && v[0] == '0'); }();
     const int gx = h->num_cus / 2;
     const int nblk = rows / OC_BM;
     hipEvent_t e = tm.begin(ST_OUT);
-    if (rchain && persist) {
-        for (int m = 0; m < 2; ++m) oa.p[m].stream = h->oproj_stream_r[m][l];
-        hipLaunchKernelGGL(iefvad_outproj_ln_rchain_bf16_kernel, dim3(nblk < gx ? nblk : gx, 2), dim3(512), OR_LDS_BYTES, stream, oa);
-    } else if (persist && nblk >= 2 * gx && (y[0] != nullptr) == (y[1] != nullptr) && (yb[0] != nullptr) == (yb[1] != nullptr) && (y[0] || yb[0])) {
+    if (h->persist && nblk >= 2 * gx && (y[0] != nullptr) == (y[1] != nullptr) && (yb[0] != nullptr) == (yb[1] != nullptr) && (y[0] || yb[0])) {
         if (y[0] && yb[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, true>), dim3(gx, 2), dim3(512), OP_LDS_BYTES, stream, oa);
         else if (y[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, false>), dim3(gx, 2), dim3(512), OP_LDS_BYTES, stream, oa);
         else hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<false, true>), dim3(gx, 2), dim3(512), OP_LDS_BYTES, stream, oa);
@@ -919,15 +897,11 @@ static int launch_heads_chain(iefvad_handle* h, HeadsChainArgs& ha, int rows, fl
     for (int m = 0; m < 2; ++m) ha.bias[m] = h->head_b[m];
     ha.stream = h->heads_stream;
     ha.M = rows; ha.factor = factor; ha.eps = h->cfg.epsilon; ha.wave_stride = (unsigned)heads_stream_wave_stride_bytes();
-#ifdef HC_DIAG
-    { static unsigned long long* dg = [] { const char* v = getenv("IEFVAD_HC_DIAG_PTR"); return v ? (unsigned long long*)strtoull(v, nullptr, 0) : nullptr; }(); ha.diag = dg; }
-#endif
     // from two blocks per workgroup on: the persistent kernel (heads_pchain_bf16.h: one workgroup per CU and column third, both
     // images by LDS-DMA under the previous block's epilogue / the first part of phase 2; same bits); IEFVAD_PERSIST=0: A/B
-    static const bool persist = [] { const char* v = getenv("IEFVAD_PERSIST"); return !(v && v[0] == '0'); }();
     const int gx = h->num_cus / HC_THIRDS;
     hipEvent_t e = tm.begin(ST_HEAD);
-    if (persist && rows / HC_BM >= 2 * gx)
+    if (h->persist && rows / HC_BM >= 2 * gx)
         hipLaunchKernelGGL(iefvad_heads_pchain_bf16_kernel, dim3(gx, HC_THIRDS), dim3(512), HP_LDS_BYTES, stream, ha);
     else
         hipLaunchKernelGGL(iefvad_heads_chain_bf16_kernel, dim3(rows / HC_BM, HC_THIRDS), dim3(512), HC_LDS_BYTES, stream, ha);
@@ -945,9 +919,6 @@ static int launch_refine_chain(iefvad_handle* h, const float* z_in, float* z_out
     ca.z_out = z_out;           // may be z_in (in place): a workgroup reads its 64 rows before it writes them
     ca.logits = logits;
     ca.M = rows; ca.K = K; ca.lambda = h->cfg.lambda_ref; ca.wave_stride = (unsigned)chain_wave_stride_bytes(K);
-#ifdef RC_DIAG
-    { static unsigned long long* dg = [] { const char* v = getenv("IEFVAD_RC_DIAG_PTR"); return v ? (unsigned long long*)strtoull(v, nullptr, 0) : nullptr; }(); ca.diag = dg; }
-#endif
     hipEvent_t e = tm.begin(ST_REFINE);
     hipLaunchKernelGGL(iefvad_refine_chain_bf16_kernel, dim3(rows / RC_BM), dim3(64 * RC_NW), RC_LDS_BYTES, stream, ca);
     tm.end(e);
@@ -1146,9 +1117,8 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
                 ab.nrows = rows;
                 // from two items per CU on: the persistent kernel (attention_pbf16.h: one 8-wave workgroup per CU, K / V staged once for
                 // both query halves by LDS-DMA, the next item's K in flight under the current item); bit-identical to the one below
-                static const bool persist_att = [] { const char* v = getenv("IEFVAD_PERSIST"); return !(v && v[0] == '0'); }();      // one switch for the three persistent kernels
                 const int items = 2 * nb * IEF_H;
-                if (persist_att && items >= 2 * h->num_cus) {
+                if (h->persist && items >= 2 * h->num_cus) {
                     if (enc_rows_mode) hipLaunchKernelGGL(iefvad_attention_pbf16_rows_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
                     else hipLaunchKernelGGL(iefvad_attention_pbf16_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
                 } else if (enc_rows_mode) hipLaunchKernelGGL(iefvad_attention_bf16_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);

@@ -6,7 +6,7 @@
 //     iefvad_wstream_pack_kernel at iefvad_set_weights): no LDS ring, no barrier in the main loop;
 //   * the fp32 residual rows a wave will normalise (4 of the first 32, in the LayerNorm kernel's lane layout: 48 registers)
 //     are requested BEFORE the main loop and arrive under it; the second 32 rows' residual is requested while the first 32
-//     are being normalised.  That overlap is the point: the first fused kernel (outproj_ln_bf16.h: 128 x 768 per
+//     are being normalised.  That overlap is the point: the first fused kernel (round 2, TRIED.md: 128 x 768 per
 //     workgroup, LDS-DMA k-tile ring) spent ~25 us per tile multiplying with HBM idle and then ~50 us moving residual and
 //     output rows with the matrix pipe idle (0.18 of the pipe, SQ_WAIT_ANY 0.49);
 //   * epilogue: the accumulators are parked in LDS 32 rows at a time ([32][772] fp32 over the dead image) and each wave
@@ -67,14 +67,7 @@ struct OutLnChainArgs {
     int M;                   // multiple of 64
     float eps;
     unsigned wave_stride;
-    int stagger;             // x 8128 cycles of start delay for every other one of the first 256 workgroups (0 = none)
-    unsigned long long* diag; // OC_DIAG builds only: 8 s_memtime stamps per workgroup (tools/outproj_diag.py)
 };
-#ifdef OC_DIAG
-#define OC_STAMP(i) do { if (args.diag && t == 0) args.diag[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OC_STAMP(i)
-#endif
 
 __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_chain_bf16_kernel(OutLnChainArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -85,12 +78,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_chain_bf16_kernel(Ou
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int m = lane & 15, q = lane >> 4;
     const int m0 = blockIdx.x * OC_BM;
-    OC_STAMP(0);
-    // De-phasing: the launch's first 256 workgroups (one per CU) start together and every block takes the same time, so chip-wide
-    // the load phases (HBM saturated, matrix pipe idle) and the multiply phases (HBM idle) coincide.  Every other one of them
-    // waits about half a block time once; from then on half of the CUs load or store while the other half multiplies.
-    if (args.stagger > 0 && blockIdx.y == 0 && blockIdx.x < 256 && (blockIdx.x & 1))
-        for (int i = 0; i < args.stagger; ++i) __builtin_amdgcn_s_sleep(127);
 
     // ---- requests in the order they are needed: the activation image (must be in LDS before the first MFMA), the first weight
     // pieces, then the residual rows of the first half (needed only after the main loop).  vmcnt completes in order: with the
@@ -149,7 +136,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_chain_bf16_kernel(Ou
     for (int j = 0; j < 4; ++j) rd[j] = m * (IEF_D * 2) + (((4 * j + q) ^ m) & 15) * 16;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     GB2_BARRIER();
-    OC_STAMP(1);
 
     f32x4 acc[4][OC_NB];
 #pragma unroll
@@ -180,10 +166,8 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_chain_bf16_kernel(Ou
 #undef OC_LOAD
 #pragma unroll
     for (int s = 0; s < OC_DEPTH; ++s) asm volatile("" :: "v"(rg[s]));      // the read-ahead (zero pad pieces) must land before the wave ends
-    OC_STAMP(2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     GB2_BARRIER();                        // every wave is done with the image: the parks reuse its space
-    OC_STAMP(3);
 
     // ---- epilogue: two halves of 32 rows; wave w normalises rows 4 w .. 4 w + 3 of each half
     const float* affl = (const float*)(lds + OC_AFF_OFF) + 4 * lane;      // + 768 i (bias, g1, b1, g2, b2) + 256 j
@@ -203,7 +187,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_chain_bf16_kernel(Ou
         if (half == 0) { OC_FETCH_RES(1) }       // in flight while the first 32 rows are normalised (their accumulators are parked)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         GB2_BARRIER();                    // all parks of this half are complete
-        OC_STAMP(4 + 2 * half);
         // the wave's four rows together (ln_rows: the rows' reduction chains interleaved; per row exactly ln_row's operations)
         f32x4 v[4][3];
 #pragma unroll
@@ -229,7 +212,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_chain_bf16_kernel(Ou
                 for (int j = 0; j < 3; ++j) *(bf16x4_t*)(yb + 256 * j) = to_bf16x4(v[u][j]);
             }
         }
-        OC_STAMP(5 + 2 * half);
         if (half == 0) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             GB2_BARRIER();                // every reader is done with this half's parks: they may be overwritten

@@ -42,10 +42,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
     const int nblk = args.M / OC_BM;
     const bool two = P.g2 != nullptr;
 
-    // De-phasing experiment (IEFVAD_OL_STAGGER = n: every other workgroup starts n x 8128 cycles late): all workgroups start together and
-    // a block takes the same time everywhere, so chip-wide the epilogues (all of a block's HBM traffic) coincide with each other.
-    if (args.stagger > 0 && (blockIdx.x & 1))
-        for (int i = 0; i < args.stagger; ++i) __builtin_amdgcn_s_sleep(127);
     // ---- once per workgroup: bias and the LayerNorms' affine terms -> LDS (5 x 768 floats, as in the round-3 kernel)
     {
         f32x4 aff[2];
@@ -86,14 +82,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
     const float* affl = (const float*)(lds + OP_AFF_OFF) + 4 * lane;      // + 768 i (bias, g1, b1, g2, b2) + 256 j
     float* park = (float*)(lds + OP_PARK_OFF);
 
-#ifdef OC_DIAG
-    unsigned long long dsum[6] = {0, 0, 0, 0, 0, 0}, dt0 = 0, dt1;      // image wait | main loop | drain + DMA issue | parks + barriers | LayerNorm + stores | blocks
-#define OP_T(i) do { dt1 = __builtin_amdgcn_s_memtime(); dsum[i] += dt1 - dt0; dt0 = dt1; } while (0)
-#define OP_T0() do { dt0 = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define OP_T(i)
-#define OP_T0()
-#endif
     // The residual rows of a block's FIRST quarter are requested in the last quarter of the block before it (here for the first block):
     // requested at the top of their own block they sat in front of the weight ring's refills, and a wave's vector-memory operations
     // retire in order -- the ring (six pieces = 400 cycles ahead) stalled for one HBM latency at the start of every main loop.
@@ -107,7 +95,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
     __builtin_amdgcn_sched_barrier(0);
     for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const int m0 = blk * OC_BM;
-        OP_T0();
         // requests of this block: the first weight pieces
         f32x4 rg[OC_DEPTH];
 #pragma unroll
@@ -116,7 +103,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
         // this wave's image pieces (and the first quarter's residual rows) were requested before those 6 loads
         asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
         GB2_BARRIER();                        // every wave's pieces have landed (and the affine vectors of the first block)
-        OP_T(0);
 
         f32x4 acc[4][OC_NB];
 #pragma unroll
@@ -146,19 +132,15 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
         }
 #pragma unroll
         for (int s = 0; s < OC_DEPTH; ++s) asm volatile("" :: "v"(rg[s]));      // the read-ahead (zero pad pieces) lands before its registers are reused
-        OP_T(1);
         // No barrier here: the first quarter parks into a region of its own (its readers left it behind the previous block's last
         // barrier), and the barrier that follows those parks is also the one that declares the image dead -- it is overwritten (by the
         // next image's DMA) two quarters later.  The waves leave the main loop up to ~4 k cycles apart (wave 0 wins the weight stream's
         // arbitration); the early ones now park and request their residual rows while the others finish.
         const int nxt = blk + (int)gridDim.x;
-#ifndef OP_PROBE_NORES
         // Inside the epilogue the residual rows run TWO quarters ahead of their use (a CU's share of the HBM stream is ~10 bytes per
         // cycle while the chip is busy: one quarter ahead, every quarter waited ~1.9 k cycles for its rows); nothing of it is issued
         // in front of the weight ring.
         OP_FETCH_RES(m0, 1)
-#endif
-        OP_T(2);
 
         // ---- epilogue: four quarters of 16 rows; wave w normalises rows 2 w, 2 w + 1 of each quarter
 #pragma unroll
@@ -170,11 +152,9 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
             for (int u = 0; u < 2; ++u)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) rcur[u][j] = res[qt & 1][u][j];
-#ifndef OP_PROBE_NORES      // timing probe (wrong results): the residual rows of quarters 1 - 3 are not fetched
             // (two quarters ahead; with quarters 0 AND 1 requested at the top of the block it was measured SLOWER, 16.6 -> 17.3 ms per step:
             // the weight ring's pieces retire in order behind every HBM request in front of them; TRIED.md)
             if (qt < 2) { OP_FETCH_RES(m0, qt + 2) }     // in flight while this quarter and the next are normalised
-#endif
             // ... and the next block's first quarter (behind a workgroup's last block: its own rows again, requested and not used)
             if (qt == 3) { OP_FETCH_RES((nxt < nblk ? nxt : blk) * OC_BM, 0) }
             // The next block's image is requested HERE, behind the last residual request: a wave's vector-memory operations retire
@@ -184,11 +164,8 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
             // (behind the last block of a workgroup `nxt` lies outside the descriptor's range: the pieces are dropped by the range check)
             if (qt == 2) { OP_IMAGE_DMA(nxt); }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#if !defined(OP_PROBE_NOBAR) || OP_PROBE_NOBAR < 2      // timing probes only (wrong results): -DOP_PROBE_NOBAR=1 drops the four end barriers, =2 the park barriers too
             GB2_BARRIER();                    // all parks of this quarter are complete
-#endif
-            OP_T(3);
-            f32x4 v[2][3];
+                f32x4 v[2][3];
 #pragma unroll
             for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -198,12 +175,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
                 }
             ln_rows<2>(v, affl + IEF_D - 4 * lane, affl + 2 * IEF_D - 4 * lane, lane, args.eps);       // ln_rows adds 4 lane itself
             if (two) ln_rows<2>(v, affl + 3 * IEF_D - 4 * lane, affl + 4 * IEF_D - 4 * lane, lane, args.eps);
-#ifdef OP_PROBE_NOSTORE     // timing probe (wrong results): the normalised rows are not stored
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) asm volatile("" :: "v"(v[u][j]));
-#else
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const size_t row = (size_t)(m0 + OP_PARK_ROWS * qt + 2 * wave + u);
@@ -218,23 +189,11 @@ __global__ __launch_bounds__(512, 2) void iefvad_outproj_ln_pchain_bf16_kernel(O
                     for (int j = 0; j < 3; ++j) *(bf16x4_t*)(yb + 256 * j) = to_bf16x4(v[u][j]);
                 }
             }
-#endif
-            OP_T(4);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifndef OP_PROBE_NOBAR
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             GB2_BARRIER();                    // every reader is done with this quarter's parks: they may be overwritten
-#endif
-            OP_T(3);
-        }
-#ifdef OC_DIAG
-        dsum[5] += 1;
-#endif
+            }
 #undef OP_FETCH_RES
     }
-#ifdef OC_DIAG
-    if (args.diag && t == 0)
-        for (int i = 0; i < 6; ++i) args.diag[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + i] = dsum[i];
-#endif
 #undef OP_LOAD
 #undef OP_IMAGE_DMA
 }

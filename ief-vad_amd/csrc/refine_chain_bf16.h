@@ -15,7 +15,7 @@
 //     read it -- no LDS ring, no barrier, hipcc's own counted s_waitcnt vmcnt, and the stream keeps running across
 //     projection boundaries.  (Round 3's first version filled a private LDS ring by LDS-DMA: an LDS-DMA instruction costs
 //     its wave 60-180 issue cycles per KB beside 64 cycles of MFMA work for that KB, and the kernel sat at 0.50 MFMA-busy and
-//     65 GB/s of weight stream per CU where the stream alone runs 110-120: tools/ingest_probe.hip, tools/refine_chain_bf16_v1_ldsdma_ring.h.)
+//     65 GB/s of weight stream per CU where the stream alone runs 110-120: tools/ingest_probe.hip; TRIED.md, round 3.)
 //   * the MFMA is issued with the operands swapped (A = weight fragment, B = activation fragment), so a lane holds four
 //     CONSECUTIVE output columns of one row: h / bf16(z) go back into the image as one 8-byte LDS store per tile, and the
 //     products and their k order are those of the projection kernels (gemm_bf16.h): z and the logits are bit-identical
@@ -106,13 +106,7 @@ struct ChainArgs {
     int K;                   // >= 1
     float lambda;
     unsigned wave_stride;    // bytes between the waves' streams
-    unsigned long long* diag; // RC_DIAG builds only: 16 s_memtime stamps per workgroup over projections 2 and 3 (tools/rowblock_diag.py chain)
 };
-#ifdef RC_DIAG
-#define RC_STAMP(i) do { if (args.diag && t == 0 && (g == 2 || g == 3)) args.diag[(size_t)blockIdx.x * 16 + (g - 2) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define RC_STAMP(i)
-#endif
 
 __global__ __launch_bounds__(512, 2) void iefvad_refine_chain_bf16_kernel(ChainArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -182,7 +176,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_refine_chain_bf16_kernel(ChainA
             for (int a = 0; a < 4; ++a)
 #pragma unroll
                 for (int b = 0; b < RC_NBP; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-            RC_STAMP(3 * pass);
 #if RC_KUNROLL == RC_KT
 #pragma unroll
 #else
@@ -212,7 +205,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_refine_chain_bf16_kernel(ChainA
             }
 
             // ---- the pass's epilogue; its bias pieces are the next ones of the ring
-            RC_STAMP(3 * pass + 1);
             asm volatile("" : "+v"(mo), "+v"(qo));
             f32x4 bias[RC_NBP];
 #pragma unroll
@@ -223,7 +215,6 @@ __global__ __launch_bounds__(512, 2) void iefvad_refine_chain_bf16_kernel(ChainA
                 ++p;
             }
             if (pass == RC_NPASS - 1) GB2_BARRIER();      // every wave is done reading the image: it may be rewritten
-            RC_STAMP(3 * pass + 2);
             if (first) {
 #pragma unroll
                 for (int b = 0; b < RC_NBP; ++b)
@@ -258,10 +249,8 @@ __global__ __launch_bounds__(512, 2) void iefvad_refine_chain_bf16_kernel(ChainA
                     }
             }
             if (pass == RC_NPASS - 1) {
-                RC_STAMP(6);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 GB2_BARRIER();                            // the image holds the next operand
-                RC_STAMP(7);
             }
         }
     }

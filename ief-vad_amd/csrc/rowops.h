@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void iefvad_layernorm_kernel(LnArgs a) {
 // (/root/reference/model/imf_vad.py:130-144):
 //   w_m = factor * exp(-logvar_m) ; den = w_i + w_e + eps ; n_m = w_m / den ; z = n_i*mu_i + n_e*mu_e
 // The literal formula is kept (including its inf/inf = NaN behaviour for logvar < -88.7).
-// one element of the fusion; the literal operation order of the reference (shared with heads_fused_bf16.h)
+// one element of the fusion; the literal operation order of the reference (shared with the heads row-block kernels)
 __device__ __forceinline__ void fuse_elem(float mi, float li, float me, float le, float factor, float eps,
                                           float& ni, float& ne, float& z) {
     const float wi = __fmul_rn(factor, expf(-li));

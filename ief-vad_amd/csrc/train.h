@@ -42,12 +42,9 @@ static int splitk_splits(int rows, int n_out) {
 }
 
 // Train-mode attention runs as two fused launches per layer in bf16x6 (attention_split.h TRAIN / BWD) and as the three-launch path in
-// the f32 arithmetic (or with IEFVAD_TRAIN_ATTN=unfused, the A/B test's switch, read when a forward starts; the backward follows its
-// forward's record).  Both keep P and dropout(P) as ONE sign-carrying tensor: the layout is the same.
-static bool train_attn_fused(const iefvad_handle* h) {
-    const char* v = getenv("IEFVAD_TRAIN_ATTN");
-    return h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && !(v && v[0] == 'u');
-}
+// the f32 arithmetic (or with IEFVAD_TRAIN_ATTN=unfused at iefvad_create, the A/B test's switch; the backward follows its forward's
+// record).  Both keep P and dropout(P) as ONE sign-carrying tensor: the layout is the same.
+static bool train_attn_fused(const iefvad_handle* h) { return h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && !h->train_attn_unfused; }
 
 static TrainLayout train_layout(int L, int K, int B) {
     TrainLayout t;
@@ -225,33 +222,24 @@ static int launch_dw(const float* dY, int ldy, int n_out, const float* X, float*
     if ((size_t)splits * per > part_floats) return fail("train_backward: split-K scratch too small");
     const int ms = rows / splits;
     if (split_tn && ms % TN_BK == 0 && n_out % 128 == 0 && (ldy & 3) == 0) {
-        // bf16x6 handles: the same partial products on the bf16 matrix pipe (gemm_split_tn.h), the same fixed-order reduction behind them.
-        // Default: the 128 x 256 block (64 x 128 per wave, two workgroups per CU) over as many RAGGED row slices as fill the chip's
-        // workgroup slots once (at most the slices the scratch was sized for); IEFVAD_TN=128 keeps the 128 x 128 block over the
-        // power-of-two slices (A/B).
-        const char* tn_env = getenv("IEFVAD_TN");
-        const bool wide = !(tn_env && tn_env[0] == '1');
+        // bf16x6 handles: the same partial products on the bf16 matrix pipe (gemm_split_tn.h), the same fixed-order reduction behind them:
+        // the 128 x 256 block (64 x 128 per wave, two workgroups per CU) over as many RAGGED row slices as fill the chip's workgroup slots
+        // once (at most the slices the scratch was sized for)
         TnArgs g;
         memset(&g, 0, sizeof(g));
         g.A = dY; g.B = X; g.C = part; g.M = n_out; g.N = IEF_D; g.lda = ldy; g.ldb = IEF_D; g.ldc = IEF_D;
         g.nk_total = rows / TN_BK;
-        int slices = splits;
-        if (wide) {
-            const int tiles = (n_out / 128) * (IEF_D / 256);
-            slices = (2 * g_num_cus) / tiles;
-            if (slices > g.nk_total / 8) slices = g.nk_total / 8;
-            if (slices > splits) slices = splits;          // the scratch (part, cpart) holds `splits` partial results
-            if (slices < 1) slices = 1;
-        }
+        const int tiles = (n_out / 128) * (IEF_D / 256);
+        int slices = (2 * g_num_cus) / tiles;
+        if (slices > g.nk_total / 8) slices = g.nk_total / 8;
+        if (slices > splits) slices = splits;          // the scratch (part, cpart) holds `splits` partial results
+        if (slices < 1) slices = 1;
         g.slices = slices;
-        g.tiles_n = wide ? IEF_D / 256 : IEF_D / 128;
+        g.tiles_n = IEF_D / 256;
         // the bias gradient of the same Linear (column sums of dY) rides along in the first column block's workgroups
         const bool with_db = (db || db2) && cpart && db_done && (size_t)slices * n_out <= cpart_floats;
         g.colsum = with_db ? cpart : nullptr;
-        if (wide)
-            hipLaunchKernelGGL(iefvad_gemm_split_tn256_kernel, dim3((unsigned)((n_out / 128) * g.tiles_n * slices)), dim3(256), TN_LDS_BYTES_OF(4), stream, g);
-        else
-            hipLaunchKernelGGL(iefvad_gemm_split_tn_kernel, dim3((unsigned)((n_out / 128) * g.tiles_n * slices)), dim3(256), TN_LDS_BYTES, stream, g);
+        hipLaunchKernelGGL(iefvad_gemm_split_tn256_kernel, dim3((unsigned)((n_out / 128) * g.tiles_n * slices)), dim3(256), TN_LDS_BYTES_OF(4), stream, g);
         HIP_TRY(hipGetLastError());
         // one launch reduces the weight partials (both halves of a stacked product) and the bias partials that rode along
         ReduceBatch rb;
@@ -453,8 +441,8 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_QKV)) return rc;
 
         // bf16x6: S = q k^T -> softmax -> dropout -> Pd v in ONE launch for both modalities (attention_split.h, TRAIN: the eval kernel
-        // with the sign-carrying P stored for the backward); IEFVAD_TRAIN_ATTN=unfused keeps the three launches below (A/B: read per
-        // call, the test flips it between two forwards).  The fp32 arithmetic keeps them: its products stay on the fp32 MFMA instruction.
+        // with the sign-carrying P stored for the backward); IEFVAD_TRAIN_ATTN=unfused keeps the three launches below (A/B: the test
+        // runs one model of each).  The fp32 arithmetic keeps them: its products stay on the fp32 MFMA instruction.
         if (fused) {
             AttnArgs aa;
             AttnTrainArgs tx;
@@ -604,8 +592,7 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
     float* da = ws + t.da;
     if (int rc = ensure_train_planes(h, stream)) return rc;
     const bool tp = h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && h->tplanes_valid;      // dX on the split kernel where the grid fills it
-    static const bool tn_off = [] { const char* v = getenv("IEFVAD_TRAIN_TN"); return v && v[0] == '0'; }();
-    const bool tn = h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && !tn_off;              // dW on the split TN kernel (gemm_split_tn.h)
+    const bool tn = h->cfg.compute == IEFVAD_COMPUTE_BF16X6;              // dW on the split TN kernel (gemm_split_tn.h)
 
     // classifier (imf_vad.py:150)
     {

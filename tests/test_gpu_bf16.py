@@ -456,8 +456,8 @@ def test_row_block_encoder_and_heads_against_fp64_of_the_same_rounded_operands()
 
 def test_persistent_kernels_equal_the_one_block_kernels(tmp_path):
     """The three persistent kernels of the bf16 mode (out_proj + LayerNorm, heads + fusion, attention: one workgroup per CU walking
-    blocks / items, the next image by LDS-DMA) against the kernels they replace from two blocks per CU on -- IEFVAD_PERSIST=0, a
-    process-wide switch, hence two child processes.  B = 96 chunks (384 row blocks, 1,536 attention items: every persistent kernel
+    blocks / items, the next image by LDS-DMA) against the kernels they replace from two blocks per CU on -- IEFVAD_PERSIST=0, read
+    when the library handle is created; one child process per value.  B = 96 chunks (384 row blocks, 1,536 attention items: every persistent kernel
     runs), dense and as a list of videos (the row-compressed attention variant): every output bit for bit, the row means of the
     fusion weights to fp32 rounding (their summation order belongs to the kernel)."""
     import os
