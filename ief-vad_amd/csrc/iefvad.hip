@@ -892,6 +892,25 @@ static int launch_outproj_ln_chain(iefvad_handle* h, int l, bool whiten, const b
     return 0;
 }
 
+// bf16-mode attention over `nb` chunks per modality; `chunks` != nullptr: the row-compressed chunks of a whole-video pass (`_rows` kernels)
+static void launch_attention_bf16(iefvad_handle* h, const bf16_t* const qkv[2], bf16_t* const out[2], int nb, const RaggedChunk* chunks,
+                                  bool head_major, int rows, hipStream_t stream) {
+    AttnBArgs ab;
+    for (int m = 0; m < 2; ++m) { ab.qkv[m] = qkv[m]; ab.out[m] = out[m]; }
+    ab.nchunks = nb;
+    ab.chunks = chunks;
+    ab.head_major = head_major ? 1 : 0;
+    ab.nrows = rows;
+    // from two items per CU on: the persistent kernel (attention_pbf16.h: one 8-wave workgroup per CU, K / V staged once for
+    // both query halves by LDS-DMA, the next item's K in flight under the current item); bit-identical to the one below
+    const int items = 2 * nb * IEF_H;
+    if (h->persist && items >= 2 * h->num_cus) {
+        if (chunks) hipLaunchKernelGGL(iefvad_attention_pbf16_rows_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
+        else hipLaunchKernelGGL(iefvad_attention_pbf16_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
+    } else if (chunks) hipLaunchKernelGGL(iefvad_attention_bf16_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);
+    else hipLaunchKernelGGL(iefvad_attention_bf16_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);
+}
+
 // `ha` arrives with its tensors filled in; the stream, scalars and the kernel choice are set here
 static int launch_heads_chain(iefvad_handle* h, HeadsChainArgs& ha, int rows, float factor, hipStream_t stream, Timer& tm) {
     for (int m = 0; m < 2; ++m) ha.bias[m] = h->head_b[m];
@@ -1109,20 +1128,7 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
 
             hipEvent_t e = tm.begin(ST_ATT);
             if (bf) {
-                AttnBArgs ab;
-                for (int m = 0; m < 2; ++m) { ab.qkv[m] = qkvb[m]; ab.out[m] = attb[m]; }
-                ab.nchunks = nb;
-                ab.chunks = enc_rows_mode ? rg->d_chunks : nullptr;
-                ab.head_major = ip_chain ? 1 : 0;
-                ab.nrows = rows;
-                // from two items per CU on: the persistent kernel (attention_pbf16.h: one 8-wave workgroup per CU, K / V staged once for
-                // both query halves by LDS-DMA, the next item's K in flight under the current item); bit-identical to the one below
-                const int items = 2 * nb * IEF_H;
-                if (h->persist && items >= 2 * h->num_cus) {
-                    if (enc_rows_mode) hipLaunchKernelGGL(iefvad_attention_pbf16_rows_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
-                    else hipLaunchKernelGGL(iefvad_attention_pbf16_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
-                } else if (enc_rows_mode) hipLaunchKernelGGL(iefvad_attention_bf16_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);
-                else hipLaunchKernelGGL(iefvad_attention_bf16_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);
+                launch_attention_bf16(h, qkvb, attb, nb, enc_rows_mode ? rg->d_chunks : nullptr, ip_chain, rows, stream);
             } else {
                 AttnArgs aa;
                 memset(&aa, 0, sizeof(aa));
@@ -2073,6 +2079,7 @@ extern "C" int iefvad_rowblock_unit(iefvad_handle* h, int32_t stage, int32_t lay
     if (h->D != IEF_D) return fail("iefvad_rowblock_unit: the row-block kernels are built for D=768 (this handle has D=%d)", h->D);
     if (h->cfg.compute != IEFVAD_COMPUTE_BF16) return fail("iefvad_rowblock_unit: the row-block kernels belong to compute = BF16 (got %d)", h->cfg.compute);
     if (rows <= 0 || rows % 64) return fail("iefvad_rowblock_unit: rows = %d must be a positive multiple of 64", rows);
+    if (stage == IEFVAD_UNIT_ATTENTION && rows % IEF_T) return fail("iefvad_rowblock_unit: ATTENTION runs whole chunks, rows = %d must be a multiple of %d", rows, IEF_T);
     hipStream_t stream = (hipStream_t)stream_;
     const int L = h->cfg.num_layers, K = h->cfg.num_steps;
     Timer tm;
@@ -2117,6 +2124,15 @@ extern "C" int iefvad_rowblock_unit(iefvad_handle* h, int32_t stage, int32_t lay
         if (K < 1 || !h->chain_stream) return fail("iefvad_rowblock_unit: the refinement chain needs K >= 1 (K = %d)", K);
         if (!io->x[0] || !io->logits || !aligned(io->x[0]) || !aligned(io->z)) return fail("iefvad_rowblock_unit: REFINE needs x[0] (z_0) and logits");
         return launch_refine_chain(h, (const float*)io->x[0], io->z, io->logits, rows, stream, tm);
+    }
+    case IEFVAD_UNIT_ATTENTION: {
+        const bf16_t* qkv[2] = {(const bf16_t*)io->x[0], (const bf16_t*)io->x[1]};
+        bf16_t* out[2] = {(bf16_t*)io->yb[0], (bf16_t*)io->yb[1]};
+        for (int m = 0; m < 2; ++m)
+            if (!qkv[m] || !out[m] || !aligned(qkv[m]) || !aligned(out[m])) return fail("iefvad_rowblock_unit: ATTENTION needs x[m] and yb[m], 16-byte aligned");
+        launch_attention_bf16(h, qkv, out, rows / IEF_T, nullptr, true, rows, stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
     }
     default:
         return fail("iefvad_rowblock_unit: unknown stage %d", stage);

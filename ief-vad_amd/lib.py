@@ -103,7 +103,7 @@ class UnitIO(C.Structure):
                 ("logvar", C.c_void_p * 2), ("w", C.c_void_p * 2), ("z", C.c_void_p), ("logits", C.c_void_p)]
 
 
-UNIT_INPROJ, UNIT_OUTPROJ_LN, UNIT_HEADS, UNIT_REFINE = 0, 1, 2, 3
+UNIT_INPROJ, UNIT_OUTPROJ_LN, UNIT_HEADS, UNIT_REFINE, UNIT_ATTENTION = 0, 1, 2, 3, 4
 
 
 class ResblockWeights(C.Structure):

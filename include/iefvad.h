@@ -429,11 +429,16 @@ int iefvad_resblock_forward(const float* x, const iefvad_resblock_weights* w, co
  *   IEFVAD_UNIT_HEADS       x[m] = whitened rows bf16 [rows,768] -> mu[m], logvar[m], w[m] (each nullable) and the fused z
  *                           (imf_vad.py:125-144)
  *   IEFVAD_UNIT_REFINE      x[0] = z_0 fp32 [rows,768] -> z = z_K (nullable), logits [rows] (imf_vad.py:146-150)
+ *   IEFVAD_UNIT_ATTENTION   x[m] = bf16 q | k | v in the head-major layout IEFVAD_UNIT_INPROJ writes (q in log2 units: the kernels
+ *                           compute softmax2(q k^T) v per 256-row chunk and head, imf_vad.py:115,121) -> yb[m] = bf16 [rows,768];
+ *                           rows is a multiple of 256; the one-block kernel, or the persistent one from two (chunk, head,
+ *                           modality) items per compute unit on, as in the forward.  `layer` is ignored (no weights are read).
  * All pointers 16-byte aligned.  Enqueued on `stream`. */
 #define IEFVAD_UNIT_INPROJ 0
 #define IEFVAD_UNIT_OUTPROJ_LN 1
 #define IEFVAD_UNIT_HEADS 2
 #define IEFVAD_UNIT_REFINE 3
+#define IEFVAD_UNIT_ATTENTION 4   /* added without a change of layout or of the other stages: IEFVAD_ABI_VERSION stays */
 typedef struct iefvad_unit_io {
     const void* x[2];
     const float* resid[2];

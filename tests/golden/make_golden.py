@@ -38,11 +38,13 @@ def ref_args(L=2, H=8, K=10, lam=0.5, noise="StudentT", nu=8):
                               noise_model=noise, nu=nu)
 
 
-def build_reference(seed, L=2, K=10, lam=0.5, noise="StudentT", nu=8):
+def build_reference(seed, L=2, K=10, lam=0.5, noise="StudentT", nu=8, factors=None):
     sys.path.insert(0, REF)
     from model.imf_vad import MMFMIL  # the reference model
     model = MMFMIL(14, 768, 256, 768, 8, L, 8, 10, 10, device="cpu", args=ref_args(L, 8, K, lam, noise, nu))
     sd = synth.make_state_dict(seed, 768, L, K)
+    if factors is not None:
+        sd = synth.sharpen_qk(sd, factors)
     missing = model.load_state_dict(sd, strict=True)
     assert not missing.missing_keys and not missing.unexpected_keys
     model.eval()
@@ -101,6 +103,94 @@ def gen_forward_cases(cases=None, chunk_subset=None):
         path = os.path.join(HERE, f"fwd_{name}.npz")
         np.savez_compressed(path, **store)
         print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
+# The peaked-attention regime (synth.sharpen_qk): with make_state_dict's own weights softmax is an almost flat average over the 256
+# keys, so a forward could run with broken attention and stay inside the bf16 gates.  "sharp" = q / k rows x (8, 4): a dominant key per
+# query; "over" = x (16, 4): layer-0 scores beyond what exp can represent without the max subtraction.
+# (name, weight seed, input seed, B, L, K, lambda, noise, nu, input dtype, input edit, factors, chunk subset)
+SHARP_CASES = [
+    ("sharp_k3_student8", 11, 12, 3, 2, 3, 0.5, "StudentT", 8, "f32", "tail", (8, 4), None),   # pad keys in a peaked softmax
+    ("sharp_b48_k3", 17, 29, 48, 2, 3, 0.5, "StudentT", 8, "f32", "tail", (8, 4), [17, 47]),   # two chunks' 768-d outputs: file size
+    ("over_k3_student8", 11, 12, 2, 2, 3, 0.5, "StudentT", 8, "f32", None, (16, 4), None),
+]
+
+
+def attention_statistics(model, run, L, D):
+    """Per (modality, layer) of a reference model: max |q k^T / sqrt(d)| and the mean over queries of max_k P, in fp64 from the
+    model's own in_proj parameters on the inputs its attention layers receive during `run()` (forward pre-hooks)."""
+    seen, hooks = {}, []
+    for m, layers in enumerate((model.temporal.image_attn_layers, model.temporal.event_attn_layers)):
+        for l, mod in enumerate(layers):
+            hooks.append(mod.register_forward_pre_hook(lambda _m, a, key=(m, l): seen.__setitem__(key, a[0].detach().double())))
+    run()
+    for h in hooks:
+        h.remove()
+    smax, pmax = np.zeros((2, L)), np.zeros((2, L))
+    for m, layers in enumerate((model.temporal.image_attn_layers, model.temporal.event_attn_layers)):
+        for l, mod in enumerate(layers):
+            x = seen[(m, l)]
+            qk = x @ mod.in_proj_weight.detach().double()[: 2 * D].t() + mod.in_proj_bias.detach().double()[: 2 * D]
+            q, k = (t.reshape(x.shape[0], 256, 8, D // 8).transpose(1, 2) for t in qk.split(D, dim=-1))
+            sc = q @ k.transpose(-1, -2) / np.sqrt(D // 8)
+            smax[m, l] = float(sc.abs().max())
+            pmax[m, l] = float(torch.softmax(sc, dim=-1).amax(-1).mean())
+    return smax, pmax
+
+
+def sharp_fields(model, img, ev, out, factors, L, D=768):
+    """The three fields every peaked-regime fixture carries besides the outputs: the factors, the reference's own fp32-vs-fp64
+    distance on the three gated quantities (the model once more in .double()), and the attention statistics per (modality, layer).
+    Returns (fields, fp64 outputs)."""
+    import copy
+    m64 = copy.deepcopy(model).double()
+    with torch.no_grad():
+        o64 = m64.temporal(torch.from_numpy(img).double(), torch.from_numpy(ev).double())   # MMFMIL.forward casts to float
+    sig = lambda t: torch.sigmoid(t.double())
+    fields = {"factors": np.array(factors, np.float64),
+              "floor_big": np.array(max(float((out[k].double() - o64[k]).abs().max()) for k in BIG_KEYS)),
+              "floor_logit": np.array(float((out["logits"].double() - o64["logits"]).abs().max())),
+              "floor_sigmoid": np.array(float((sig(out["logits"]) - sig(o64["logits"])).abs().max()))}
+    run = lambda: m64.temporal(torch.from_numpy(img).double(), torch.from_numpy(ev).double())
+    with torch.no_grad():
+        fields["att_max_score"], fields["att_mean_max_p"] = attention_statistics(m64, run, L, D)
+    return fields, o64
+
+
+def gen_sharp_cases(only=None):
+    """Forward fixtures of the peaked regime, written as gen_forward_cases writes them plus `sharp_fields`, plus -- for the cases
+    the bf16 mode is gated on -- the distance between the fp64 restatement of that mode's rounding points
+    (tests/test_gpu_bf16.py::bf16_mode_emulation, CPU only) and the fixture: the mode's own rounding noise, which has to fit
+    under the bf16 gates without a kernel being asked."""
+    from tests.test_gpu_bf16 import bf16_mode_emulation
+    for name, wseed, iseed, B, L, K, lam, noise, nu, dt, edit, factors, chunk_subset in SHARP_CASES:
+        if only and name not in only:
+            continue
+        model = build_reference(wseed, L, K, lam, noise, nu, factors)
+        img, ev = case_inputs(iseed, B, dt, edit)
+        with torch.no_grad():
+            out = model(torch.from_numpy(img), torch.from_numpy(ev), None, None, None)
+        fields, _ = sharp_fields(model, img, ev, out, factors, L)
+        sd = synth.sharpen_qk(synth.make_state_dict(wseed, 768, L, K), factors)
+        emu = bf16_mode_emulation(sd, torch.from_numpy(img), torch.from_numpy(ev), L, K, lam, nu)
+        sig = lambda t: torch.sigmoid(t.double())
+        fields["bf16_floor_big"] = np.array(max(float((emu[k] - out[k].double()).abs().max()) for k in BIG_KEYS))
+        fields["bf16_floor_logit"] = np.array(float((emu["logits"] - out["logits"].double()).abs().max()))
+        fields["bf16_floor_sigmoid"] = np.array(float((sig(emu["logits"]) - sig(out["logits"])).abs().max()))
+        store = {"logits": out["logits"].numpy().reshape(B, 256),
+                 "w_i_mean": out["w_i"].mean(dim=-1).numpy(), "w_e_mean": out["w_e"].mean(dim=-1).numpy(),
+                 "rows": np.array(ROW_SUBSET),
+                 "meta": np.array([wseed, iseed, B, L, K, nu]), "lam": np.array(lam),
+                 "noise": np.array(noise), "in_dtype": np.array(dt), "edit": np.array(str(edit)), **fields}
+        for k in BIG_KEYS:
+            store[k] = out[k].numpy()[:, ROW_SUBSET, :]
+            if chunk_subset is not None:
+                store[k] = store[k][chunk_subset]
+        if chunk_subset is not None:
+            store["chunks"] = np.array(chunk_subset)
+        path = os.path.join(HERE, f"fwd_{name}.npz")
+        np.savez_compressed(path, **store)
+        print("wrote", path, os.path.getsize(path) // 1024, "KiB", {k: np.round(v, 9).tolist() for k, v in fields.items()})
 
 
 def gen_harness_case():
@@ -490,23 +580,25 @@ def gen_loss_grad_case():
     print("wrote", path, os.path.getsize(path), "bytes;", float(store["seed1_total"]), np.abs(store["seed1_image_mu_zero_row"]).max())
 
 
-# (name, weight seed, batch seed, B, L, K, noise, nu, lambda_reg, lambda_kl, dropout p with an injected mask (0 = no dropout))
+# (name, weight seed, batch seed, B, L, K, noise, nu, lambda_reg, lambda_kl, dropout p with an injected mask (0 = no dropout),
+#  synth.sharpen_qk factors or None)
 GRAD_CASES = [
-    ("k2_student8", 31, 41, 3, 2, 2, "StudentT", 8, 1.0, 1.0, 0.0),
-    ("k10_student8_mask", 32, 42, 2, 2, 10, "StudentT", 8, 1.0, 1.0, 0.1),
-    ("k0_gauss_l1", 33, 43, 2, 1, 0, "Gaussian", 8, 0.01, 0.01, 0.0),
+    ("k2_student8", 31, 41, 3, 2, 2, "StudentT", 8, 1.0, 1.0, 0.0, None),
+    ("k10_student8_mask", 32, 42, 2, 2, 10, "StudentT", 8, 1.0, 1.0, 0.1, None),
+    ("k0_gauss_l1", 33, 43, 2, 1, 0, "Gaussian", 8, 0.01, 0.01, 0.0, None),
+    ("sharp_k2_student8", 31, 41, 3, 2, 2, "StudentT", 8, 1.0, 1.0, 0.0, (8, 4)),     # the softmax backward where P is not ~ 1/256
 ]
 GRAD_SAMPLES = 192
 
 
-def _reference_train_model(wseed, L, K, noise, nu, dtype, p, mask):
+def _reference_train_model(wseed, L, K, noise, nu, dtype, p, mask, factors=None):
     """The reference MMFMIL in train() mode with seeded weights.  Attention dropout: every nn.MultiheadAttention's `.dropout` is
     set to `p`; for p > 0 torch.nn.functional.dropout is replaced, for the duration of the caller's forward, by a function that
     applies the NEXT injected keep mask exactly as F.dropout applies its own (x * mask / (1 - p)) -- so the reference and the
     build see the same mask.  Returns (model, context manager)."""
     import contextlib
     import torch.nn.functional as F
-    model = build_reference(wseed, L, K, 0.5, noise, nu)
+    model = build_reference(wseed, L, K, 0.5, noise, nu, factors)
     model = model.to(dtype)
     model.train()
     for mod in list(model.temporal.image_attn_layers) + list(model.temporal.event_attn_layers):
@@ -551,15 +643,17 @@ def _trainer_loss(outputs, labels, lengths, noise, nu, lam_reg, lam_kl, CLAS2):
     return cls + lam_reg * loss_reg + lam_kl * kl
 
 
-def gen_model_grad_cases():
+def gen_model_grad_cases(only=None):
     """f-4, the model's backward pass: the REFERENCE model in train() mode (fp64 copy), the reference's own CLAS2 and the trainers'
     torch calls, `loss.backward()` -- every parameter gradient of SURVEY.md Appendix B.  Stored per parameter: its L1 and L2
     norms and GRAD_SAMPLES seeded entries; plus the total loss and the logits (forward check of the train-mode path)."""
     sys.path.insert(0, REF)
     from train.loss import CLAS2
-    for name, wseed, bseed, B, L, K, noise, nu, lam_reg, lam_kl, p in GRAD_CASES:
+    for name, wseed, bseed, B, L, K, noise, nu, lam_reg, lam_kl, p, factors in GRAD_CASES:
+        if only and name not in only:
+            continue
         mask = synth.make_dropout_mask(bseed, L, B, p) if p > 0 else None
-        model, inject = _reference_train_model(wseed, L, K, noise, nu, torch.float64, p, mask)
+        model, inject = _reference_train_model(wseed, L, K, noise, nu, torch.float64, p, mask, factors)
         img, ev, labels, lengths = synth.make_train_batch(bseed, B)
         with inject():
             # MMFMIL.forward (imf_vad.py:40-44) is `.to(torch.float)` + this call; entering one level below keeps the graph in fp64
@@ -568,6 +662,8 @@ def gen_model_grad_cases():
         total.backward()
         store = {"cfg": np.array([wseed, bseed, B, L, K, nu]), "noise": np.array(noise), "lams": np.array([lam_reg, lam_kl]),
                  "p": np.array(p), "total": np.array(float(total)), "logits": out["logits"].detach().numpy().reshape(B, 256)}
+        if factors is not None:
+            store["factors"] = np.array(factors, np.float64)
         names = []
         for i, (key, prm) in enumerate(model.named_parameters()):
             g = prm.grad.numpy().reshape(-1)
@@ -577,6 +673,23 @@ def gen_model_grad_cases():
             store[f"g{i}_idx"] = idx.astype(np.int64)
             store[f"g{i}_val"] = g[idx]
             store[f"g{i}_norms"] = np.array([np.abs(g).sum(), np.sqrt((g * g).sum()), np.abs(g).max()])
+        if factors is not None:
+            # the reference's OWN fp32 autograd (what its trainers run) against the fp64 gradients just stored, in units of the gate of
+            # tests/test_gpu_train.py (1e-4 |want| + 1e-6 max|grad| per sampled entry), worst over all parameters: the floor of the
+            # number format on this case.  One thread, so that the summation order -- and with it this field -- reproduces.
+            threads = torch.get_num_threads()
+            torch.set_num_threads(1)
+            m32, _ = _reference_train_model(wseed, L, K, noise, nu, torch.float32, p, mask, factors)
+            o32 = m32.temporal(torch.from_numpy(img), torch.from_numpy(ev))
+            _trainer_loss(o32, torch.from_numpy(labels), torch.from_numpy(lengths), noise, nu, lam_reg, lam_kl, CLAS2).backward()
+            torch.set_num_threads(threads)
+            floor = 0.0
+            for i, (key, prm) in enumerate(m32.named_parameters()):
+                g32 = prm.grad.double().numpy().reshape(-1)[store[f"g{i}_idx"]]
+                want = store[f"g{i}_val"]
+                floor = max(floor, float((np.abs(g32 - want) / (1e-4 * np.abs(want) + 1e-6 * store[f"g{i}_norms"][2])).max()))
+            store["grad_floor"] = np.array(floor)
+            print("reference fp32 autograd vs fp64, worst sampled entry in units of the 1e-4 gate:", floor)
         store["names"] = np.array(names)
         path = os.path.join(HERE, f"grad_{name}.npz")
         np.savez_compressed(path, **store)
@@ -623,7 +736,7 @@ def gen_train_step_case():
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "modelgrad":
-        gen_model_grad_cases()
+        gen_model_grad_cases(sys.argv[2:])
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "trainstep":
         gen_train_step_case()
@@ -640,6 +753,9 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "init":
         gen_init_checksums()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "sharp":
+        gen_sharp_cases(sys.argv[2:])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "b48":
         gen_forward_cases([BIG_CASE], BIG_CASE_CHUNKS)
         sys.exit(0)
@@ -655,6 +771,7 @@ if __name__ == "__main__":
     torch.manual_seed(0)
     gen_forward_cases()
     gen_forward_cases([BIG_CASE], BIG_CASE_CHUNKS)
+    gen_sharp_cases()
     gen_harness_case()
     gen_harness_xd_case()
     gen_init_checksums()

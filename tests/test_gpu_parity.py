@@ -241,7 +241,15 @@ def test_graph_replay_is_bit_identical_to_direct_launches():
     """Calls with B <= graph_chunks replay a cached hipGraph (inputs and outputs staged through library-owned buffers);
     graph_chunks = -1 launches the same kernels one by one.  Same bits, for every output, every input dtype, repeated
     calls with fresh tensors, interleaved batch sizes, and after a weight update."""
-    sd = synth.make_state_dict(93, 768, 2, 3)
+    _graph_replay_equals_direct(synth.make_state_dict(93, 768, 2, 3))
+
+
+def test_graph_replay_is_bit_identical_to_direct_launches_with_peaked_attention():
+    """The same with the q / k rows sharpened (synth.sharpen_qk (8, 4)): both sides share the flat regime otherwise."""
+    _graph_replay_equals_direct(synth.sharpen_qk(synth.make_state_dict(93, 768, 2, 3), (8, 4)))
+
+
+def _graph_replay_equals_direct(sd):
     img, ev = synth.make_inputs(94, 6)
     direct = make_model(2, 3, 0.5, "StudentT", 8, sd, graph_chunks=-1)
     graphed = make_model(2, 3, 0.5, "StudentT", 8, sd, graph_chunks=4)

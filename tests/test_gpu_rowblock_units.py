@@ -206,6 +206,128 @@ def test_refinement_chain_kernel_alone_one_step(rows):
     assert torch.equal(zin, z1)
 
 
+# ---- attention alone ----------------------------------------------------------------------------------------------------------------
+ATT_KINDS = ["flat", "std5", "std20", "dominant", "ties", "extreme"]      # chunk c of a modality is of kind (c + modality) % 6
+ATT_DOMINANT = [0, 255, 127, 128, 15, 16, 143, 144]                         # first / last key, the lane-pair split of a softmax row, 16-key tile edges
+U32 = 2.0 ** -24                                                            # unit roundoff of fp32
+
+
+def attention_case(nchunks, mod, seed):
+    """bf16 q (log2 units, as in_proj stores it), k, v [nchunks, 8, 256, 96], made here and not by in_proj, so the test controls the scores
+    s = q k^T.  Per chunk kind, different per head (seeded per head; the dominant positions rotate with the head) so a head mix-up shows:
+      flat / std5 / std20   q, k normal with std(s) = 0.3 / 5 / 20
+      dominant              query i of head h: key ATT_DOMINANT[(i + h) % 8] leads by ~12 (P ~ 0.9, the other keys share the rest)
+      ties                  queries 0..63: q = 0, every score equal, P = 1/256 exactly; the others: two identical key rows (j, j + 1 of the
+                            dominant list) tied for the maximum
+      extreme               coordinate 0 of every k is 1, of every q -120; coordinate 1 of k is 1 for key j only.  Queries 0..127: q[1] =
+                            240, so key j sits near +120 and the rest near -120 (exp2 underflows to exact zeros, P_j = 1); queries 128..255:
+                            q[1] = 0, every score near -120 (only the max subtraction brings them back).  Odd heads: 140 instead of 120 --
+                            2^120 and 2^-120 are still fp32 numbers, 2^140 and 2^-140 are not, so without the max subtraction these
+                            heads return NaN
+    v is asymmetric in key and column with a positive mean per column (gain 2^(c % 5 - 2)): no symmetric fragment permutation cancels, and
+    the output does not cancel to a value whose bf16 step is smaller than the effect of one probability's rounding."""
+    g = torch.Generator().manual_seed(seed)
+    q = torch.zeros(nchunks, 8, 256, 96, dtype=torch.float64)
+    k = torch.randn(nchunks, 8, 256, 96, generator=g, dtype=torch.float64)
+    gain = torch.exp2((torch.arange(96) % 5 - 2).double())
+    v = gain * (1.0 + 0.5 * torch.randn(nchunks, 8, 256, 96, generator=g, dtype=torch.float64))
+    qi = torch.arange(256)
+    for c in range(nchunks):
+        kind = ATT_KINDS[(c + mod) % len(ATT_KINDS)]
+        noise = torch.randn(8, 256, 96, generator=g, dtype=torch.float64)
+        if kind in ("flat", "std5", "std20"):
+            q[c] = noise * ({"flat": 0.3, "std5": 5.0, "std20": 20.0}[kind] / math.sqrt(96.0))
+            continue
+        for h in range(8):
+            j = torch.tensor(ATT_DOMINANT)[(qi + h + c) % 8]                  # the leading key of each query
+            if kind == "extreme":
+                k[c, h, :, 0] = 1.0
+                k[c, h, :, 1] = 0.0
+                jj = ATT_DOMINANT[(h + c) % 8]
+                k[c, h, jj, 1] = 1.0
+                q[c, h] = noise[h] * 0.05
+                big = 120.0 if h % 2 == 0 else 140.0
+                q[c, h, :, 0] = -big
+                q[c, h, :, 1] = torch.where(qi < 128, 2 * big, 0.0).double()
+                continue
+            if kind == "ties":
+                for a in range(0, 8, 2):                                      # keys (0, 255), (127, 128), (15, 16), (143, 144) become identical rows
+                    k[c, h, ATT_DOMINANT[a + 1]] = k[c, h, ATT_DOMINANT[a]]
+            kb = bf(k[c, h])
+            lead = kb[j]                                                      # [256, 96]
+            q[c, h] = 0.1 * noise[h] + 12.0 * lead / (lead * lead).sum(-1, keepdim=True)
+            if kind == "ties":
+                q[c, h, :64] = 0.0
+    return bf(q), bf(k), bf(v)
+
+
+def attention_model(q, k, v):
+    """fp64 softmax2(q k^T) v on the same bf16 q, k, v, the normalised probability rounded to bf16 where the kernels round it (csrc/
+    attention_bf16.h, attention_pbf16.h: `(bf16)(p * inv)` -- AFTER the normalisation, the sum taken over the unrounded p), and the
+    allowance per output element: the kernel's probability before its rounding is p (1 +- eps) with
+        eps = ln 2 (12 u sum_d |q_d k_d| + u |s - max|)      the score: six fp32 MFMA accumulations of 16-product blocks, each block's own
+                                                             sum counted as another six; the subtraction's rounding
+            + 2 u + 130 u + 3 u                              v_exp_f32 (1 ulp), the row sum (128 sequential fp32 additions of positive
+                                                             terms + the lane-pair exchange, worst case), 1 / sum and the product
+    so its bf16 value lies between P_lo = bf16(p (1 - eps)) and P_hi = bf16(p (1 + eps)), as does the model's; P V accumulates exact
+    products in fp32 over 16 MFMA steps (20 u sum |P v|).  tol = (P_hi - P_lo) |v| + 20 u P |v|: nothing in it comes from a kernel run."""
+    s = q @ k.transpose(-1, -2)
+    sm = s - s.amax(-1, keepdim=True)
+    p = torch.exp2(sm)
+    p = p / p.sum(-1, keepdim=True)
+    eps = math.log(2.0) * (12 * U32 * (q.abs() @ k.abs().transpose(-1, -2)) + U32 * sm.abs()) + 135 * U32
+    P, spread = bf(p), bf(p * (1 + eps)) - bf(p * (1 - eps))
+    ref = P @ v
+    tol = spread @ v.abs() + 20 * U32 * (P @ v.abs()) + 1e-30      # 1e-30: a probability below 2^-126 may be flushed to zero
+    return ref, tol, P
+
+
+def attention_rows(rows):
+    return -(-rows // 256) * 256          # the file's ROWS rounded up to whole chunks: 2048 (8 chunks), 16640 (65 chunks)
+
+
+@pytest.mark.parametrize("rows", [attention_rows(r) for r in ROWS])
+def test_attention_kernel_alone(rows):
+    """iefvad_attention_bf16_kernel (rows = 2048: 128 items, below two per compute unit) and iefvad_attention_pbf16_kernel (rows = 16640:
+    1,040 items): softmax2(q k^T) v per chunk and head on q, k, v the test designs (attention_case), against the fp64 model with the
+    probability rounded where the kernels round it (attention_model).  Besides the boundary check, finite everywhere and exact where the
+    arithmetic is exact: a query with P = 1/256 returns the fp32-accumulated column mean, a query whose other keys underflow returns v[j]."""
+    torch.set_num_threads(harness.host_cpu_share())
+    model, _ = handle(1, 1, 66)
+    nchunks = rows // 256
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    import os
+    persistent = os.environ.get("IEFVAD_PERSIST", "1") != "0" and 2 * nchunks * 8 >= 2 * cus       # launch_attention_bf16's own rule
+    assert persistent == (rows > 4096), (rows, cus)          # 2048 rows -> the one-block kernel, 16640 -> the persistent one, on any CDNA part
+    data = [attention_case(nchunks, m, 1000 * rows + m) for m in range(2)]
+    x = [torch.stack([t.permute(1, 0, 2, 3).reshape(8, rows, 96) for t in d]).to(torch.bfloat16).contiguous().cuda() for d in data]
+    yb = [torch.full((rows, D), float("nan"), dtype=torch.bfloat16, device="cuda") for _ in range(2)]
+    run(model, L.UNIT_ATTENTION, 0, rows, x=x, yb=yb)
+    for m, (q, k, v) in enumerate(data):
+        worst, ndiff = 0.0, 0
+        got = yb[m].cpu().reshape(nchunks, 256, 8, 96).permute(0, 2, 1, 3)          # [chunk, head, query, 96]
+        assert bool(torch.isfinite(got.float()).all()), m
+        fracs = []
+        for c0 in range(0, nchunks, 6):                                            # six chunks (one of each kind) at a time: memory
+            sl = slice(c0, min(c0 + 6, nchunks))
+            ref, tol, P = attention_model(q[sl], k[sl], v[sl])
+            fracs.append((check_bf16_output(got[sl], ref, tol, f"attention modality {m} chunks {c0}.."), ref.numel()))
+            differ = got[sl].double() != bf(ref)
+            ndiff += int(differ.sum())
+            worst = max(worst, float(((got[sl].double() - ref).abs() / (tol + bf_ulp(ref))).max()))
+            for c in range(sl.start, sl.stop):
+                kind = ATT_KINDS[(c + m) % len(ATT_KINDS)]
+                if kind == "extreme":      # queries 0..127 of every head: P is one-hot, the output IS v[j]
+                    for h in range(8):
+                        jj = ATT_DOMINANT[(h + c) % 8]
+                        assert torch.equal(got[c, h, :128].double(), v[c, h, jj].expand(128, 96)), (m, c, h)
+                if kind == "ties":         # queries 0..63: P = 2^-8 exactly
+                    assert bool((P[c - sl.start, :, :64] == 2.0 ** -8).all())
+        frac = sum(f * n for f, n in fracs) / sum(n for _, n in fracs)
+        print(f"attention rows {rows} modality {m} ({'persistent' if persistent else 'one-block'} kernel): {ndiff / got.numel():.2e} of the outputs differ from bf16(fp64 model), "
+              f"max |y - model| / (allowance + one bf16 step) = {worst:.2f}, {frac:.2e} of the outputs on a bf16 rounding boundary")
+
+
 def test_unit_entry_rejects_what_it_cannot_run():
     model, _ = handle(2, 0, 65)          # K = 0: no refinement chain on this handle
     lib = L.load_library()
@@ -216,6 +338,13 @@ def test_unit_entry_rejects_what_it_cannot_run():
     assert lib.iefvad_rowblock_unit(model._handle, L.UNIT_INPROJ, 5, 64, C.byref(io), st) != 0 and "layer" in L.last_error()
     assert lib.iefvad_rowblock_unit(model._handle, L.UNIT_HEADS, 0, 64, C.byref(io), st) != 0
     assert lib.iefvad_rowblock_unit(model._handle, 9, 0, 64, C.byref(io), st) != 0 and "unknown stage" in L.last_error()
+    assert lib.iefvad_rowblock_unit(model._handle, L.UNIT_ATTENTION, 0, 320, C.byref(io), st) != 0 and "multiple of 256" in L.last_error()
+    assert lib.iefvad_rowblock_unit(model._handle, L.UNIT_ATTENTION, 0, 256, C.byref(io), st) != 0 and "ATTENTION needs" in L.last_error()
+    buf = torch.zeros(3 * 8 * 256 * 96 + 8, dtype=torch.bfloat16, device="cuda")
+    for m in range(2):
+        io.x[m], io.yb[m] = buf.data_ptr() + 2, buf.data_ptr()                 # x not 16-byte aligned
+    assert lib.iefvad_rowblock_unit(model._handle, L.UNIT_ATTENTION, 0, 256, C.byref(io), st) != 0 and "aligned" in L.last_error()
+    io = L.UnitIO()
     a = argparse.Namespace(visual_layers=1, visual_head=8, num_refinement_steps=1, lambda_ref=0.5, noise_model="StudentT", nu=8)
     m32 = iefvad_amd.MMFMIL(14, D, 256, D, 8, 1, 8, 10, 10, "cuda", a).to("cuda:0").eval()
     with torch.cuda.device(0):

@@ -22,11 +22,13 @@ from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 
-GRAD_CASES = ["k2_student8", "k10_student8_mask", "k0_gauss_l1"]
+GRAD_CASES = ["k2_student8", "k10_student8_mask", "k0_gauss_l1", "sharp_k2_student8"]
 
 
-def make_model(wseed, L, K, noise, nu, compute="f32", p=0.0):
+def make_model(wseed, L, K, noise, nu, compute="f32", p=0.0, factors=None):
     sd = synth.make_state_dict(wseed, 768, L, K)
+    if factors is not None:
+        sd = synth.sharpen_qk(sd, factors)
     args = argparse.Namespace(visual_layers=L, visual_head=8, num_refinement_steps=K, lambda_ref=0.5, noise_model=noise, nu=nu)
     m = iefvad_amd.MMFMIL(14, 768, 256, 768, 8, L, 8, 10, 10, "cuda", args, compute=compute)
     m.load_state_dict(sd)
@@ -46,7 +48,8 @@ def run_case(name, compute="f32"):
     wseed, bseed, B, L, K, nu = (int(v) for v in g["cfg"])
     noise, p = str(g["noise"]), float(g["p"])
     lam_reg, lam_kl = (float(v) for v in g["lams"])
-    model, _ = make_model(wseed, L, K, noise, nu, compute, p)
+    factors = tuple(float(f) for f in g["factors"]) if "factors" in g.files else None      # peaked attention: synth.sharpen_qk
+    model, _ = make_model(wseed, L, K, noise, nu, compute, p, factors)
     if p > 0:
         model.dropout_mask = torch.from_numpy(synth.make_dropout_mask(bseed, L, B, p)).cuda()
     model.train()
@@ -60,8 +63,17 @@ def run_case(name, compute="f32"):
 @pytest.mark.parametrize("name", GRAD_CASES)
 def test_every_parameter_gradient_matches_the_reference_autograd(name):
     """Done-criterion of the round-3 verdict: every parameter gradient within 1e-4 relative (+ 1e-6 x the tensor's scale) of the
-    reference's fp64 autograd, on sampled entries and in both norms."""
+    reference's fp64 autograd, on sampled entries and in both norms.
+
+    sharp_k2_student8 (peaked attention, synth.sharpen_qk (8, 4): the softmax backward P o (dP - sum P o dP) where P is not ~ 1/256): here
+    the per-entry gate lies below what fp32 can give.  The reference's OWN fp32 autograd misses it against its fp64 gradients by 1.22x
+    on its worst sampled entry (fixture field `grad_floor`, recorded by the generator; 0.65x on k2_student8, the same seeds with flat
+    attention), so for a fixture that records such a floor the per-entry gate is max(1, 3 x floor) times the usual one -- 3.66x here,
+    the margin over a reference-side floor the forward cases use; nothing in it comes from a kernel.  Measured on MI355X (f32 kernels):
+    worst entry 2.6x the usual gate (event layer-0 out_proj.bias; 0.97x on k2_student8), i.e. 2.2x the reference's own fp32 error; both
+    norms within 5.2e-7, and they keep the 1e-4 gate.  ARITHMETIC.md, "Gradients under peaked attention"."""
     g, model, out, total = run_case(name)
+    entry_gate = max(1.0, 3.0 * float(g["grad_floor"])) if "grad_floor" in g.files else 1.0
     assert abs(float(total.detach()) - float(g["total"])) <= 2e-5 * max(1.0, abs(float(g["total"])))
     assert float(np.abs(out["logits"].detach().cpu().numpy().reshape(g["logits"].shape) - g["logits"]).max()) <= H.TOL_LOGIT
     names = [str(n) for n in g["names"]]
@@ -78,9 +90,10 @@ def test_every_parameter_gradient_matches_the_reference_autograd(name):
         err = np.abs(got[g[f"g{i}_idx"]] - want)
         tol = 1e-4 * np.abs(want) + 1e-6 * mx
         worst[n] = float((err / tol).max())
-        assert (err <= tol).all(), (n, float(err.max()), mx, worst[n])
+        assert (err <= entry_gate * tol).all(), (n, float(err.max()), mx, worst[n], entry_gate)
         assert abs(np.abs(got).sum() - l1) <= 1e-4 * l1 + 1e-12, (n, "L1")
         assert abs(np.sqrt((got * got).sum()) - l2) <= 1e-4 * l2 + 1e-12, (n, "L2")
+    print(name, "worst sampled entry in units of the 1e-4 gate:", max(worst.items(), key=lambda t: t[1]), "entry gate", entry_gate)
 
 
 def test_gradients_bf16x6_forward_arithmetic_meets_the_same_gate():
@@ -193,6 +206,16 @@ def test_fused_train_attention_equals_the_three_launch_path(mode, monkeypatch):
     stored) against the three launches it replaced (IEFVAD_TRAIN_ATTN=unfused: fp32-MFMA products, stand-alone softmax + dropout): same
     mask element for element (injected, or the counter-based bits of common.h), all eight outputs and every parameter gradient at the
     fp32 gates.  /root/reference/model/imf_vad.py:69-72,115,121 under model.train()."""
+    _fused_train_attention_equals_unfused(mode, monkeypatch, None)
+
+
+def test_fused_train_attention_equals_the_three_launch_path_with_peaked_attention(monkeypatch):
+    """The same (injected mask) with the q / k rows sharpened (synth.sharpen_qk (8, 4)): P is far from 1/256, so the stored P, the
+    dropout of a dominant key and the softmax backward P o (dP - sum P o dP) all carry weight."""
+    _fused_train_attention_equals_unfused("injected_mask", monkeypatch, (8, 4))
+
+
+def _fused_train_attention_equals_unfused(mode, monkeypatch, factors):
     p = 0.0 if mode == "no_dropout" else 0.1
     B, L = 3, 2
     img, ev, labels, lengths = batch(52, B)
@@ -202,7 +225,7 @@ def test_fused_train_attention_equals_the_three_launch_path(mode, monkeypatch):
             monkeypatch.setenv("IEFVAD_TRAIN_ATTN", "unfused")
         else:
             monkeypatch.delenv("IEFVAD_TRAIN_ATTN", raising=False)
-        model, _ = make_model(41, L, 2, "StudentT", 8, "bf16x6", p)
+        model, _ = make_model(41, L, 2, "StudentT", 8, "bf16x6", p, factors)
         if mode == "injected_mask":
             model.dropout_mask = torch.from_numpy(synth.make_dropout_mask(7, L, B, p)).cuda()
         model.dropout_seed = 4321
@@ -219,7 +242,7 @@ def test_fused_train_attention_equals_the_three_launch_path(mode, monkeypatch):
         scale = float(g2[n].abs().max())
         assert float((g1[n] - g2[n]).abs().max()) <= 1e-4 * scale + 1e-9, n
     if mode != "no_dropout":       # the mask did something: the outputs differ from a no-dropout forward
-        model, _ = make_model(41, L, 2, "StudentT", 8, "bf16x6", 0.0)
+        model, _ = make_model(41, L, 2, "StudentT", 8, "bf16x6", 0.0, factors)
         model.train()
         o0 = model(img, ev, None, None, lengths)
         assert float((o0["image_mu"].detach() - o1["image_mu"]).abs().mean()) > 1e-4

@@ -20,8 +20,10 @@ pytestmark = pytest.mark.gpu
 EDGE_LENGTHS = [37, 255, 256, 257, 512, 1500, 1, 300, 64, 768]      # SURVEY 8d config 1's chunk-edge cases and then some
 
 
-def make_model(compute, L=2, K=3, **kw):
+def make_model(compute, L=2, K=3, factors=None, **kw):
     sd = synth.make_state_dict(41, 768, L, K)
+    if factors is not None:
+        sd = synth.sharpen_qk(sd, factors)
     args = argparse.Namespace(visual_layers=L, visual_head=8, num_refinement_steps=K, lambda_ref=0.5, noise_model="StudentT", nu=8)
     m = iefvad_amd.MMFMIL(14, 768, 256, 768, 8, L, 8, 10, 10, "cuda", args, compute=compute, **kw)
     m.load_state_dict(sd)
@@ -61,7 +63,19 @@ def ragged(model, vids, **kw):
 def test_forward_videos_is_bit_identical_to_the_padded_forward(compute, micro_batch):
     """Chunk-edge lengths (len < 256, == 255 / 256 / 257, multiples of 256, a one-snippet video, a six-chunk video); with a
     small micro-batch the call runs as several passes, each compacting its own valid rows."""
-    model, _ = make_model(compute, outputs="scores", micro_batch=micro_batch)
+    _videos_equal_padded(compute, micro_batch, None)
+
+
+@pytest.mark.parametrize("compute", ["f32", "bf16", "fp16x3"])
+def test_forward_videos_is_bit_identical_to_the_padded_forward_with_peaked_attention(compute):
+    """The same with the q / k rows sharpened (synth.sharpen_qk (8, 4)): a short video's pad rows are keys of its last chunk, and
+    with flat attention each of them carries 1/256 of the weight whatever the `_rows` kernels read for it; here a pad key's
+    score decides whether it takes part at all."""
+    _videos_equal_padded(compute, 0, (8, 4))
+
+
+def _videos_equal_padded(compute, micro_batch, factors):
+    model, _ = make_model(compute, outputs="scores", micro_batch=micro_batch, factors=factors)
     vids = videos(EDGE_LENGTHS)
     want = dense_reference(model, vids)
     got = ragged(model, vids)

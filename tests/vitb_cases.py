@@ -9,7 +9,7 @@ from iefvad_amd import synth
 from tests import helpers as H
 
 D = 512
-FWD_CASES = ["base", "k0_gauss_l1", "f16_k3"]
+FWD_CASES = ["base", "k0_gauss_l1", "f16_k3", "sharp_k3"]     # sharp_*: peaked attention (synth.sharpen_qk by the fixture's factors)
 
 
 def load_case(name):
@@ -25,6 +25,8 @@ def load_case(name):
     if cfg["in_dtype"] == "f16":
         img, ev = img.astype(np.float16), ev.astype(np.float16)
     sd = synth.make_state_dict(wseed, D, L, K)
+    if "factors" in g.files:
+        sd = synth.sharpen_qk(sd, tuple(float(f) for f in g["factors"]))
     return g, cfg, sd, img, ev
 
 
