@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <exception>
 #include <new>
 #include <thread>
@@ -32,6 +33,7 @@
 #include "heads_chain_bf16.h"
 #include "heads_pchain_bf16.h"
 #include "ragged.h"
+#include "resample.h"
 #include "loss.h"
 #include "gemm_split_tn.h"
 #include "backward.h"
@@ -2064,6 +2066,77 @@ extern "C" int iefvad_auc_ap(const float* scores, const uint8_t* gt_frames, int6
                        w.ap_part);
     hipLaunchKernelGGL(iefvad_metric_finish_kernel, dim3(1), dim3(256), 0, stream, tp_incl, (long long)n, (int)repeat, w.auc_num, w.ap_part, tiles, w.flags,
                        auc, ap);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// training input pipeline: ragged rows -> 256-segment windows, and a step's batch out of the cached windows (resample.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t iefvad_resample_workspace_bytes(int32_t nvideos) {
+    if (nvideos <= 0) return 0;
+    return ((size_t)nvideos * sizeof(ResampleVideo) + 255) & ~(size_t)255;
+}
+
+extern "C" int iefvad_resample_videos(const void* rows, int32_t in_dtype, const int32_t* lengths, int32_t nvideos, int32_t T, int32_t D,
+                                      void* workspace, size_t workspace_bytes, float* out, int32_t* out_lengths, void* stream_) {
+    if (!rows || !lengths || !workspace || !out || !out_lengths) return fail("iefvad_resample_videos: null argument");
+    if (nvideos <= 0) return fail("iefvad_resample_videos: nvideos must be positive (got %d)", nvideos);
+    if (T != IEF_T) return fail("iefvad_resample_videos: T = %d, the window is %d segments", T, IEF_T);
+    if (D <= 0 || D % 8) return fail("iefvad_resample_videos: D = %d must be a positive multiple of 8", D);
+    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16)
+        return fail("iefvad_resample_videos: in_dtype %d (fp32 and fp16 feature files only)", in_dtype);
+    const size_t need = iefvad_resample_workspace_bytes(nvideos);
+    if (workspace_bytes < need) return fail("iefvad_resample_videos: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    if (((uintptr_t)rows & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)out & 15) || ((uintptr_t)out_lengths & 3))
+        return fail("iefvad_resample_videos: rows, workspace and out must be 16-byte aligned, out_lengths 4-byte");
+    const int groups = D / (in_dtype == IEFVAD_IN_F32 ? 4 : 8);
+    if ((long long)nvideos * groups > 0xffffffffLL / 256)       // grid.x * block.x of one launch stays below 2^32
+        return fail("iefvad_resample_videos: %d videos of D = %d exceed one launch (%lld at this width)", nvideos, D, 0xffffffffLL / 256 / groups);
+    std::vector<ResampleVideo> table;
+    try {
+        table.resize((size_t)nvideos);
+    } catch (const std::exception&) {
+        return fail("iefvad_resample_videos: out of host memory");
+    }
+    long long row = 0;
+    for (int v = 0; v < nvideos; ++v) {
+        if (lengths[v] < 1) return fail("iefvad_resample_videos: lengths[%d] = %d (every video has at least one row)", v, lengths[v]);
+        table[v].src_row = row;
+        table[v].n = lengths[v];
+        table[v].out = v;
+        row += lengths[v];
+    }
+    // longest video first (resample.h); ties in list order, so the table is a function of the lengths alone
+    std::stable_sort(table.begin(), table.end(), [](const ResampleVideo& a, const ResampleVideo& b) { return a.n > b.n; });
+    hipStream_t stream = (hipStream_t)stream_;
+    // the table is host memory of this call: the copy is ordered on `stream` behind whatever still reads the workspace, and waited for
+    HIP_TRY(hipMemcpyAsync(workspace, table.data(), (size_t)nvideos * sizeof(ResampleVideo), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    const dim3 grid((unsigned)((long long)nvideos * groups));
+    if (in_dtype == IEFVAD_IN_F32)
+        hipLaunchKernelGGL(iefvad_resample_rows_kernel<float>, grid, dim3(256), 0, stream, (const float*)rows, (const ResampleVideo*)workspace, (int)D, out,
+                           (int*)out_lengths);
+    else
+        hipLaunchKernelGGL(iefvad_resample_rows_kernel<__half>, grid, dim3(256), 0, stream, (const __half*)rows, (const ResampleVideo*)workspace, (int)D, out,
+                           (int*)out_lengths);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int iefvad_gather_windows(const float* img_set, const float* ev_set, const int32_t* set_lengths, int32_t nset, const int32_t* index,
+                                     int32_t B, int32_t T, int32_t D, float* img_out, float* ev_out, int32_t* len_out, void* stream_) {
+    if (!img_set || !ev_set || !set_lengths || !index || !img_out || !ev_out || !len_out) return fail("iefvad_gather_windows: null argument");
+    if (nset <= 0 || B <= 0) return fail("iefvad_gather_windows: nset = %d, B = %d must be positive", nset, B);
+    if (B > 65535) return fail("iefvad_gather_windows: B = %d exceeds one launch (65535 windows)", B);
+    if (T != IEF_T) return fail("iefvad_gather_windows: T = %d, the window is %d segments", T, IEF_T);
+    if (D <= 0 || D % 8) return fail("iefvad_gather_windows: D = %d must be a positive multiple of 8", D);
+    if (((uintptr_t)img_set & 15) || ((uintptr_t)ev_set & 15) || ((uintptr_t)img_out & 15) || ((uintptr_t)ev_out & 15) ||
+        ((uintptr_t)set_lengths & 3) || ((uintptr_t)index & 3) || ((uintptr_t)len_out & 3))
+        return fail("iefvad_gather_windows: the window tensors must be 16-byte aligned, the int32 vectors 4-byte");
+    const int nvec = IEF_T * D / 4, per_wg = 256 * IEF_GW_VEC;
+    hipLaunchKernelGGL(iefvad_gather_windows_kernel, dim3((nvec + per_wg - 1) / per_wg, B, 2), dim3(256), 0, (hipStream_t)stream_, img_set, ev_set,
+                       (const int*)set_lengths, (int)nset, (const int*)index, (int)D, img_out, ev_out, (int*)len_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -98,6 +98,102 @@ def get_test_loader(args, dataset: Optional[str] = None):
 
 
 # ------------------------------------------------------------------------------------------------
+# the training loader (data/tools.py:65-97, the test_mode == False branch of data/dataset.py, data/__getter__.py:5-84)
+# ------------------------------------------------------------------------------------------------
+NORMAL_LABEL = {'ucfcrime': 'Normal', 'msad': 'Normal', 'shang': 'normal'}        # dataset.py:24,28,100,104; xd has no filter
+
+
+def segment_bounds(n: int, length: int = 256) -> np.ndarray:
+    """`np.linspace(0, n, length + 1, dtype=np.int32)` of uniform_extract (tools.py:67) in integers: (i n) >> 8 for length = 256
+    (n / 256 and i (n / 256) are exact in fp64, so linspace truncates exactly these values)."""
+    if length & (length - 1):
+        raise ValueError(f"segment_bounds: the integer identity holds for a power-of-two window, not for {length}")
+    i = np.arange(length + 1, dtype=np.int64)
+    return (i * int(n)) // length
+
+
+def process_feat(feat: np.ndarray, length: int) -> Tuple[np.ndarray, int]:
+    """Train-time window (tools.py:89-97 with is_random False, which is all the reference ever selects): n <= length rows ->
+    the rows, zero padded, clip length n; more -> `length` segments (`segment_bounds`), each replaced by np.mean of its rows,
+    clip length `length`.  Always fp32 (the reference hands back a short fp16 file as fp16; widening is exact).
+
+    np.mean over axis 0 is an fp32 accumulator starting at +0, one add per row in ascending order, one division by the count,
+    and for an fp16 file a rounding of the quotient to fp16.  Restated here over all segments at once: the j-th row of every
+    segment is added in one vector operation, n // length (+ 1) of them instead of `length` np.mean calls -- the same adds in the
+    same order per output element, so the same bits, and the host model of csrc/resample.h."""
+    n, D = int(feat.shape[0]), int(feat.shape[1])
+    out = np.zeros((length, D), dtype=np.float32)
+    if n <= length:
+        out[:n] = feat
+        return out, n
+    r = segment_bounds(n, length)
+    start, count = r[:-1], r[1:] - r[:-1]
+    with np.errstate(invalid='ignore', over='ignore'):      # non-finite values pass through as the arithmetic has it
+        for j in range(int(count.max())):
+            if j < int(count.min()):
+                out += feat[start + j]                      # fp16 rows are widened by the fp32 destination of the add
+            else:
+                sel = np.nonzero(count > j)[0]
+                out[sel] += feat[start[sel] + j]
+        out /= count.astype(np.float32)[:, None]
+        if feat.dtype == np.float16:
+            out = out.astype(np.float16).astype(np.float32)
+    return out, length
+
+
+class TrainFeatureDataset(torch.utils.data.Dataset):
+    """Train-mode counterpart of UCF_Dataset / XD_Dataset / Shang_Dataset over a `path,label` CSV.  `normal` True keeps the rows
+    whose label is the dataset's normal label ('Normal'; 'normal' for shang), False the others, in file order (the reference's
+    `.loc[...]` + `reset_index`); None keeps the whole list, which is also what 'xd' always does (XD_Dataset has no filter).
+    Items are the reference's: (img [clip_dim, D] fp32, ev [clip_dim, D] fp32, label, clip length of the IMAGE file); the event
+    file is resampled by its own row count."""
+
+    def __init__(self, clip_dim: int, file_path: str, dataset: str = 'ucfcrime', normal: Optional[bool] = None):
+        if dataset not in EVENT_DIR:
+            raise ValueError('Dataset not supported')
+        with open(file_path, newline='') as f:
+            rows = list(csv.DictReader(f))
+        if dataset != 'xd' and normal is not None:
+            key = NORMAL_LABEL[dataset]
+            rows = [r for r in rows if (r['label'] == key) == bool(normal)]
+        self.paths = [r['path'] for r in rows]
+        self.labels = [r['label'] for r in rows]
+        self.clip_dim = clip_dim
+        self.dataset = dataset
+        self.normal = normal
+        self.event_dir = EVENT_DIR[dataset]
+
+    def __len__(self):
+        return len(self.paths)
+
+    def event_path(self, index: int) -> str:
+        return self.paths[index].replace('rgb', self.event_dir)
+
+    def load_raw(self, index: int) -> Tuple[np.ndarray, np.ndarray]:
+        """The two feature files of an item as stored, [n_img, D] and [n_ev, D]."""
+        return np.load(self.paths[index]), np.load(self.event_path(index))
+
+    def __getitem__(self, index):
+        img, ev = self.load_raw(index)
+        img, n = process_feat(img, self.clip_dim)
+        ev, _ = process_feat(ev, self.clip_dim)
+        return torch.from_numpy(img), torch.from_numpy(ev), self.labels[index], n
+
+
+def get_train_loaders(args, dataset: Optional[str] = None):
+    """The train side of `get_loader` (data/__getter__.py): (normal_loader, abnormal_loader), both `shuffle=True, drop_last=True`,
+    for ucfcrime / shang / msad; ONE loader with `shuffle=True` for xd.  batch_size = args.batch_size."""
+    dataset = dataset or args.dataset
+    if dataset not in EVENT_DIR:
+        raise ValueError('Dataset not supported')
+    if dataset == 'xd':
+        ds = TrainFeatureDataset(args.visual_length, args.train_list, 'xd')
+        return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True)
+    sets = [TrainFeatureDataset(args.visual_length, args.train_list, dataset, normal=flag) for flag in (True, False)]
+    return tuple(torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, drop_last=True) for ds in sets)
+
+
+# ------------------------------------------------------------------------------------------------
 # metrics (sklearn, exactly the calls the reference makes)
 # ------------------------------------------------------------------------------------------------
 def compute_ano_auc(classwise_gt, classwise_roc, repeat_factor=16, normal_keys=('Normal',)):

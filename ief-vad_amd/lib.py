@@ -31,7 +31,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_forward_videos_host", "iefvad_host_gather_bf16", "iefvad_auc_ap", "iefvad_auc_ap_workspace_bytes", "iefvad_forward_scaled", "iefvad_rowblock_unit",
            "iefvad_similarity_adj", "iefvad_similarity_adj_workspace_bytes", "iefvad_distance_adj", "iefvad_gcn_forward",
            "iefvad_gcn_workspace_bytes", "iefvad_gat_forward", "iefvad_gat_workspace_bytes", "iefvad_resblock_forward",
-           "iefvad_resblock_workspace_bytes", "iefvad_adamw_step_multi"]
+           "iefvad_resblock_workspace_bytes", "iefvad_adamw_step_multi", "iefvad_resample_workspace_bytes", "iefvad_resample_videos",
+           "iefvad_gather_windows"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -197,6 +198,12 @@ def load_library() -> C.CDLL:
     lib.iefvad_resblock_workspace_bytes.restype = C.c_size_t
     lib.iefvad_resblock_forward.argtypes = [vp, C.POINTER(ResblockWeights), vp, vp, i32, i32, i32, i32, vp, vp, C.c_size_t, vp]
     lib.iefvad_resblock_forward.restype = C.c_int
+    lib.iefvad_resample_workspace_bytes.argtypes = [i32]
+    lib.iefvad_resample_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_resample_videos.argtypes = [vp, i32, C.POINTER(C.c_int32), i32, i32, i32, vp, C.c_size_t, vp, vp, vp]
+    lib.iefvad_resample_videos.restype = C.c_int
+    lib.iefvad_gather_windows.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.iefvad_gather_windows.restype = C.c_int
     lib.iefvad_gemm_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p]
     lib.iefvad_gemm_bias.restype = C.c_int

@@ -371,6 +371,31 @@ size_t iefvad_auc_ap_workspace_bytes(int64_t n);
 int iefvad_auc_ap(const float* scores, const uint8_t* gt_frames, int64_t n, int32_t repeat, double* auc, double* ap,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- training input pipeline ----------------------------------------------------------
+ * The reference's train-mode loader rule (/root/reference/data/tools.py:65-97: process_feat -> uniform_extract / pad) on the DEVICE:
+ * a video of n feature rows becomes one [256, D] fp32 window.  n <= 256: the rows, zero rows behind them, length n.  n > 256: 256
+ * segments with boundaries (i n) >> 8 (= np.linspace(0, n, 257, dtype=np.int32)), output row i = np.mean of its segment, length 256.
+ * The mean is numpy's bit for bit: an fp32 accumulator starting at +0, rows added in ascending order, one correctly rounded fp32
+ * division by the count; the quotient of an fp16 file is rounded to fp16 and widened again.  No NaN rule is applied.
+ *   rows        DEVICE [sum(lengths), D], IEFVAD_IN_F32 or IEFVAD_IN_F16: the videos' rows concatenated in list order, 16-byte aligned
+ *   lengths     HOST [nvideos], every entry >= 1; consumed before the call returns
+ *   T, D        T must be 256; D a multiple of 8 (768 and 512 occur)
+ *   workspace   DEVICE, iefvad_resample_workspace_bytes(nvideos) bytes (16 per video), 16-byte aligned
+ *   out         DEVICE [nvideos, 256, D] fp32, window v = video v whatever order the kernel takes them in (longest first)
+ *   out_lengths DEVICE int32 [nvideos]: min(lengths[v], 256)
+ * Enqueued on `stream`; the call waits for what `stream` held before it (the table upload), not for the resampling itself. */
+size_t iefvad_resample_workspace_bytes(int32_t nvideos);
+int iefvad_resample_videos(const void* rows, int32_t in_dtype, const int32_t* lengths, int32_t nvideos, int32_t T, int32_t D,
+                           void* workspace, size_t workspace_bytes, float* out, int32_t* out_lengths, void* stream);
+
+/* One training step's batch out of a cached set of windows, in ONE launch: img_out[b] = img_set[index[b]], ev_out[b] =
+ * ev_set[index[b]], len_out[b] = set_lengths[index[b]].  img_set, ev_set: DEVICE [nset, 256, D] fp32; set_lengths: DEVICE int32
+ * [nset]; index: DEVICE int32 [B], every entry in [0, nset) -- the caller checks that on the host; an entry outside it does not
+ * fault, it yields a zero window of length 0; img_out, ev_out: DEVICE [B, 256, D] fp32; len_out: DEVICE int32 [B].  T must be 256,
+ * D a multiple of 8, B <= 65535, the window tensors 16-byte aligned.  Enqueued on `stream`; returns without synchronising. */
+int iefvad_gather_windows(const float* img_set, const float* ev_set, const int32_t* set_lengths, int32_t nset, const int32_t* index,
+                          int32_t B, int32_t T, int32_t D, float* img_out, float* ev_out, int32_t* len_out, void* stream);
+
 /* ---- the VadCLIP-residue modules the north star names (SURVEY.md 8 rows a12 / a13 = f-5) ------------------------------------------
  * /root/reference/model/layers.py and /root/reference/model/module.py are dead code upstream (nothing imports them, a checkpoint holds
  * no key of theirs), so they are exposed at MODULE level: one entry per class, fp32, on the library's MFMA GEMM + LayerNorm kernels
