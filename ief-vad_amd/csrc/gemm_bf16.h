@@ -257,7 +257,12 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_bf16_v1_kernel(GemmBArgs a
 #else
 #define GB2_STORE(ptr, val) (*(ptr) = (val))
 #endif
-template <bool MF16, int PASSES>
+// DOT (the bf16x6 split kernels only) adds EPI_BIAS_RELU_DOT: the last refinement step's first projection, whose result h feeds
+// the scorer only through v . h (v = -lambda W2^T c, formed at iefvad_set_weights).  After bias and ReLU a lane multiplies its four
+// columns by v[ncol .. ncol + 3] and the 32 lanes of a row are summed by DPP in one fixed order; the sum over the wave tile's 128
+// columns goes to C2[row][column tile] as a plain store (no atomics: the scorer adds the N / 128 partials in ascending order, so a
+// row's logit never depends on which workgroup finished first).  h itself is stored only if C is non-null.
+template <bool MF16, int PASSES, bool DOT = false>
 __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const GemmBProblem& P, float* smem, int m0, int n0,
                                                    int wrow0, int wcol0, f32x16 (&acc)[PASSES][4],
                                                    f32x4 (&acc16)[2 * PASSES][8], float cscale = 1.0f, float* amax_out = nullptr) {
@@ -325,6 +330,44 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
             }
         }
         return;
+    }
+    if constexpr (DOT && MF16) {
+        if (epi == EPI_BIAS_RELU_DOT) {
+            const f32x4 dv = *(const f32x4*)(P.R + ncol);
+            float* part = P.C2 + (n0 + wcol0) / 128;
+            const int ntile = args.N / 128;
+#pragma unroll
+            for (int a = 0; a < PASSES; ++a) {
+                const int mrow = m0 + wrow0 + a * 32 + rq;
+#pragma unroll
+                for (int x = 0; x < 2; ++x)
+#pragma unroll
+                    for (int b = 0; b < 8; ++b)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            E[(x * 16 + 4 * q16 + r) * GB2_EPI_LD + b * 16 + r16] = acc16[2 * a + x][b][r];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    f32x4 v = *(const f32x4*)(E + (rq + 2 * u) * GB2_EPI_LD + 4 * cq);
+                    v = v * cscale + bv;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (v[e] < 0.f) ? 0.f : v[e];
+                    if (C32) GB2_STORE((f32x4*)(C32 + (size_t)(mrow + 2 * u) * ldc + ncol), v);
+                    float d = v[0] * dv[0];
+                    d += v[1] * dv[1];
+                    d += v[2] * dv[2];
+                    d += v[3] * dv[3];
+                    // the 32 lanes of the row (one half of the wave): wave_sum's first five steps; lanes 16..31 / 48..63 end with the sum
+                    d += dpp_take<0xB1, 0xF>(d, d);          // quad_perm [1,0,3,2]
+                    d += dpp_take<0x4E, 0xF>(d, d);          // quad_perm [2,3,0,1]
+                    d += dpp_take<0x141, 0xF>(d, d);         // row_half_mirror
+                    d += dpp_take<0x140, 0xF>(d, d);         // row_mirror
+                    d += dpp_take<0x142, 0xA>(0.f, d);       // row_bcast:15 into rows 1 and 3
+                    if (cq == 16) part[(size_t)(mrow + 2 * u) * ntile] = d;
+                }
+            }
+            return;
+        }
     }
 #pragma unroll
     for (int a = 0; a < PASSES; ++a) {

@@ -29,6 +29,8 @@ enum GemmEpilogue {
     EPI_REFINE = 4,      // C = R - alpha * (acc + bias)                      z - lambda * block(z)
     EPI_HEADS = 5,       // n < ldc: C = acc + bias ; n >= ldc: C2 = acc + bias   (mu | logvar heads share A; N = 2 ldc = 2 D)
     EPI_GATE = 6,        // C = R > 0 ? alpha * (acc + bias) : 0   (split kernel only: ReLU backward on the saved activation, train.h)
+    EPI_BIAS_RELU_DOT = 7,   // h = relu(acc + bias); C2[m][n / 128] = sum over the 128-column tile of h[m][n] * R[n]; C = h if non-null
+                             // (bf16x6 split kernel only: R is a vector [N], C2 is [M, N / 128]; the last refinement step, gemm_bf16.h)
 };
 
 struct GemmProblem {

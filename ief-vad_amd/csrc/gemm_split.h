@@ -455,7 +455,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmBArgs& args, float* sm
 #undef GLDS16
     // (the last tile ended with lgkmcnt(0) + barrier: the ring is dead, the epilogue image may overwrite it)
     f32x16 unused[NA / 2][4];
-    gemm_wave_epilogue<true, NA / 2>(args, P, smem, m0, n0, wrow0, wcol0, unused, acc16, cscale, F16 ? P.amaxC : nullptr);
+    gemm_wave_epilogue<true, NA / 2, !F16>(args, P, smem, m0, n0, wrow0, wcol0, unused, acc16, cscale, F16 ? P.amaxC : nullptr);
 #ifdef GB2_CLOCK_DIAG
     if (threadIdx.x == 0 && P.C2) {
         unsigned long long* dy = (unsigned long long*)P.C2 + 5 * gridDim.x * gridDim.z + 2 * (blockIdx.x + gridDim.x * blockIdx.z);

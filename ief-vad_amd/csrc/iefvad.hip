@@ -102,6 +102,7 @@ struct iefvad_handle {
     float* ref_b2[IEFVAD_MAX_STEPS];
     float* cls_w;
     float* cls_b;
+    float* score_fold;     // bf16x6, K >= 1: v = -lambda W2_K^T c [D] and s0 = b_c - lambda (c . b2_K) [1] of the folded scorer (rowops.h)
     // bf16 copies of the projection matrices (IEFVAD_COMPUTE_BF16 only)
     bf16_t* arena_b;
     bf16_t* in_wb[2][IEFVAD_MAX_LAYERS];
@@ -446,7 +447,7 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     if (!w->cls_w || !w->cls_b) return fail("iefvad_set_weights: null classifier weight");
 
     const size_t total = 2 * L * (3 * DD + 3 * D + DD + D + 2 * D) + 2 * (2 * D) + 2 * (2 * DD + 2 * D) +
-                         (size_t)K * (2 * DD + 2 * D) + D + 4;
+                         (size_t)K * (2 * DD + 2 * D) + D + 4 + (D + 4);
     if (!h->arena) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipMalloc((void**)&h->arena, total * sizeof(float)));
@@ -497,6 +498,16 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     HIP_TRY(put(&h->cls_w, w->cls_w, D));
     HIP_TRY(put(&h->cls_b, w->cls_b, 1));
     HIP_TRY(flush());
+    p += 3;                                      // back to a 16-byte boundary: the folded scorer's vector is read 16 bytes per lane
+    h->score_fold = nullptr;
+    if (h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && K >= 1) {
+        // the scores-only forward drops the last refinement projection: logits = c . z_{K-1} + v . h + s0 (forward_pass, step 4)
+        h->score_fold = p;
+        p += D + 4;
+        hipLaunchKernelGGL(iefvad_scorer_fold_weights_kernel, dim3((unsigned)(D / 16 + 1)), dim3(256), 0, stream, h->ref_w2[K - 1],
+                           h->ref_b2[K - 1], h->cls_w, h->cls_b, h->cfg.lambda_ref, h->score_fold, (int)D);
+        HIP_TRY(hipGetLastError());
+    }
     if ((size_t)(p - h->arena) > h->arena_floats) return fail("iefvad_set_weights: arena overflow");
     if (h->cfg.compute == IEFVAD_COMPUTE_BF16) {
         // bf16 (round-to-nearest-even) copies of every projection matrix; biases, LayerNorm and the scorer stay fp32
@@ -771,6 +782,8 @@ static bool split_eligible(int M, int N, int K, int nz) {
 static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false) {
     if (a.M % GS_BM || a.N % kSplitBN || a.K % 64 || a.K < 64)
         return fail("gemm(bf16x6): shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", a.M, a.N, a.K, GS_BM, kSplitBN);
+    if (a.epi == EPI_BIAS_RELU_DOT && (f16 || nz != 1 || !a.p[0].R || !a.p[0].C2))
+        return fail("gemm(bf16x6): the dot-product epilogue takes one bf16x6 problem with its vector (R) and its partial sums (C2)");
     dim3 grid((a.M / GS_BM) * (a.N / kSplitBN), 1, nz);
     hipEvent_t e = tm.begin(stage);
     if (f16) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
@@ -807,6 +820,8 @@ struct Proj {
 // D: the contraction length (the row width of A), the handle's embed dim
 static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage) {
     const bool bf16 = (compute == IEFVAD_COMPUTE_BF16);
+    if (p.epi == EPI_BIAS_RELU_DOT && !(use_split && compute == IEFVAD_COMPUTE_BF16X6))
+        return fail("gemm: the dot-product epilogue exists in the bf16x6 split kernel only");
     if (use_split) {   // one rule for every projection of a micro-batch: the 768-wide, single-problem grid fills the chip
         const bool f16 = (compute == IEFVAD_COMPUTE_FP16X3);
         GemmBArgs g;
@@ -1301,15 +1316,41 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
         if (chain)
             if (int rc = launch_refine_chain(h, z, out->fused ? z : nullptr, logits, rows, stream, tm)) return rc;
 
+        // bf16x6 on the split kernels: the last step's second projection is folded into the scorer,
+        //   logits = c . z_K + b_c = c . z_{K-1} + v . h + s0     (v, s0: iefvad_set_weights; rowops.h),
+        // v . h taken in the epilogue of the last step's FIRST projection (EPI_BIAS_RELU_DOT: six partial sums per row, into the y
+        // region, dead since the last LayerNorm).  Without `fused` in the outputs that projection stores no h and the last W2 launch
+        // does not run; with it, h is stored and z_K is formed as always, after the scorer has read z_{K-1} (EPI_REFINE updates z
+        // in place) -- so the logits of both output sets are the same bits.
+        const bool fold = tail_split && c.compute == IEFVAD_COMPUTE_BF16X6 && K >= 1;
+        float* const fold_part = ybuf[0];
+        auto launch_scorer_fold = [&]() -> int {
+            hipEvent_t e = tm.begin(ST_SCORER);
+            hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0,
+                               stream, z, h->cls_w, fold_part, h->score_fold, logits, rows);
+            tm.end(e);
+            HIP_TRY(hipGetLastError());
+            return 0;
+        };
+
         // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
         for (int k = 0; k < K && !chain; ++k) {
+            const bool dot = fold && k == K - 1;
             Proj p;
             memset(&p, 0, sizeof(p));
             p.N = (int)D; p.ldc = (int)D; p.epi = EPI_BIAS_RELU; p.nz = 1;
             p.A32[0] = z; p.A16[0] = zb; p.W32[0] = h->ref_w1[k]; p.W16[0] = h->ref_w1b[k]; p.Ws[0] = h->ref_w1s[k]; p.bias[0] = h->ref_b1[k];
             p.Wh[0] = h->ref_w1h[k]; p.amaxW[0] = h->ref_w1a[k]; p.amaxA[0] = am_z(k); p.amaxC[0] = am_h(k);
             p.C[0] = bf ? nullptr : hbuf; p.Cb[0] = bf ? hb : nullptr;
+            if (dot) {
+                p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
+                if (!out->fused) p.C[0] = nullptr;
+            }
             if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_REFINE)) return rc;
+            if (dot) {
+                if (int rc = launch_scorer_fold()) return rc;
+                if (!out->fused) break;
+            }
             memset(&p, 0, sizeof(p));
             p.N = (int)D; p.ldc = (int)D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
             p.A32[0] = hbuf; p.A16[0] = hb; p.W32[0] = h->ref_w2[k]; p.W16[0] = h->ref_w2b[k]; p.Ws[0] = h->ref_w2s[k]; p.bias[0] = h->ref_b2[k];
@@ -1319,7 +1360,7 @@ static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int3
         }
 
         // 5. scorer (imf_vad.py:150)
-        if (!chain) {
+        if (!chain && !fold) {
             hipEvent_t e = tm.begin(ST_SCORER);
             if (d512)
                 hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, z,

@@ -230,6 +230,63 @@ __global__ __launch_bounds__(256) void iefvad_scorer_kernel(const float* z, cons
     if (lane == 0) logits[row] = s + b[0];
 }
 
+// ---- scorer with the last refinement projection folded in (bf16x6 inference, iefvad.hip forward_pass):
+//   logits = c . z_K + b_c,  z_K = z_{K-1} - lambda (W2 h + b2)
+//          = c . z_{K-1} + v . h + s0,   v = -lambda W2^T c,  s0 = b_c - lambda (c . b2)      (fold[0 .. D-1] = v, fold[D] = s0)
+// c . z_{K-1} is taken exactly as iefvad_scorer_kernel takes c . z; v . h arrives as NPART per-column-tile partial sums per row from the
+// EPI_BIAS_RELU_DOT epilogue (gemm_bf16.h) and is added in ascending tile order, then s0.
+template <int D, int NPART>
+__global__ __launch_bounds__(256) void iefvad_scorer_fold_kernel(const float* z, const float* w, const float* part, const float* fold,
+                                                                  float* logits, int nrows) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * ROW_WAVES + (threadIdx.x >> 6);
+    if (row >= nrows) return;
+    const float* zp = z + (size_t)row * D + 4 * lane;
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < D / 256; ++j) {
+        const f32x4 zv = *(const f32x4*)(zp + 256 * j);
+        const f32x4 wv = *(const f32x4*)(w + 4 * lane + 256 * j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += zv[e] * wv[e];
+    }
+    s = wave_sum(s);
+    if (lane == 0) {
+        const float* pp = part + (size_t)row * NPART;
+#pragma unroll
+        for (int t = 0; t < NPART; ++t) s += pp[t];
+        logits[row] = s + fold[D];
+    }
+}
+
+// v and s0 of the folded scorer, once per iefvad_set_weights (a training step sets the weights every step, so this is a few
+// microseconds, not a 768-long dependent chain per thread): fp64 throughout, rounded once to fp32.  A workgroup takes 16 elements;
+// thread (seg = t >> 4, jj = t & 15) sums n = 48 seg .. 48 seg + 47 in ascending order, thread (0, jj) then adds the 16 segment sums
+// in ascending order -- a fixed order that no launch parameter changes.  Block b < D / 16: v[16 b + jj]; block D / 16: s0.  D = 768.
+#define FOLD_SEGS 16
+__global__ __launch_bounds__(256) void iefvad_scorer_fold_weights_kernel(const float* __restrict__ w2, const float* __restrict__ b2,
+                                                                         const float* __restrict__ c, const float* __restrict__ bc,
+                                                                         float lambda, float* __restrict__ fold, int D) {
+    __shared__ double part[FOLD_SEGS][16];
+    const int seg = threadIdx.x >> 4, jj = threadIdx.x & 15;
+    const int len = D / FOLD_SEGS, n0 = seg * len;
+    const bool is_s0 = (int)blockIdx.x == D / 16;
+    double s = 0.0;
+    if (!is_s0) {
+        const int j = blockIdx.x * 16 + jj;
+        for (int n = n0; n < n0 + len; ++n) s = __builtin_fma((double)c[n], (double)w2[(size_t)n * D + j], s);
+    } else if (jj == 0) {
+        for (int n = n0; n < n0 + len; ++n) s = __builtin_fma((double)c[n], (double)b2[n], s);
+    }
+    part[seg][jj] = s;
+    __syncthreads();
+    if (seg != 0 || (is_s0 && jj != 0)) return;
+    double t = 0.0;
+    for (int g = 0; g < FOLD_SEGS; ++g) t += part[g][jj];
+    if (!is_s0) fold[blockIdx.x * 16 + jj] = (float)(-(double)lambda * t);
+    else fold[D] = (float)((double)bc[0] - (double)lambda * t);
+}
+
 // ---- input cast: the reference's `.to(torch.float)` (imf_vad.py:41-42) for fp16 / bf16 feature files, and
 // the bf16 operand copies of the bf16-projection mode.  Two sources per launch (blockIdx.y), fp32 and/or
 // bf16 destinations (nullable).
