@@ -62,6 +62,19 @@ static int fail(const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
+// Every resident form of one projection matrix W [N, D] with its bias [N].  The fp32 pair lives in the handle's arena; each other
+// form is filled only in the arithmetic that reads it, in an arena of its own, by a walk in for_each_proj's order.
+struct ProjW {
+    int N;                 // output features: 3 D (in_proj), D (out_proj, refinement), 2 D (mu.weight stacked over logvar.weight)
+    float* w;
+    float* b;
+    bf16_t* wb;            // IEFVAD_COMPUTE_BF16: round-to-nearest-even copy
+    bf16_t* ws;            // IEFVAD_COMPUTE_BF16X6: three-plane split [3][N][D]
+    _Float16* wh;          // IEFVAD_COMPUTE_FP16X3: two scaled fp16 planes [2][N][D] ...
+    const float* wa;       // ... and the matrix's running-max word (in [0, kAmaxActBase) of amax_dev)
+    bf16_t* wst;           // bf16x6 training: three-plane split of the TRANSPOSE [3][D][N] (dX = dY W as an NT product; train.h)
+};
+
 struct iefvad_handle {
     iefvad_config cfg;
     int D, DH;             // embed dim and head dim: 768 / 96, or 512 / 64 (iefvad_create_ex: the f32 forward only)
@@ -85,56 +98,27 @@ struct iefvad_handle {
     char* chain_stream;    // bf16 mode: the refinement weights in the chain kernel's per-wave piece order (refine_chain_bf16.h)
     float* arena;          // one allocation holding every repacked weight
     size_t arena_floats;
-    // pointers into the arena
-    float* in_w[2][IEFVAD_MAX_LAYERS];
-    float* in_b[2][IEFVAD_MAX_LAYERS];
-    float* out_w[2][IEFVAD_MAX_LAYERS];
-    float* out_b[2][IEFVAD_MAX_LAYERS];
+    // the projection matrices, and the pointers of the other parameters into the arena
+    ProjW in[2][IEFVAD_MAX_LAYERS], out[2][IEFVAD_MAX_LAYERS], head[2], ref1[IEFVAD_MAX_STEPS], ref2[IEFVAD_MAX_STEPS];
     float* norm_w[2][IEFVAD_MAX_LAYERS];
     float* norm_b[2][IEFVAD_MAX_LAYERS];
     float* whiten_w[2];
     float* whiten_b[2];
-    float* head_w[2];      // [1536, 768] = mu.weight stacked over logvar.weight
-    float* head_b[2];      // [1536]
-    float* ref_w1[IEFVAD_MAX_STEPS];
-    float* ref_b1[IEFVAD_MAX_STEPS];
-    float* ref_w2[IEFVAD_MAX_STEPS];
-    float* ref_b2[IEFVAD_MAX_STEPS];
     float* cls_w;
     float* cls_b;
     float* score_fold;     // bf16x6, K >= 1: v = -lambda W2_K^T c [D] and s0 = b_c - lambda (c . b2_K) [1] of the folded scorer (rowops.h)
-    // bf16 copies of the projection matrices (IEFVAD_COMPUTE_BF16 only)
+    // the arenas of the ProjW forms: bf16 copies (BF16), three-plane splits (BF16X6), fp16 planes (FP16X3); amax_dev holds the
+    // running-max words of the matrices (filled at set_weights) and, behind them, of the activations of the current micro-batch
     bf16_t* arena_b;
-    bf16_t* in_wb[2][IEFVAD_MAX_LAYERS];
-    bf16_t* out_wb[2][IEFVAD_MAX_LAYERS];
-    bf16_t* head_wb[2];
-    bf16_t* ref_w1b[IEFVAD_MAX_STEPS];
-    bf16_t* ref_w2b[IEFVAD_MAX_STEPS];
-    // three-plane bf16 splits [3][N][768] of the projection matrices (IEFVAD_COMPUTE_BF16X6 only)
     bf16_t* arena_s;
-    bf16_t* in_ws[2][IEFVAD_MAX_LAYERS];
-    bf16_t* out_ws[2][IEFVAD_MAX_LAYERS];
-    bf16_t* head_ws[2];
-    bf16_t* ref_w1s[IEFVAD_MAX_STEPS];
-    bf16_t* ref_w2s[IEFVAD_MAX_STEPS];
-    // IEFVAD_COMPUTE_FP16X3: two scaled fp16 planes [2][N][768] per projection matrix, the running-max words of the
-    // matrices ([0, kAmaxActBase) of amax_dev, filled at set_weights) and of the activations of the current micro-batch
     _Float16* arena_h;
     float* amax_dev;
-    _Float16* in_wh[2][IEFVAD_MAX_LAYERS];  const float* in_wa[2][IEFVAD_MAX_LAYERS];
-    _Float16* out_wh[2][IEFVAD_MAX_LAYERS]; const float* out_wa[2][IEFVAD_MAX_LAYERS];
-    _Float16* head_wh[2];                   const float* head_wa[2];
-    _Float16* ref_w1h[IEFVAD_MAX_STEPS];    const float* ref_w1a[IEFVAD_MAX_STEPS];
-    _Float16* ref_w2h[IEFVAD_MAX_STEPS];    const float* ref_w2a[IEFVAD_MAX_STEPS];
     struct EventPool* events;   // hipEvents of iefvad_forward_timed, reused across calls
     struct GraphCache* graphs;  // hipGraphs of small-batch forwards (cfg.graph_chunks)
     struct MetaRing* meta;      // pinned / device metadata buffers of iefvad_forward_videos
     int num_cus;                // compute units of the device: grid size of the persistent row-block kernels
-    // training in the bf16x6 arithmetic: three-plane splits of the TRANSPOSED projection matrices ([3][768][n_out]: dX = dY W as an NT
-    // product on the split kernel), rebuilt by the first train-mode forward after every iefvad_set_weights (train.h)
+    // training in the bf16x6 arithmetic: the arena of ProjW::wst, rebuilt by the first backward after every iefvad_set_weights (train.h)
     bf16_t* arena_st; float* zero_bias; bool tplanes_valid;
-    bf16_t* in_wst[2][IEFVAD_MAX_LAYERS]; bf16_t* out_wst[2][IEFVAD_MAX_LAYERS]; bf16_t* head_wst[2];
-    bf16_t* ref_w1st[IEFVAD_MAX_STEPS]; bf16_t* ref_w2st[IEFVAD_MAX_STEPS];
     struct HostPipe* hostpipe;  // staging slots, copy stream and workspace of iefvad_forward_videos_host (hostpipe.h)
     struct TrainState* train;   // records of the train-mode forwards whose backward is outstanding (train.h)
     const float* row_scale[2];  // set for the duration of one iefvad_forward_scaled call: per-row input scales (image, event), nullable
@@ -154,6 +138,30 @@ static const int kDefaultMicroBatchBF16 = 1024;
 static int micro_batch(const iefvad_handle* h) {
     if (h->cfg.micro_batch > 0) return h->cfg.micro_batch < 16384 ? h->cfg.micro_batch : 16384;   // attention grid.z = 2 x chunks
     return h->cfg.compute == IEFVAD_COMPUTE_F32 ? kDefaultMicroBatchF32 : kDefaultMicroBatchBF16;
+}
+
+// The one walk over the projection matrices: modality -> layer -> {in, out}, then the heads; then step -> {W1, W2}.  Every derived
+// arena (bf16, planes, fp16 planes, transposed planes) is carved in this order, so the order fixes each pointer's offset (the kernels
+// assume 16-byte alignment), the fp16x3 running-max word of each matrix and the entry order of a SplitMany table.
+template <typename F>
+static int for_each_proj(iefvad_handle* h, F f) {
+    for (int m = 0; m < 2; ++m) {
+        for (int l = 0; l < h->cfg.num_layers; ++l) {
+            if (int rc = f(h->in[m][l])) return rc;
+            if (int rc = f(h->out[m][l])) return rc;
+        }
+        if (int rc = f(h->head[m])) return rc;
+    }
+    for (int k = 0; k < h->cfg.num_steps; ++k) {
+        if (int rc = f(h->ref1[k])) return rc;
+        if (int rc = f(h->ref2[k])) return rc;
+    }
+    return 0;
+}
+// elements of all the matrices for_each_proj visits
+static size_t proj_elems(const iefvad_handle* h) {
+    const size_t DD = (size_t)h->D * h->D;
+    return 2 * (size_t)h->cfg.num_layers * (3 * DD + DD) + 2 * (2 * DD) + (size_t)h->cfg.num_steps * 2 * DD;
 }
 
 extern "C" int iefvad_abi_version(void) { return IEFVAD_ABI_VERSION; }
@@ -334,6 +342,25 @@ extern "C" void iefvad_destroy(iefvad_handle* h) {
     delete h;
 }
 
+// The two run-time choices that pick template arguments, each made in one place.  dispatch_in calls f(element-type tag, width
+// constant) for an (input dtype, embed dim) pair and returns f's status; dispatch_d calls f(width constant).  In the callable:
+// `typename decltype(t)::type` is the element type, `decltype(w)::value` the row width.
+template <typename T> struct InType { using type = T; };
+template <int W> struct RowWidth { static constexpr int value = W; };
+template <typename F>
+static void dispatch_d(bool d512, F&& f) {
+    if (d512) f(RowWidth<IEF_D512>{});
+    else f(RowWidth<IEF_D>{});
+}
+template <typename F>
+static int dispatch_in(int in_dtype, bool d512, F&& f) {
+    int rc = 0;
+    dispatch_d(d512, [&](auto w) {
+        rc = in_dtype == IEFVAD_IN_F32 ? f(InType<float>{}, w) : in_dtype == IEFVAD_IN_F16 ? f(InType<__half>{}, w) : f(InType<__hip_bfloat16>{}, w);
+    });
+    return rc;
+}
+
 template <typename T>
 static int launch_cast(const void* in0, const void* in1, float* o0, float* o1, bf16_t* b0, bf16_t* b1, size_t n, int nsrc,
                        hipStream_t stream) {
@@ -473,27 +500,32 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     };
     for (int m = 0; m < 2; ++m) {
         for (int l = 0; l < L; ++l) {
-            HIP_TRY(put(&h->in_w[m][l], w->in_proj_w[m][l], 3 * DD));
-            HIP_TRY(put(&h->in_b[m][l], w->in_proj_b[m][l], 3 * D));
-            HIP_TRY(put(&h->out_w[m][l], w->out_proj_w[m][l], DD));
-            HIP_TRY(put(&h->out_b[m][l], w->out_proj_b[m][l], D));
+            ProjW& in = h->in[m][l];
+            ProjW& out = h->out[m][l];
+            in.N = 3 * (int)D; out.N = (int)D;
+            HIP_TRY(put(&in.w, w->in_proj_w[m][l], 3 * DD));
+            HIP_TRY(put(&in.b, w->in_proj_b[m][l], 3 * D));
+            HIP_TRY(put(&out.w, w->out_proj_w[m][l], DD));
+            HIP_TRY(put(&out.b, w->out_proj_b[m][l], D));
             HIP_TRY(put(&h->norm_w[m][l], w->norm_w[m][l], D));
             HIP_TRY(put(&h->norm_b[m][l], w->norm_b[m][l], D));
         }
         HIP_TRY(put(&h->whiten_w[m], w->whiten_w[m], D));
         HIP_TRY(put(&h->whiten_b[m], w->whiten_b[m], D));
         // mu | logvar heads share their A operand: stack them into one [1536, 768] projection
-        HIP_TRY(put(&h->head_w[m], w->mu_w[m], DD));
+        h->head[m].N = 2 * (int)D;
+        HIP_TRY(put(&h->head[m].w, w->mu_w[m], DD));
         float* dummy;
         HIP_TRY(put(&dummy, w->logvar_w[m], DD));
-        HIP_TRY(put(&h->head_b[m], w->mu_b[m], D));
+        HIP_TRY(put(&h->head[m].b, w->mu_b[m], D));
         HIP_TRY(put(&dummy, w->logvar_b[m], D));
     }
     for (int k = 0; k < K; ++k) {
-        HIP_TRY(put(&h->ref_w1[k], w->ref_w1[k], DD));
-        HIP_TRY(put(&h->ref_b1[k], w->ref_b1[k], D));
-        HIP_TRY(put(&h->ref_w2[k], w->ref_w2[k], DD));
-        HIP_TRY(put(&h->ref_b2[k], w->ref_b2[k], D));
+        h->ref1[k].N = h->ref2[k].N = (int)D;
+        HIP_TRY(put(&h->ref1[k].w, w->ref_w1[k], DD));
+        HIP_TRY(put(&h->ref1[k].b, w->ref_b1[k], D));
+        HIP_TRY(put(&h->ref2[k].w, w->ref_w2[k], DD));
+        HIP_TRY(put(&h->ref2[k].b, w->ref_b2[k], D));
     }
     HIP_TRY(put(&h->cls_w, w->cls_w, D));
     HIP_TRY(put(&h->cls_b, w->cls_b, 1));
@@ -504,43 +536,35 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
         // the scores-only forward drops the last refinement projection: logits = c . z_{K-1} + v . h + s0 (forward_pass, step 4)
         h->score_fold = p;
         p += D + 4;
-        hipLaunchKernelGGL(iefvad_scorer_fold_weights_kernel, dim3((unsigned)(D / 16 + 1)), dim3(256), 0, stream, h->ref_w2[K - 1],
-                           h->ref_b2[K - 1], h->cls_w, h->cls_b, h->cfg.lambda_ref, h->score_fold, (int)D);
+        hipLaunchKernelGGL(iefvad_scorer_fold_weights_kernel, dim3((unsigned)(D / 16 + 1)), dim3(256), 0, stream, h->ref2[K - 1].w,
+                           h->ref2[K - 1].b, h->cls_w, h->cls_b, h->cfg.lambda_ref, h->score_fold, (int)D);
         HIP_TRY(hipGetLastError());
     }
     if ((size_t)(p - h->arena) > h->arena_floats) return fail("iefvad_set_weights: arena overflow");
+    // the other resident forms, each one walk over the records (for_each_proj) that carves the form's arena in visiting order;
+    // biases, LayerNorm and the scorer stay fp32 in every arithmetic
+    const size_t nb = proj_elems(h);
     if (h->cfg.compute == IEFVAD_COMPUTE_BF16) {
-        // bf16 (round-to-nearest-even) copies of every projection matrix; biases, LayerNorm and the scorer stay fp32
-        const size_t nb = 2 * (size_t)L * (3 * DD + DD) + 2 * (2 * DD) + (size_t)K * 2 * DD;
+        // bf16 (round-to-nearest-even) copies
         if (!h->arena_b) HIP_TRY(hipMalloc((void**)&h->arena_b, nb * sizeof(bf16_t)));
         bf16_t* q = h->arena_b;
-        auto conv = [&](bf16_t** dst, const float* src, size_t n) -> int {
-            *dst = q;
-            q += n;
-            return launch_cast<float>(src, nullptr, nullptr, nullptr, *dst, nullptr, n, 1, stream);
-        };
-        for (int m = 0; m < 2; ++m) {
-            for (int l = 0; l < L; ++l) {
-                if (int rc = conv(&h->in_wb[m][l], h->in_w[m][l], 3 * DD)) return rc;
-                if (int rc = conv(&h->out_wb[m][l], h->out_w[m][l], DD)) return rc;
-            }
-            if (int rc = conv(&h->head_wb[m], h->head_w[m], 2 * DD)) return rc;
-        }
-        for (int k = 0; k < K; ++k) {
-            if (int rc = conv(&h->ref_w1b[k], h->ref_w1[k], DD)) return rc;
-            if (int rc = conv(&h->ref_w2b[k], h->ref_w2[k], DD)) return rc;
-        }
+        if (int rc = for_each_proj(h, [&](ProjW& r) {
+                const size_t n = r.N * D;
+                r.wb = q;
+                q += n;
+                return launch_cast<float>(r.w, nullptr, nullptr, nullptr, r.wb, nullptr, n, 1, stream);
+            })) return rc;
         for (int m = 0; m < 2; ++m)
             for (int l = 0; l < L; ++l) {
                 if (!h->oproj_stream[m][l]) HIP_TRY(hipMalloc((void**)&h->oproj_stream[m][l], wstream_bytes()));
-                hipLaunchKernelGGL(iefvad_wstream_pack_kernel, dim3(256), dim3(256), 0, stream, h->out_wb[m][l], h->oproj_stream[m][l], 1);
+                hipLaunchKernelGGL(iefvad_wstream_pack_kernel, dim3(256), dim3(256), 0, stream, h->out[m][l].wb, h->oproj_stream[m][l], 1);
                 HIP_TRY(hipGetLastError());
                 if (!h->iproj_stream[m][l]) HIP_TRY(hipMalloc((void**)&h->iproj_stream[m][l], wstream_bytes(IC_NPASS)));
-                hipLaunchKernelGGL(iefvad_wstream_pack_kernel, dim3(512), dim3(256), 0, stream, h->in_wb[m][l], h->iproj_stream[m][l], IC_NPASS);
+                hipLaunchKernelGGL(iefvad_wstream_pack_kernel, dim3(512), dim3(256), 0, stream, h->in[m][l].wb, h->iproj_stream[m][l], IC_NPASS);
                 HIP_TRY(hipGetLastError());
             }
         if (!h->heads_stream) HIP_TRY(hipMalloc((void**)&h->heads_stream, heads_stream_bytes()));
-        hipLaunchKernelGGL(iefvad_heads_pack_kernel, dim3(512), dim3(256), 0, stream, h->head_wb[0], h->head_wb[1], h->heads_stream);
+        hipLaunchKernelGGL(iefvad_heads_pack_kernel, dim3(512), dim3(256), 0, stream, h->head[0].wb, h->head[1].wb, h->heads_stream);
         HIP_TRY(hipGetLastError());
         if (K > 0) {
             // the same bf16 matrices (and the fp32 biases) once more, in the chain kernel's per-wave piece order
@@ -548,8 +572,8 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
             ChainPackArgs pa;
             memset(&pa, 0, sizeof(pa));
             for (int k = 0; k < K; ++k) {
-                pa.W[2 * k] = h->ref_w1b[k]; pa.bias[2 * k] = h->ref_b1[k];
-                pa.W[2 * k + 1] = h->ref_w2b[k]; pa.bias[2 * k + 1] = h->ref_b2[k];
+                pa.W[2 * k] = h->ref1[k].wb; pa.bias[2 * k] = h->ref1[k].b;
+                pa.W[2 * k + 1] = h->ref2[k].wb; pa.bias[2 * k + 1] = h->ref2[k].b;
             }
             pa.stream = h->chain_stream;
             pa.K = K;
@@ -558,61 +582,39 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
         }
     }
     if (h->cfg.compute == IEFVAD_COMPUTE_BF16X6) {
-        // exact three-term bf16 split of every projection matrix (gemm_split.h); biases, LayerNorm, scorer stay fp32
-        const size_t nb = 2 * (size_t)L * (3 * DD + DD) + 2 * (2 * DD) + (size_t)K * 2 * DD;
+        // exact three-term bf16 split (gemm_split.h)
         if (!h->arena_s) HIP_TRY(hipMalloc((void**)&h->arena_s, 3 * nb * sizeof(bf16_t)));
         bf16_t* q = h->arena_s;
         SplitMany sm(stream);                 // all 10 + 2 K matrices in one launch (two from K = 12 on)
-        auto split = [&](bf16_t** dst, const float* src, size_t n) -> int {
-            *dst = q;
-            q += 3 * n;
-            return sm.add(src, *dst, n, 0);
-        };
-        for (int m = 0; m < 2; ++m) {
-            for (int l = 0; l < L; ++l) {
-                if (int rc = split(&h->in_ws[m][l], h->in_w[m][l], 3 * DD)) return rc;
-                if (int rc = split(&h->out_ws[m][l], h->out_w[m][l], DD)) return rc;
-            }
-            if (int rc = split(&h->head_ws[m], h->head_w[m], 2 * DD)) return rc;
-        }
-        for (int k = 0; k < K; ++k) {
-            if (int rc = split(&h->ref_w1s[k], h->ref_w1[k], DD)) return rc;
-            if (int rc = split(&h->ref_w2s[k], h->ref_w2[k], DD)) return rc;
-        }
+        if (int rc = for_each_proj(h, [&](ProjW& r) {
+                const size_t n = r.N * D;
+                r.ws = q;
+                q += 3 * n;
+                return sm.add(r.w, r.ws, n, 0);
+            })) return rc;
         if (int rc = sm.flush()) return rc;
     }
     if (h->cfg.compute == IEFVAD_COMPUTE_FP16X3) {
-        // two fp16 planes per projection matrix, scaled by a power of two from the matrix's max |w| (gemm_split.h, F16)
-        const size_t nb = 2 * (size_t)L * (3 * DD + DD) + 2 * (2 * DD) + (size_t)K * 2 * DD;
+        // two fp16 planes, scaled by a power of two from the matrix's max |w| (gemm_split.h, F16)
         if (!h->arena_h) HIP_TRY(hipMalloc((void**)&h->arena_h, 2 * nb * sizeof(_Float16)));
         HIP_TRY(hipMemsetAsync(h->amax_dev, 0, kAmaxActBase * IEF_AMAX_FLOATS * sizeof(float), stream));
         _Float16* q = h->arena_h;
         int widx = 0;
-        auto split = [&](_Float16** dst, const float** amax, const float* src, size_t n) -> int {
-            if (widx >= kAmaxActBase) return fail("iefvad_set_weights: too many projection matrices");
-            *dst = q;
-            q += 2 * n;
-            float* word = h->amax_dev + IEF_AMAX_FLOATS * widx++;
-            *amax = word;
-            size_t blocks = (n / 4 + 255) / 256;
-            if (blocks > 1024) blocks = 1024;
-            hipLaunchKernelGGL(iefvad_amax_kernel, dim3((unsigned)blocks, 1), dim3(256), 0, stream, src, src, word, word, n);
-            hipLaunchKernelGGL(iefvad_split_planes_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src, *dst, n,
-                               (const float*)word);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        };
-        for (int m = 0; m < 2; ++m) {
-            for (int l = 0; l < L; ++l) {
-                if (int rc = split(&h->in_wh[m][l], &h->in_wa[m][l], h->in_w[m][l], 3 * DD)) return rc;
-                if (int rc = split(&h->out_wh[m][l], &h->out_wa[m][l], h->out_w[m][l], DD)) return rc;
-            }
-            if (int rc = split(&h->head_wh[m], &h->head_wa[m], h->head_w[m], 2 * DD)) return rc;
-        }
-        for (int k = 0; k < K; ++k) {
-            if (int rc = split(&h->ref_w1h[k], &h->ref_w1a[k], h->ref_w1[k], DD)) return rc;
-            if (int rc = split(&h->ref_w2h[k], &h->ref_w2a[k], h->ref_w2[k], DD)) return rc;
-        }
+        if (int rc = for_each_proj(h, [&](ProjW& r) -> int {
+                if (widx >= kAmaxActBase) return fail("iefvad_set_weights: too many projection matrices");
+                const size_t n = r.N * D;
+                r.wh = q;
+                q += 2 * n;
+                float* word = h->amax_dev + IEF_AMAX_FLOATS * widx++;
+                r.wa = word;
+                size_t blocks = (n / 4 + 255) / 256;
+                if (blocks > 1024) blocks = 1024;
+                hipLaunchKernelGGL(iefvad_amax_kernel, dim3((unsigned)blocks, 1), dim3(256), 0, stream, r.w, r.w, word, word, n);
+                hipLaunchKernelGGL(iefvad_split_planes_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, r.w, r.wh, n,
+                                   (const float*)word);
+                HIP_TRY(hipGetLastError());
+                return 0;
+            })) return rc;
     }
     h->weights_set = true;
     h->tplanes_valid = false;
@@ -815,6 +817,10 @@ struct Proj {
     int N, ldc, epi, nz;
     float alpha;
     int qcols;
+    // problem m takes its weight, in every resident form, and its bias from one record
+    void set_w(int m, const ProjW& r) {
+        W32[m] = r.w; W16[m] = r.wb; Ws[m] = r.ws; Wh[m] = r.wh; amaxW[m] = r.wa; bias[m] = r.b;
+    }
 };
 
 // D: the contraction length (the row width of A), the handle's embed dim
@@ -866,7 +872,7 @@ static int launch_inproj_chain(iefvad_handle* h, int l, const void* const A[2], 
     memset(&ia, 0, sizeof(ia));
     for (int m = 0; m < 2; ++m) {
         ia.p[m].A = A[m];
-        ia.p[m].stream = h->iproj_stream[m][l]; ia.p[m].bias = h->in_b[m][l]; ia.p[m].C = C[m];
+        ia.p[m].stream = h->iproj_stream[m][l]; ia.p[m].bias = h->in[m][l].b; ia.p[m].C = C[m];
     }
     // q is pre-scaled for the softmax by log2(e)/sqrt(96): both attention kernels use exp2
     ia.M = rows; ia.alpha = (1.0f / sqrtf((float)IEF_DH)) * 1.4426950408889634f; ia.wave_stride = (unsigned)wstream_wave_stride_bytes(IC_NPASS);
@@ -885,7 +891,7 @@ static int launch_outproj_ln_chain(iefvad_handle* h, int l, bool whiten, const b
     memset(&oa, 0, sizeof(oa));
     for (int m = 0; m < 2; ++m) {
         OutLnChainProblem& q = oa.p[m];
-        q.A = A[m]; q.stream = h->oproj_stream[m][l]; q.bias = h->out_b[m][l]; q.R = R[m];
+        q.A = A[m]; q.stream = h->oproj_stream[m][l]; q.bias = h->out[m][l].b; q.R = R[m];
         q.g1 = h->norm_w[m][l]; q.b1 = h->norm_b[m][l];
         if (whiten) { q.g2 = h->whiten_w[m]; q.b2 = h->whiten_b[m]; }
         q.y = y[m];
@@ -930,7 +936,7 @@ static void launch_attention_bf16(iefvad_handle* h, const bf16_t* const qkv[2], 
 
 // `ha` arrives with its tensors filled in; the stream, scalars and the kernel choice are set here
 static int launch_heads_chain(iefvad_handle* h, HeadsChainArgs& ha, int rows, float factor, hipStream_t stream, Timer& tm) {
-    for (int m = 0; m < 2; ++m) ha.bias[m] = h->head_b[m];
+    for (int m = 0; m < 2; ++m) ha.bias[m] = h->head[m].b;
     ha.stream = h->heads_stream;
     ha.M = rows; ha.factor = factor; ha.eps = h->cfg.epsilon; ha.wave_stride = (unsigned)heads_stream_wave_stride_bytes();
     // from two blocks per workgroup on: the persistent kernel (heads_pchain_bf16.h: one workgroup per CU and column third, both
@@ -978,414 +984,410 @@ struct RaggedPass {
     float* w_e_mean;
 };
 
+// The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it.
+struct PassBuffers {
+    int nb, rows;             // chunks; rows of the current row set (the compaction step shrinks it)
+    size_t R;                 // region stride in rows: the dense capacity nb * 256
+    bool enc_rows_mode;       // row-compressed chunks: valid rows + one pad row each
+    bool ip_chain;            // bf16 mode, full grids: in_proj on the row-block kernel (inproj_chain_bf16.h); its first layer reads the fp32 rows
+    bool need_xb0;            // bf16 mode also needs the bf16 copy of the inputs (unless ip_chain)
+    bool splitmb, f16mb;      // the split kernels take this micro-batch's projections; ... in the fp16x3 arithmetic
+    bool compacted, tail_split;
+    // workspace regions, in units of R*D floats: xin 0..2 | qkv 2..8 | att 8..10 | y 10..12 | x 12..14 | logits
+    float *xin[2], *qkv[2], *att[2], *ybuf[2], *xbuf[2];
+    bf16_t *qkvb[2], *attb[2], *xb[2];      // bf16 mode: q|k|v as bf16 in the qkv region; the att region holds attb | xb
+    float* lg_scratch;        // R floats; the 3 R behind it (ws_floats_per_row) hold the ragged path's row means
+    // tail buffers: the caller's tensors, else aliases of the (dead by then) qkv region: mu_i lv_i mu_e lv_e z | h  (bf16 mode: hb, zb in h's slot)
+    float *mu_i, *lv_i, *mu_e, *lv_e, *z, *hbuf, *n_i, *n_e, *logits, *wim_out, *wem_out;
+    bf16_t *hb, *zb;
+    const float* cur[2];      // the encoder's current fp32 rows: the inputs, then each layer's output
+    const float* xt[2];       // the tail's fp32 / bf16 A operands
+    const bf16_t* xtb[2];
+    // fp16x3: the running-max words of this micro-batch's activations (one word per tensor that feeds a projection); activation
+    // tensor t owns IEF_AMAX_PARTS words per chunk of the micro-batch
+    float* am; size_t mbs; int L, K;
+    float* am_t(int t) const { return f16mb ? am + mbs * t : nullptr; }
+    float* am_in(int m) const { return am_t(m); }
+    float* am_att(int l, int m) const { return am_t(2 + 6 * l + m); }
+    float* am_x(int l, int m) const { return am_t(2 + 6 * l + 2 + m); }
+    float* am_qkv(int l, int m) const { return am_t(2 + 6 * l + 4 + m); }
+    float* am_z(int k) const { return am_t(2 + 6 * L + k); }
+    float* am_h(int k) const { return am_t(2 + 6 * L + (K + 1) + k); }
+};
+
+static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, void* workspace, const iefvad_outputs* out, const RaggedPass* rg) {
+    const iefvad_config& c = h->cfg;
+    const size_t D = h->D, R = (size_t)nb * IEF_T;
+    PassBuffers b;
+    memset(&b, 0, sizeof(b));
+    b.nb = nb; b.R = R;
+    b.enc_rows_mode = rg && rg->enc_rows > 0;
+    b.rows = b.enc_rows_mode ? rg->enc_rows : nb * IEF_T;
+    float* ws = (float*)workspace;
+    float* t0 = ws + 2 * R * D;
+    for (int m = 0; m < 2; ++m) {
+        b.xin[m] = ws + m * R * D;
+        b.qkv[m] = t0 + 3 * m * R * D;
+        b.qkvb[m] = (bf16_t*)t0 + 3 * m * R * D;
+        b.att[m] = ws + (8 + m) * R * D;
+        b.attb[m] = (bf16_t*)(ws + 8 * R * D) + m * R * D;
+        b.xb[m] = (bf16_t*)(ws + 9 * R * D) + m * R * D;
+        b.ybuf[m] = ws + (10 + m) * R * D;
+        b.xbuf[m] = ws + (12 + m) * R * D;
+        b.xt[m] = b.xbuf[m];
+        b.xtb[m] = b.xb[m];
+    }
+    b.lg_scratch = ws + 14 * R * D;
+    b.mu_i = out->image_mu ? out->image_mu + row0 * D : t0;
+    b.lv_i = out->image_logvar ? out->image_logvar + row0 * D : t0 + R * D;
+    b.mu_e = out->event_mu ? out->event_mu + row0 * D : t0 + 2 * R * D;
+    b.lv_e = out->event_logvar ? out->event_logvar + row0 * D : t0 + 3 * R * D;
+    b.z = out->fused ? out->fused + row0 * D : t0 + 4 * R * D;
+    b.hbuf = t0 + 5 * R * D;
+    b.hb = (bf16_t*)b.hbuf; b.zb = b.hb + R * D;
+    b.n_i = out->w_i ? out->w_i + row0 * D : nullptr;
+    b.n_e = out->w_e ? out->w_e + row0 * D : nullptr;
+    b.logits = out->logits ? out->logits + row0 : b.lg_scratch;
+    b.wim_out = out->w_i_mean ? out->w_i_mean + row0 : nullptr;
+    b.wem_out = out->w_e_mean ? out->w_e_mean + row0 : nullptr;
+    if (rg) {                                     // per-row results of the pass land in scratch, then in rg's packed vectors
+        b.logits = b.lg_scratch;
+        b.wim_out = rg->w_i_mean ? b.lg_scratch + R : nullptr;
+        b.wem_out = rg->w_e_mean ? b.lg_scratch + 2 * R : nullptr;
+    }
+    b.ip_chain = c.compute == IEFVAD_COMPUTE_BF16 && !h->no_inproj_chain && b.rows % IC_BM == 0 && (b.rows / IC_BM) * 2 >= h->rowblock_min_wgs;
+    b.need_xb0 = c.compute == IEFVAD_COMPUTE_BF16 && !b.ip_chain;
+    b.splitmb = (c.compute == IEFVAD_COMPUTE_BF16X6 || c.compute == IEFVAD_COMPUTE_FP16X3) && split_eligible(b.rows, IEF_D, IEF_D, 1);
+    b.f16mb = b.splitmb && c.compute == IEFVAD_COMPUTE_FP16X3;
+    b.am = h->amax_dev ? h->amax_dev + kAmaxActBase * IEF_AMAX_FLOATS : nullptr;
+    b.mbs = (size_t)micro_batch(h) * IEF_AMAX_PARTS;
+    b.L = c.num_layers; b.K = c.num_steps;
+    return b;
+}
+
+// 0. inputs: `.to(torch.float)` (imf_vad.py:41-42) into b.cur; bf16 mode also gets the bf16 operand copy (b.need_xb0)
+static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const void* pi, const void* pe, int32_t in_dtype, size_t row0, const RaggedPass* rg,
+                            hipStream_t stream, Timer& tm) {
+    const size_t D = h->D, n = b.R * D;
+    const bool d512 = h->D == IEF_D512;
+    bf16_t* const b0p = b.need_xb0 ? b.xb[0] : nullptr;
+    bf16_t* const b1p = b.need_xb0 ? b.xb[1] : nullptr;
+    b.cur[0] = b.xin[0]; b.cur[1] = b.xin[1];
+    if (rg) {
+        // the chunker (tools.py:100-114) and the conditional nan_to_num (test.py:90-95) on the device: ragged.h
+        if (b.enc_rows_mode && rg->enc_used_rows < b.rows) {     // the zero rows that round the set up to whole 256-row tiles
+            const size_t o = (size_t)rg->enc_used_rows * D, nz = (size_t)(b.rows - rg->enc_used_rows) * D;
+            for (int m = 0; m < 2; ++m) {
+                HIP_TRY(hipMemsetAsync(b.xin[m] + o, 0, nz * sizeof(float), stream));
+                if (b.need_xb0) HIP_TRY(hipMemsetAsync(b.xb[m] + o, 0, nz * sizeof(bf16_t), stream));
+            }
+        }
+        hipEvent_t e = tm.begin(ST_CAST);
+        // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
+        // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
+        dispatch_in(in_dtype, d512, [&](auto t, auto w) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((iefvad_scatter_rows_kernel<T, decltype(w)::value>), dim3(b.nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream,
+                               (const T*)rg->img_rows, (const T*)rg->ev_rows, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p,
+                               b.enc_rows_mode ? 0 : IEF_T);
+            return 0;
+        });
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    } else if (h->row_scale[0] || h->row_scale[1]) {
+        // iefvad_forward_scaled: the rows pass through the cast kernel whatever their type, scaled on the way (rowops.h)
+        hipEvent_t e = tm.begin(ST_CAST);
+        const float* s0 = h->row_scale[0] ? h->row_scale[0] + row0 : nullptr;
+        const float* s1 = h->row_scale[1] ? h->row_scale[1] + row0 : nullptr;
+        const int rc = dispatch_in(in_dtype, d512, [&](auto t, auto w) {
+            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, s0, s1, stream);
+        });
+        tm.end(e);
+        if (rc) return rc;
+    } else if (in_dtype == IEFVAD_IN_F32) {
+        b.cur[0] = (const float*)pi; b.cur[1] = (const float*)pe;
+        if (b.need_xb0) {
+            hipEvent_t e = tm.begin(ST_CAST);
+            const int rc = launch_cast<float>(pi, pe, nullptr, nullptr, b.xb[0], b.xb[1], n, 2, stream);
+            tm.end(e);
+            if (rc) return rc;
+        }
+    } else {
+        hipEvent_t e = tm.begin(ST_CAST);
+        const int rc = dispatch_in(in_dtype, d512, [&](auto t, auto) {
+            return launch_cast<typename decltype(t)::type>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, 2, stream);
+        });
+        tm.end(e);
+        if (rc) return rc;
+    }
+    if (b.f16mb) {
+        HIP_TRY(hipMemsetAsync(b.am, 0, (size_t)amax_act_tensors(b.L, b.K) * b.mbs * sizeof(float), stream));
+        hipEvent_t e = tm.begin(ST_CAST);
+        hipLaunchKernelGGL(iefvad_amax_chunk_kernel, dim3(b.nb, 2), dim3(256), 0, stream, b.cur[0], b.cur[1], b.am_in(0), b.am_in(1));
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+// 1. one layer of the temporal encoder (imf_vad.py:113-123): in_proj, attention, out_proj + residual, LayerNorm; b.cur moves to its output
+static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+    const iefvad_config& c = h->cfg;
+    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
+    const int D = h->D, L = c.num_layers, rows = b.rows, nb = b.nb;
+    const bool d512 = h->D == IEF_D512;      // iefvad_create_ex: f32 arithmetic only, so every bf16 / split branch below is 768-wide
+    const RaggedChunk* enc_chunks = b.enc_rows_mode ? rg->d_chunks : nullptr;
+    Proj p;
+    if (b.ip_chain) {
+        const void* ipA[2] = {(l == 0) ? (const void*)b.cur[0] : (const void*)b.xb[0], (l == 0) ? (const void*)b.cur[1] : (const void*)b.xb[1]};
+        if (int rc = launch_inproj_chain(h, l, ipA, l == 0, b.qkvb, rows, stream, tm)) return rc;
+    } else {
+        memset(&p, 0, sizeof(p));
+        p.N = 3 * D; p.ldc = 3 * D; p.epi = EPI_QKV; p.qcols = D; p.nz = 2;
+        // q is pre-scaled for the softmax by log2(e)/sqrt(d_h): both attention kernels use exp2
+        p.alpha = 1.0f / sqrtf((float)h->DH) * 1.4426950408889634f;
+        for (int m = 0; m < 2; ++m) {
+            p.set_w(m, h->in[m][l]);
+            p.A32[m] = b.cur[m]; p.A16[m] = b.xb[m]; p.amaxA[m] = l == 0 ? b.am_in(m) : b.am_x(l - 1, m);
+            p.amaxC[m] = b.am_qkv(l, m);
+            if (bf) p.Cb[m] = b.qkvb[m]; else p.C[m] = b.qkv[m];
+        }
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV)) return rc;
+    }
+
+    hipEvent_t e = tm.begin(ST_ATT);
+    if (bf) {
+        launch_attention_bf16(h, b.qkvb, b.attb, nb, enc_chunks, b.ip_chain, rows, stream);
+    } else {
+        AttnArgs aa;
+        memset(&aa, 0, sizeof(aa));
+        for (int m = 0; m < 2; ++m) { aa.qkv[m] = b.qkv[m]; aa.out[m] = b.att[m]; }
+        aa.nchunks = nb;
+        aa.chunks = enc_chunks;
+        // bf16x6: the split attention kernel goes with the split projections (same batch-size rule), so a small
+        // batch is computed exactly as in the f32 mode
+        for (int m = 0; m < 2; ++m) { aa.amax[m] = b.am_att(l, m); aa.amax_in[m] = b.am_qkv(l, m); }
+        void (*const kernel)(AttnArgs) = b.f16mb    ? iefvad_attention_split_f16_kernel
+                                         : b.splitmb ? (enc_chunks ? iefvad_attention_split_rows_kernel : iefvad_attention_split_kernel)
+                                         : d512      ? (enc_chunks ? iefvad_attention_f32_rows_d64_kernel : iefvad_attention_f32_d64_kernel)
+                                                     : (enc_chunks ? iefvad_attention_f32_rows_kernel : iefvad_attention_f32_kernel);
+        hipLaunchKernelGGL(kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), b.splitmb ? ATS_LDS_BYTES : 0, stream, aa);
+    }
+    tm.end(e);
+    HIP_TRY(hipGetLastError());
+
+    // out_proj + residual + LayerNorm(s) in one row-owning kernel (bf16 mode, full grids): 64-row blocks on the refinement chain's
+    // structure (outproj_ln_chain_bf16.h); same bits as the GEMM + LayerNorm kernels
+    const bool ln_fused = bf && !h->no_ln_fusion && rows % OC_BM == 0 && (rows / OC_BM) * 2 >= h->rowblock_min_wgs;
+    if (ln_fused) {
+        float* oy[2] = {(l < L - 1) ? b.xbuf[0] : nullptr, (l < L - 1) ? b.xbuf[1] : nullptr};      // fp32 rows are only the next layer's residual
+        if (int rc = launch_outproj_ln_chain(h, l, l == L - 1, b.attb, b.cur, oy, b.xb, rows, stream, tm)) return rc;
+    } else {
+        memset(&p, 0, sizeof(p));
+        p.N = D; p.ldc = D; p.epi = EPI_BIAS_RESID; p.nz = 2;
+        for (int m = 0; m < 2; ++m) {
+            p.set_w(m, h->out[m][l]);
+            p.A32[m] = b.att[m]; p.A16[m] = b.attb[m]; p.amaxA[m] = b.am_att(l, m);
+            p.C[m] = b.ybuf[m]; p.R[m] = b.cur[m];
+        }
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT)) return rc;
+
+        LnArgs la;
+        memset(&la, 0, sizeof(la));
+        la.nrows = rows; la.eps = 1e-5f;
+        for (int m = 0; m < 2; ++m) {
+            la.x[m] = b.ybuf[m]; la.g1[m] = h->norm_w[m][l]; la.b1[m] = h->norm_b[m][l];
+            if (l == L - 1) { la.g2[m] = h->whiten_w[m]; la.b2[m] = h->whiten_b[m]; }   // whitening LN, :117,:123
+            // fp32 mode: x feeds both the next projection and the next residual; bf16 mode: the bf16 copy feeds the
+            // projection, the fp32 tensor is only the next layer's residual (not needed after the last layer)
+            la.y[m] = (!bf || l < L - 1) ? b.xbuf[m] : nullptr;
+            la.yb[m] = bf ? b.xb[m] : nullptr;
+            la.amax[m] = b.am_x(l, m);
+        }
+        e = tm.begin(ST_LN);
+        dispatch_d(d512, [&](auto w) {
+            hipLaunchKernelGGL(iefvad_layernorm_kernel<decltype(w)::value>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
+        });
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
+    b.cur[0] = b.xbuf[0]; b.cur[1] = b.xbuf[1];
+    return 0;
+}
+
+// Ragged pass with whole chunks in the encoder (IEFVAD_DENSE_ENCODER=1): everything behind the encoder is row-wise
+// (imf_vad.py:125-150) and the reference slices the pad rows away (test.py:121), so the valid rows of the last
+// LayerNorm's output are gathered (packed order, padded with zero rows to whole 256-row tiles) and b.rows shrinks to
+// that count from here on.  fp16x3 keeps whole chunks: its operand scales are per chunk.  The compact operands live in
+// the attention-output region, dead by now.  (Row-compressed chunks, the default: the tail runs on the encoder's row set.)
+static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+    const bool bf = (h->cfg.compute == IEFVAD_COMPUTE_BF16);
+    const size_t D = h->D;
+    if (rg && !b.enc_rows_mode && h->cfg.compute != IEFVAD_COMPUTE_FP16X3) {
+        const int mc = (rg->valid_rows + 255) / 256 * 256;
+        if (mc < b.rows) {
+            CompactArgs ca;
+            memset(&ca, 0, sizeof(ca));
+            for (int m = 0; m < 2; ++m) {
+                if (bf) { ca.xb[m] = b.xb[m]; ca.xcb[m] = b.attb[m]; b.xtb[m] = b.attb[m]; }
+                else { ca.x[m] = b.xbuf[m]; ca.xc[m] = b.att[m]; b.xt[m] = b.att[m]; }
+            }
+            ca.chunks = rg->d_chunks;
+            const size_t tail0 = (size_t)rg->valid_rows * D, tailn = (size_t)(mc - rg->valid_rows) * D;
+            if (tailn)
+                for (int m = 0; m < 2; ++m)
+                    HIP_TRY(bf ? hipMemsetAsync(b.attb[m] + tail0, 0, tailn * sizeof(bf16_t), stream)
+                               : hipMemsetAsync(b.att[m] + tail0, 0, tailn * sizeof(float), stream));
+            hipEvent_t e = tm.begin(ST_CAST);
+            dispatch_d(h->D == IEF_D512, [&](auto w) {
+                hipLaunchKernelGGL(iefvad_compact_rows_kernel<decltype(w)::value>, dim3(b.nb, 2), dim3(256), 0, stream, ca);
+            });
+            tm.end(e);
+            HIP_TRY(hipGetLastError());
+            b.rows = mc;
+            b.compacted = true;
+        }
+    }
+    b.tail_split = b.splitmb && (!b.compacted || split_eligible(b.rows, IEF_D, IEF_D, 1));   // bf16x6: a small compact set runs on the fp32 kernels
+    return 0;
+}
+
+// 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer; a ragged pass then writes its rows out
+static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+    const iefvad_config& c = h->cfg;
+    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
+    const int D = h->D, L = c.num_layers, K = c.num_steps, rows = b.rows;
+    const bool d512 = h->D == IEF_D512;
+    const float factor = (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;   // imf_vad.py:134
+    const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
+    float* const z = b.z;
+
+    // 2 + 3 in one kernel (bf16 mode, full grids): heads of both modalities + fusion on the row-block structure (heads_chain_bf16.h).
+    // The four head tensors are stored only if the caller asked for them.
+    const bool heads_rows = bf && !h->no_heads_fusion && h->heads_stream && rows % HC_BM == 0 && (rows / HC_BM) * HC_THIRDS >= h->rowblock_min_wgs;
+    // 4 + 5 in one kernel (bf16 mode): the K refinement steps and the scorer with the state on chip, refine_chain_bf16.h
+    const bool chain = bf && K > 0 && !h->no_chain && h->chain_stream && rows % RC_BM == 0 && rows / RC_BM >= h->chain_min_blocks;
+    if (heads_rows) {
+        HeadsChainArgs ha;
+        memset(&ha, 0, sizeof(ha));
+        for (int m = 0; m < 2; ++m) ha.A[m] = b.xtb[m];
+        ha.mu[0] = out->image_mu ? b.mu_i : nullptr; ha.lv[0] = out->image_logvar ? b.lv_i : nullptr;
+        ha.mu[1] = out->event_mu ? b.mu_e : nullptr; ha.lv[1] = out->event_logvar ? b.lv_e : nullptr;
+        ha.n[0] = b.n_i; ha.n[1] = b.n_e;
+        ha.z = z;
+        ha.zb = chain ? nullptr : b.zb;
+        const bool means = b.wim_out || b.wem_out;
+        ha.nsum_part = means ? b.ybuf[0] : nullptr;        // y is dead after the last LayerNorm: 48 of its 768 floats per row
+        if (int rc = launch_heads_chain(h, ha, rows, factor, stream, tm)) return rc;
+        if (means) {
+            hipEvent_t e = tm.begin(ST_FUSION);
+            hipLaunchKernelGGL(iefvad_rowmean_finish_kernel, dim3((2 * rows + 255) / 256), dim3(256), 0, stream, ha.nsum_part,
+                               b.wim_out, b.wem_out, rows, HC_NPART);
+            tm.end(e);
+            HIP_TRY(hipGetLastError());
+        }
+    } else {
+        // 2. mu / logvar heads (imf_vad.py:125-128): one [768 -> 1536] projection per modality
+        Proj p;
+        memset(&p, 0, sizeof(p));
+        p.N = 2 * D; p.ldc = D; p.epi = EPI_HEADS; p.nz = 2;
+        for (int m = 0; m < 2; ++m) {
+            p.set_w(m, h->head[m]);
+            p.A32[m] = b.xt[m]; p.A16[m] = b.xtb[m]; p.amaxA[m] = b.am_x(L - 1, m);
+        }
+        p.C[0] = b.mu_i; p.C2[0] = b.lv_i; p.C[1] = b.mu_e; p.C2[1] = b.lv_e;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD)) return rc;
+
+        // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
+        FusionArgs fa;
+        memset(&fa, 0, sizeof(fa));
+        fa.mu_i = b.mu_i; fa.lv_i = b.lv_i; fa.mu_e = b.mu_e; fa.lv_e = b.lv_e;
+        fa.n_i = b.n_i; fa.n_e = b.n_e; fa.n_i_mean = b.wim_out; fa.n_e_mean = b.wem_out;
+        fa.z = z;
+        fa.zb = (bf && !chain) ? b.zb : nullptr;
+        fa.nrows = rows; fa.factor = factor; fa.eps = c.epsilon;
+        fa.z_amax = b.am_z(0);
+        hipEvent_t e = tm.begin(ST_FUSION);
+        dispatch_d(d512, [&](auto w) { hipLaunchKernelGGL(iefvad_fusion_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, fa); });
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
+
+    if (chain)
+        if (int rc = launch_refine_chain(h, z, out->fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
+
+    // bf16x6 on the split kernels: the last step's second projection is folded into the scorer,
+    //   logits = c . z_K + b_c = c . z_{K-1} + v . h + s0     (v, s0: iefvad_set_weights; rowops.h),
+    // v . h taken in the epilogue of the last step's FIRST projection (EPI_BIAS_RELU_DOT: six partial sums per row, into the y
+    // region, dead since the last LayerNorm).  Without `fused` in the outputs that projection stores no h and the last W2 launch
+    // does not run; with it, h is stored and z_K is formed as always, after the scorer has read z_{K-1} (EPI_REFINE updates z
+    // in place) -- so the logits of both output sets are the same bits.
+    const bool fold = b.tail_split && c.compute == IEFVAD_COMPUTE_BF16X6 && K >= 1;
+    float* const fold_part = b.ybuf[0];
+
+    // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
+    for (int k = 0; k < K && !chain; ++k) {
+        const bool dot = fold && k == K - 1;
+        Proj p;
+        memset(&p, 0, sizeof(p));
+        p.N = D; p.ldc = D; p.epi = EPI_BIAS_RELU; p.nz = 1;
+        p.set_w(0, h->ref1[k]);
+        p.A32[0] = z; p.A16[0] = b.zb; p.amaxA[0] = b.am_z(k); p.amaxC[0] = b.am_h(k);
+        p.C[0] = bf ? nullptr : b.hbuf; p.Cb[0] = bf ? b.hb : nullptr;
+        if (dot) {
+            p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
+            if (!out->fused) p.C[0] = nullptr;
+        }
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE)) return rc;
+        if (dot) {
+            hipEvent_t e = tm.begin(ST_SCORER);
+            hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
+                               h->score_fold, b.logits, rows);
+            tm.end(e);
+            HIP_TRY(hipGetLastError());
+            if (!out->fused) break;
+        }
+        memset(&p, 0, sizeof(p));
+        p.N = D; p.ldc = D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
+        p.set_w(0, h->ref2[k]);
+        p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
+        p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE)) return rc;
+    }
+
+    // 5. scorer (imf_vad.py:150)
+    if (!chain && !fold) {
+        hipEvent_t e = tm.begin(ST_SCORER);
+        dispatch_d(d512, [&](auto w) {
+            hipLaunchKernelGGL(iefvad_scorer_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, z, h->cls_w, h->cls_b, b.logits, rows);
+        });
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
+
+    // ragged pass: the valid rows' results -> the caller's packed vectors (test.py:119-121: logits1[0:len_cur])
+    if (rg) {
+        hipEvent_t e = tm.begin(ST_SCORER);
+        // a compacted set is already in packed order: one thread per valid row, no chunk table
+        hipLaunchKernelGGL(iefvad_rows_out_kernel, dim3(b.compacted ? (rg->valid_rows + 255) / 256 : b.nb), dim3(256), 0, stream, b.logits, b.wim_out,
+                           b.wem_out, rg->logits, rg->w_i_mean, rg->w_e_mean, b.compacted ? nullptr : rg->d_chunks, rg->valid_rows);
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 // One micro-batch of `nb` chunks.  Dense (rg == nullptr): pi / pe are the pass's [nb, 256, 768] blocks of `in_dtype`, results go
 // to `out` at row offset row0.  Ragged: the chunks are built on the device from rg's packed rows, everything behind the encoder
 // runs on the valid rows only, results go to rg's packed vectors (`out` must be all-null).
-static int forward_pass(iefvad_handle* h, const void* pi_, const void* pe_, int32_t in_dtype, int nb, size_t row0, void* workspace,
+static int forward_pass(iefvad_handle* h, const void* pi, const void* pe, int32_t in_dtype, int nb, size_t row0, void* workspace,
                         const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
-    const iefvad_config& c = h->cfg;
-    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
-    const int L = c.num_layers, K = c.num_steps;
-    const int mb = micro_batch(h);
-    const size_t D = h->D;
-    const bool d512 = h->D == IEF_D512;      // iefvad_create_ex: f32 arithmetic only, so every bf16 / split branch below is 768-wide
-    const float factor = (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;   // imf_vad.py:134
-    const float qscale = 1.0f / sqrtf((float)h->DH);
-    {
-        const bool enc_rows_mode = rg && rg->enc_rows > 0;       // row-compressed chunks: valid rows + one pad row each
-        int rows = enc_rows_mode ? rg->enc_rows : nb * IEF_T;
-        const size_t R = (size_t)nb * IEF_T;                     // region stride: the dense capacity
-        // workspace regions, in units of R*D floats: xin 0..2 | qkv 2..8 | att 8..10 | y 10..12 | x 12..14 | logits
-        float* ws = (float*)workspace;
-        float* xin[2] = {ws, ws + R * D};
-        float* qkv[2] = {ws + 2 * R * D, ws + 5 * R * D};
-        bf16_t* qkvb[2] = {(bf16_t*)(ws + 2 * R * D), (bf16_t*)(ws + 2 * R * D) + 3 * R * D};   // bf16 mode: q|k|v as bf16
-        float* att[2] = {ws + 8 * R * D, ws + 9 * R * D};                       // fp32 mode: attention output
-        bf16_t* attb[2] = {(bf16_t*)(ws + 8 * R * D), (bf16_t*)(ws + 8 * R * D) + R * D};   // bf16 mode: the same region
-        bf16_t* xb[2] = {(bf16_t*)(ws + 9 * R * D), (bf16_t*)(ws + 9 * R * D) + R * D};     // holds attb | xb
-        float* ybuf[2] = {ws + 10 * R * D, ws + 11 * R * D};
-        float* xbuf[2] = {ws + 12 * R * D, ws + 13 * R * D};
-        float* lg_scratch = ws + 14 * R * D;          // R floats; the 3 R behind it (kWsFloatsPerRow) hold the ragged path's row means
-        // tail buffers alias the (dead by then) qkv region: mu_i lv_i mu_e lv_e z | h  (bf16 mode: hb, zb in h's slot)
-        float* t0 = ws + 2 * R * D;
-        float* mu_i = out->image_mu ? out->image_mu + row0 * D : t0;
-        float* lv_i = out->image_logvar ? out->image_logvar + row0 * D : t0 + R * D;
-        float* mu_e = out->event_mu ? out->event_mu + row0 * D : t0 + 2 * R * D;
-        float* lv_e = out->event_logvar ? out->event_logvar + row0 * D : t0 + 3 * R * D;
-        float* z = out->fused ? out->fused + row0 * D : t0 + 4 * R * D;
-        float* hbuf = t0 + 5 * R * D;
-        bf16_t* hb = (bf16_t*)(t0 + 5 * R * D);
-        bf16_t* zb = hb + R * D;
-        float* logits = out->logits ? out->logits + row0 : lg_scratch;
-        float* wim_out = out->w_i_mean ? out->w_i_mean + row0 : nullptr;
-        float* wem_out = out->w_e_mean ? out->w_e_mean + row0 : nullptr;
-        if (rg) {                                     // per-row results of the pass land in scratch, then in rg's packed vectors
-            logits = lg_scratch;
-            wim_out = rg->w_i_mean ? lg_scratch + R : nullptr;
-            wem_out = rg->w_e_mean ? lg_scratch + 2 * R : nullptr;
-        }
-
-        // bf16 mode, full grids: in_proj on the row-block kernel (inproj_chain_bf16.h); its first layer reads the fp32 rows
-        const bool ip_chain = bf && !h->no_inproj_chain && rows % IC_BM == 0 && (rows / IC_BM) * 2 >= h->rowblock_min_wgs;
-        // 0. inputs: `.to(torch.float)` (imf_vad.py:41-42); bf16 mode also needs the bf16 operand copy (unless ip_chain)
-        const bool need_xb0 = bf && !ip_chain;
-        const float* cur[2];
-        const char* pi = (const char*)pi_;
-        const char* pe = (const char*)pe_;
-        if (rg) {
-            // the chunker (tools.py:100-114) and the conditional nan_to_num (test.py:90-95) on the device: ragged.h
-            if (enc_rows_mode && rg->enc_used_rows < rows) {     // the zero rows that round the set up to whole 256-row tiles
-                const size_t o = (size_t)rg->enc_used_rows * D, n = (size_t)(rows - rg->enc_used_rows) * D;
-                for (int m = 0; m < 2; ++m) {
-                    HIP_TRY(hipMemsetAsync(xin[m] + o, 0, n * sizeof(float), stream));
-                    if (need_xb0) HIP_TRY(hipMemsetAsync(xb[m] + o, 0, n * sizeof(bf16_t), stream));
-                }
-            }
-            hipEvent_t e = tm.begin(ST_CAST);
-            // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
-            // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
-#define RAGGED_IN(T, W)                                                                                                     \
-    do {                                                                                                                    \
-        hipLaunchKernelGGL((iefvad_scatter_rows_kernel<T, W>), dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)rg->img_rows, \
-                           (const T*)rg->ev_rows, rg->d_chunks, rg->d_flags, xin[0], xin[1], need_xb0 ? xb[0] : (bf16_t*)nullptr, \
-                           need_xb0 ? xb[1] : (bf16_t*)nullptr, enc_rows_mode ? 0 : IEF_T);                                  \
-    } while (0)
-            if (d512) {
-                if (in_dtype == IEFVAD_IN_F32) RAGGED_IN(float, IEF_D512);
-                else if (in_dtype == IEFVAD_IN_F16) RAGGED_IN(__half, IEF_D512);
-                else RAGGED_IN(__hip_bfloat16, IEF_D512);
-            } else if (in_dtype == IEFVAD_IN_F32) RAGGED_IN(float, IEF_D);
-            else if (in_dtype == IEFVAD_IN_F16) RAGGED_IN(__half, IEF_D);
-            else RAGGED_IN(__hip_bfloat16, IEF_D);
-#undef RAGGED_IN
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-            cur[0] = xin[0];
-            cur[1] = xin[1];
-        } else if (h->row_scale[0] || h->row_scale[1]) {
-            // iefvad_forward_scaled: the rows pass through the cast kernel whatever their type, scaled on the way (rowops.h)
-            hipEvent_t e = tm.begin(ST_CAST);
-            bf16_t* b0p = need_xb0 ? xb[0] : nullptr;
-            bf16_t* b1p = need_xb0 ? xb[1] : nullptr;
-            const float* s0 = h->row_scale[0] ? h->row_scale[0] + row0 : nullptr;
-            const float* s1 = h->row_scale[1] ? h->row_scale[1] + row0 : nullptr;
-            int rc = d512 ? ((in_dtype == IEFVAD_IN_F32)   ? launch_cast_scaled<float, IEF_D512>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
-                             : (in_dtype == IEFVAD_IN_F16) ? launch_cast_scaled<__half, IEF_D512>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
-                                                           : launch_cast_scaled<__hip_bfloat16, IEF_D512>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream))
-                          : ((in_dtype == IEFVAD_IN_F32)   ? launch_cast_scaled<float, IEF_D>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
-                             : (in_dtype == IEFVAD_IN_F16) ? launch_cast_scaled<__half, IEF_D>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream)
-                                                           : launch_cast_scaled<__hip_bfloat16, IEF_D>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, s0, s1, stream));
-            tm.end(e);
-            if (rc) return rc;
-            cur[0] = xin[0];
-            cur[1] = xin[1];
-        } else if (in_dtype == IEFVAD_IN_F32) {
-            cur[0] = (const float*)pi;
-            cur[1] = (const float*)pe;
-            if (need_xb0) {
-                hipEvent_t e = tm.begin(ST_CAST);
-                int rc = launch_cast<float>(pi, pe, nullptr, nullptr, xb[0], xb[1], R * D, 2, stream);
-                tm.end(e);
-                if (rc) return rc;
-            }
-        } else {
-            hipEvent_t e = tm.begin(ST_CAST);
-            bf16_t* b0p = need_xb0 ? xb[0] : nullptr;
-            bf16_t* b1p = need_xb0 ? xb[1] : nullptr;
-            int rc = (in_dtype == IEFVAD_IN_F16) ? launch_cast<__half>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, 2, stream)
-                                                 : launch_cast<__hip_bfloat16>(pi, pe, xin[0], xin[1], b0p, b1p, R * D, 2, stream);
-            tm.end(e);
-            if (rc) return rc;
-            cur[0] = xin[0];
-            cur[1] = xin[1];
-        }
-
-        // fp16x3: the running-max words of this micro-batch's activations (one word per tensor that feeds a projection)
-        const bool splitmb = (c.compute == IEFVAD_COMPUTE_BF16X6 || c.compute == IEFVAD_COMPUTE_FP16X3) &&
-                             split_eligible(rows, IEF_D, IEF_D, 1);
-        const bool f16mb = splitmb && c.compute == IEFVAD_COMPUTE_FP16X3;
-        // activation tensor t owns IEF_AMAX_PARTS words per chunk of the micro-batch
-        float* am = h->amax_dev ? h->amax_dev + kAmaxActBase * IEF_AMAX_FLOATS : nullptr;
-        const size_t mbs = (size_t)mb * IEF_AMAX_PARTS;
-        auto am_t = [&](int t) { return f16mb ? am + mbs * t : nullptr; };
-        auto am_in = [&](int m) { return am_t(m); };
-        auto am_att = [&](int l, int m) { return am_t(2 + 6 * l + m); };
-        auto am_x = [&](int l, int m) { return am_t(2 + 6 * l + 2 + m); };
-        auto am_qkv = [&](int l, int m) { return am_t(2 + 6 * l + 4 + m); };
-        auto am_z = [&](int k) { return am_t(2 + 6 * L + k); };
-        auto am_h = [&](int k) { return am_t(2 + 6 * L + (K + 1) + k); };
-        if (f16mb) {
-            HIP_TRY(hipMemsetAsync(am, 0, (size_t)amax_act_tensors(L, K) * mbs * sizeof(float), stream));
-            hipEvent_t e = tm.begin(ST_CAST);
-            hipLaunchKernelGGL(iefvad_amax_chunk_kernel, dim3(nb, 2), dim3(256), 0, stream, cur[0], cur[1], am_in(0), am_in(1));
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
-
-        // 1. temporal encoder (imf_vad.py:113-123): L x { in_proj, attention, out_proj + residual, LayerNorm }
-        for (int l = 0; l < L; ++l) {
-            Proj p;
-            if (ip_chain) {
-                const void* ipA[2] = {(l == 0) ? (const void*)cur[0] : (const void*)xb[0], (l == 0) ? (const void*)cur[1] : (const void*)xb[1]};
-                if (int rc = launch_inproj_chain(h, l, ipA, l == 0, qkvb, rows, stream, tm)) return rc;
-            }
-            memset(&p, 0, sizeof(p));
-            p.N = 3 * (int)D; p.ldc = 3 * (int)D; p.epi = EPI_QKV; p.qcols = (int)D; p.nz = 2;
-            // q is pre-scaled for the softmax by log2(e)/sqrt(d_h): both attention kernels use exp2
-            p.alpha = qscale * 1.4426950408889634f;
-            for (int m = 0; m < 2; ++m) {
-                p.A32[m] = cur[m]; p.A16[m] = xb[m]; p.W32[m] = h->in_w[m][l]; p.W16[m] = h->in_wb[m][l]; p.Ws[m] = h->in_ws[m][l];
-                p.Wh[m] = h->in_wh[m][l]; p.amaxW[m] = h->in_wa[m][l]; p.amaxA[m] = l == 0 ? am_in(m) : am_x(l - 1, m);
-                p.amaxC[m] = am_qkv(l, m);
-                p.bias[m] = h->in_b[m][l];
-                if (bf) p.Cb[m] = qkvb[m]; else p.C[m] = qkv[m];
-            }
-            if (!ip_chain)
-                if (int rc = launch_proj(p, c.compute, splitmb, (int)D, rows, stream, tm, ST_QKV)) return rc;
-
-            hipEvent_t e = tm.begin(ST_ATT);
-            if (bf) {
-                launch_attention_bf16(h, qkvb, attb, nb, enc_rows_mode ? rg->d_chunks : nullptr, ip_chain, rows, stream);
-            } else {
-                AttnArgs aa;
-                memset(&aa, 0, sizeof(aa));
-                for (int m = 0; m < 2; ++m) { aa.qkv[m] = qkv[m]; aa.out[m] = att[m]; }
-                aa.nchunks = nb;
-                aa.chunks = enc_rows_mode ? rg->d_chunks : nullptr;
-                // bf16x6: the split attention kernel goes with the split projections (same batch-size rule), so a small
-                // batch is computed exactly as in the f32 mode
-                for (int m = 0; m < 2; ++m) { aa.amax[m] = am_att(l, m); aa.amax_in[m] = am_qkv(l, m); }
-                if (f16mb)
-                    hipLaunchKernelGGL(iefvad_attention_split_f16_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), ATS_LDS_BYTES, stream, aa);
-                else if (splitmb && enc_rows_mode)
-                    hipLaunchKernelGGL(iefvad_attention_split_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), ATS_LDS_BYTES, stream, aa);
-                else if (splitmb)
-                    hipLaunchKernelGGL(iefvad_attention_split_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), ATS_LDS_BYTES, stream, aa);
-                else if (d512 && enc_rows_mode)
-                    hipLaunchKernelGGL(iefvad_attention_f32_rows_d64_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
-                else if (d512)
-                    hipLaunchKernelGGL(iefvad_attention_f32_d64_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
-                else if (enc_rows_mode)
-                    hipLaunchKernelGGL(iefvad_attention_f32_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
-                else
-                    hipLaunchKernelGGL(iefvad_attention_f32_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, aa);
-            }
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-
-            // out_proj + residual + LayerNorm(s) in one row-owning kernel (bf16 mode, full grids): 64-row blocks on the refinement chain's
-            // structure (outproj_ln_chain_bf16.h); same bits as the GEMM + LayerNorm kernels
-            const bool ln_fused = bf && !h->no_ln_fusion && rows % OC_BM == 0 && (rows / OC_BM) * 2 >= h->rowblock_min_wgs;
-            if (ln_fused) {
-                const bf16_t* oA[2] = {attb[0], attb[1]};
-                float* oy[2] = {(l < L - 1) ? xbuf[0] : nullptr, (l < L - 1) ? xbuf[1] : nullptr};      // fp32 rows are only the next layer's residual
-                if (int rc = launch_outproj_ln_chain(h, l, l == L - 1, oA, cur, oy, xb, rows, stream, tm)) return rc;
-                cur[0] = xbuf[0];
-                cur[1] = xbuf[1];
-                continue;
-            }
-
-            memset(&p, 0, sizeof(p));
-            p.N = (int)D; p.ldc = (int)D; p.epi = EPI_BIAS_RESID; p.nz = 2;
-            for (int m = 0; m < 2; ++m) {
-                p.A32[m] = att[m]; p.A16[m] = attb[m]; p.W32[m] = h->out_w[m][l]; p.W16[m] = h->out_wb[m][l]; p.Ws[m] = h->out_ws[m][l];
-                p.Wh[m] = h->out_wh[m][l]; p.amaxW[m] = h->out_wa[m][l]; p.amaxA[m] = am_att(l, m);
-                p.bias[m] = h->out_b[m][l]; p.C[m] = ybuf[m]; p.R[m] = cur[m];
-            }
-            if (int rc = launch_proj(p, c.compute, splitmb, (int)D, rows, stream, tm, ST_OUT)) return rc;
-
-            LnArgs la;
-            memset(&la, 0, sizeof(la));
-            la.nrows = rows; la.eps = 1e-5f;
-            for (int m = 0; m < 2; ++m) {
-                la.x[m] = ybuf[m]; la.g1[m] = h->norm_w[m][l]; la.b1[m] = h->norm_b[m][l];
-                if (l == L - 1) { la.g2[m] = h->whiten_w[m]; la.b2[m] = h->whiten_b[m]; }   // whitening LN, :117,:123
-                // fp32 mode: x feeds both the next projection and the next residual; bf16 mode: the bf16 copy feeds the
-                // projection, the fp32 tensor is only the next layer's residual (not needed after the last layer)
-                la.y[m] = (!bf || l < L - 1) ? xbuf[m] : nullptr;
-                la.yb[m] = bf ? xb[m] : nullptr;
-                la.amax[m] = am_x(l, m);
-            }
-            e = tm.begin(ST_LN);
-            if (d512) hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
-            else hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-            cur[0] = xbuf[0];
-            cur[1] = xbuf[1];
-        }
-
-        // Ragged pass with whole chunks in the encoder (IEFVAD_DENSE_ENCODER=1): everything behind the encoder is row-wise
-        // (imf_vad.py:125-150) and the reference slices the pad rows away (test.py:121), so the valid rows of the last
-        // LayerNorm's output are gathered (packed order, padded with zero rows to whole 256-row tiles) and `rows` shrinks to
-        // that count from here on.  fp16x3 keeps whole chunks: its operand scales are per chunk.  The compact operands live in
-        // the attention-output region, dead by now.  (Row-compressed chunks, the default: the tail runs on the encoder's row set.)
-        const float* xt[2] = {xbuf[0], xbuf[1]};      // the tail's fp32 / bf16 A operands
-        const bf16_t* xtb[2] = {xb[0], xb[1]};
-        bool compacted = false;
-        if (rg && !enc_rows_mode && c.compute != IEFVAD_COMPUTE_FP16X3) {
-            const int mc = (rg->valid_rows + 255) / 256 * 256;
-            if (mc < rows) {
-                CompactArgs ca;
-                memset(&ca, 0, sizeof(ca));
-                for (int m = 0; m < 2; ++m) {
-                    if (bf) { ca.xb[m] = xb[m]; ca.xcb[m] = attb[m]; xtb[m] = attb[m]; }
-                    else { ca.x[m] = xbuf[m]; ca.xc[m] = att[m]; xt[m] = att[m]; }
-                }
-                ca.chunks = rg->d_chunks;
-                const size_t tail0 = (size_t)rg->valid_rows * D, tailn = (size_t)(mc - rg->valid_rows) * D;
-                if (tailn)
-                    for (int m = 0; m < 2; ++m)
-                        HIP_TRY(bf ? hipMemsetAsync(attb[m] + tail0, 0, tailn * sizeof(bf16_t), stream)
-                                   : hipMemsetAsync(att[m] + tail0, 0, tailn * sizeof(float), stream));
-                hipEvent_t e = tm.begin(ST_CAST);
-                if (d512) hipLaunchKernelGGL(iefvad_compact_rows_kernel<IEF_D512>, dim3(nb, 2), dim3(256), 0, stream, ca);
-                else hipLaunchKernelGGL(iefvad_compact_rows_kernel<IEF_D>, dim3(nb, 2), dim3(256), 0, stream, ca);
-                tm.end(e);
-                HIP_TRY(hipGetLastError());
-                rows = mc;
-                compacted = true;
-            }
-        }
-        const bool tail_split = splitmb && (!compacted || split_eligible(rows, IEF_D, IEF_D, 1));   // bf16x6: a small compact set runs on the fp32 kernels
-
-        // 2 + 3 in one kernel (bf16 mode, full grids): heads of both modalities + fusion on the row-block structure (heads_chain_bf16.h).
-        // The four head tensors are stored only if the caller asked for them.
-        const bool heads_rows = bf && !h->no_heads_fusion && h->heads_stream && rows % HC_BM == 0 && (rows / HC_BM) * HC_THIRDS >= h->rowblock_min_wgs;
-        const bool heads_fused = heads_rows;
-        // 4 + 5 in one kernel (bf16 mode): the K refinement steps and the scorer with the state on chip, refine_chain_bf16.h
-        const bool chain = bf && K > 0 && !h->no_chain && h->chain_stream && rows % RC_BM == 0 && rows / RC_BM >= h->chain_min_blocks;
-        if (heads_rows) {
-            HeadsChainArgs ha;
-            memset(&ha, 0, sizeof(ha));
-            for (int m = 0; m < 2; ++m) ha.A[m] = xtb[m];
-            ha.mu[0] = out->image_mu ? mu_i : nullptr;
-            ha.lv[0] = out->image_logvar ? lv_i : nullptr;
-            ha.mu[1] = out->event_mu ? mu_e : nullptr;
-            ha.lv[1] = out->event_logvar ? lv_e : nullptr;
-            ha.n[0] = out->w_i ? out->w_i + row0 * D : nullptr;
-            ha.n[1] = out->w_e ? out->w_e + row0 * D : nullptr;
-            ha.z = z;
-            ha.zb = chain ? nullptr : zb;
-            const bool means = wim_out || wem_out;
-            ha.nsum_part = means ? ybuf[0] : nullptr;        // y is dead after the last LayerNorm: 48 of its 768 floats per row
-            if (int rc = launch_heads_chain(h, ha, rows, factor, stream, tm)) return rc;
-            hipEvent_t e;
-            if (means) {
-                e = tm.begin(ST_FUSION);
-                hipLaunchKernelGGL(iefvad_rowmean_finish_kernel, dim3((2 * rows + 255) / 256), dim3(256), 0, stream, ha.nsum_part,
-                                   wim_out, wem_out, rows, HC_NPART);
-                tm.end(e);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-
-        // 2. mu / logvar heads (imf_vad.py:125-128): one [768 -> 1536] projection per modality
-        if (!heads_fused) {
-            Proj p;
-            memset(&p, 0, sizeof(p));
-            p.N = 2 * (int)D; p.ldc = (int)D; p.epi = EPI_HEADS; p.nz = 2;
-            for (int m = 0; m < 2; ++m) {
-                p.A32[m] = xt[m]; p.A16[m] = xtb[m]; p.W32[m] = h->head_w[m]; p.W16[m] = h->head_wb[m]; p.Ws[m] = h->head_ws[m]; p.bias[m] = h->head_b[m];
-                p.Wh[m] = h->head_wh[m]; p.amaxW[m] = h->head_wa[m]; p.amaxA[m] = am_x(L - 1, m);
-            }
-            p.C[0] = mu_i; p.C2[0] = lv_i; p.C[1] = mu_e; p.C2[1] = lv_e;
-            if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_HEAD)) return rc;
-        }
-
-        // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
-        if (!heads_fused) {
-            FusionArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.mu_i = mu_i; fa.lv_i = lv_i; fa.mu_e = mu_e; fa.lv_e = lv_e;
-            fa.n_i = out->w_i ? out->w_i + row0 * D : nullptr;
-            fa.n_e = out->w_e ? out->w_e + row0 * D : nullptr;
-            fa.z = z;
-            fa.zb = (bf && !chain) ? zb : nullptr;
-            fa.n_i_mean = wim_out;
-            fa.n_e_mean = wem_out;
-            fa.nrows = rows; fa.factor = factor; fa.eps = c.epsilon;
-            fa.z_amax = am_z(0);
-            hipEvent_t e = tm.begin(ST_FUSION);
-            if (d512) hipLaunchKernelGGL(iefvad_fusion_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
-            else hipLaunchKernelGGL(iefvad_fusion_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
-
-        if (chain)
-            if (int rc = launch_refine_chain(h, z, out->fused ? z : nullptr, logits, rows, stream, tm)) return rc;
-
-        // bf16x6 on the split kernels: the last step's second projection is folded into the scorer,
-        //   logits = c . z_K + b_c = c . z_{K-1} + v . h + s0     (v, s0: iefvad_set_weights; rowops.h),
-        // v . h taken in the epilogue of the last step's FIRST projection (EPI_BIAS_RELU_DOT: six partial sums per row, into the y
-        // region, dead since the last LayerNorm).  Without `fused` in the outputs that projection stores no h and the last W2 launch
-        // does not run; with it, h is stored and z_K is formed as always, after the scorer has read z_{K-1} (EPI_REFINE updates z
-        // in place) -- so the logits of both output sets are the same bits.
-        const bool fold = tail_split && c.compute == IEFVAD_COMPUTE_BF16X6 && K >= 1;
-        float* const fold_part = ybuf[0];
-        auto launch_scorer_fold = [&]() -> int {
-            hipEvent_t e = tm.begin(ST_SCORER);
-            hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0,
-                               stream, z, h->cls_w, fold_part, h->score_fold, logits, rows);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-            return 0;
-        };
-
-        // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
-        for (int k = 0; k < K && !chain; ++k) {
-            const bool dot = fold && k == K - 1;
-            Proj p;
-            memset(&p, 0, sizeof(p));
-            p.N = (int)D; p.ldc = (int)D; p.epi = EPI_BIAS_RELU; p.nz = 1;
-            p.A32[0] = z; p.A16[0] = zb; p.W32[0] = h->ref_w1[k]; p.W16[0] = h->ref_w1b[k]; p.Ws[0] = h->ref_w1s[k]; p.bias[0] = h->ref_b1[k];
-            p.Wh[0] = h->ref_w1h[k]; p.amaxW[0] = h->ref_w1a[k]; p.amaxA[0] = am_z(k); p.amaxC[0] = am_h(k);
-            p.C[0] = bf ? nullptr : hbuf; p.Cb[0] = bf ? hb : nullptr;
-            if (dot) {
-                p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
-                if (!out->fused) p.C[0] = nullptr;
-            }
-            if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_REFINE)) return rc;
-            if (dot) {
-                if (int rc = launch_scorer_fold()) return rc;
-                if (!out->fused) break;
-            }
-            memset(&p, 0, sizeof(p));
-            p.N = (int)D; p.ldc = (int)D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
-            p.A32[0] = hbuf; p.A16[0] = hb; p.W32[0] = h->ref_w2[k]; p.W16[0] = h->ref_w2b[k]; p.Ws[0] = h->ref_w2s[k]; p.bias[0] = h->ref_b2[k];
-            p.Wh[0] = h->ref_w2h[k]; p.amaxW[0] = h->ref_w2a[k]; p.amaxA[0] = am_h(k); p.amaxC[0] = am_z(k + 1);
-            p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? zb : nullptr;
-            if (int rc = launch_proj(p, c.compute, tail_split, (int)D, rows, stream, tm, ST_REFINE)) return rc;
-        }
-
-        // 5. scorer (imf_vad.py:150)
-        if (!chain && !fold) {
-            hipEvent_t e = tm.begin(ST_SCORER);
-            if (d512)
-                hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D512>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, z,
-                                   h->cls_w, h->cls_b, logits, rows);
-            else
-                hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, z,
-                                   h->cls_w, h->cls_b, logits, rows);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
-
-        // ragged pass: the valid rows' results -> the caller's packed vectors (test.py:119-121: logits1[0:len_cur])
-        if (rg) {
-            hipEvent_t e = tm.begin(ST_SCORER);
-            if (compacted)
-                hipLaunchKernelGGL(iefvad_rows_out_kernel, dim3((rg->valid_rows + 255) / 256), dim3(256), 0, stream, logits, wim_out, wem_out,
-                                   rg->logits, rg->w_i_mean, rg->w_e_mean, (const RaggedChunk*)nullptr, rg->valid_rows);
-            else
-                hipLaunchKernelGGL(iefvad_rows_out_kernel, dim3(nb), dim3(256), 0, stream, logits, wim_out, wem_out, rg->logits,
-                                   rg->w_i_mean, rg->w_e_mean, rg->d_chunks, rg->valid_rows);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    return 0;
+    PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
+    if (int rc = pass_load_inputs(h, b, pi, pe, in_dtype, row0, rg, stream, tm)) return rc;
+    for (int l = 0; l < h->cfg.num_layers; ++l)
+        if (int rc = pass_encoder_layer(h, b, l, rg, stream, tm)) return rc;
+    if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
+    return pass_tail(h, b, out, rg, stream, tm);
 }
 
 static int forward_impl(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
@@ -1543,15 +1545,12 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
             const int nb = (int)((total_chunks - c0 < mb) ? (total_chunks - c0) : mb);
             const void* pi = (const char*)img_rows + (size_t)r0 * h->D * esz;
             const void* pe = (const char*)ev_rows + (size_t)r0 * h->D * esz;
-#define NANFLAG(T, W) hipLaunchKernelGGL((iefvad_nanflag_kernel<T, W>), dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)pi, (const T*)pe, dc + c0, (int*)dflags)
-            if (h->D == IEF_D512) {
-                if (in_dtype == IEFVAD_IN_F32) NANFLAG(float, IEF_D512);
-                else if (in_dtype == IEFVAD_IN_F16) NANFLAG(__half, IEF_D512);
-                else NANFLAG(__hip_bfloat16, IEF_D512);
-            } else if (in_dtype == IEFVAD_IN_F32) NANFLAG(float, IEF_D);
-            else if (in_dtype == IEFVAD_IN_F16) NANFLAG(__half, IEF_D);
-            else NANFLAG(__hip_bfloat16, IEF_D);
-#undef NANFLAG
+            dispatch_in(in_dtype, h->D == IEF_D512, [&](auto t, auto w) {
+                using T = typename decltype(t)::type;
+                hipLaunchKernelGGL((iefvad_nanflag_kernel<T, decltype(w)::value>), dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)pi,
+                                   (const T*)pe, dc + c0, (int*)dflags);
+                return 0;
+            });
             for (int j = 0; j < nb; ++j) r0 += hc[c0 + j].valid;
         }
         tm.end(e);

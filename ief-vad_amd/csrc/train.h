@@ -140,32 +140,19 @@ static int launch_bgemm(const BgemmArgs& a, bool akc, bool bkc, int nz, hipStrea
 // dX[rows, 768] = dY[rows, n_out] (W^T)[768, n_out]^T on iefvad_gemm_split_n128_kernel (fp32-accurate, 1.7x the fp32 MFMA rate)
 static int ensure_train_planes(iefvad_handle* h, hipStream_t stream) {
     if (h->cfg.compute != IEFVAD_COMPUTE_BF16X6 || h->tplanes_valid) return 0;
-    const int L = h->cfg.num_layers, K = h->cfg.num_steps;
-    const size_t D = IEF_D, DD = D * D;
-    const size_t nb = 2 * (size_t)L * (3 * DD + DD) + 2 * (2 * DD) + (size_t)K * 2 * DD;
-    if (!h->arena_st) HIP_TRY(hipMalloc((void**)&h->arena_st, 3 * nb * sizeof(bf16_t)));
+    if (!h->arena_st) HIP_TRY(hipMalloc((void**)&h->arena_st, 3 * proj_elems(h) * sizeof(bf16_t)));
     if (!h->zero_bias) {
-        HIP_TRY(hipMalloc((void**)&h->zero_bias, 3 * D * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(h->zero_bias, 0, 3 * D * sizeof(float), stream));
+        HIP_TRY(hipMalloc((void**)&h->zero_bias, 3 * IEF_D * sizeof(float)));
+        HIP_TRY(hipMemsetAsync(h->zero_bias, 0, 3 * IEF_D * sizeof(float), stream));
     }
     bf16_t* q = h->arena_st;
     SplitMany sm(stream);                     // one launch for all of them (gemm_split.h: transpose and split in one pass)
-    auto tsplit = [&](bf16_t** dst, const float* W, int n_out) -> int {      // W [n_out, 768] -> planes of W^T [768, n_out]
-        *dst = q;
-        q += 3 * (size_t)n_out * D;
-        return sm.add(W, *dst, (size_t)n_out * D, n_out);
-    };
-    for (int m = 0; m < 2; ++m) {
-        for (int l = 0; l < L; ++l) {
-            if (int rc = tsplit(&h->in_wst[m][l], h->in_w[m][l], 3 * IEF_D)) return rc;
-            if (int rc = tsplit(&h->out_wst[m][l], h->out_w[m][l], IEF_D)) return rc;
-        }
-        if (int rc = tsplit(&h->head_wst[m], h->head_w[m], 2 * IEF_D)) return rc;
-    }
-    for (int k = 0; k < K; ++k) {
-        if (int rc = tsplit(&h->ref_w1st[k], h->ref_w1[k], IEF_D)) return rc;
-        if (int rc = tsplit(&h->ref_w2st[k], h->ref_w2[k], IEF_D)) return rc;
-    }
+    if (int rc = for_each_proj(h, [&](ProjW& r) {      // W [N, 768] -> planes of W^T [768, N]
+            const size_t n = (size_t)r.N * IEF_D;
+            r.wst = q;
+            q += 3 * n;
+            return sm.add(r.w, r.wst, n, r.N);
+        })) return rc;
     if (int rc = sm.flush()) return rc;
     h->tplanes_valid = true;
     return 0;
@@ -423,10 +410,9 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
     auto xin = [&](int m, int l) -> const float* { return l == 0 ? rec->x0[m] : ws + t.x[m][l]; };
     auto zst = [&](int k) -> float* { return k == K ? rec->zK : ws + t.z[k]; };
     if (in_dtype != IEFVAD_IN_F32) {
-        const int rc = (in_dtype == IEFVAD_IN_F16)
-                           ? launch_cast<__half>(img, ev, ws + t.x[0][0], ws + t.x[1][0], nullptr, nullptr, t.U, 2, stream)
-                           : launch_cast<__hip_bfloat16>(img, ev, ws + t.x[0][0], ws + t.x[1][0], nullptr, nullptr, t.U, 2, stream);
-        if (rc) return rc;
+        if (int rc = dispatch_in(in_dtype, false, [&](auto ty, auto) {
+                return launch_cast<typename decltype(ty)::type>(img, ev, ws + t.x[0][0], ws + t.x[1][0], nullptr, nullptr, t.U, 2, stream);
+            })) return rc;
     }
 
     for (int l = 0; l < L; ++l) {
@@ -435,8 +421,8 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         p.N = 3 * IEF_D; p.ldc = 3 * IEF_D; p.epi = EPI_QKV; p.qcols = IEF_D; p.nz = 2;
         p.alpha = qscale;                               // q * 1/sqrt(dh) before the bmm, as F.multi_head_attention_forward does
         for (int m = 0; m < 2; ++m) {
-            p.A32[m] = xin(m, l); p.W32[m] = h->in_w[m][l]; p.Ws[m] = h->in_ws[m][l]; p.bias[m] = h->in_b[m][l];
-            p.C[m] = ws + t.qkv[m][l];
+            p.set_w(m, h->in[m][l]);
+            p.A32[m] = xin(m, l); p.C[m] = ws + t.qkv[m][l];
         }
         if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_QKV)) return rc;
 
@@ -500,8 +486,8 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         memset(&p, 0, sizeof(p));
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RESID; p.nz = 2;
         for (int m = 0; m < 2; ++m) {
-            p.A32[m] = ws + t.att[m][l]; p.W32[m] = h->out_w[m][l]; p.Ws[m] = h->out_ws[m][l]; p.bias[m] = h->out_b[m][l];
-            p.C[m] = ws + t.s[m][l]; p.R[m] = xin(m, l);
+            p.set_w(m, h->out[m][l]);
+            p.A32[m] = ws + t.att[m][l]; p.C[m] = ws + t.s[m][l]; p.R[m] = xin(m, l);
         }
         if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_OUT)) return rc;
 
@@ -529,8 +515,8 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         memset(&p, 0, sizeof(p));
         p.N = 2 * IEF_D; p.ldc = IEF_D; p.epi = EPI_HEADS; p.nz = 2;
         for (int m = 0; m < 2; ++m) {
-            p.A32[m] = ws + t.E[m]; p.W32[m] = h->head_w[m]; p.Ws[m] = h->head_ws[m]; p.bias[m] = h->head_b[m];
-            p.C[m] = rec->mu[m]; p.C2[m] = rec->lv[m];
+            p.set_w(m, h->head[m]);
+            p.A32[m] = ws + t.E[m]; p.C[m] = rec->mu[m]; p.C2[m] = rec->lv[m];
         }
         if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_HEAD)) return rc;
     }
@@ -548,12 +534,13 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         Proj p;
         memset(&p, 0, sizeof(p));
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RELU; p.nz = 1;
-        p.A32[0] = zst(k); p.W32[0] = h->ref_w1[k]; p.Ws[0] = h->ref_w1s[k]; p.bias[0] = h->ref_b1[k]; p.C[0] = ws + t.hid[k];
+        p.set_w(0, h->ref1[k]);
+        p.A32[0] = zst(k); p.C[0] = ws + t.hid[k];
         if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE)) return rc;
         memset(&p, 0, sizeof(p));
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
-        p.A32[0] = ws + t.hid[k]; p.W32[0] = h->ref_w2[k]; p.Ws[0] = h->ref_w2s[k]; p.bias[0] = h->ref_b2[k];
-        p.C[0] = zst(k + 1); p.R[0] = zst(k);
+        p.set_w(0, h->ref2[k]);
+        p.A32[0] = ws + t.hid[k]; p.C[0] = zst(k + 1); p.R[0] = zst(k);
         if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE)) return rc;
     }
     float* logits = out->logits ? out->logits : ws + t.logits;
@@ -614,13 +601,13 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
             if (!db_done)
                 if (int rc = launch_db(g, IEF_D, IEF_D, dw->ref_b2[k], nullptr, 0, nl, rows, cpart, stream)) return rc; }
         // d a = (-lambda g W2) gated by h > 0  (ReLU backward on the saved activation)
-        if (int rc = launch_dx(h, tp ? h->ref_w2st[k] : nullptr, g, IEF_D, h->ref_w2[k], IEF_D, IEF_D, da, nullptr, ws + t.hid[k], nl, rows, stream)) return rc;
+        if (int rc = launch_dx(h, tp ? h->ref2[k].wst : nullptr, g, IEF_D, h->ref2[k].w, IEF_D, IEF_D, da, nullptr, ws + t.hid[k], nl, rows, stream)) return rc;
         { bool db_done = false;
             if (int rc = launch_dw(da, IEF_D, IEF_D, k == K ? rec->zK : ws + t.z[k], dw->ref_w1[k], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->ref_b1[k], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
             if (!db_done)
                 if (int rc = launch_db(da, IEF_D, IEF_D, dw->ref_b1[k], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
         // d z_k = g + d a W1   (in place: every element of g is read by the thread that overwrites it)
-        if (int rc = launch_dx(h, tp ? h->ref_w1st[k] : nullptr, da, IEF_D, h->ref_w1[k], IEF_D, IEF_D, g, g, nullptr, 1.f, rows, stream)) return rc;
+        if (int rc = launch_dx(h, tp ? h->ref1[k].wst : nullptr, da, IEF_D, h->ref1[k].w, IEF_D, IEF_D, g, g, nullptr, 1.f, rows, stream)) return rc;
     }
     // fusion (imf_vad.py:130-144) -> d mu | d logvar of both modalities, stacked
     {
@@ -643,7 +630,7 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
             if (int rc = launch_dw(dhm, 2 * IEF_D, 2 * IEF_D, ws + t.E[m], dw->mu_w[m], dw->logvar_w[m], IEF_D, 1.f, rows, part, t.part_floats, stream, tn, dw->mu_b[m], dw->logvar_b[m], cpart, t.cpart_floats, &db_done)) return rc;
             if (!db_done)
                 if (int rc = launch_db(dhm, 2 * IEF_D, 2 * IEF_D, dw->mu_b[m], dw->logvar_b[m], IEF_D, 1.f, rows, cpart, stream)) return rc; }
-        if (int rc = launch_dx(h, tp ? h->head_wst[m] : nullptr, dhm, 2 * IEF_D, h->head_w[m], 2 * IEF_D, IEF_D, gx, nullptr, nullptr, 1.f, rows, stream)) return rc;
+        if (int rc = launch_dx(h, tp ? h->head[m].wst : nullptr, dhm, 2 * IEF_D, h->head[m].w, 2 * IEF_D, IEF_D, gx, nullptr, nullptr, 1.f, rows, stream)) return rc;
         // whitening LayerNorm (imf_vad.py:117,123), then the layers last to first
         auto ln_bwd = [&](const float* x, const float* gamma, float* dgamma, float* dbeta) -> int {
             LnBwdArgs la;
@@ -674,7 +661,7 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
             if (int rc = launch_dw(gx, IEF_D, IEF_D, ws + t.att[m][l], dw->out_proj_w[m][l], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->out_proj_b[m][l], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
             if (!db_done)
                 if (int rc = launch_db(gx, IEF_D, IEF_D, dw->out_proj_b[m][l], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
-            if (int rc = launch_dx(h, tp ? h->out_wst[m][l] : nullptr, gx, IEF_D, h->out_w[m][l], IEF_D, IEF_D, datt, nullptr, nullptr, 1.f, rows, stream)) return rc;
+            if (int rc = launch_dx(h, tp ? h->out[m][l].wst : nullptr, gx, IEF_D, h->out[m][l].w, IEF_D, IEF_D, datt, nullptr, nullptr, 1.f, rows, stream)) return rc;
             const long long sQ = (long long)IEF_T * 3 * IEF_D, sP1 = (long long)IEF_H * IEF_T * IEF_T, sP2 = (long long)IEF_T * IEF_T,
                             sA = (long long)IEF_T * IEF_D;
             BgemmArgs a;
@@ -735,7 +722,7 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
                 if (int rc = launch_db(dqkv, 3 * IEF_D, 3 * IEF_D, dw->in_proj_b[m][l], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
             // d x_l = d s_l (residual) + d qkv W_in; the input features need no gradient
             if (l > 0)
-                if (int rc = launch_dx(h, tp ? h->in_wst[m][l] : nullptr, dqkv, 3 * IEF_D, h->in_w[m][l], 3 * IEF_D, IEF_D, gx, gx, nullptr, 1.f, rows, stream)) return rc;
+                if (int rc = launch_dx(h, tp ? h->in[m][l].wst : nullptr, dqkv, 3 * IEF_D, h->in[m][l].w, 3 * IEF_D, IEF_D, gx, gx, nullptr, 1.f, rows, stream)) return rc;
         }
     }
     const_cast<TrainRecord*>(rec)->stamp = 0;      // the scratch tensors have overwritten the saved refinement states
