@@ -2047,7 +2047,9 @@ extern "C" int iefvad_adamw_step_multi(const iefvad_adamw_tensor* table_dev, int
 // metric tail of the evaluation loop (metrics.h)
 // ------------------------------------------------------------------------------------------------
 static size_t mt_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static size_t metric_layout(int64_t n, char* base, MetricWs* w) {
+// ngroups = 0: the layout of iefvad_auc_ap; ngroups >= 1: iefvad_auc_ap_grouped's (one AP partial per (group, tile), 64 numerators and the
+// NaN mask in the tail, the group table)
+static size_t metric_layout(int64_t n, int ngroups, char* base, MetricWs* w) {
     const size_t tiles = (size_t)((n + MT_TILE - 1) / MT_TILE);
     size_t off = 0;
     auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += mt_align(bytes); return p; };
@@ -2056,20 +2058,39 @@ static size_t metric_layout(int64_t n, char* base, MetricWs* w) {
     char* hist = take(tiles * MT_RADIX * 4);
     char* bsum = take(tiles * 4);
     char* bstart = take(tiles * 4);
-    char* ap_part = take(tiles * 8);
-    char* tail = take(16);
+    char* ap_part = take(tiles * 8 * (size_t)(ngroups > 0 ? ngroups : 1));
+    const size_t tail_bytes = ngroups > 0 ? 8 * (size_t)(MT_MAXG + 1) : 16;
+    char* tail = take(tail_bytes);
     char* dtotal = take(MT_RADIX * 4);
+    char* tab = ngroups > 0 ? take(sizeof(MetricGroupTab)) : nullptr;
     if (w) {
         w->dtotal = (unsigned*)dtotal;
         w->a = (unsigned long long*)a; w->b = (unsigned long long*)b; w->hist = (unsigned*)hist; w->bsum = (unsigned*)bsum;
-        w->bstart = (unsigned*)bstart; w->ap_part = (double*)ap_part; w->auc_num = (unsigned long long*)tail; w->flags = (unsigned*)(tail + 8);
+        w->bstart = (unsigned*)bstart; w->ap_part = (double*)ap_part; w->auc_num = (unsigned long long*)tail;
+        w->flags = (unsigned*)(tail + tail_bytes - 8);
+        w->tab = (MetricGroupTab*)tab;
     }
     return off;
 }
 
+// the LSD sort of the pairs in w.a: four 8-bit digits of the key (the upper word of a pair), then, in the grouped format, the group byte.
+// Returns the buffer the sorted pairs end up in (w.a after four passes, w.b after five); the other one is free afterwards.
+static const unsigned long long* metric_sort(const MetricWs& w, int64_t n, int tiles, bool grouped, hipStream_t stream) {
+    unsigned long long* src = w.a;
+    unsigned long long* dst = w.b;
+    for (int pass = 0; pass < (grouped ? 5 : 4); ++pass) {
+        const int shift = pass < 4 ? 32 + 8 * pass : MT_POS_BITS;
+        hipLaunchKernelGGL(iefvad_metric_hist_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, shift, w.hist, tiles);
+        hipLaunchKernelGGL(iefvad_metric_digit_scan_kernel, dim3(MT_RADIX), dim3(256), 0, stream, w.hist, tiles, w.dtotal);
+        hipLaunchKernelGGL(iefvad_metric_scatter_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, dst, (long long)n, shift, w.hist, tiles, w.dtotal);
+        unsigned long long* t = src; src = dst; dst = t;
+    }
+    return src;
+}
+
 extern "C" size_t iefvad_auc_ap_workspace_bytes(int64_t n) {
     if (n <= 0) return 0;
-    return metric_layout(n, nullptr, nullptr);
+    return metric_layout(n, 0, nullptr, nullptr);
 }
 
 extern "C" int iefvad_auc_ap(const float* scores, const uint8_t* gt_frames, int64_t n, int32_t repeat, double* auc, double* ap,
@@ -2080,32 +2101,67 @@ extern "C" int iefvad_auc_ap(const float* scores, const uint8_t* gt_frames, int6
         return fail("iefvad_auc_ap: n * repeat = %llu frames do not fit the 32-bit frame counters", (unsigned long long)n * (unsigned long long)repeat);
     if (((uintptr_t)workspace & 255) != 0) return fail("iefvad_auc_ap: the workspace must be 256-byte aligned");
     MetricWs w;
-    const size_t need = metric_layout(n, (char*)workspace, &w);
+    const size_t need = metric_layout(n, 0, (char*)workspace, &w);
     if (workspace_bytes < need) return fail("iefvad_auc_ap: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t stream = (hipStream_t)stream_;
     const int tiles = (int)((n + MT_TILE - 1) / MT_TILE);
     HIP_TRY(hipMemsetAsync(w.auc_num, 0, 16, stream));
     hipLaunchKernelGGL(iefvad_metric_pairs_kernel, dim3((unsigned)((n + MT_THREADS - 1) / MT_THREADS)), dim3(MT_THREADS), 0, stream, scores,
                        (const unsigned char*)gt_frames, (long long)n, (int)repeat, w.a, w.flags);
-    unsigned long long* src = w.a;
-    unsigned long long* dst = w.b;
-    for (int pass = 0; pass < 4; ++pass) {          // the key is the upper word of a pair
-        const int shift = 32 + 8 * pass;
-        hipLaunchKernelGGL(iefvad_metric_hist_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, shift, w.hist, tiles);
-        hipLaunchKernelGGL(iefvad_metric_digit_scan_kernel, dim3(MT_RADIX), dim3(256), 0, stream, w.hist, tiles, w.dtotal);
-        hipLaunchKernelGGL(iefvad_metric_scatter_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, dst, (long long)n, shift, w.hist, tiles, w.dtotal);
-        unsigned long long* t = src; src = dst; dst = t;
-    }
-    // four passes: the sorted pairs are back in w.a, w.b is free for the two scanned columns
+    const unsigned long long* src = metric_sort(w, n, tiles, false, stream);          // back in w.a: w.b is free for the two scanned columns
     unsigned* tp_incl = (unsigned*)w.b;
     unsigned* gstart = tp_incl + n;
-    hipLaunchKernelGGL(iefvad_metric_tile_sums_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, w.bsum, w.bstart);
+    hipLaunchKernelGGL(iefvad_metric_tile_sums_kernel<false>, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, w.bsum, w.bstart);
     hipLaunchKernelGGL(iefvad_metric_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, w.bsum, w.bstart, tiles);
-    hipLaunchKernelGGL(iefvad_metric_tile_apply_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, w.bsum, w.bstart, tp_incl, gstart);
+    hipLaunchKernelGGL(iefvad_metric_tile_apply_kernel<false>, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, w.bsum, w.bstart, tp_incl, gstart);
     hipLaunchKernelGGL(iefvad_metric_groups_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, (int)repeat, tp_incl, gstart, w.auc_num,
                        w.ap_part);
     hipLaunchKernelGGL(iefvad_metric_finish_kernel, dim3(1), dim3(256), 0, stream, tp_incl, (long long)n, (int)repeat, w.auc_num, w.ap_part, tiles, w.flags,
                        auc, ap);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" size_t iefvad_auc_ap_grouped_workspace_bytes(int64_t n, int32_t ngroups) {
+    if (n <= 0 || ngroups < 1 || ngroups > MT_MAXG) return 0;
+    return metric_layout(n, ngroups, nullptr, nullptr);
+}
+
+extern "C" int iefvad_auc_ap_grouped(const float* scores, const uint8_t* gt_frames, const uint8_t* group, int64_t n, int32_t repeat, int32_t ngroups,
+                                     double* auc, double* ap, int64_t* frames, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!scores) return fail("iefvad_auc_ap_grouped: scores is null");
+    if (!gt_frames) return fail("iefvad_auc_ap_grouped: gt_frames is null");
+    if (!group) return fail("iefvad_auc_ap_grouped: group is null");
+    if (!auc && !ap) return fail("iefvad_auc_ap_grouped: auc and ap are both null");
+    if (!workspace) return fail("iefvad_auc_ap_grouped: workspace is null");
+    if (ngroups < 1 || ngroups > MT_MAXG) return fail("iefvad_auc_ap_grouped: ngroups = %d, 1 .. %d groups per call", ngroups, MT_MAXG);
+    if (n <= 0) return fail("iefvad_auc_ap_grouped: n = %lld", (long long)n);
+    if (repeat <= 0 || repeat > (int32_t)MT_POS_MASK)       // a snippet's positives share the payload word with the group byte
+        return fail("iefvad_auc_ap_grouped: repeat = %d, 1 .. %u frames per snippet", repeat, MT_POS_MASK);
+    if ((unsigned long long)n * (unsigned long long)repeat >= (1ull << 32))
+        return fail("iefvad_auc_ap_grouped: n * repeat = %llu frames do not fit the 32-bit frame counters", (unsigned long long)n * (unsigned long long)repeat);
+    if (((uintptr_t)workspace & 255) != 0) return fail("iefvad_auc_ap_grouped: the workspace must be 256-byte aligned");
+    MetricWs w;
+    const size_t need = metric_layout(n, ngroups, (char*)workspace, &w);
+    if (workspace_bytes < need) return fail("iefvad_auc_ap_grouped: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    hipStream_t stream = (hipStream_t)stream_;
+    const int tiles = (int)((n + MT_TILE - 1) / MT_TILE);
+    unsigned long long* nanmask = (unsigned long long*)w.flags;
+    HIP_TRY(hipMemsetAsync(w.auc_num, 0, 8 * (MT_MAXG + 1), stream));          // the numerators and, behind them, the NaN mask
+    hipLaunchKernelGGL(iefvad_metric_pairs_grouped_kernel, dim3((unsigned)((n + MT_THREADS - 1) / MT_THREADS)), dim3(MT_THREADS), 0, stream, scores,
+                       (const unsigned char*)gt_frames, (const unsigned char*)group, (long long)n, (int)repeat, (int)ngroups, w.a, nanmask);
+    // ordered by (group, key); w.dtotal keeps the last digit's totals = the pairs per group.  The other buffer takes the scanned columns
+    const unsigned long long* src = metric_sort(w, n, tiles, true, stream);
+    unsigned* tp_incl = (unsigned*)(src == w.a ? w.b : w.a);
+    unsigned* gstart = tp_incl + n;
+    hipLaunchKernelGGL(iefvad_metric_tile_sums_kernel<true>, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, w.bsum, w.bstart);
+    hipLaunchKernelGGL(iefvad_metric_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, w.bsum, w.bstart, tiles);
+    hipLaunchKernelGGL(iefvad_metric_tile_apply_kernel<true>, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, w.bsum, w.bstart, tp_incl, gstart);
+    hipLaunchKernelGGL(iefvad_metric_group_table_kernel, dim3(1), dim3(128), 0, stream, w.dtotal, tp_incl, (int)ngroups, w.tab);
+    hipLaunchKernelGGL(iefvad_metric_groups_grouped_kernel, dim3(tiles), dim3(MT_THREADS), 0, stream, src, (long long)n, (int)repeat, (int)ngroups, tp_incl,
+                       gstart, w.tab, w.auc_num, w.ap_part, tiles);
+    hipLaunchKernelGGL(iefvad_metric_finish_grouped_kernel, dim3(ngroups), dim3(256), 0, stream, w.tab, (int)repeat, w.auc_num, w.ap_part, tiles, nanmask,
+                       auc, ap, (long long*)frames);
     HIP_TRY(hipGetLastError());
     return 0;
 }

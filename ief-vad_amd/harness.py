@@ -289,6 +289,111 @@ def device_auc_ap(scores: torch.Tensor, gt: torch.Tensor, repeat: int = 16) -> T
     return auc, ap
 
 
+def _metric_inputs(scores: torch.Tensor, gt, repeat: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp32 scores [N] and one-byte ground truth [N * repeat] on the scores' device, as the metric entries read them (a tensor that
+    already has that form comes back as it is)."""
+    s = scores.reshape(-1).to(torch.float32).contiguous()
+    g = torch.as_tensor(gt).reshape(-1)
+    if g.numel() != s.numel() * repeat:
+        raise ValueError("gt must hold `repeat` frames per snippet")
+    g = g if g.dtype in (torch.uint8, torch.bool) else (g != 0).to(torch.uint8)
+    return s, g.to(s.device, non_blocking=True).contiguous()
+
+
+def device_grouped_auc_ap(scores: torch.Tensor, gt: torch.Tensor, group: torch.Tensor, ngroups: int,
+                          repeat: int = 16) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`device_auc_ap` for up to 64 disjoint groups of snippets in one pass (the library's `iefvad_auc_ap_grouped`): the per-class
+    loops of test.py:165-174 with group = class, the Ano-AUC of test.py:161 with one group that leaves the normal videos out.
+    `group` [N] bytes: a value in [0, ngroups) puts the snippet into that group, 255 into none.  Returns
+    (auc [ngroups], ap [ngroups], frames [ngroups, 2] = {frames, positive frames} per group) as numpy arrays, in ONE read-back.
+    An empty group gives NaN / NaN, one class only gives auc NaN (sklearn raises there), no positive frame gives ap 0."""
+    from . import lib as _lib
+    import ctypes as C
+    if not scores.is_cuda:
+        raise RuntimeError("device_grouped_auc_ap runs on a HIP device only (iefvad_auc_ap_grouped); on the host use evaluate_scores (sklearn)")
+    s, g = _metric_inputs(scores, gt, repeat)
+    grp = torch.as_tensor(group).reshape(-1)
+    if grp.numel() != s.numel():
+        raise ValueError("group must hold one byte per snippet")
+    grp = grp.to(device=s.device, dtype=torch.uint8).contiguous()
+    lib = _lib.load_library()
+    n = s.numel()
+    with torch.cuda.device(s.device):
+        ws = torch.empty(lib.iefvad_auc_ap_grouped_workspace_bytes(n, ngroups) + 256, dtype=torch.uint8, device=s.device)
+        off = (-ws.data_ptr()) % 256
+        out = torch.empty(4 * max(ngroups, 1), dtype=torch.float64, device=s.device)      # auc | ap | frames (int64 bits)
+        rc = lib.iefvad_auc_ap_grouped(C.c_void_p(s.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(grp.data_ptr()), n, repeat, ngroups,
+                                       C.c_void_p(out.data_ptr()), C.c_void_p(out.data_ptr() + 8 * ngroups),
+                                       C.c_void_p(out.data_ptr() + 16 * ngroups), C.c_void_p(ws.data_ptr() + off), ws.numel() - off,
+                                       C.c_void_p(torch.cuda.current_stream(s.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError("iefvad_auc_ap_grouped: " + _lib.last_error())
+    host = out.cpu().numpy()
+    return host[:ngroups].copy(), host[ngroups:2 * ngroups].copy(), host[2 * ngroups:].view(np.int64).reshape(ngroups, 2).copy()
+
+
+def evaluate_scores_device(scores, classes: Sequence[str], gt, dataset: str, verbose: bool = True, normal_keys=('Normal',),
+                           total_samples: bool = False, log: Optional[Callable] = None) -> Dict[str, object]:
+    """`evaluate_scores` with all three groups of sklearn calls replaced by library calls on ONE device-resident copy of the
+    concatenated scores and of `gt`: `iefvad_auc_ap` for the global pair (test.py:158-159), one `iefvad_auc_ap_grouped` call with the
+    class index of every snippet for the per-class pairs (test.py:165-174), one with a single group that leaves the `normal_keys`
+    classes out for the Ano-AUC (test.py:161).  Same dict, same printed lines in the same order, same `log` calls.
+
+    `scores`: per-video host vectors in test-list order (uploaded once), or `(tensor, lengths)` -- one device tensor of the
+    concatenated scores plus the per-video lengths; then only the per-video class bytes go up and the results come back.  `gt` may be
+    a host array or a device tensor.  The Ano-AUC is NaN where `compute_ano_auc` returns NaN; a class of `CLASS_KEYS[dataset]` without
+    a video raises ValueError where the host function's `np.concatenate` does.  Where sklearn raises (a class whose frames are all
+    positive, NaN scores) the value is NaN instead."""
+    keys = CLASS_KEYS[dataset]
+    if isinstance(scores, tuple) and len(scores) == 2 and torch.is_tensor(scores[0]):
+        flat, lengths = scores[0].reshape(-1), [int(n) for n in scores[1]]
+    else:
+        lengths = [len(s) for s in scores]
+        flat = torch.from_numpy(np.concatenate([np.asarray(s, dtype=np.float32).reshape(-1) for s in scores]))
+    if not flat.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError("evaluate_scores_device runs on a HIP device only (iefvad_auc_ap, iefvad_auc_ap_grouped); "
+                               "on the host use evaluate_scores (sklearn)")
+        flat = flat.cuda()
+    if len(lengths) != len(classes) or sum(lengths) != flat.numel():
+        raise ValueError("one class and one length per video, the lengths adding up to the number of scores")
+    index = {k: i for i, k in enumerate(keys)}
+    cls_idx = np.array([index[c] for c in classes], dtype=np.uint8)          # KeyError for a class outside the table, as cw_pred[c] gives
+    videos = np.bincount(cls_idx, minlength=len(keys))
+    normal = np.array([k in normal_keys for k in keys])
+    s, g = _metric_inputs(flat, gt, 16)
+    # per-snippet group bytes from the per-video ones, expanded on the device: [class index | 0 = abnormal, 255 = left out]
+    per_video = torch.from_numpy(np.stack([cls_idx, np.where(normal[cls_idx], 255, 0).astype(np.uint8)])).to(s.device)
+    groups = torch.repeat_interleave(per_video, torch.tensor(lengths, device=s.device), dim=1, output_size=s.numel())
+    roc, ap = device_auc_ap(s, g)
+    c_roc, c_ap, c_frames = device_grouped_auc_ap(s, g, groups[0], len(keys))
+    ano = float(device_grouped_auc_ap(s, g, groups[1], 1)[0][0])
+    if verbose:
+        print("AUC1: {:.2f}  AP1: {:.2f}".format(roc * 100, ap * 100))
+        print("Ano-AUC: {:.2f}".format(ano * 100))
+    if log is not None:
+        log({'test/AP1': ap, 'test/ROC1': roc, 'test/Ano-AUC': ano})
+    per_class = {}
+    for i, c in enumerate(keys):
+        if videos[i] == 0:
+            raise ValueError("need at least one array to concatenate")      # np.concatenate([]) of test.py:166-167
+        frames, positives = int(c_frames[i, 0]), int(c_frames[i, 1])
+        if frames == 0 or positives == 0:
+            continue
+        r, a = float(c_roc[i]), float(c_ap[i])
+        if verbose and total_samples:
+            print(c, 'ROC: {:.2f}  AP: {:.2f}'.format(r * 100, a * 100), end='\t')
+            print(f"Total Samples: {frames}")
+        elif verbose:
+            print(c, 'ROC: {:.2f}  AP: {:.2f}'.format(r * 100, a * 100))
+        if log is not None:
+            log({'classwise/ROC/' + c: r, 'classwise/AP/' + c: a})
+        per_class[c] = (r, a)
+    if verbose:
+        print('-------------------------------------------------')
+    return {"roc": roc, "ap": ap, "ano_auc": ano, "per_class": per_class}
+
+
 # ------------------------------------------------------------------------------------------------
 # the evaluation loop
 # ------------------------------------------------------------------------------------------------
@@ -460,7 +565,8 @@ class _RowStager:
 
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
-                 ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False):
+                 ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
+                 return_device: bool = False):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -483,7 +589,10 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     lanes > 1 (HIP devices, `iefvad_amd.MMFMIL`): consecutive forwards go round-robin to `lanes` HIP streams, each with a
     lane of the model (`MMFMIL.lanes`: same parameters, own library handle and workspace) and its own pinned staging.
     Same kernels on the same inputs, so every score is bit-identical to lanes = 1; what changes is that the one- and
-    two-chunk forwards of the per-video pattern, each of which fills a fraction of the chip, overlap."""
+    two-chunk forwards of the per-video pattern, each of which fills a fraction of the chip, overlap.
+
+    `return_device`: a fifth result, the scores of all videos as ONE tensor on the model's device (valid snippets in loader order --
+    what `evaluate_scores_device` takes together with the per-video lengths), so a device metric tail needs no upload."""
     classes: List[str] = []
     pend: List[Tuple[torch.Tensor, torch.Tensor, int]] = []
     pend_chunks = 0
@@ -671,14 +780,22 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                 torch.cuda.current_stream(device).wait_stream(s)
         if dev_prob:
             # ONE device-to-host copy for the three vectors (sigmoid on the device: logits1[0:len_cur] -> sigmoid, test.py:119-121)
-            allv = torch.stack([torch.sigmoid(torch.cat(dev_prob)), torch.cat(dev_wi), torch.cat(dev_we)]).cpu().numpy()
+            alld = torch.stack([torch.sigmoid(torch.cat(dev_prob)), torch.cat(dev_wi), torch.cat(dev_we)])
+            allv = alld.cpu().numpy()
             prob, wi, we = allv[0], allv[1], allv[2]
         else:
+            alld = torch.zeros(3, 0, device=device)
             prob = wi = we = np.zeros(0, np.float32)
     # per-video views of the three host vectors (contiguous spans in loader order; padded routes leave gaps between them)
     scores = [prob[o:o + n] for o, n in spans]
     wi_means = [wi[o:o + n] for o, n in spans]
     we_means = [we[o:o + n] for o, n in spans]
+    if return_device:
+        # the packed routes leave the valid snippets back to back; the padded ones leave gaps between the videos
+        ends = np.cumsum([n for _, n in spans], dtype=np.int64)
+        packed = [o for o, _ in spans] == [0, *ends[:-1]] and (ends[-1] if len(ends) else 0) == alld.shape[1]
+        dev = alld[0] if packed else torch.cat([alld[0, o:o + n] for o, n in spans] or [alld[0, :0]])
+        return scores, classes, wi_means, we_means, dev
     return scores, classes, wi_means, we_means
 
 
@@ -883,11 +1000,15 @@ def evaluate_files(args, model, gt, device, dataset: Optional[str] = None, batch
 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
-              batch_chunks, lanes):
+              batch_chunks, lanes, metric_tail="host"):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
-    xd_test.py:155-159,170-173), which go to `log` when the caller supplies one (wandb itself is out of scope)."""
+    xd_test.py:155-159,170-173), which go to `log` when the caller supplies one (wandb itself is out of scope).
+    `metric_tail`: "host" = sklearn (`evaluate_scores`); "device" = the library's metric entries on the scores as the loop left them
+    on the device (`evaluate_scores_device`)."""
+    if metric_tail not in ("host", "device"):
+        raise ValueError('metric_tail must be "host" or "device"')
     model.to(device)
     model.eval()
     if batch_chunks is None:
@@ -898,10 +1019,16 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
         # UCF-sized list.
         packed_same_bits = (getattr(model, "compute", None) in ("f32", "bf16") and torch.device(device).type == "cuda" and lanes == 1)
         batch_chunks = 64 if packed_same_bits else 0
-    scores, classes, wi, we = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks,
-                                           lanes=lanes)
-    res = evaluate_scores(scores, classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
-                          total_samples=total_samples, log=log)
+    if metric_tail == "device":
+        scores, classes, wi, we, dev = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks,
+                                                    lanes=lanes, return_device=True)
+        res = evaluate_scores_device((dev, [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
+                                     total_samples=total_samples, log=log)
+    else:
+        scores, classes, wi, we = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks,
+                                               lanes=lanes)
+        res = evaluate_scores(scores, classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
+                              total_samples=total_samples, log=log)
     last = dict(res, scores=scores, classes=classes, w_i_mean=wi, w_e_mean=we)
     if vis:
         print("[iefvad_amd] vis=True: plotting (test.py:177-207) is outside the hot-path scope; skipped")
@@ -911,30 +1038,32 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
-         batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1):
+         batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host"):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
     (ROC1, AP1, attn_weights, labels) when attn=True.  For `train/ucf_test.py` and `train/xd_test.py` -- whose
-    positional orders differ from this one and from each other -- use `ucf_test` / `xd_test` below."""
+    positional orders differ from this one and from each other -- use `ucf_test` / `xd_test` below.
+    `metric_tail="device"` (opt-in, here and in `ucf_test` / `xd_test`): the whole metric tail -- global, Ano-AUC and per-class --
+    through the library on the device-resident scores (`evaluate_scores_device`) instead of sklearn on the host."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
-                                      False, None, batch_chunks, lanes)
+                                      False, None, batch_chunks, lanes, metric_tail)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
-             batch_chunks: Optional[int] = None, lanes: int = 1):
+             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host"):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
-                                          ('Normal', 'normal'), True, log, batch_chunks, lanes)
+                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
-            batch_chunks: Optional[int] = None, lanes: int = 1):
+            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host"):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -942,7 +1071,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
     if label_map is None:
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
-                                         ('normal',), False, log, batch_chunks, lanes)
+                                         ('normal',), False, log, batch_chunks, lanes, metric_tail)
     test.last_result = xd_test.last_result
     return ret
 

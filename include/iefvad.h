@@ -357,6 +357,7 @@ int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int
 /* ---- metric tail of the evaluation loop --------------------------------------------------------------
  * What /root/reference/test.py:158-159 (train/ucf_test.py:153-154, train/xd_test.py:146-147) computes with sklearn on the host,
  *     ROC1 = roc_auc_score(gt, np.repeat(ap1, 16));   AP1 = average_precision_score(gt, np.repeat(ap1, 16))
+ * (the GLOBAL pair; the per-class pairs and the Ano-AUC behind it are iefvad_auc_ap_grouped below)
  * on the DEVICE from the n per-snippet scores and the frame-level ground truth, without materialising the x`repeat` copy: one
  * radix sort of n (score, positive-frames-of-the-snippet) pairs, a scan, a reduction over the tie groups.  Thresholds are the
  * DISTINCT score values as in sklearn's _binary_clf_curve (tied snippets share one threshold; -0.0 == +0.0); the AUC numerator is
@@ -370,6 +371,28 @@ int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int
 size_t iefvad_auc_ap_workspace_bytes(int64_t n);
 int iefvad_auc_ap(const float* scores, const uint8_t* gt_frames, int64_t n, int32_t repeat, double* auc, double* ap,
                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same two numbers for up to 64 disjoint GROUPS of the snippets in one pass: the per-class ROC-AUC / AP loops of test.py:165-174
+ * (train/ucf_test.py, train/xd_test.py alike) with group = class of the snippet's video, and the Ano-AUC of test.py:161
+ * (compute_ano_auc, :332-348) with one group that leaves the normal videos out.  These two tails are OPT-IN in the Python harness
+ * (metric_tail="device"); its default keeps sklearn on the host.  The group byte is a fifth radix digit above the score key, so
+ * the pairs are sorted by (group, score) once; within a group everything is iefvad_auc_ap: thresholds are the group's distinct
+ * scores (-0.0 == +0.0; a tie never spans two groups), exact 64-bit integer AUC numerators, AP terms in doubles reduced in a
+ * fixed order (no floating-point atomics: the same bits every run).
+ *   group       DEVICE [n] bytes: a value in [0, ngroups) puts the snippet into that group, 255 into none; every other value is
+ *               treated as 255
+ *   ngroups     1 .. 64
+ *   auc, ap     DEVICE [ngroups] doubles, each nullable (not both).  Per group: a NaN score makes ITS two results NaN (no other
+ *               group's); one class only -> auc NaN; no positive frame -> ap 0; an empty group -> both NaN
+ *   frames      DEVICE [2 * ngroups] int64, nullable: {frames in the group, positive frames in the group} -- what the reference's
+ *               skip rule `len(cls_gt) == 0 or sum(cls_gt) == 0` and its "Total Samples" print need
+ *   workspace   DEVICE, iefvad_auc_ap_grouped_workspace_bytes(n, ngroups) bytes (the ungrouped call's plus 8 ngroups bytes per 4096
+ *               snippets and ~2 KB), 256-byte aligned; 0 for n <= 0 or ngroups outside 1 .. 64
+ * n * repeat must stay below 2^32 frames, and repeat below 2^24: a snippet's positive-frame count shares the pair's 32-bit payload
+ * with the group byte.  Every argument is checked before the first HIP call.  Enqueued on `stream`; returns without synchronising. */
+size_t iefvad_auc_ap_grouped_workspace_bytes(int64_t n, int32_t ngroups);
+int iefvad_auc_ap_grouped(const float* scores, const uint8_t* gt_frames, const uint8_t* group, int64_t n, int32_t repeat, int32_t ngroups,
+                          double* auc, double* ap, int64_t* frames, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training input pipeline ----------------------------------------------------------
  * The reference's train-mode loader rule (/root/reference/data/tools.py:65-97: process_feat -> uniform_extract / pad) on the DEVICE:
