@@ -10,7 +10,6 @@ The model is any callable with the reference's `model(img, ev, padding_mask, tex
 """
 from __future__ import annotations
 
-import collections
 import concurrent.futures
 import contextlib
 import csv
@@ -407,13 +406,24 @@ def _has_nan(t: torch.Tensor) -> bool:
     return bool(torch.isnan(s)) and bool(torch.isnan(t).any())
 
 
+def video_chunks(n: int, T: int) -> int:
+    # chunks of a video of n rows without the loader's all-zero chunk: the rule of `video_chunks` in csrc/iefvad.hip
+    return n // T + (1 if n % T else 0) if n >= T else 1
+
+
+def _item_class(item, dataset, label_map):
+    """Class name of one DataLoader item (batch_size=1), remapped where the reference remaps it."""
+    cls = item[2][0] if isinstance(item[2], (list, tuple)) else item[2]
+    if label_map is not None and (dataset == 'xd' or isinstance(label_map, _AlwaysRemap)):
+        cls = label_map[cls.split('-')[0]]            # xd_test.py:68 / test.py:80-81
+    return cls
+
+
 def _unpack_item(item, maxlen, dataset, label_map):
     """Shape rule of test.py:77-88 applied to one DataLoader item (batch_size=1)."""
     img = item[0].squeeze(0)
     ev = item[1].squeeze(0)
-    cls = item[2][0] if isinstance(item[2], (list, tuple)) else item[2]
-    if label_map is not None and (dataset == 'xd' or isinstance(label_map, _AlwaysRemap)):
-        cls = label_map[cls.split('-')[0]]            # xd_test.py:68 / test.py:80-81
+    cls = _item_class(item, dataset, label_map)
     length = int(item[3])
     if length < maxlen:
         img = img.unsqueeze(0)
@@ -429,9 +439,7 @@ def _unpack_rows(item, maxlen, dataset, label_map):
     """One DataLoader item (batch_size=1, chunked and zero padded by the loader as the reference's is) reduced to what
     crosses the boundary in the ragged path: per modality the item's own [..., D] tensor, whose first `length` rows are the
     valid ones (no view is built: two tensor ops per video were a third of the loop's host time on short videos)."""
-    cls = item[2][0] if isinstance(item[2], (list, tuple)) else item[2]
-    if label_map is not None and (dataset == 'xd' or isinstance(label_map, _AlwaysRemap)):
-        cls = label_map[cls.split('-')[0]]            # xd_test.py:68 / test.py:80-81
+    cls = _item_class(item, dataset, label_map)
     length = int(item[3])
     img, ev = item[0], item[1]
     if not img.is_contiguous():
@@ -441,12 +449,9 @@ def _unpack_rows(item, maxlen, dataset, label_map):
     return img, ev, cls, length
 
 
-class _PinnedStager:
-    """Host -> device hand-over of the evaluation loop.  The reference does `img.to(device)` on pageable tensors
-    (test.py:90-95), a synchronous staged copy at a few GB/s that blocks the host for longer than a one-chunk forward
-    takes on the device.  Here the chunks of a forward are gathered into one of two reusable PINNED buffers (one host
-    memcpy, which also does the torch.cat of a packed batch) and sent with an asynchronous copy on the current stream;
-    a buffer is reused only after the event behind its last copy has completed."""
+class _Stager:
+    """`slots` reusable PINNED staging slots, taken in turn; a slot is reused only after the event behind its last copy has
+    completed.  What is staged, and how a slot's buffers grow, is the subclass's."""
 
     def __init__(self, device, slots: int = 2, threads: int = 0):
         self.device = torch.device(device)
@@ -454,6 +459,25 @@ class _PinnedStager:
         self.bufs = [[None, None] for _ in range(slots)]      # per slot: image / event pinned byte buffers
         self.events = [None] * slots
         self.turn = 0
+
+    def _next_slot(self):
+        slot = self.turn
+        self.turn = (self.turn + 1) % len(self.bufs)
+        if self.events[slot] is not None:
+            self.events[slot].synchronize()
+        return slot
+
+    def _sent(self, slot):
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self.events[slot] = ev
+
+
+class _PinnedStager(_Stager):
+    """Host -> device hand-over of the evaluation loop.  The reference does `img.to(device)` on pageable tensors
+    (test.py:90-95), a synchronous staged copy at a few GB/s that blocks the host for longer than a one-chunk forward
+    takes on the device.  Here the chunks of a forward are gathered into one of two reusable PINNED buffers (one host
+    memcpy, which also does the torch.cat of a packed batch) and sent with an asynchronous copy on the current stream."""
 
     def _buffer(self, slot, m, nbytes):
         b = self.bufs[slot][m]
@@ -463,10 +487,7 @@ class _PinnedStager:
         return b
 
     def upload(self, imgs, evs, dt):
-        slot = self.turn
-        self.turn = (self.turn + 1) % len(self.bufs)
-        if self.events[slot] is not None:
-            self.events[slot].synchronize()
+        slot = self._next_slot()
         out = []
         for m, parts in enumerate((imgs, evs)):
             n = sum(int(p.shape[0]) for p in parts)
@@ -479,24 +500,15 @@ class _PinnedStager:
                 host[off:off + p.shape[0]].copy_(p)          # casts when the batch was widened
                 off += p.shape[0]
             out.append(host.to(self.device, non_blocking=True))
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self.events[slot] = ev
+        self._sent(slot)
         return out[0], out[1]
 
 
-class _RowStager:
+class _RowStager(_Stager):
     """Host -> device hand-over of VALID rows (the packed evaluation loop through `MMFMIL.forward_videos`): the feature rows
     of a batch of videos are copied, without their zero padding, into one of `slots` reusable pinned buffers -- by a few
     threads when the batch is large -- and sent with one asynchronous copy per modality on the current stream.  Nothing on
     the host reads the rows: the NaN scan of test.py:90-95 happens on the device (csrc/ragged.h)."""
-
-    def __init__(self, device, slots: int = 2, threads: int = 0):
-        self.device = torch.device(device)
-        self.threads = threads or max(1, min(8, host_cpu_share() // 2))      # host threads of one staging copy
-        self.bufs = [[None, None] for _ in range(slots)]
-        self.events = [None] * slots
-        self.turn = 0
 
     def _buffer(self, slot, m, nbytes):
         b = self.bufs[slot][m]
@@ -518,10 +530,7 @@ class _RowStager:
         """Host half of `upload`: the rows of all videos into the next pinned slot.  Touches no stream (it only waits for the
         slot's previous copy), so a worker thread can run it while the caller's thread enqueues the previous batch.
         `lens` given: imgs / evs are contiguous [..., D] tensors whose FIRST lens[i] rows are taken."""
-        slot = self.turn
-        self.turn = (self.turn + 1) % len(self.bufs)
-        if self.events[slot] is not None:
-            self.events[slot].synchronize()
+        slot = self._next_slot()
         D = int(imgs[0].shape[-1])
         if lens is None:
             lens = [int(p.shape[0]) for p in imgs]
@@ -552,15 +561,177 @@ class _RowStager:
         """Device half: one asynchronous copy per modality on the current stream.  Returns two [sum(len), D] device tensors."""
         slot, hosts = staged
         out = [h.to(self.device, non_blocking=True) for h in hosts]
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self.events[slot] = ev
+        self._sent(slot)
         return out[0], out[1]
 
     def upload(self, imgs, evs, dt, lens=None):
         """imgs / evs: per video [len, D] host tensors (views are fine), or with `lens` contiguous [..., D] tensors of which the
         first lens[i] rows count.  Returns two [sum(len), D] device tensors."""
         return self.send(self.stage(imgs, evs, dt, lens))
+
+
+class _ScoreSink:
+    """What the forwards of one `score_loader` call leave behind.  Results stay on the model's device until the loop is over: the
+    reference synchronises three times per video (`.cpu()` of prob / w_i / w_e, test.py:119-151); here the forwards are enqueued
+    back to back and the scores of all videos come back in ONE device-to-host copy at the end (`finish`)."""
+
+    def __init__(self):
+        self.classes: List[str] = []
+        self.dev_prob, self.dev_wi, self.dev_we = [], [], []      # per forward: flat fp32 device vectors
+        self.spans: List[Tuple[int, int]] = []     # (offset into the concatenated device vectors, valid length) per video
+        self.total = 0
+
+    def add(self, logits, wi, we, lens, stride=None):
+        """One forward's flat fp32 vectors over videos of `lens` snippets: back to back (the valid-row routes), or video i in
+        stride[i] slots of which the first lens[i] count (the padded route: its chunks * maxlen)."""
+        self.dev_prob.append(logits)
+        self.dev_wi.append(wi)
+        self.dev_we.append(we)
+        off = self.total
+        for n, s in zip(lens, lens if stride is None else stride):
+            self.spans.append((off, n))                      # logits1[0:len_cur] -> sigmoid, test.py:119-121
+            off += s
+        self.total = off
+
+    def finish(self, device, return_device):
+        """(scores, classes, w_i_mean, w_e_mean[, all scores as one device tensor]): per-video views of three host vectors."""
+        if self.dev_prob:
+            # ONE device-to-host copy for the three vectors (sigmoid once, on the device, on the concatenated logits)
+            alld = torch.stack([torch.sigmoid(torch.cat(self.dev_prob)), torch.cat(self.dev_wi), torch.cat(self.dev_we)])
+            allv = alld.cpu().numpy()
+        else:
+            alld = torch.zeros(3, 0, device=device)
+            allv = np.zeros((3, 0), np.float32)
+        scores, wi_means, we_means = ([v[o:o + n] for o, n in self.spans] for v in allv)
+        if not return_device:
+            return scores, self.classes, wi_means, we_means
+        packed = sum(n for _, n in self.spans) == self.total      # no gaps: the valid snippets already lie back to back
+        dev = alld[0] if packed else torch.cat([alld[0, o:o + n] for o, n in self.spans])
+        return scores, self.classes, wi_means, we_means, dev
+
+
+def _batch_dtype(pend):
+    """(dtype in which a batch of (img, ev, ...) entries is staged, whether that widens any of them).  The dtype is the files'
+    (dataset.py:37-38,49-50); the model widens with `.to(torch.float)` per modality (imf_vad.py:41-42), so a batch that mixes
+    dtypes -- across videos OR between the two modalities -- is widened to fp32 rather than narrowed to the first tensor's type."""
+    dts = {p[0].dtype for p in pend} | {p[1].dtype for p in pend}
+    return (torch.float32, True) if len(dts) > 1 else (pend[0][0].dtype, False)
+
+
+def _lane_stream(stream):
+    """Where a lane's copies and forwards are enqueued: on its own HIP stream, with one lane on the current stream."""
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
+
+
+def _score_padded(models, stagers, streams, loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks):
+    """Padded route (the only one on the CPU): `model(img, ev, ...)` on zero-padded chunks, one forward per video
+    (batch_chunks <= 0) or per batch, which closes as soon as it holds `batch_chunks` chunks; forwards round-robin over the lanes.
+    `_unpack_item` has applied the NaN rule in each tensor's own dtype; a mixed batch is widened while it is staged."""
+    def forward(pend, k):
+        dt, _ = _batch_dtype(pend)
+        with _lane_stream(streams[k]):
+            if stagers[k] is not None:
+                img, ev = stagers[k].upload([p[0] for p in pend], [p[1] for p in pend], dt)
+            else:
+                img = torch.cat([p[0].to(dt) for p in pend], dim=0).to(device)
+                ev = torch.cat([p[1].to(dt) for p in pend], dim=0).to(device)
+            out = models[k](img, ev, None, None, None)
+            logits = out['logits'].reshape(-1)
+            if 'w_i_mean' in out:
+                wi, we = out['w_i_mean'].reshape(-1), out['w_e_mean'].reshape(-1)
+            else:
+                wi = out['w_i'].reshape(-1, out['w_i'].shape[-1]).mean(dim=-1)     # test.py:131-136
+                we = out['w_e'].reshape(-1, out['w_e'].shape[-1]).mean(dim=-1)
+            sink.add(logits.float(), wi.float(), we.float(), [n for _, _, n in pend], [ci.shape[0] * maxlen for ci, _, _ in pend])
+
+    pend, pend_chunks, nsent = [], 0, 0
+    for item in loader:
+        img, ev, cls, n = _unpack_item(item, maxlen, dataset, label_map)
+        sink.classes.append(cls)
+        if batch_chunks > 0 and skip_empty_chunks and n >= maxlen and n % maxlen == 0:
+            img, ev = img[:-1], ev[:-1]               # the all-zero chunk (tools.py:105-112)
+        pend.append((img, ev, n))
+        pend_chunks += img.shape[0]
+        if batch_chunks <= 0 or pend_chunks >= batch_chunks:
+            forward(pend, nsent % len(models))
+            pend, pend_chunks, nsent = [], 0, nsent + 1
+    if pend:
+        forward(pend, nsent % len(models))
+
+
+def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks):
+    """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
+    round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
+    while this thread sends batch k and enqueues its forward; batches complete in order."""
+    def stage(pend, k):
+        dt, widened = _batch_dtype(pend)
+        if widened:               # a narrower video is widened at staging: its own dtype's inf -> max rule applies first (test.py:90-95)
+            pend = [tuple(torch.nan_to_num(t, nan=0.0) if (t.dtype != dt and _has_nan(t)) else t for t in (p[0], p[1])) + (p[2],)
+                    for p in pend]
+        lens = [n for _, _, n in pend]
+        return k, stage_pool.submit(stagers[k].stage, [p[0] for p in pend], [p[1] for p in pend], dt, lens), lens
+
+    def send_and_forward(k, fut, lens):
+        staged = fut.result()
+        with _lane_stream(streams[k]):
+            img, ev = stagers[k].send(staged)
+            out = models[k].forward_videos(img, ev, lens, nan_to_num=True)
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens)
+
+    stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
+    inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
+    pend, pend_chunks, nstaged = [], 0, 0
+    try:
+        for item in loader:
+            img, ev, cls, n = _unpack_rows(item, maxlen, dataset, label_map)
+            sink.classes.append(cls)
+            pend.append((img, ev, n))
+            pend_chunks += video_chunks(n, maxlen)
+            if pend_chunks >= batch_chunks:
+                inflight.append(stage(pend, nstaged % len(models)))
+                pend, pend_chunks, nstaged = [], 0, nstaged + 1
+                if len(inflight) > 1:
+                    send_and_forward(*inflight.pop(0))
+        if pend:
+            inflight.append(stage(pend, nstaged % len(models)))
+        for batch in inflight:
+            send_and_forward(*batch)
+    finally:
+        stage_pool.shutdown(wait=True)              # also when a forward raised: the worker thread must not outlive the call
+
+
+def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16):
+    """Valid-row route with the walk inside the library (`MMFMIL.forward_videos_host`, csrc/hostpipe.h): this thread only collects
+    each video's host tensor and length; one library call per `host_list_bytes` of features stages, sends and scores them pass by
+    pass.  Same batches, same kernels as `_score_rows_loop` (which remains for models without the entry, lanes > 1 callers that
+    ask for it with host_list=False, and device-resident loaders)."""
+    def forward(group):
+        wire = torch.bfloat16 if (wire_bf16 and group[0][0].dtype == torch.float32) else None
+        lens = [g[2] for g in group]
+        out = model.forward_videos_host([g[0] for g in group], [g[1] for g in group], lens, nan_to_num=True,
+                                        batch_chunks=batch_chunks, wire_dtype=wire)
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens)
+
+    group, gbytes = [], 0
+    for item in loader:
+        img, ev, cls, n = _unpack_rows(item, maxlen, dataset, label_map)
+        sink.classes.append(cls)
+        if img.is_cuda or ev.is_cuda:
+            raise ValueError("host_list=True expects the loader's tensors in host memory")
+        if img.dtype != ev.dtype or img.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            # the model widens both with `.to(torch.float)` (imf_vad.py:41-42); the NaN rule applies in the file's own dtype first
+            img, ev = (torch.nan_to_num(t, nan=0.0) if _has_nan(t) else t for t in (img, ev))
+            img, ev = img.float(), ev.float()
+        if group and group[0][0].dtype != img.dtype:
+            forward(group)                                    # a library call takes one feature dtype
+            group, gbytes = [], 0
+        group.append((img, ev, n))
+        gbytes += 2 * n * img.shape[-1] * img.element_size()
+        if gbytes >= host_list_bytes:
+            forward(group)
+            group, gbytes = [], 0
+    if group:
+        forward(group)
 
 
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
@@ -593,18 +764,6 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
 
     `return_device`: a fifth result, the scores of all videos as ONE tensor on the model's device (valid snippets in loader order --
     what `evaluate_scores_device` takes together with the per-video lengths), so a device metric tail needs no upload."""
-    classes: List[str] = []
-    pend: List[Tuple[torch.Tensor, torch.Tensor, int]] = []
-    pend_chunks = 0
-    # results stay on the model's device until the loop is over: the reference synchronises three times per video
-    # (`.cpu()` of prob / w_i / w_e, test.py:119-151); here the forwards are enqueued back to back and the scores of
-    # all videos come back in ONE device-to-host copy at the end
-    dev_prob: List[torch.Tensor] = []
-    dev_wi: List[torch.Tensor] = []
-    dev_we: List[torch.Tensor] = []
-    spans: List[Tuple[int, int]] = []          # (offset into the concatenated device vectors, valid length) per video
-    total = 0
-
     on_gpu = torch.device(device).type == 'cuda'
     nl = lanes if (on_gpu and lanes > 1 and hasattr(model, 'lanes')) else 1
     models = model.lanes(nl) if nl > 1 else [model]
@@ -612,191 +771,29 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         ragged = on_gpu and batch_chunks > 0 and skip_empty_chunks and hasattr(model, 'forward_videos')
     elif ragged and not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos')):
         raise ValueError("ragged=True needs a HIP device, batch_chunks > 0 and a model with forward_videos")
+    use_list = bool(ragged and host_list and hasattr(model, 'forward_videos_host'))
     # staging buffers are pinned allocations: they live with the lane (model object) across calls, not with the call
-    stagers = []
-    for m in models:
-        if not on_gpu:
-            stagers.append(None)
-            continue
+    stagers = [None] * nl
+    for k, m in enumerate(models if on_gpu else ()):
         cache = m.__dict__.setdefault("_stagers", {}) if hasattr(m, "__dict__") else {}
         key = ("rows" if ragged else "chunks", str(device))
         if key not in cache:
             cache[key] = _RowStager(device) if ragged else _PinnedStager(device)
-        stagers.append(cache[key])
+        stagers[k] = cache[key]
     streams = [torch.cuda.Stream(device=device) for _ in range(nl)] if nl > 1 else [None]
-    if nl > 1:
-        for s in streams:
-            s.wait_stream(torch.cuda.current_stream(device))     # e.g. a `model.to(device)` still in flight
-    nflush = 0
-    # packed valid-row loop: the staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker
-    # thread while this thread sends batch k and enqueues its forward; batches complete in order
-    inflight: collections.deque = collections.deque()
-    stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1) if ragged else None
-
-    def run_oldest():
-        nonlocal total
-        fut, k, lens = inflight.popleft()
-        staged = fut.result()
-        ctx = torch.cuda.stream(streams[k]) if nl > 1 else contextlib.nullcontext()
-        with ctx:
-            img, ev = stagers[k].send(staged)
-            out = models[k].forward_videos(img, ev, lens, nan_to_num=True)
-        dev_prob.append(out['logits'])
-        dev_wi.append(out['w_i_mean'])
-        dev_we.append(out['w_e_mean'])
-        off = total
-        for n in lens:
-            spans.append((off, n))
-            off += n
-        total = off
-
-    def flush():
-        nonlocal nflush, pend, pend_chunks
-        if not pend:
-            return
-        k = nflush % nl
-        nflush += 1
-        if ragged:
-            dts = {p[0].dtype for p in pend} | {p[1].dtype for p in pend}
-            dt = torch.float32 if len(dts) > 1 else pend[0][0].dtype
-            if len(dts) > 1:      # a narrower video is widened at staging: its own dtype's inf -> max rule applies first (test.py:90-95)
-                pend = [tuple(torch.nan_to_num(t, nan=0.0) if (t.dtype != dt and _has_nan(t)) else t for t in (p[0], p[1])) + (p[2],)
-                        for p in pend]
-            lens = [n for _, _, n in pend]
-            fut = stage_pool.submit(stagers[k].stage, [p[0] for p in pend], [p[1] for p in pend], dt, lens)
-            inflight.append((fut, k, lens))
-            pend, pend_chunks = [], 0
-            while len(inflight) > 1:
-                run_oldest()
-            return
-        if nl > 1:
-            with torch.cuda.stream(streams[k]):
-                flush_on(models[k], stagers[k])
-        else:
-            flush_on(models[0], stagers[0])
-
-    def flush_on(model, stager):
-        nonlocal pend, pend_chunks, total
-        # dtype as the files hold it (dataset.py:37-38,49-50); the model widens with `.to(torch.float)` per modality
-        # (imf_vad.py:41-42), so a batch that mixes dtypes -- across videos OR between the two modalities -- is widened
-        # to fp32 here rather than narrowed to the first tensor's type
-        dts = {p[0].dtype for p in pend} | {p[1].dtype for p in pend}
-        dt = torch.float32 if len(dts) > 1 else pend[0][0].dtype
-        if stager is not None:
-            img, ev = stager.upload([p[0] for p in pend], [p[1] for p in pend], dt)
-        else:
-            img = torch.cat([p[0].to(dt) for p in pend], dim=0).to(device)
-            ev = torch.cat([p[1].to(dt) for p in pend], dim=0).to(device)
-        out = model(img, ev, None, None, None)
-        logits = out['logits'].reshape(-1)
-        if 'w_i_mean' in out:
-            wi, we = out['w_i_mean'].reshape(-1), out['w_e_mean'].reshape(-1)
-        else:
-            wi = out['w_i'].reshape(-1, out['w_i'].shape[-1]).mean(dim=-1)     # test.py:131-136
-            we = out['w_e'].reshape(-1, out['w_e'].shape[-1]).mean(dim=-1)
-        dev_prob.append(logits.float())                      # sigmoid once, on the concatenated logits, after the loop
-        dev_wi.append(wi.float())
-        dev_we.append(we.float())
-        off = total
-        for ci, _, n in pend:
-            spans.append((off, n))                           # logits1[0:len_cur] -> sigmoid, test.py:119-121
-            off += ci.shape[0] * maxlen
-        total = off
-        pend, pend_chunks = [], 0
-
-    # packed valid-row loop with the walk inside the library (`MMFMIL.forward_videos_host`, csrc/hostpipe.h): this thread only
-    # collects each video's host tensor and length; one library call per `host_list_bytes` of features stages, sends and scores
-    # them pass by pass.  Same batches, same kernels as the loop below (which remains for models without the entry, lanes > 1
-    # callers that ask for it with host_list=False, and device-resident loaders).
-    use_list = bool(ragged and host_list and hasattr(model, 'forward_videos_host'))
-    if use_list:
-        group: List[Tuple[torch.Tensor, torch.Tensor, int]] = []
-        gbytes = 0
-
-        def flush_list():
-            nonlocal group, gbytes, total
-            if not group:
-                return
-            wire = torch.bfloat16 if (wire_bf16 and group[0][0].dtype == torch.float32) else None
-            out = model.forward_videos_host([g[0] for g in group], [g[1] for g in group], [g[2] for g in group], nan_to_num=True,
-                                            batch_chunks=batch_chunks, wire_dtype=wire)
-            dev_prob.append(out['logits'])
-            dev_wi.append(out['w_i_mean'])
-            dev_we.append(out['w_e_mean'])
-            off = total
-            for _, _, n in group:
-                spans.append((off, n))
-                off += n
-            total = off
-            group, gbytes = [], 0
-
-        with torch.no_grad():
-            for item in test_loader:
-                img, ev, cls, n = _unpack_rows(item, maxlen, dataset, label_map)
-                classes.append(cls)
-                if img.is_cuda or ev.is_cuda:
-                    raise ValueError("host_list=True expects the loader's tensors in host memory")
-                if img.dtype != ev.dtype or img.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                    # the model widens both with `.to(torch.float)` (imf_vad.py:41-42); the NaN rule applies in the file's own dtype first
-                    img, ev = (torch.nan_to_num(t, nan=0.0) if _has_nan(t) else t for t in (img, ev))
-                    img, ev = img.float(), ev.float()
-                if group and group[0][0].dtype != img.dtype:
-                    flush_list()                                  # a library call takes one feature dtype
-                group.append((img, ev, n))
-                gbytes += 2 * n * img.shape[-1] * img.element_size()
-                if gbytes >= host_list_bytes:
-                    flush_list()
-            flush_list()
-        test_loader = ()
-        ragged = False
-
+    sink = _ScoreSink()
     with torch.no_grad():
-        try:
-            for item in test_loader:
-                if ragged:
-                    img, ev, cls, n = _unpack_rows(item, maxlen, dataset, label_map)
-                    classes.append(cls)
-                    pend.append((img, ev, n))
-                    pend_chunks += n // maxlen + (1 if n % maxlen else 0) if n >= maxlen else 1
-                    if pend_chunks >= batch_chunks:
-                        flush()
-                    continue
-                img, ev, cls, n = _unpack_item(item, maxlen, dataset, label_map)
-                classes.append(cls)
-                if batch_chunks > 0 and skip_empty_chunks and n >= maxlen and n % maxlen == 0:
-                    img, ev = img[:-1], ev[:-1]               # the all-zero chunk (tools.py:105-112)
-                pend.append((img, ev, n))
-                pend_chunks += img.shape[0]
-                if batch_chunks <= 0 or pend_chunks >= batch_chunks:
-                    flush()
-            flush()
-            while inflight:
-                run_oldest()
-        finally:
-            if stage_pool is not None:         # also when a forward raised: the worker thread must not outlive the call
-                stage_pool.shutdown(wait=True)
-        if nl > 1:
-            for s in streams:
-                torch.cuda.current_stream(device).wait_stream(s)
-        if dev_prob:
-            # ONE device-to-host copy for the three vectors (sigmoid on the device: logits1[0:len_cur] -> sigmoid, test.py:119-121)
-            alld = torch.stack([torch.sigmoid(torch.cat(dev_prob)), torch.cat(dev_wi), torch.cat(dev_we)])
-            allv = alld.cpu().numpy()
-            prob, wi, we = allv[0], allv[1], allv[2]
+        for s in streams if nl > 1 else ():
+            s.wait_stream(torch.cuda.current_stream(device))         # e.g. a `model.to(device)` still in flight
+        if use_list:
+            _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16)
+        elif ragged:
+            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks)
         else:
-            alld = torch.zeros(3, 0, device=device)
-            prob = wi = we = np.zeros(0, np.float32)
-    # per-video views of the three host vectors (contiguous spans in loader order; padded routes leave gaps between them)
-    scores = [prob[o:o + n] for o, n in spans]
-    wi_means = [wi[o:o + n] for o, n in spans]
-    we_means = [we[o:o + n] for o, n in spans]
-    if return_device:
-        # the packed routes leave the valid snippets back to back; the padded ones leave gaps between the videos
-        ends = np.cumsum([n for _, n in spans], dtype=np.int64)
-        packed = [o for o, _ in spans] == [0, *ends[:-1]] and (ends[-1] if len(ends) else 0) == alld.shape[1]
-        dev = alld[0] if packed else torch.cat([alld[0, o:o + n] for o, n in spans] or [alld[0, :0]])
-        return scores, classes, wi_means, we_means, dev
-    return scores, classes, wi_means, we_means
+            _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks)
+        for s in streams if nl > 1 else ():
+            torch.cuda.current_stream(device).wait_stream(s)
+        return sink.finish(device, return_device)
 
 
 class FeatureFilePipeline:
@@ -876,7 +873,7 @@ class FeatureFilePipeline:
             plans, cur, cur_chunks = [], [], 0
             for idx, (mi, _) in enumerate(maps):
                 n = int(mi[1][0])
-                nch = (n // T + (1 if n % T else 0)) if n >= T else 1
+                nch = video_chunks(n, T)
                 cur.append((idx, n, nch))
                 cur_chunks += nch
                 if cur_chunks >= self.batch_chunks:

@@ -162,6 +162,57 @@ def test_mixed_dtype_between_modalities_is_widened_not_narrowed():
         assert torch.equal(seen[0][2][0, :40], torch.from_numpy(ev))          # event features bit-exact, not fp16-rounded
 
 
+def test_return_device_on_the_padded_route(config1):
+    """The padded route leaves gaps between the videos in the concatenated vectors: the fifth result is put together from the
+    valid spans, and asking for it changes none of the other four."""
+    g, args, gt, sd = config1
+    model = orc.OracleMMFMIL(sd, orc.OracleConfig())
+    s4, c4, wi4, we4 = harness.score_loader(model, harness.get_test_loader(args), 256, "cpu", "ucfcrime", batch_chunks=8)
+    s5, c5, wi5, we5, dev = harness.score_loader(model, harness.get_test_loader(args), 256, "cpu", "ucfcrime", batch_chunks=8,
+                                                 return_device=True)
+    assert dev.device.type == "cpu" and dev.shape == (int(g["lengths"].sum()),)
+    assert np.array_equal(dev.numpy(), np.concatenate(s5))
+    assert c4 == c5 and len(s4) == len(s5) == len(g["lengths"])
+    for a, b in zip(s4 + wi4 + we4, s5 + wi5 + we5):
+        assert np.array_equal(a, b)
+
+
+def _chunk_recorder(seen):
+    def model(img, ev, *_):
+        seen.append(int(img.shape[0]))
+        return {"logits": torch.zeros(img.shape[0], img.shape[1], 1), "w_i": torch.zeros_like(img, dtype=torch.float32),
+                "w_e": torch.zeros_like(img, dtype=torch.float32)}
+    return model
+
+
+def _zero_item(n, D=8):
+    ci, _ = harness.process_split(np.zeros((n, D), np.float32), 256)
+    return torch.tensor(ci).unsqueeze(0), torch.tensor(ci).unsqueeze(0), ("Normal",), torch.tensor([n])
+
+
+def test_padded_route_call_sequence():
+    """Which forwards the padded route issues: a batch is sent as soon as it holds `batch_chunks` chunks or more, so videos of
+    1, 3, 1, 2, 1 chunks with batch_chunks=3 go as 1+3, 1+2 and 1; the loader's all-zero second chunk of a 256-row video is sent
+    only with skip_empty_chunks=False."""
+    seen = []
+    lengths = [40, 600, 100, 300, 7]
+    scores, _, _, _ = harness.score_loader(_chunk_recorder(seen), [_zero_item(n) for n in lengths], 256, "cpu", "ucfcrime", batch_chunks=3)
+    assert seen == [4, 3, 1]
+    assert [len(s) for s in scores] == lengths
+    seen.clear()
+    harness.score_loader(_chunk_recorder(seen), [_zero_item(256)], 256, "cpu", "ucfcrime", batch_chunks=3, skip_empty_chunks=False)
+    assert seen == [2]
+    seen.clear()
+    harness.score_loader(_chunk_recorder(seen), [_zero_item(256)], 256, "cpu", "ucfcrime", batch_chunks=3)
+    assert seen == [1]
+
+
+def test_video_chunks_follows_the_library_rule():
+    """Chunks a video of n rows occupies once the loader's all-zero chunk is dropped -- the values
+    test_streaming_file_pipeline_matches_per_video_loop expects of the pipeline."""
+    assert [harness.video_chunks(n, 256) for n in (1, 37, 255, 256, 257, 512, 1500)] == [1, 1, 1, 1, 2, 2, 6]
+
+
 def test_pipeline_rejects_event_file_of_another_length(tmp_path):
     d = tmp_path / "rgb"
     d.mkdir()
