@@ -38,6 +38,7 @@
 #include "gemm_split_tn.h"
 #include "backward.h"
 #include "metrics.h"
+#include "similarity.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -2233,6 +2234,32 @@ extern "C" int iefvad_gather_windows(const float* img_set, const float* ev_set, 
     const int nvec = IEF_T * D / 4, per_wg = 256 * IEF_GW_VEC;
     hipLaunchKernelGGL(iefvad_gather_windows_kernel, dim3((nvec + per_wg - 1) / per_wg, B, 2), dim3(256), 0, (hipStream_t)stream_, img_set, ev_set,
                        (const int*)set_lengths, (int)nset, (const int*)index, (int)D, img_out, ev_out, (int*)len_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the similarity series of the vis=True plots (similarity.h)
+// ------------------------------------------------------------------------------------------------
+extern "C" int iefvad_similarity_rows(const float* fused, const float* image_mu, const float* event_mu, int64_t rows, int32_t D,
+                                      const int32_t* src_rows, int64_t nout, float* out, void* stream_) {
+    if (!fused || !image_mu || !event_mu) return fail("iefvad_similarity_rows: null tensor (fused, image_mu, event_mu)");
+    if (!out) return fail("iefvad_similarity_rows: null out");
+    if (rows <= 0) return fail("iefvad_similarity_rows: rows = %lld must be positive", (long long)rows);
+    if (nout < 0) return fail("iefvad_similarity_rows: nout = %lld is negative", (long long)nout);
+    if (D != 768 && D != 512) return fail("iefvad_similarity_rows: D = %d (768 and 512 are built)", D);
+    if (!src_rows && nout > rows) return fail("iefvad_similarity_rows: nout = %lld exceeds rows = %lld without src_rows", (long long)nout, (long long)rows);
+    if (nout > 0x7fffffffLL) return fail("iefvad_similarity_rows: nout = %lld exceeds one launch (2^31 - 1 rows)", (long long)nout);
+    if (((uintptr_t)fused & 15) || ((uintptr_t)image_mu & 15) || ((uintptr_t)event_mu & 15) || ((uintptr_t)out & 15) || ((uintptr_t)src_rows & 3))
+        return fail("iefvad_similarity_rows: misaligned pointer (the tensors and out 16-byte, src_rows 4-byte)");
+    if (nout == 0) return 0;
+    const dim3 grid((unsigned)((nout + ROW_WAVES - 1) / ROW_WAVES));
+    if (D == 768)
+        hipLaunchKernelGGL(iefvad_similarity_rows_kernel<768>, grid, dim3(256), 0, (hipStream_t)stream_, fused, image_mu, event_mu, (long long)rows,
+                           (const int*)src_rows, (long long)nout, out);
+    else
+        hipLaunchKernelGGL(iefvad_similarity_rows_kernel<512>, grid, dim3(256), 0, (hipStream_t)stream_, fused, image_mu, event_mu, (long long)rows,
+                           (const int*)src_rows, (long long)nout, out);
     HIP_TRY(hipGetLastError());
     return 0;
 }

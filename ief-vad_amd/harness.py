@@ -13,6 +13,7 @@ from __future__ import annotations
 import concurrent.futures
 import contextlib
 import csv
+import os
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -393,6 +394,47 @@ def evaluate_scores_device(scores, classes: Sequence[str], gt, dataset: str, ver
     return {"roc": roc, "ap": ap, "ano_auc": ano, "per_class": per_class}
 
 
+SIMILARITY_KEYS = ("cos_i", "cos_e", "dist_i", "dist_e")
+
+
+def similarity_rows(fused: torch.Tensor, image_mu: torch.Tensor, event_mu: torch.Tensor,
+                    src_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The four per-snippet series of the reference's similarity plots (test.py:235-238, ucf_test.py:243-247) as ONE [4, nout] fp32
+    tensor on the inputs' device, rows in `SIMILARITY_KEYS` order:
+        F.cosine_similarity(fused, image_mu), F.cosine_similarity(fused, event_mu), torch.norm(fused - image_mu), torch.norm(fused - event_mu)
+    over the last dimension.  The three tensors are [..., D] (leading dimensions are flattened); output row j reads flattened row
+    `src_rows[j]` (every row in order without an index) -- the `[0:len]` slice of a padded batch is an index, not a copy.  On a HIP
+    device one launch of the library's `iefvad_similarity_rows` (csrc/similarity.h; D = 768 or 512, fp32); on the CPU the four torch
+    calls themselves."""
+    D = int(fused.shape[-1])
+    if image_mu.shape != fused.shape or event_mu.shape != fused.shape:
+        raise ValueError("fused, image_mu and event_mu must have one shape")
+    f, i, e = (t.reshape(-1, D) for t in (fused, image_mu, event_mu))
+    if not f.is_cuda:
+        if src_rows is not None:
+            idx = torch.as_tensor(src_rows, dtype=torch.long, device=f.device)
+            f, i, e = f[idx], i[idx], e[idx]
+        f, i, e = f.float(), i.float(), e.float()
+        return torch.stack([torch.nn.functional.cosine_similarity(f, i, dim=-1), torch.nn.functional.cosine_similarity(f, e, dim=-1),
+                            torch.norm(f - i, dim=-1), torch.norm(f - e, dim=-1)])
+    from . import lib as _lib
+    import ctypes as C
+    f, i, e = (t.to(torch.float32).contiguous() for t in (f, i, e))
+    rows = int(f.shape[0])
+    idx = None
+    if src_rows is not None:
+        idx = torch.as_tensor(src_rows).to(device=f.device, dtype=torch.int32).contiguous()
+    nout = rows if idx is None else int(idx.numel())
+    out = torch.empty(4, nout, dtype=torch.float32, device=f.device)
+    with torch.cuda.device(f.device):
+        rc = _lib.load_library().iefvad_similarity_rows(C.c_void_p(f.data_ptr()), C.c_void_p(i.data_ptr()), C.c_void_p(e.data_ptr()), rows, D,
+                                                        C.c_void_p(idx.data_ptr() if idx is not None and nout else None), nout,
+                                                        C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(f.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError("iefvad_similarity_rows: " + _lib.last_error())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # the evaluation loop
 # ------------------------------------------------------------------------------------------------
@@ -580,10 +622,14 @@ class _ScoreSink:
         self.dev_prob, self.dev_wi, self.dev_we = [], [], []      # per forward: flat fp32 device vectors
         self.spans: List[Tuple[int, int]] = []     # (offset into the concatenated device vectors, valid length) per video
         self.total = 0
+        self.dev_sim: Optional[List[torch.Tensor]] = None     # score_loader(similarity=True): per forward [4, valid snippets of its videos]
 
-    def add(self, logits, wi, we, lens, stride=None):
+    def add(self, logits, wi, we, lens, stride=None, sim=None):
         """One forward's flat fp32 vectors over videos of `lens` snippets: back to back (the valid-row routes), or video i in
-        stride[i] slots of which the first lens[i] count (the padded route: its chunks * maxlen)."""
+        stride[i] slots of which the first lens[i] count (the padded route: its chunks * maxlen).  `sim`: the forward's
+        `similarity_rows` over the valid snippets of its videos, back to back."""
+        if sim is not None:
+            self.dev_sim.append(sim)
         self.dev_prob.append(logits)
         self.dev_wi.append(wi)
         self.dev_we.append(we)
@@ -594,20 +640,32 @@ class _ScoreSink:
         self.total = off
 
     def finish(self, device, return_device):
-        """(scores, classes, w_i_mean, w_e_mean[, all scores as one device tensor]): per-video views of three host vectors."""
+        """(scores, classes, w_i_mean, w_e_mean[, all scores as one device tensor][, similarity]): per-video views of three host
+        vectors; with `dev_sim` a last result {key of SIMILARITY_KEYS: per-video views of that series}."""
+        valid = sum(n for _, n in self.spans)
+        simv = None
         if self.dev_prob:
             # ONE device-to-host copy for the three vectors (sigmoid once, on the device, on the concatenated logits)
             alld = torch.stack([torch.sigmoid(torch.cat(self.dev_prob)), torch.cat(self.dev_wi), torch.cat(self.dev_we)])
-            allv = alld.cpu().numpy()
+            if self.dev_sim is None:
+                allv = alld.cpu().numpy()
+            else:                                # ... and the four similarity series ride in the same copy
+                flat = torch.cat([alld.reshape(-1), torch.cat(self.dev_sim, dim=1).reshape(-1)]).cpu().numpy()
+                allv, simv = flat[:3 * self.total].reshape(3, self.total), flat[3 * self.total:].reshape(4, valid)
         else:
             alld = torch.zeros(3, 0, device=device)
             allv = np.zeros((3, 0), np.float32)
         scores, wi_means, we_means = ([v[o:o + n] for o, n in self.spans] for v in allv)
-        if not return_device:
-            return scores, self.classes, wi_means, we_means
-        packed = sum(n for _, n in self.spans) == self.total      # no gaps: the valid snippets already lie back to back
-        dev = alld[0] if packed else torch.cat([alld[0, o:o + n] for o, n in self.spans])
-        return scores, self.classes, wi_means, we_means, dev
+        res = (scores, self.classes, wi_means, we_means)
+        if return_device:
+            packed = valid == self.total      # no gaps: the valid snippets already lie back to back
+            res += (alld[0] if packed else torch.cat([alld[0, o:o + n] for o, n in self.spans]),)
+        if self.dev_sim is not None:
+            if simv is None:
+                simv = np.zeros((4, 0), np.float32)
+            offs = np.concatenate([[0], np.cumsum([n for _, n in self.spans])]).astype(np.int64)
+            res += ({k: [v[offs[i]:offs[i + 1]] for i in range(len(self.spans))] for k, v in zip(SIMILARITY_KEYS, simv)},)
+        return res
 
 
 def _batch_dtype(pend):
@@ -623,10 +681,13 @@ def _lane_stream(stream):
     return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
 
-def _score_padded(models, stagers, streams, loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks):
+def _score_padded(models, stagers, streams, loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
+                  similarity=False):
     """Padded route (the only one on the CPU): `model(img, ev, ...)` on zero-padded chunks, one forward per video
     (batch_chunks <= 0) or per batch, which closes as soon as it holds `batch_chunks` chunks; forwards round-robin over the lanes.
-    `_unpack_item` has applied the NaN rule in each tensor's own dtype; a mixed batch is widened while it is staged."""
+    `_unpack_item` has applied the NaN rule in each tensor's own dtype; a mixed batch is widened while it is staged.
+    `similarity`: each forward's `fused` / `image_mu` / `event_mu` are reduced to the four series of `similarity_rows` before the next
+    forward overwrites them; the index is the `[0:len]` slice of every video of the batch (test.py:142)."""
     def forward(pend, k):
         dt, _ = _batch_dtype(pend)
         with _lane_stream(streams[k]):
@@ -642,7 +703,15 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
             else:
                 wi = out['w_i'].reshape(-1, out['w_i'].shape[-1]).mean(dim=-1)     # test.py:131-136
                 we = out['w_e'].reshape(-1, out['w_e'].shape[-1]).mean(dim=-1)
-            sink.add(logits.float(), wi.float(), we.float(), [n for _, _, n in pend], [ci.shape[0] * maxlen for ci, _, _ in pend])
+            lens, stride = [n for _, _, n in pend], [ci.shape[0] * maxlen for ci, _, _ in pend]
+            sim = None
+            if similarity:
+                if any(k not in out for k in ('fused', 'image_mu', 'event_mu')):
+                    raise ValueError(_NEEDS_FULL)
+                starts = np.concatenate([[0], np.cumsum(stride)[:-1]])
+                index = np.concatenate([np.arange(o, o + n, dtype=np.int32) for o, n in zip(starts, lens)])
+                sim = similarity_rows(out['fused'], out['image_mu'], out['event_mu'], torch.from_numpy(index))
+            sink.add(logits.float(), wi.float(), we.float(), lens, stride, sim)
 
     pend, pend_chunks, nsent = [], 0, 0
     for item in loader:
@@ -657,6 +726,10 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
             pend, pend_chunks, nsent = [], 0, nsent + 1
     if pend:
         forward(pend, nsent % len(models))
+
+
+_NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_mu: build the model with outputs="full" '
+               '(outputs="scores" / "weights" do not return them)')
 
 
 def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks):
@@ -737,7 +810,7 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
-                 return_device: bool = False):
+                 return_device: bool = False, similarity: bool = False):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -763,8 +836,20 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     two-chunk forwards of the per-video pattern, each of which fills a fraction of the chip, overlap.
 
     `return_device`: a fifth result, the scores of all videos as ONE tensor on the model's device (valid snippets in loader order --
-    what `evaluate_scores_device` takes together with the per-video lengths), so a device metric tail needs no upload."""
+    what `evaluate_scores_device` takes together with the per-video lengths), so a device metric tail needs no upload.
+
+    `similarity`: a last result, {"cos_i", "cos_e", "dist_i", "dist_e"} -> per-video arrays: cosine similarity and Euclidean distance of
+    every snippet's `fused` row to its `image_mu` / `event_mu` rows (`similarity_rows`; the series of test.py:235-238).  The padded route
+    is taken with the caller's `batch_chunks` -- the valid-row entries return no 768-wide tensors; in f32 and bf16 both routes give the
+    same bits, so the scores do not move -- and the model must return the full dict (`outputs="full"`).  The series stay on the device
+    and come back with the scores' one copy."""
     on_gpu = torch.device(device).type == 'cuda'
+    if similarity:
+        if ragged:
+            raise ValueError("similarity=True takes the padded route: ragged=True returns no fused / image_mu / event_mu")
+        if getattr(model, 'outputs', 'full') != 'full':
+            raise ValueError(_NEEDS_FULL)
+        ragged = False
     nl = lanes if (on_gpu and lanes > 1 and hasattr(model, 'lanes')) else 1
     models = model.lanes(nl) if nl > 1 else [model]
     if ragged is None:
@@ -782,6 +867,8 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         stagers[k] = cache[key]
     streams = [torch.cuda.Stream(device=device) for _ in range(nl)] if nl > 1 else [None]
     sink = _ScoreSink()
+    if similarity:
+        sink.dev_sim = []
     with torch.no_grad():
         for s in streams if nl > 1 else ():
             s.wait_stream(torch.cuda.current_stream(device))         # e.g. a `model.to(device)` still in flight
@@ -790,7 +877,8 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         elif ragged:
             _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks)
         else:
-            _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks)
+            _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
+                          similarity)
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
         return sink.finish(device, return_device)
@@ -996,14 +1084,118 @@ def evaluate_files(args, model, gt, device, dataset: Optional[str] = None, batch
     return res
 
 
+# ------------------------------------------------------------------------------------------------
+# vis=True: what the three test() files plot (test.py:177-207,276-328; ucf_test.py:181-211,219-333; xd_test.py:175-327)
+# ------------------------------------------------------------------------------------------------
+VIS_FRAMES = 3000      # frames per figure: a page of root test.py (chunk_size), the truncation of the train/ files
+VIS_FLAVOURS = ("test", "ucf_test", "xd_test")
+
+
+def vis_series(last_result: Dict[str, object], gt, flavour: str = "test", repeat: int = 16) -> Dict[str, Dict[str, object]]:
+    """The data of every figure a vis=True run writes, keyed by file name -- a pure function of a `last_result` and the frame-level
+    `gt`, so the plotted numbers can be checked without reading a PNG; `draw_vis` draws exactly this.
+
+    Per class (first appearance in the list; the videos of a class concatenated in list order, every per-snippet series repeated
+    x `repeat` to frames, gt = the class's frames of the running snippet offset, test.py:129):
+      "test"                 pages of VIS_FRAMES frames, `{cls}_{page}.png` (page from 1): scores | w_i_mean, w_e_mean, the gt == 1 frames
+                             as contiguous regions (first frame, last frame); root test.py draws no similarity figure (its call is
+                             commented out, test.py:190)
+      "ucf_test", "xd_test"  the first VIS_FRAMES frames only: `similarity_{cls}.png` cos_i, cos_e | dist_i, dist_e and `{cls}.png`
+                             scores | w_i_mean, w_e_mean, the gt == 1 frames as marked points
+    Each entry: {"x", "panels": [[(name, y), ...], [(name, y), ...]] (upper, lower), "gt_indices" (into x), "gt_regions" (list of
+    (x_first, x_last), or None where points are marked), "title"}.  The title of a class figure carries the class ROC for an abnormal
+    class that has one (`last_result["per_class"]`)."""
+    if flavour not in VIS_FLAVOURS:
+        raise ValueError(f"flavour must be one of {VIS_FLAVOURS}")
+    gt = np.asarray(gt)
+    classes = list(last_result["classes"])
+    lens = [len(s) for s in last_result["scores"]]
+    starts = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    per_class = last_result.get("per_class", {})
+    sim = last_result.get("similarity")
+
+    def frames(per_video, members):
+        return np.repeat(np.concatenate([np.asarray(per_video[v]).reshape(-1) for v in members]), repeat)
+
+    out: Dict[str, Dict[str, object]] = {}
+    for cls in dict.fromkeys(classes):
+        members = [v for v, c in enumerate(classes) if c == cls]
+        cls_gt = np.concatenate([gt[repeat * starts[v]:repeat * starts[v + 1]] for v in members])
+        prob, wi, we = (frames(last_result[k], members) for k in ("scores", "w_i_mean", "w_e_mean"))
+        roc = "" if cls in ('Normal', 'normal') or cls not in per_class else f" | ROC {per_class[cls][0]:.2f}"
+        if flavour == "test":
+            for page in range((len(prob) + VIS_FRAMES - 1) // VIS_FRAMES):
+                a, b = page * VIS_FRAMES, min((page + 1) * VIS_FRAMES, len(prob))
+                x = np.arange(a, b)
+                idx = np.where(cls_gt[a:b] == 1)[0]
+                runs = np.split(idx, np.where(np.diff(idx) != 1)[0] + 1) if idx.size else []
+                out[f"{cls}_{page + 1}.png"] = {"x": x, "panels": [[("scores", prob[a:b])], [("w_i_mean", wi[a:b]), ("w_e_mean", we[a:b])]],
+                                                "gt_indices": idx, "gt_regions": [(int(x[r[0]]), int(x[r[-1]])) for r in runs],
+                                                "title": f"Class: {cls} Chunk {page + 1}{roc}"}
+            continue
+        n = min(len(prob), VIS_FRAMES)
+        x = np.arange(n)
+        idx = np.where(cls_gt[:n] == 1)[0]
+        if sim is not None:
+            ci, ce, di, de = (frames(sim[k], members)[:n] for k in SIMILARITY_KEYS)
+            out[f"similarity_{cls}.png"] = {"x": x, "panels": [[("cos_i", ci), ("cos_e", ce)], [("dist_i", di), ("dist_e", de)]],
+                                            "gt_indices": idx, "gt_regions": None, "title": f"Similarity Metrics over Time for Class {cls}"}
+        out[f"{cls}.png"] = {"x": x, "panels": [[("scores", prob[:n])], [("w_i_mean", wi[:n]), ("w_e_mean", we[:n])]],
+                             "gt_indices": idx, "gt_regions": None, "title": f"Class: {cls}{roc}"}
+    return out
+
+
+_VIS_LABELS = {"scores": "predicted probability", "w_i_mean": "$w_i$ (image)", "w_e_mean": "$w_e$ (event)",
+               "cos_i": "cosine sim (fused, image)", "cos_e": "cosine sim (fused, event)",
+               "dist_i": "Euclidean dist (fused, image)", "dist_e": "Euclidean dist (fused, event)"}
+_VIS_COLOURS = {"scores": "gray", "w_i_mean": "skyblue", "cos_i": "skyblue", "dist_i": "skyblue"}
+
+
+def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 100) -> List[str]:
+    """One two-panel 12 x 8 inch PNG per entry of `vis_series` under `directory` (created); returns the paths.  Figures are built on
+    `matplotlib.figure.Figure` with an Agg canvas of their own: pyplot is not imported and the process's backend is not touched.
+    A figure of 3,000 frames costs matplotlib 0.2 s (dpi 40) to 0.5 s (dpi 100) on the host, whatever the device did."""
+    from matplotlib.backends.backend_agg import FigureCanvasAgg
+    from matplotlib.figure import Figure
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for name, spec in series.items():
+        fig = Figure(figsize=(12, 8), dpi=dpi)
+        FigureCanvasAgg(fig)
+        axs = fig.subplots(2, 1, sharex=True)
+        fig.suptitle(spec["title"], fontsize=16)
+        x, idx = spec["x"], spec["gt_indices"]
+        for ax, panel in zip(axs, spec["panels"]):
+            for key, y in panel:
+                ax.plot(x, y, label=_VIS_LABELS[key], color=_VIS_COLOURS.get(key, "#90EE90"))
+                if spec["gt_regions"] is None and len(idx):
+                    ax.scatter(x[idx], y[idx], color="red", s=50)
+            if spec["gt_regions"]:      # every region from its first to its last frame, as ONE collection (hundreds of patches per axis draw slowly)
+                inside = np.zeros(len(x), bool)
+                inside[idx] = True
+                ax.fill_between(x, 0, 1, where=inside, transform=ax.get_xaxis_transform(), color="red", alpha=0.3, linewidth=0)
+            ax.legend(loc="upper right")
+            ax.grid(True)
+        if spec["panels"][0][0][0] == "scores":
+            axs[0].set_ylim(0, 1)
+        axs[1].set_xlabel("frame")
+        path = os.path.join(directory, name)
+        fig.savefig(path, format="png")
+        paths.append(path)
+    return paths
+
+
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
-              batch_chunks, lanes, metric_tail="host"):
+              batch_chunks, lanes, metric_tail="host", vis_flavour="test"):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
     xd_test.py:155-159,170-173), which go to `log` when the caller supplies one (wandb itself is out of scope).
     `metric_tail`: "host" = sklearn (`evaluate_scores`); "device" = the library's metric entries on the scores as the loop left them
-    on the device (`evaluate_scores_device`)."""
+    on the device (`evaluate_scores_device`).
+    `vis`: the plots of the file named by `vis_flavour` (`vis_series` / `draw_vis`) under vis/{args.exp_name}/, at `args.vis_dpi` dots
+    per inch where the namespace has one (100 otherwise); the result dict gains "similarity" (the four series of `similarity_rows`,
+    per video) and "vis_files" (the PNG paths written)."""
     if metric_tail not in ("host", "device"):
         raise ValueError('metric_tail must be "host" or "device"')
     model.to(device)
@@ -1016,19 +1208,21 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
         # UCF-sized list.
         packed_same_bits = (getattr(model, "compute", None) in ("f32", "bf16") and torch.device(device).type == "cuda" and lanes == 1)
         batch_chunks = 64 if packed_same_bits else 0
+    # vis=True: the same loop with the four similarity series collected on the device (`score_loader(similarity=True)`, a last result)
+    got = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks, lanes=lanes,
+                       return_device=metric_tail == "device", similarity=bool(vis))
+    scores, classes, wi, we = got[:4]
     if metric_tail == "device":
-        scores, classes, wi, we, dev = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks,
-                                                    lanes=lanes, return_device=True)
-        res = evaluate_scores_device((dev, [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
+        res = evaluate_scores_device((got[4], [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
                                      total_samples=total_samples, log=log)
     else:
-        scores, classes, wi, we = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks,
-                                               lanes=lanes)
         res = evaluate_scores(scores, classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
                               total_samples=total_samples, log=log)
     last = dict(res, scores=scores, classes=classes, w_i_mean=wi, w_e_mean=we)
     if vis:
-        print("[iefvad_amd] vis=True: plotting (test.py:177-207) is outside the hot-path scope; skipped")
+        last["similarity"] = got[-1]
+        last["vis_files"] = draw_vis(vis_series(last, gt, vis_flavour), os.path.join('vis', str(args.exp_name)),      # test.py:59-62
+                                     dpi=getattr(args, 'vis_dpi', 100))
     if attn:     # the reference returns the empty list it never fills (test.py:73,209-210)
         return (res["roc"], res["ap"], [], classes), last
     return (res["roc"], res["ap"]), last
@@ -1054,7 +1248,7 @@ def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=Fal
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
-                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail)
+                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test")
     test.last_result = ucf_test.last_result
     return ret
 
@@ -1068,7 +1262,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
     if label_map is None:
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
-                                         ('normal',), False, log, batch_chunks, lanes, metric_tail)
+                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test")
     test.last_result = xd_test.last_result
     return ret
 

@@ -32,7 +32,7 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_similarity_adj", "iefvad_similarity_adj_workspace_bytes", "iefvad_distance_adj", "iefvad_gcn_forward",
            "iefvad_gcn_workspace_bytes", "iefvad_gat_forward", "iefvad_gat_workspace_bytes", "iefvad_resblock_forward",
            "iefvad_resblock_workspace_bytes", "iefvad_adamw_step_multi", "iefvad_resample_workspace_bytes", "iefvad_resample_videos",
-           "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes"]
+           "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -209,6 +209,8 @@ def load_library() -> C.CDLL:
     lib.iefvad_resample_videos.restype = C.c_int
     lib.iefvad_gather_windows.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp]
     lib.iefvad_gather_windows.restype = C.c_int
+    lib.iefvad_similarity_rows.argtypes = [vp, vp, vp, C.c_int64, i32, vp, C.c_int64, vp, vp]
+    lib.iefvad_similarity_rows.restype = C.c_int
     lib.iefvad_gemm_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p]
     lib.iefvad_gemm_bias.restype = C.c_int

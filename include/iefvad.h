@@ -394,6 +394,21 @@ size_t iefvad_auc_ap_grouped_workspace_bytes(int64_t n, int32_t ngroups);
 int iefvad_auc_ap_grouped(const float* scores, const uint8_t* gt_frames, const uint8_t* group, int64_t n, int32_t repeat, int32_t ngroups,
                           double* auc, double* ap, int64_t* frames, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The four per-snippet series of the reference's similarity plots (/root/reference/test.py:235-238, train/ucf_test.py:243-247) in ONE
+ * launch (csrc/similarity.h): for output row j and source row s = src_rows ? src_rows[j] : j
+ *   out[0][j] = F.cosine_similarity(fused[s], image_mu[s])      out[2][j] = torch.norm(fused[s] - image_mu[s])
+ *   out[1][j] = F.cosine_similarity(fused[s], event_mu[s])      out[3][j] = torch.norm(fused[s] - event_mu[s])
+ * cosine = dot / (max(|a|, 1e-8) max(|b|, 1e-8)); the squared distance is summed directly.  fp32 sums in the library's own order (not
+ * torch's bits); NaN propagates as in torch.  Rows whose squared sums overflow fp32 are outside the contract.
+ *   fused, image_mu, event_mu   DEVICE [rows, D] fp32, 16-byte aligned; D is 768 or 512
+ *   src_rows    DEVICE int32 [nout], nullable (identity; then nout <= rows).  Every entry lies in [0, rows): a precondition the
+ *               caller keeps; an entry outside it is not read for and yields four NaNs
+ *   out         DEVICE [4, nout] fp32, 16-byte aligned
+ * Null tensors or a null out, rows <= 0, nout < 0, another D and misaligned pointers are refused before any launch; nout == 0 succeeds
+ * without one.  Enqueued on `stream`; returns without synchronising. */
+int iefvad_similarity_rows(const float* fused, const float* image_mu, const float* event_mu, int64_t rows, int32_t D, const int32_t* src_rows,
+                           int64_t nout, float* out, void* stream);
+
 /* ---- training input pipeline ----------------------------------------------------------
  * The reference's train-mode loader rule (/root/reference/data/tools.py:65-97: process_feat -> uniform_extract / pad) on the DEVICE:
  * a video of n feature rows becomes one [256, D] fp32 window.  n <= 256: the rows, zero rows behind them, length n.  n > 256: 256
