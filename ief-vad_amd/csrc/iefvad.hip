@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <exception>
 #include <new>
 #include <thread>
@@ -25,6 +26,7 @@
 #include "gemm_f32.h"
 #include "gemm_bf16.h"
 #include "gemm_split.h"
+#include "gemm_split_wide.h"
 #include "rowops.h"
 #include "refine_chain_bf16.h"
 #include "outproj_ln_chain_bf16.h"
@@ -94,6 +96,7 @@ struct iefvad_handle {
     bool dense_encoder;    // IEFVAD_DENSE_ENCODER=1: whole-video passes run the encoder on whole 256-row chunks (pad rows computed), the tail on the gathered valid rows
     bool persist;          // bf16 mode: the persistent out_proj + LayerNorm, heads + fusion and attention kernels from two blocks per CU on (IEFVAD_PERSIST=0: off)
     bool train_attn_unfused; // IEFVAD_TRAIN_ATTN=unfused: bf16x6 train-mode attention on the three-launch path (train.h)
+    int split_tile;        // IEFVAD_SPLIT_TILE=128 / 256: the bf16x6 projections on one tiling of the split kernel (unset: launch_gemm_split's rule)
     bool hostpipe_trace;   // IEFVAD_HOSTPIPE_TRACE=1: iefvad_forward_videos_host prints its per-pass timeline to stderr (hostpipe.h)
     bool no_chain;
     char* chain_stream;    // bf16 mode: the refinement weights in the chain kernel's per-wave piece order (refine_chain_bf16.h)
@@ -224,6 +227,7 @@ static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg
     { const char* v = getenv("IEFVAD_DENSE_ENCODER"); h->dense_encoder = v && v[0] == '1'; }
     { const char* v = getenv("IEFVAD_TRAIN_ATTN"); h->train_attn_unfused = v && v[0] == 'u'; }
     { const char* v = getenv("IEFVAD_HOSTPIPE_TRACE"); h->hostpipe_trace = v && v[0] == '1'; }
+    { const char* v = getenv("IEFVAD_SPLIT_TILE"); const int t = v ? atoi(v) : 0; h->split_tile = (t == 128 || t == 256) ? t : 0; }
     hipError_t e = hipGetDevice(&h->device);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)iefvad_gemm_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -269,6 +273,9 @@ static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg
                                 GB2_LDS_BYTES);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                GS_LDS_BYTES_OF(2));
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 GS_LDS_BYTES_OF(2));
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)iefvad_attention_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -782,14 +789,31 @@ static bool split_eligible(int M, int N, int K, int nz) {
     return M % GS_BM == 0 && N % kSplitBN == 0 && K % 64 == 0 && K >= 64 && (M / GS_BM) * (N / kSplitBN) * nz >= kSplitMinWgs;
 }
 
-static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false) {
+// Two bit-identical tilings of the bf16x6 arithmetic (gemm_split.h): 128 x 128, and 128 x 256 as two column halves that share the
+// A planes (half the split work and A staging per MFMA: 7 % less time at 262,144 rows).  The wide one takes a launch whose wide grid
+// has at least kSplitWideMinWgs workgroups, the measured crossover (`tools/gemm_tune_split sweep` at N = 768, 1536 and 2304, bias and
+// refine epilogues, profiles/split_wide_gemm_tune.log): from three rounds of the chip's 512 workgroup slots on it wins at all three
+// widths (time ratio 0.93-0.98); at two rounds it ties (0.99-1.01), at one round and below the narrow grid's twice as many, half as
+// long workgroups win by 6-15 %.  tile_n = 128 / 256 forces a tiling (the unit entry iefvad_gemm_split_unit, IEFVAD_SPLIT_TILE);
+// the fp16x3 arithmetic has the narrow tiling only.
+static const int kSplitWideMinWgs = 1536;     // 3 x 512
+static std::atomic<unsigned long long> g_split_wide_launches{0};     // iefvad_gemm_split_wide_launches: which tiling ran is otherwise invisible
+static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false, int tile_n = 0) {
     if (a.M % GS_BM || a.N % kSplitBN || a.K % 64 || a.K < 64)
         return fail("gemm(bf16x6): shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", a.M, a.N, a.K, GS_BM, kSplitBN);
+    if (tile_n != 0 && tile_n != 128 && tile_n != 256) return fail("gemm(bf16x6): tile_n = %d (128, 256 or 0 for the launch rule)", tile_n);
+    if (tile_n == 256 && (f16 || a.N % 256))
+        return fail("gemm(bf16x6): the 128 x 256 tiling takes bf16x6 problems with N %% 256 == 0 (N = %d%s)", a.N, f16 ? ", fp16x3" : "");
+    const bool wide = !f16 && a.N % 256 == 0 && (tile_n == 256 || (tile_n == 0 && (a.M / GS_BM) * (a.N / 256) * nz >= kSplitWideMinWgs));
     if (a.epi == EPI_BIAS_RELU_DOT && (f16 || nz != 1 || !a.p[0].R || !a.p[0].C2))
         return fail("gemm(bf16x6): the dot-product epilogue takes one bf16x6 problem with its vector (R) and its partial sums (C2)");
-    dim3 grid((a.M / GS_BM) * (a.N / kSplitBN), 1, nz);
+    dim3 grid((a.M / GS_BM) * (a.N / (wide ? 256 : kSplitBN)), 1, nz);
     hipEvent_t e = tm.begin(stage);
-    if (f16) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
+    if (wide) {
+        hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
+        g_split_wide_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    else if (f16) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
     else hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
     tm.end(e);
     tm.gemm_launches += 1;
@@ -825,7 +849,7 @@ struct Proj {
 };
 
 // D: the contraction length (the row width of A), the handle's embed dim
-static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage) {
+static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage, int split_tile = 0) {
     const bool bf16 = (compute == IEFVAD_COMPUTE_BF16);
     if (p.epi == EPI_BIAS_RELU_DOT && !(use_split && compute == IEFVAD_COMPUTE_BF16X6))
         return fail("gemm: the dot-product epilogue exists in the bf16x6 split kernel only");
@@ -844,7 +868,8 @@ static int launch_proj(const Proj& p, int compute, bool use_split, int D, int ro
                 g.p[m].amaxA = p.amaxA[m]; g.p[m].amaxW = p.amaxW[m]; g.p[m].amaxC = p.amaxC[m];
             }
         }
-        return launch_gemm_split(g, p.nz, stream, tm, stage, f16);
+        // IEFVAD_SPLIT_TILE is a preference: a projection the wide tiling cannot take (fp16x3, N % 256 != 0) runs on the narrow one
+        return launch_gemm_split(g, p.nz, stream, tm, stage, f16, (f16 || (split_tile == 256 && p.N % 256)) ? (f16 ? 0 : 128) : split_tile);
     }
     if (!bf16) {
         GemmArgs g;
@@ -1153,7 +1178,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             p.amaxC[m] = b.am_qkv(l, m);
             if (bf) p.Cb[m] = b.qkvb[m]; else p.C[m] = b.qkv[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV, h->split_tile)) return rc;
     }
 
     hipEvent_t e = tm.begin(ST_ATT);
@@ -1191,7 +1216,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             p.A32[m] = b.att[m]; p.A16[m] = b.attb[m]; p.amaxA[m] = b.am_att(l, m);
             p.C[m] = b.ybuf[m]; p.R[m] = b.cur[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT, h->split_tile)) return rc;
 
         LnArgs la;
         memset(&la, 0, sizeof(la));
@@ -1297,7 +1322,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             p.A32[m] = b.xt[m]; p.A16[m] = b.xtb[m]; p.amaxA[m] = b.am_x(L - 1, m);
         }
         p.C[0] = b.mu_i; p.C2[0] = b.lv_i; p.C[1] = b.mu_e; p.C2[1] = b.lv_e;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD, h->split_tile)) return rc;
 
         // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
         FusionArgs fa;
@@ -1339,7 +1364,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
             if (!out->fused) p.C[0] = nullptr;
         }
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->split_tile)) return rc;
         if (dot) {
             hipEvent_t e = tm.begin(ST_SCORER);
             hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
@@ -1353,7 +1378,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         p.set_w(0, h->ref2[k]);
         p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
         p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->split_tile)) return rc;
     }
 
     // 5. scorer (imf_vad.py:150)
@@ -2360,8 +2385,48 @@ extern "C" int iefvad_gemm_bias(const void* A, const void* W, const float* bias,
         g.p[0].A = (const bf16_t*)A; g.p[0].W = (const bf16_t*)W; g.p[0].bias = bias; g.p[0].C = C;
         hipError_t e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            GS_LDS_BYTES_OF(2));
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2));
         if (e != hipSuccess) return fail("iefvad_gemm_bias: %s", hipGetErrorString(e));
         return launch_gemm_split(g, 1, (hipStream_t)stream, tm, ST_QKV);
     }
     return fail("iefvad_gemm_bias: unknown compute mode %d", compute);
+}
+
+extern "C" uint64_t iefvad_gemm_split_wide_launches(void) { return g_split_wide_launches.load(std::memory_order_relaxed); }
+
+extern "C" int iefvad_gemm_split_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
+                                      int32_t qcols, float alpha, int32_t nz, int32_t tile_n, void* stream) {
+    static const int epi_of[] = {EPI_BIAS, EPI_QKV, EPI_BIAS_RELU, EPI_BIAS_RESID, EPI_REFINE, EPI_HEADS, EPI_BIAS_RELU_DOT};
+    if (!io) return fail("iefvad_gemm_split_unit: null argument");
+    auto aligned = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+    if (epilogue < 0 || epilogue >= (int)(sizeof(epi_of) / sizeof(epi_of[0]))) return fail("iefvad_gemm_split_unit: unknown epilogue %d", epilogue);
+    if (nz < 1 || nz > 2) return fail("iefvad_gemm_split_unit: nz = %d (1 or 2)", nz);
+    if (tile_n != 128 && tile_n != 256) return fail("iefvad_gemm_split_unit: tile_n = %d (128 or 256)", tile_n);
+    if (M <= 0 || N <= 0 || K < 64 || M % GS_BM || N % tile_n || K % 64)
+        return fail("iefvad_gemm_split_unit: shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", M, N, K, GS_BM, tile_n);
+    const int epi = epi_of[epilogue];
+    const bool heads = epi == EPI_HEADS, dot = epi == EPI_BIAS_RELU_DOT;
+    const bool resid = epi == EPI_BIAS_RESID || epi == EPI_REFINE;
+    if (heads ? (N != 2 * ldc || ldc % 128) : (ldc < N || ldc % 4)) return fail("iefvad_gemm_split_unit: ldc = %d does not fit N = %d", ldc, N);
+    if (epi == EPI_QKV && (qcols < 0 || qcols > N || qcols % 8)) return fail("iefvad_gemm_split_unit: qcols = %d", qcols);
+    GemmBArgs g;
+    memset(&g, 0, sizeof(g));
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = ldc; g.epi = epi; g.alpha = alpha; g.qcols = qcols;
+    g.wplane = N * K * 2;
+    for (int m = 0; m < nz; ++m) {
+        if (!io->A[m] || !io->W[m] || !io->bias[m] || (!io->C[m] && !dot) || ((resid || dot) && !io->R[m]) || ((heads || dot) && !io->C2[m]))
+            return fail("iefvad_gemm_split_unit: problem %d lacks an operand of epilogue %d", m, epilogue);
+        if (!aligned(io->A[m]) || !aligned(io->W[m]) || !aligned(io->bias[m]) || !aligned(io->C[m]) || !aligned(io->R[m]) || !aligned(io->C2[m]))
+            return fail("iefvad_gemm_split_unit: operands must be 16-byte aligned");
+        g.p[m].A = (const bf16_t*)io->A[m]; g.p[m].W = (const bf16_t*)io->W[m]; g.p[m].bias = io->bias[m]; g.p[m].C = io->C[m];
+        g.p[m].R = (resid || dot) ? io->R[m] : nullptr;
+        g.p[m].C2 = (heads || dot) ? io->C2[m] : nullptr;
+    }
+    hipError_t e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2));
+    if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2));
+    if (e != hipSuccess) return fail("iefvad_gemm_split_unit: %s", hipGetErrorString(e));
+    Timer tm;
+    return launch_gemm_split(g, nz, (hipStream_t)stream, tm, ST_QKV, false, tile_n);
 }

@@ -32,7 +32,7 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_similarity_adj", "iefvad_similarity_adj_workspace_bytes", "iefvad_distance_adj", "iefvad_gcn_forward",
            "iefvad_gcn_workspace_bytes", "iefvad_gat_forward", "iefvad_gat_workspace_bytes", "iefvad_resblock_forward",
            "iefvad_resblock_workspace_bytes", "iefvad_adamw_step_multi", "iefvad_resample_workspace_bytes", "iefvad_resample_videos",
-           "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows"]
+           "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows", "iefvad_gemm_split_unit", "iefvad_gemm_split_wide_launches"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -105,6 +105,15 @@ class UnitIO(C.Structure):
 
 
 UNIT_INPROJ, UNIT_OUTPROJ_LN, UNIT_HEADS, UNIT_REFINE, UNIT_ATTENTION = 0, 1, 2, 3, 4
+
+
+class GemmSplitIO(C.Structure):
+    """iefvad_gemm_split_io (include/iefvad.h)."""
+    _fields_ = [(n, C.c_void_p * 2) for n in ("A", "W", "bias", "R", "C", "C2")]
+
+
+(SPLIT_EPI_BIAS, SPLIT_EPI_QKV, SPLIT_EPI_BIAS_RELU, SPLIT_EPI_BIAS_RESID, SPLIT_EPI_REFINE, SPLIT_EPI_HEADS,
+ SPLIT_EPI_BIAS_RELU_DOT) = range(7)
 
 
 class ResblockWeights(C.Structure):
@@ -214,6 +223,11 @@ def load_library() -> C.CDLL:
     lib.iefvad_gemm_bias.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_int32, C.c_void_p]
     lib.iefvad_gemm_bias.restype = C.c_int
+    lib.iefvad_gemm_split_unit.argtypes = [C.POINTER(GemmSplitIO), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_float, C.c_int32, C.c_int32, C.c_void_p]
+    lib.iefvad_gemm_split_unit.restype = C.c_int
+    lib.iefvad_gemm_split_wide_launches.argtypes = []
+    lib.iefvad_gemm_split_wide_launches.restype = C.c_uint64
     lib.iefvad_split_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.iefvad_split_bf16x3.restype = C.c_int
     lib.iefvad_split_bf16x3_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -523,6 +523,42 @@ int iefvad_rowblock_unit(iefvad_handle* h, int32_t stage, int32_t layer, int32_t
 int iefvad_gemm_bias(const void* A, const void* W, const float* bias, float* C,
                      int32_t M, int32_t N, int32_t K, int32_t compute, void* stream);
 
+/* One projection (or nz = 2 problems of one shape in one launch) on the bf16x6 split kernel, on the tiling the caller names:
+ * tile_n = 128 (128 x 128 block tile) or 256 (128 x 256 as two column halves; N % 256 == 0).  The two tilings sum every output
+ * element in the same order, so they agree bit for bit; the library's own launches choose between them by grid size, and this entry
+ * lets a unit test hold one against the other on every epilogue.  A[m] is fp32 [M, K]; W[m] the three-plane split [3][N][K] of
+ * iefvad_split_bf16x3; bias[m] fp32 [N].  M % 128 == 0, N % tile_n == 0, K % 64 == 0; every pointer 16-byte aligned.  With
+ * acc = A W^T:
+ *   IEFVAD_SPLIT_EPI_BIAS            C[M, ldc] = acc + bias
+ *   IEFVAD_SPLIT_EPI_QKV             C = (acc + bias) * (column < qcols ? alpha : 1)
+ *   IEFVAD_SPLIT_EPI_BIAS_RELU       C = relu(acc + bias)
+ *   IEFVAD_SPLIT_EPI_BIAS_RESID      C = acc + bias + R                       (R [M, ldc])
+ *   IEFVAD_SPLIT_EPI_REFINE          C = R - alpha * (acc + bias)             (C may be R: in place)
+ *   IEFVAD_SPLIT_EPI_HEADS           N = 2 ldc: columns < ldc go to C, the others to C2, both [M, ldc]
+ *   IEFVAD_SPLIT_EPI_BIAS_RELU_DOT   nz = 1: h = relu(acc + bias); C2[M, N / 128] receives, per 128-column tile, the sum of
+ *                                    h[m][n] * R[n] (R [N]); h goes to C unless C is null
+ * Added without a change to any other entry: IEFVAD_ABI_VERSION stays. */
+#define IEFVAD_SPLIT_EPI_BIAS 0
+#define IEFVAD_SPLIT_EPI_QKV 1
+#define IEFVAD_SPLIT_EPI_BIAS_RELU 2
+#define IEFVAD_SPLIT_EPI_BIAS_RESID 3
+#define IEFVAD_SPLIT_EPI_REFINE 4
+#define IEFVAD_SPLIT_EPI_HEADS 5
+#define IEFVAD_SPLIT_EPI_BIAS_RELU_DOT 6
+typedef struct iefvad_gemm_split_io {
+    const float* A[2];
+    const void* W[2];
+    const float* bias[2];
+    const float* R[2];
+    float* C[2];
+    float* C2[2];
+} iefvad_gemm_split_io;
+/* Launches of the 128 x 256 tiling since the library was loaded, by any handle or entry of the process (counted where the kernel
+ * is launched; a replayed hipGraph counts at capture).  The two tilings give the same bits, so nothing else shows which one ran. */
+uint64_t iefvad_gemm_split_wide_launches(void);
+int iefvad_gemm_split_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
+                           int32_t qcols, float alpha, int32_t nz, int32_t tile_n, void* stream);
+
 /* The exact three-term bf16 split of n fp32 values (n % 4 == 0): planes[0..n) = bf16(x),
  * planes[n..2n) = bf16(x - p0), planes[2n..3n) = bf16(x - p0 - p1), round-to-nearest-even; x == p0 + p1 + p2
  * for finite x.  What iefvad_set_weights applies to every projection matrix in IEFVAD_COMPUTE_BF16X6. */

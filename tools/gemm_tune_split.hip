@@ -9,6 +9,7 @@
 #include <math.h>
 #define GS_EXPERIMENT_F16
 #include "../ief-vad_amd/csrc/gemm_split.h"
+#include "../ief-vad_amd/csrc/gemm_split_wide.h"
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1);} } while (0)
 
@@ -33,6 +34,7 @@ static float run(const Variant& v, GemmBArgs gs, GemmBArgs gf, int iters) {
         else if (v.kind == 2) hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid2, dim3(256), GS_LDS_BYTES_OF(2), 0, gs);
         else if (v.kind == 3) hipLaunchKernelGGL(iefvad_gemm_split_f16_kernel, grid, dim3(256), GS_LDS_BYTES, 0, gh);
         else if (v.kind == 4) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid2, dim3(256), GS_LDS_BYTES_OF(2), 0, gh);
+        else if (v.kind == 5) hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, gs);   // 128 x 256 as two halves (N % 256 == 0)
         else hipLaunchKernelGGL(iefvad_gemm_f32_t256_kernel, grid, dim3(256), GB2_LDS_BYTES, 0, gf);
     }
     CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
@@ -41,8 +43,55 @@ static float run(const Variant& v, GemmBArgs gs, GemmBArgs gf, int iters) {
     return ms / iters;
 }
 
+// `gemm_tune_split sweep`: the crossover of the two bf16x6 tilings (launch_gemm_split's kSplitWideMinWgs): 128 x 128 (kind 2) against
+// 128 x 256 in two halves (kind 5) at N = 768, 1536, 2304 over grids from a fraction of one round of the chip's 512 workgroup slots
+// up to M = 262,144 rows; bias and refine epilogues, fp32 stores; medians of 5 alternating rounds.
+static int sweep(float* A, bf16_t* Wp, float* bias, float* C, float* R, const std::vector<float>& hW, int K, int Mmax) {
+    const int Ns[3] = {768, 1536, 2304}, grids[] = {128, 256, 384, 512, 768, 1024, 1536, 2048, 4096, 8192, 1 << 30};
+    for (int ni = 0; ni < 3; ++ni) {
+        const int N = Ns[ni];
+        std::vector<unsigned short> hp((size_t)3 * N * K);
+        for (size_t q = 0; q < (size_t)N * K; ++q) {
+            const float x = hW[q];
+            const unsigned short b1 = f2bf(x); const float r1 = x - bf2f(b1);
+            const unsigned short b2 = f2bf(r1); const float r2 = r1 - bf2f(b2);
+            hp[q] = b1; hp[(size_t)N * K + q] = b2; hp[(size_t)2 * N * K + q] = f2bf(r2);
+        }
+        CK(hipMemcpy(Wp, hp.data(), hp.size() * 2, hipMemcpyHostToDevice));
+        GemmBArgs gs; memset(&gs, 0, sizeof(gs));
+        gs.N = N; gs.K = K; gs.lda = K; gs.ldc = N; gs.wplane = N * K * 2;
+        gs.p[0].A = (const bf16_t*)A; gs.p[0].W = Wp; gs.p[0].bias = bias; gs.p[0].C = C; gs.p[0].R = R; gs.p[1] = gs.p[0];
+        {   // same bits, both epilogues
+            gs.M = 4096;
+            std::vector<float> c0((size_t)gs.M * N), c1(c0.size());
+            for (int e = 0; e < 2; ++e) {
+                const Variant vn = {"n128", 2, e ? EPI_REFINE : EPI_BIAS, true}, vw = {"wide", 5, e ? EPI_REFINE : EPI_BIAS, true};
+                CK(hipMemset(C, 0xff, c0.size() * 4)); run(vn, gs, gs, 1); CK(hipMemcpy(c0.data(), C, c0.size() * 4, hipMemcpyDeviceToHost));
+                CK(hipMemset(C, 0xff, c0.size() * 4)); run(vw, gs, gs, 1); CK(hipMemcpy(c1.data(), C, c1.size() * 4, hipMemcpyDeviceToHost));
+                printf("N=%d %s: wide vs n128: %s\n", N, e ? "refine" : "bias", memcmp(c0.data(), c1.data(), c0.size() * 4) ? "DIFFERENT BITS" : "same bits");
+            }
+        }
+        for (int e = 0; e < 2; ++e)
+            for (int g : grids) {
+                int M = (int)std::min<long long>(Mmax, ((long long)g + N / 256 - 1) / (N / 256) * GS_BM);
+                gs.M = M;
+                const Variant vn = {"n128", 2, e ? EPI_REFINE : EPI_BIAS, true}, vw = {"wide", 5, e ? EPI_REFINE : EPI_BIAS, true};
+                const double fl = 2.0 * M * N * K;
+                const int iters = std::max(3, (int)(0.03 / (fl / 200e12)));      // ~30 ms per timing
+                run(vn, gs, gs, 2); run(vw, gs, gs, 2);
+                std::vector<float> tn, tw;
+                for (int r = 0; r < 5; ++r) { tn.push_back(run(vn, gs, gs, iters)); tw.push_back(run(vw, gs, gs, iters)); }
+                std::sort(tn.begin(), tn.end()); std::sort(tw.begin(), tw.end());
+                printf("  N=%-5d %-6s M=%-7d wide grid %-6d n128 %.4f ms %6.1f TF-eq | wide %.4f ms %6.1f TF-eq | wide / n128 time %.4f (best %.4f worst %.4f)\n", N,
+                       e ? "refine" : "bias", M, (M / GS_BM) * (N / 256), tn[2], fl / tn[2] * 1e-9, tw[2], fl / tw[2] * 1e-9, tw[2] / tn[2], tw[0] / tn[4], tw[4] / tn[0]);
+            }
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    const int M = argc > 1 ? atoi(argv[1]) : 65536, K = 768;
+    const bool do_sweep = argc > 1 && !strcmp(argv[1], "sweep");
+    const int M = do_sweep ? 262144 : argc > 1 ? atoi(argv[1]) : 65536, K = 768;
     const int iters = argc > 2 ? atoi(argv[2]) : 50, rounds = 5;
     const int Ns[2] = {768, 2304};
     const int NW = 2304;
@@ -67,6 +116,8 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute((const void*)iefvad_gemm_split_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES));
     CK(hipFuncSetAttribute((const void*)iefvad_gemm_split_f16_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2)));
     CK(hipFuncSetAttribute((const void*)iefvad_gemm_f32_t256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GB2_LDS_BYTES));
+    CK(hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2)));
+    if (do_sweep) return sweep(A, Wp, bias, C, R, hW, K, M);
     for (int ni = 0; ni < 2; ++ni) {
         const int N = Ns[ni];
         {   // planes of the first N rows, plane stride N*K
@@ -115,6 +166,10 @@ int main(int argc, char** argv) {
             CK(hipMemset(C, 0, cs.size() * 4)); run(vn0, gs, gf, 1); CK(hipMemcpy(cn.data(), C, cn.size() * 4, hipMemcpyDeviceToHost));
             size_t bad = 0; for (size_t q = 0; q < cs.size(); ++q) bad += (cn[q] != cs[q]);
             printf("N=%d: split n128 vs split: %zu mismatching elements of %zu\n", N, bad, cs.size());
+            const Variant vw0 = {"split n128x2", 5, EPI_BIAS, true};
+            CK(hipMemset(C, 0, cs.size() * 4)); run(vw0, gs, gf, 1); CK(hipMemcpy(cn.data(), C, cn.size() * 4, hipMemcpyDeviceToHost));
+            bad = 0; for (size_t q = 0; q < cs.size(); ++q) bad += (cn[q] != cs[q]);
+            printf("N=%d: split n128x2 (two column halves) vs split: %zu mismatching elements of %zu\n", N, bad, cs.size());
         }
         printf("N=%d accuracy vs fp64 on %zu sampled outputs: split max %.3g rms %.3g | fp32 MFMA max %.3g rms %.3g | split vs fp32 MFMA max %.3g\n",
                N, cnt, es, sqrt(ss / cnt), ef, sqrt(sf / cnt), md);
@@ -134,6 +189,7 @@ int main(int argc, char** argv) {
         }
         const Variant vs[] = {{"split bias C32", 0, EPI_BIAS, true}, {"split refine C32", 0, EPI_REFINE, true}, {"split none", 0, EPI_BIAS, false},
                               {"n128  bias C32", 2, EPI_BIAS, true}, {"n128  refine C32", 2, EPI_REFINE, true}, {"n128  none", 2, EPI_BIAS, false},
+                              {"n128x2 bias C32", 5, EPI_BIAS, true}, {"n128x2 refine C32", 5, EPI_REFINE, true}, {"n128x2 none", 5, EPI_BIAS, false},
                               {"f16x3 256 bias C32", 3, EPI_BIAS, true}, {"f16x3 256 refine", 3, EPI_REFINE, true}, {"f16x3 256 none", 3, EPI_BIAS, false},
                               {"f16x3 128 bias C32", 4, EPI_BIAS, true}, {"f16x3 128 refine", 4, EPI_REFINE, true}, {"f16x3 128 none", 4, EPI_BIAS, false},
                               {"f32   bias C32", 1, EPI_BIAS, true}, {"f32   refine C32", 1, EPI_REFINE, true}, {"f32   none", 1, EPI_BIAS, false}};
@@ -154,12 +210,13 @@ int main(int argc, char** argv) {
         GemmBArgs g; memset(&g, 0, sizeof(g));
         g.M = M; g.N = 768; g.K = K; g.lda = K; g.ldc = 768; g.epi = EPI_BIAS; g.wplane = 768 * K * 2;
         g.p[0].A = (const bf16_t*)A; g.p[0].W = Wp; g.p[0].bias = bias; g.p[0].C = C; g.p[0].C2 = (float*)dclk; g.p[1] = g.p[0];
-      for (int cfgi = 0; cfgi < 3; ++cfgi) {
-        dim3 grid((M / GS_BM) * (768 / (cfgi ? 128 : GS_BN)), 1, 1);
-        printf("%s\n", cfgi == 2 ? "fp16x3, 128 x 128, two workgroups per CU:" : cfgi ? "128 x 128, two workgroups per CU:" : "128 x 256, one workgroup per CU:");
+      for (int cfgi = 0; cfgi < 4; ++cfgi) {
+        dim3 grid((M / GS_BM) * (768 / (cfgi == 1 || cfgi == 2 ? 128 : GS_BN)), 1, 1);
+        printf("%s\n", cfgi == 3 ? "128 x 256 as two column halves, two workgroups per CU:" : cfgi == 2 ? "fp16x3, 128 x 128, two workgroups per CU:" : cfgi ? "128 x 128, two workgroups per CU:" : "128 x 256, one workgroup per CU:");
         GemmBArgs g2 = gh; g2.epi = EPI_BIAS; g2.p[0].C = C; g2.p[0].C2 = (float*)dclk; g2.p[1] = g2.p[0];
         for (int it = 0; it < 4000; ++it) {
-            if (cfgi == 2) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g2);
+            if (cfgi == 3) hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g);
+            else if (cfgi == 2) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g2);
             else if (cfgi) hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g);
             else hipLaunchKernelGGL(iefvad_gemm_split_kernel, grid, dim3(256), GS_LDS_BYTES, 0, g);
         }
@@ -169,8 +226,8 @@ int main(int argc, char** argv) {
             std::vector<unsigned long long> p0, p1, p2;
             for (size_t b = 0; b < grid.x; ++b) { p0.push_back(c[2 * grid.x + 3 * b]); p1.push_back(c[2 * grid.x + 3 * b + 1]); p2.push_back(c[2 * grid.x + 3 * b + 2]); }
             std::sort(p0.begin(), p0.end()); std::sort(p1.begin(), p1.end()); std::sort(p2.begin(), p2.end());
-            printf("wave 0, per k-tile (median over blocks): MFMA body %.0f cycles, vmcnt/lgkmcnt wait %.0f, barrier wait %.0f (ideal body 3072)\n",
-                   p0[p0.size() / 2] / 24.0, p1[p1.size() / 2] / 24.0, p2[p2.size() / 2] / 24.0);
+            printf("wave 0, per k-tile (median over blocks): MFMA body %.0f cycles, vmcnt/lgkmcnt wait %.0f, barrier wait %.0f (MFMA issue alone: %d)\n",
+                   p0[p0.size() / 2] / 24.0, p1[p1.size() / 2] / 24.0, p2[p2.size() / 2] / 24.0, cfgi == 3 ? 6144 : cfgi == 2 ? 1536 : 3072);   // a SIMD's waves x MFMAs per k-tile x 16 cycles
         }
         {
             std::vector<unsigned long long> q0, q1;

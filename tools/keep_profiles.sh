@@ -13,7 +13,7 @@ cp $O/pmc_summary_bf16x6.txt profiles/${RND}_kernel_pmc_summary_bf16x6.txt
 cp $O/pmc_summary_config5.txt profiles/${RND}_kernel_pmc_summary_config5_k5_bf16.txt
 cp $O/config5_kernel_stats.csv profiles/${RND}_config5_k5_bf16_kernel_stats.csv
 cp $O/config5_run.log profiles/${RND}_config5_run.log
-cp $O/gemm_split_hbm_traffic.json profiles/${RND}_gemm_split_hbm_traffic.json
+cp $O/gemm_split_n128x2_hbm_traffic.json profiles/${RND}_gemm_split_n128x2_hbm_traffic.json
 cp $O/gemm_bf16_hbm_traffic.json profiles/${RND}_gemm_bf16_hbm_traffic.json
 (echo "== random operands: tools/gemm_tune_split (M = 65536, K = 768)"; cat $O/gemm_split_tune_zero0.log; echo
  echo "== random operands: tools/gemm_tune_split_clk (in-kernel stamps, GB2_CLOCK_DIAG)"; cat $O/gemm_split_clk_zero0.log; echo
