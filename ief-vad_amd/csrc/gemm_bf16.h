@@ -52,7 +52,7 @@ struct GemmBArgs {
     int wplane;          // split kernel (gemm_split.h): bytes between the three bf16 planes of W
 };
 
-#define GEMMB_BK 64                 // bf16 elements per k-tile (128 bytes per row)
+#include "launch_rules.h"   // GEMMB_BK, GB2_BM/BN/BK, GB3_BM
 #define GEMMB_TILE (GEMM_BM * 32)   // floats-equivalent (4-byte units) per operand tile image: 128 rows x 128 B
 #define GEMMB_EPI_LD 68             // padded row length (floats) of the per-wave epilogue image
 
@@ -231,9 +231,6 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_bf16_v1_kernel(GemmBArgs a
         __builtin_amdgcn_s_barrier();       \
         asm volatile("" ::: "memory");      \
     } while (0)
-#define GB2_BM 128
-#define GB2_BN 256
-#define GB2_BK 32                                   // bf16 elements per k-tile
 #define GB2_SLOT ((GB2_BM + GB2_BN) * 16)           // 4-byte units per ring slot (384 rows x 64 B)
 #define GB2_STAGES 3
 #define GB2_EPI_LD 132                              // padded row (floats) of the per-wave epilogue image (32 x 128)
@@ -686,7 +683,6 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_bf16_kernel(GemmBArgs args
 }
 
 // MODE 3 on the 256 x 256 block tile (8 waves, one workgroup per CU)
-#define GB3_BM 256
 #define GB3_LDS_BYTES (8 * 32 * GB2_EPI_LD * 4)        // the epilogue's eight parking images (135,168 B) > the 3-slot ring (98,304 B)
 __global__ __launch_bounds__(512, 2) void iefvad_gemm_bf16_w256_kernel(GemmBArgs args) {
     extern __shared__ __attribute__((aligned(16))) float smem[];

@@ -51,10 +51,7 @@ struct GemmArgs {
     int qcols;           // EPI_QKV: columns < qcols are scaled
 };
 
-#define GEMM_BM 128
-#define GEMM_BN 128
-#define GEMM_BK 32
-
+#include "launch_rules.h"   // GEMM_BM/BN/BK, GEMS_BM/BN, GEMT_BM/BN
 
 // Residual operand of the EPI_BIAS_RESID / EPI_REFINE epilogues, fetched in accumulator layout.
 // TM x TN = 32x32 accumulators per wave (wave tile 32 TM x 32 TN); (wr, wc) = wave position in the 2x2 wave grid.
@@ -235,8 +232,6 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_f32_kernel(GemmArgs args) 
 // which is what bounds the time when the grid does not fill 256 CUs anyway.  Same LDS image, same staging and
 // the same k summation order per output element: results are bit-identical to iefvad_gemm_f32_kernel.
 // ------------------------------------------------------------------------------------------------------------
-#define GEMS_BM 64
-#define GEMS_BN 64
 
 __global__ __launch_bounds__(256, 2) void iefvad_gemm_f32_small_kernel(GemmArgs args) {
     __shared__ __attribute__((aligned(16))) float smem[2 * (GEMS_BM + GEMS_BN) * GEMM_BK];   // 32 KB
@@ -329,8 +324,6 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_f32_small_kernel(GemmArgs 
 #ifndef GEMT_EXP          // tools/gemm_tune_tiny timing experiments (wrong results when non-zero): 1 no DMA in the loop,
 #define GEMT_EXP 0        // 2 no barrier, 4 no MFMA, 8 no fragment reads (bit mask)
 #endif
-#define GEMT_BM 32
-#define GEMT_BN 32
 #define GEMT_STAGES 4                                    // ring slots; GEMT_STAGES - 1 k-tiles are in flight (8 slots: 15.2 -> 17.3 us)
 #define GEMT_SLOT ((GEMT_BM + GEMT_BN) * GEMM_BK)        // floats per ring slot: 64 rows x 128 B = 8 KB
 

@@ -56,10 +56,9 @@
 #ifndef GS_PN              // column tiles per L2-resident group (0 = all of them), see the tile map in gemm_split_body
 #define GS_PN 6
 #endif
-#define GS_BM 128
+#include "launch_rules.h"   // GS_BM, GS_BN_OF
 #define GS_BK 32
 #define GS_A_SLOT (GS_BM * 32)                  // 4-byte units: 128 rows x 128 B
-#define GS_BN_OF(NA) ((NA) == 4 ? 256 : 128)
 #define GS_LDS_BYTES_OF(NA) ((2 * GS_A_SLOT + 2 * 3 * GS_BN_OF(NA) * 16) * 4)   // 131,072 B (NA = 4) / 81,920 B (NA = 2)
 #define GS_BN GS_BN_OF(4)                       // the one-workgroup-per-CU configuration
 #define GS_LDS_BYTES GS_LDS_BYTES_OF(4)

@@ -9,7 +9,7 @@
 // LDS-DMA instructions, 7 % fewer LDS reads; each A panel crosses the fabric for half as many column groups.  32 accumulators,
 // 243 VGPRs, no AGPRs, no scratch, two waves per SIMD.  Each output element sums its k-tiles in ascending order and the six
 // products of a k-tile in gemm_split.h's order, so the results are that kernel's BIT FOR BIT (tests/test_gpu_gemm_split_wide.py),
-// and launch_gemm_split (iefvad.hip) chooses between the two by grid size alone.
+// and plan_gemm_split (launch_rules.h) chooses between the two by grid size alone.
 // Measured against the 128 x 128 kernel in one lease: 0.93 of its time from 4,000 workgroups on (235 against 218
 // TFLOP/s-equivalent at M = 262,144, N = 768), a tie at two rounds of the chip's 512 workgroup slots, 6-15 % slower at one round
 // and below (profiles/split_wide_gemm_tune.log); in-kernel stamps at M = 65,536, N = 768: 3042 cycles per 96 MFMAs and wave at

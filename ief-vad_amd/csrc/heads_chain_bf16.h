@@ -16,8 +16,7 @@
 #pragma once
 #include "outproj_ln_chain_bf16.h"
 
-#define HC_BM 64
-#define HC_THIRDS 3
+#include "launch_rules.h"   // HC_BM, HC_THIRDS
 #define HC_NPART (HC_THIRDS * 8)                     // row-sum partials per row and modality
 #define HC_DEPTH 8                                   // pieces in flight per wave = two k-steps
 #define HC_PHASE_PIECES (OC_KT * 4)                  // 96: per k-step mu tile 0, mu tile 1, logvar tile 0, logvar tile 1

@@ -97,7 +97,7 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
     std::vector<Batch> batches;
     long long max_rows = 0, max_chunks = 0, total_chunks = 0;
     for (int v = 0; v < nvideos; ++v) total_chunks += video_chunks(lengths[v]);
-    const bool compressed = !h->dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
+    const bool compressed = !h->policy.dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
     const long long round_rows = (long long)(h->num_cus > 0 ? h->num_cus : 256) * 64;
     const long long row_cap = compressed ? round_rows * ((want + 64) / 128 > 1 ? (want + 64) / 128 : 1) : (1LL << 60);
     auto enc_rows_of = [](int n) -> long long { return (long long)(n / IEF_T) * IEF_T + (n % IEF_T ? n % IEF_T + 1 : 0); };

@@ -22,6 +22,7 @@
 #include "attention_pbf16.h"
 #include "attention_split.h"
 #include "common.h"
+#include "launch_rules.h"
 #include "gather.h"
 #include "gemm_f32.h"
 #include "gemm_bf16.h"
@@ -83,22 +84,12 @@ struct iefvad_handle {
     int D, DH;             // embed dim and head dim: 768 / 96, or 512 / 64 (iefvad_create_ex: the f32 forward only)
     int device;
     bool weights_set;
-    // IEFVAD_ROWBLOCK_OFF=<mask> at iefvad_create (A/B runs and the bit-identity tests): bf16 mode takes the stage off its row-block kernel
-    //   1 in_proj -> ring GEMM (+ the stand-alone cast); 2 out_proj + LayerNorm -> ring GEMM + LayerNorm kernel;
-    //   4 heads + fusion -> ring GEMM + fusion kernel; 8 refinement chain -> 2K projection launches + the scorer kernel
-    bool no_heads_fusion, no_ln_fusion;
+    LaunchPolicy policy;   // the environment switches of kernel selection (launch_rules.h), read once at iefvad_create
     char* iproj_stream[2][IEFVAD_MAX_LAYERS];   // bf16 mode: in_proj weights in per-wave fragment order, q | k | v passes (inproj_chain_bf16.h)
     char* heads_stream;    // bf16 mode: the four head matrices in per-wave fragment order (heads_chain_bf16.h)
-    int chain_min_blocks;  // bf16 mode: the refinement chain kernel takes a micro-batch from this many 64-row blocks on (IEFVAD_CHAIN_MIN_BLOCKS overrides)
-    int rowblock_min_wgs;  // bf16 mode: the row-block kernels take a projection from this many workgroups on (IEFVAD_ROWBLOCK_MIN_WGS overrides)
-    bool no_inproj_chain;
     char* oproj_stream[2][IEFVAD_MAX_LAYERS];   // bf16 mode: out_proj weights in per-wave fragment order (outproj_ln_chain_bf16.h)
-    bool dense_encoder;    // IEFVAD_DENSE_ENCODER=1: whole-video passes run the encoder on whole 256-row chunks (pad rows computed), the tail on the gathered valid rows
-    bool persist;          // bf16 mode: the persistent out_proj + LayerNorm, heads + fusion and attention kernels from two blocks per CU on (IEFVAD_PERSIST=0: off)
     bool train_attn_unfused; // IEFVAD_TRAIN_ATTN=unfused: bf16x6 train-mode attention on the three-launch path (train.h)
-    int split_tile;        // IEFVAD_SPLIT_TILE=128 / 256: the bf16x6 projections on one tiling of the split kernel (unset: launch_gemm_split's rule)
     bool hostpipe_trace;   // IEFVAD_HOSTPIPE_TRACE=1: iefvad_forward_videos_host prints its per-pass timeline to stderr (hostpipe.h)
-    bool no_chain;
     char* chain_stream;    // bf16 mode: the refinement weights in the chain kernel's per-wave piece order (refine_chain_bf16.h)
     float* arena;          // one allocation holding every repacked weight
     size_t arena_floats;
@@ -175,6 +166,42 @@ extern "C" const char* iefvad_last_error(void) { return g_err; }
 // The D=512 (head dim 64) forward: ViT-B/16 features, the f32 arithmetic's kernels only
 #define IEF_D512 512
 
+// Every kernel launched with more dynamic LDS than the default limit allows, with its byte count.  fn == nullptr: raise the limit of
+// all of them (iefvad_create); else of that kernel alone (the unit entries that run without a handle).  Returns the first error.
+static hipError_t raise_lds_limit(const void* fn = nullptr) {
+    static const struct { const void* fn; int bytes; } table[] = {
+        {(const void*)iefvad_gemm_bf16_kernel, GB2_LDS_BYTES},
+        {(const void*)iefvad_gemm_bf16_pipe_kernel, GB2_LDS_BYTES},
+        {(const void*)iefvad_gemm_bf16_w256_kernel, GB3_LDS_BYTES},
+        {(const void*)iefvad_refine_chain_bf16_kernel, RC_LDS_BYTES},
+        {(const void*)iefvad_outproj_ln_chain_bf16_kernel, OC_LDS_BYTES},
+        {(const void*)iefvad_outproj_ln_pchain_bf16_kernel<true, true>, OP_LDS_BYTES},
+        {(const void*)iefvad_outproj_ln_pchain_bf16_kernel<true, false>, OP_LDS_BYTES},
+        {(const void*)iefvad_outproj_ln_pchain_bf16_kernel<false, true>, OP_LDS_BYTES},
+        {(const void*)iefvad_heads_pchain_bf16_kernel, HP_LDS_BYTES},
+        {(const void*)iefvad_gemm_split_tn256_kernel, TN_LDS_BYTES_OF(4)},
+        {(const void*)iefvad_attention_pbf16_kernel, APB_LDS_BYTES},
+        {(const void*)iefvad_attention_pbf16_rows_kernel, APB_LDS_BYTES},
+        {(const void*)iefvad_gemm_f32_t256_kernel, GB2_LDS_BYTES},
+        {(const void*)iefvad_gemm_split_n128_kernel, GS_LDS_BYTES_OF(2)},
+        {(const void*)iefvad_gemm_split_n128x2_kernel, GS_LDS_BYTES_OF(2)},
+        {(const void*)iefvad_attention_split_kernel, ATS_LDS_BYTES},
+        {(const void*)iefvad_attention_split_rows_kernel, ATS_LDS_BYTES},
+        {(const void*)iefvad_attention_split_train_kernel, ATS_LDS_BYTES},
+        {(const void*)iefvad_attention_split_ds_kernel, ATS_LDS_BYTES},
+        {(const void*)iefvad_attention_split_train_mask_kernel, ATS_LDS_BYTES},
+        {(const void*)iefvad_heads_chain_bf16_kernel, HC_LDS_BYTES},
+        {(const void*)iefvad_inproj_chain_bf16_kernel, IC_LDS_BYTES},
+        {(const void*)iefvad_inproj_chain_f32in_kernel, IC_LDS_BYTES},
+        {(const void*)iefvad_attention_split_f16_kernel, ATS_LDS_BYTES},
+        {(const void*)iefvad_gemm_split_f16_n128_kernel, GS_LDS_BYTES_OF(2)},
+    };
+    for (const auto& k : table)
+        if (!fn || fn == k.fn)
+            if (hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes); e != hipSuccess) return e;
+    return hipSuccess;
+}
+
 // iefvad_create (D = 768 only) and iefvad_create_ex (also D = 512 in the f32 arithmetic): every check before the first HIP call
 static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg, iefvad_handle** out) {
     if (!cfg || !out) return fail("%s: null argument", who);
@@ -217,96 +244,21 @@ static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg
     h->DH = h->D / IEF_H;
     // The library's only environment switches: alternative paths that tests compare the default against, and a trace
     {
-        const char* v = getenv("IEFVAD_ROWBLOCK_OFF");
-        const int off = v ? atoi(v) : 0;
-        h->no_inproj_chain = off & 1; h->no_ln_fusion = off & 2; h->no_heads_fusion = off & 4; h->no_chain = off & 8;
+        auto num = [](const char* name) { const char* v = getenv(name); return v ? atoi(v) : 0; };
+        auto first = [](const char* name) { const char* v = getenv(name); return v ? v[0] : '\0'; };
+        h->policy = launch_policy(num("IEFVAD_ROWBLOCK_OFF"), num("IEFVAD_ROWBLOCK_MIN_WGS"), num("IEFVAD_CHAIN_MIN_BLOCKS"), first("IEFVAD_PERSIST") != '0',
+                                  num("IEFVAD_SPLIT_TILE"), first("IEFVAD_DENSE_ENCODER") == '1');
+        h->train_attn_unfused = first("IEFVAD_TRAIN_ATTN") == 'u';
+        h->hostpipe_trace = first("IEFVAD_HOSTPIPE_TRACE") == '1';
     }
-    { const char* v = getenv("IEFVAD_ROWBLOCK_MIN_WGS"); h->rowblock_min_wgs = (v && atoi(v) > 0) ? atoi(v) : 128; }      // tools/rowblock_threshold_probe.py
-    { const char* v = getenv("IEFVAD_CHAIN_MIN_BLOCKS"); h->chain_min_blocks = (v && atoi(v) > 0) ? atoi(v) : 4; }         // one chunk: 4 blocks take one block time, 2K launches more
-    { const char* v = getenv("IEFVAD_PERSIST"); h->persist = !(v && v[0] == '0'); }
-    { const char* v = getenv("IEFVAD_DENSE_ENCODER"); h->dense_encoder = v && v[0] == '1'; }
-    { const char* v = getenv("IEFVAD_TRAIN_ATTN"); h->train_attn_unfused = v && v[0] == 'u'; }
-    { const char* v = getenv("IEFVAD_HOSTPIPE_TRACE"); h->hostpipe_trace = v && v[0] == '1'; }
-    { const char* v = getenv("IEFVAD_SPLIT_TILE"); const int t = v ? atoi(v) : 0; h->split_tile = (t == 128 || t == 256) ? t : 0; }
     hipError_t e = hipGetDevice(&h->device);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GB2_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_bf16_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GB2_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_bf16_w256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GB3_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_refine_chain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                RC_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_outproj_ln_chain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                OC_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_outproj_ln_pchain_bf16_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                OP_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_outproj_ln_pchain_bf16_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                OP_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_outproj_ln_pchain_bf16_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                OP_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_heads_pchain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                HP_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES_OF(4));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_pbf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, APB_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_pbf16_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, APB_LDS_BYTES);
+    if (e == hipSuccess) e = raise_lds_limit();
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         e = hipGetDeviceProperties(&prop, h->device);
         h->num_cus = e == hipSuccess ? prop.multiProcessorCount : 256;
         g_num_cus = h->num_cus;
     }
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_f32_t256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GB2_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GS_LDS_BYTES_OF(2));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GS_LDS_BYTES_OF(2));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ATS_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_split_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ATS_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_split_train_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ATS_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_split_ds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ATS_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_split_train_mask_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ATS_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_heads_chain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                HC_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_inproj_chain_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                IC_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_inproj_chain_f32in_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                IC_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_attention_split_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                ATS_LDS_BYTES);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_f16_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                GS_LDS_BYTES_OF(2));
     if (e == hipSuccess && cfg->compute == IEFVAD_COMPUTE_FP16X3) e = hipMalloc((void**)&h->amax_dev, amax_words(cfg->num_layers, cfg->num_steps, micro_batch(h)) * sizeof(float));
     if (e != hipSuccess) {
         delete h;
@@ -701,34 +653,19 @@ static void release_events(iefvad_handle* h) {
     }
 }
 
-// Grid-size rules of the fp32 tilings, measured over B = 1 .. 256 chunks (profiles/r03_kernel_selection_thresholds.log): the 32x32
-// kernel below 320 blocks of 64x64, the 128x256 one from 1536 blocks of 128x256 on, the 64x64 one below 1024 blocks of 128x128.
-// They were {320, 256, 256} ("when the grid fills the chip") until measured: B = 48 forward 6.7 -> 5.5 ms.
-static const int kF32TinyMaxBlocks64 = 320;
-static const int kF32T256MinBlocks = 1536;
-static const int kF32SmallMaxBlocks128 = 1024;
-
+// The projection launches: the plan (launch_rules.h) names the kernel and the grid, the code here fills the argument block and launches it
 static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm, int stage) {
-    if (a.M % GEMM_BM || a.N % GEMM_BN || a.K % GEMM_BK)
+    const GemmPlan pl = plan_gemm_f32(a.M, a.N, a.K, nz);
+    if (pl.reject)
         return fail("gemm: shape M=%d N=%d K=%d not a multiple of the %dx%dx%d tile", a.M, a.N, a.K, GEMM_BM, GEMM_BN,
                     GEMM_BK);
-    // Four tilings of the same contraction, bit-identical to each other (same k order per output element):
-    //   128x256 / 3-slot ring (iefvad_gemm_f32_t256_kernel)  the throughput kernel, from 6 blocks per CU on (it wins 2 % at a full
-    //                                                         micro-batch and loses 10-18 % between 1 and 4 blocks per CU);
-    //   128x128 / double buffer (iefvad_gemm_f32_kernel)      mid-size grids or N not a multiple of 256;
-    //   64x64 (iefvad_gemm_f32_small_kernel)                  up to 4 blocks of 128x128 per CU: 4x the blocks, a quarter of the MFMA chain;
-    //   32x32 on 16x16x4 MFMAs (iefvad_gemm_f32_tiny_kernel)  the per-video pattern (B = 1 .. a few chunks): 16x the
-    //                                                         blocks, a wave's chain is 3.2 us instead of 10 / 41 us.
-    const int blocks128 = (a.M / GEMM_BM) * (a.N / GEMM_BN) * nz;
-    const int blocks64 = (a.M / GEMS_BM) * (a.N / GEMS_BN) * nz;
-    const bool t256_ok = (a.N % GB2_BN == 0) && (a.K % 16 == 0) && (a.K >= 32);
-    const int blocks256 = t256_ok ? (a.M / GB2_BM) * (a.N / GB2_BN) * nz : 0;
-    const bool tiny = blocks64 < kF32TinyMaxBlocks64 && a.K % 64 == 0;      // < 1.25 blocks of 64x64 per CU: the chain, not the chip, bounds it
+    const dim3 grid(pl.wgs, 1, nz);
     hipEvent_t e = tm.begin(stage);
-    if (tiny) {
-        dim3 grid((a.M / GEMT_BM) * (a.N / GEMT_BN), 1, nz);
-        hipLaunchKernelGGL(iefvad_gemm_f32_tiny_kernel, grid, dim3(256), 0, stream, a);
-    } else if (blocks256 >= kF32T256MinBlocks) {
+    switch (pl.kernel) {
+    case GEMM_F32_TINY: hipLaunchKernelGGL(iefvad_gemm_f32_tiny_kernel, grid, dim3(256), 0, stream, a); break;
+    case GEMM_F32_SMALL: hipLaunchKernelGGL(iefvad_gemm_f32_small_kernel, grid, dim3(256), 0, stream, a); break;
+    case GEMM_F32_128: hipLaunchKernelGGL(iefvad_gemm_f32_kernel, grid, dim3(256), 0, stream, a); break;
+    case GEMM_F32_T256: {
         GemmBArgs b;
         memset(&b, 0, sizeof(b));
         b.M = a.M; b.N = a.N; b.K = a.K; b.lda = a.lda; b.ldc = a.ldc; b.epi = a.epi; b.alpha = a.alpha; b.qcols = a.qcols;
@@ -736,14 +673,10 @@ static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm,
             b.p[m].A = (const bf16_t*)a.p[m].A; b.p[m].W = (const bf16_t*)a.p[m].W;     // fp32 data behind the typed pointer
             b.p[m].bias = a.p[m].bias; b.p[m].C = a.p[m].C; b.p[m].R = a.p[m].R; b.p[m].C2 = a.p[m].C2;
         }
-        dim3 grid((a.M / GB2_BM) * (a.N / GB2_BN), 1, nz);
         hipLaunchKernelGGL(iefvad_gemm_f32_t256_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, b);
-    } else if (blocks128 < kF32SmallMaxBlocks128) {
-        dim3 grid((a.M / GEMS_BM) * (a.N / GEMS_BN), 1, nz);
-        hipLaunchKernelGGL(iefvad_gemm_f32_small_kernel, grid, dim3(256), 0, stream, a);
-    } else {
-        dim3 grid((a.M / GEMM_BM) * (a.N / GEMM_BN), 1, nz);
-        hipLaunchKernelGGL(iefvad_gemm_f32_kernel, grid, dim3(256), 0, stream, a);
+        break;
+    }
+    default: break;
     }
     tm.end(e);
     tm.gemm_launches += 1;
@@ -752,26 +685,17 @@ static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm,
 }
 
 static int launch_gemm_b(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage) {
-    hipEvent_t e;
-    if (a.N % GB2_BN == 0 && a.M % GB2_BM == 0 && a.K % GB2_BK == 0 && a.K >= 2 * GB2_BK) {
-        e = tm.begin(stage);
-        // two bit-identical tilings: 256 x 256 / 8 waves / one workgroup per CU is 2-6 % faster with bias-type epilogues
-        // (in_proj, out_proj, heads, the refinement's first projection), 128 x 256 / 4 waves / two per CU with the refinement
-        // epilogue (residual read + two stores): tools/gemm_tune_bf16, profiles/r02_gemm_bf16_w256.log
-        if (a.M % GB3_BM == 0 && a.epi != EPI_REFINE && (a.M / GB3_BM) * (a.N / GB2_BN) * nz >= 256) {
-            dim3 grid((a.M / GB3_BM) * (a.N / GB2_BN), 1, nz);
-            hipLaunchKernelGGL(iefvad_gemm_bf16_w256_kernel, grid, dim3(512), GB3_LDS_BYTES, stream, a);
-        } else {
-            dim3 grid((a.M / GB2_BM) * (a.N / GB2_BN), 1, nz);
-            hipLaunchKernelGGL(iefvad_gemm_bf16_pipe_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, a);   // pinned issue order: +1..3 %, same bits
-        }
-    } else {
-        if (a.M % GEMM_BM || a.N % GEMM_BN || a.K % GEMMB_BK)
-            return fail("gemm(bf16): shape M=%d N=%d K=%d not a multiple of the %dx%dx%d tile", a.M, a.N, a.K, GEMM_BM,
-                        GEMM_BN, GEMMB_BK);
-        dim3 grid((a.M / GEMM_BM) * (a.N / GEMM_BN), 1, nz);
-        e = tm.begin(stage);
-        hipLaunchKernelGGL(iefvad_gemm_bf16_v1_kernel, grid, dim3(256), 0, stream, a);
+    const GemmPlan pl = plan_gemm_bf16(a.M, a.N, a.K, nz, a.epi == EPI_REFINE);
+    if (pl.reject)
+        return fail("gemm(bf16): shape M=%d N=%d K=%d not a multiple of the %dx%dx%d tile", a.M, a.N, a.K, GEMM_BM,
+                    GEMM_BN, GEMMB_BK);
+    const dim3 grid(pl.wgs, 1, nz);
+    hipEvent_t e = tm.begin(stage);
+    switch (pl.kernel) {
+    case GEMM_BF16_W256: hipLaunchKernelGGL(iefvad_gemm_bf16_w256_kernel, grid, dim3(512), GB3_LDS_BYTES, stream, a); break;
+    case GEMM_BF16_PIPE: hipLaunchKernelGGL(iefvad_gemm_bf16_pipe_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, a); break;
+    case GEMM_BF16_V1: hipLaunchKernelGGL(iefvad_gemm_bf16_v1_kernel, grid, dim3(256), 0, stream, a); break;
+    default: break;
     }
     tm.end(e);
     tm.gemm_launches += 1;
@@ -779,42 +703,29 @@ static int launch_gemm_b(const GemmBArgs& a, int nz, hipStream_t stream, Timer& 
     return 0;
 }
 
-// BF16X6: the split kernel (128 x 128 tiles, two workgroups per CU; tools/gemm_tune_split: +5..8 % over the 128 x 256 /
-// one-workgroup configuration, same bits) takes a micro-batch's projections from 72 workgroups of a 768-wide projection on
-// (6 chunks: measured crossover, B = 24 forward 3.55 -> 1.97 ms; it was 512 workgroups, "fills the chip", until the end of
-// round 3; profiles/r03_kernel_selection_thresholds.log); smaller problems run on the fp32 kernels (launch_gemm)
-static const int kSplitBN = GS_BN_OF(2);
-static const int kSplitMinWgs = 72;      // 6 chunks
-static bool split_eligible(int M, int N, int K, int nz) {
-    return M % GS_BM == 0 && N % kSplitBN == 0 && K % 64 == 0 && K >= 64 && (M / GS_BM) * (N / kSplitBN) * nz >= kSplitMinWgs;
-}
-
-// Two bit-identical tilings of the bf16x6 arithmetic (gemm_split.h): 128 x 128, and 128 x 256 as two column halves that share the
-// A planes (half the split work and A staging per MFMA: 7 % less time at 262,144 rows).  The wide one takes a launch whose wide grid
-// has at least kSplitWideMinWgs workgroups, the measured crossover (`tools/gemm_tune_split sweep` at N = 768, 1536 and 2304, bias and
-// refine epilogues, profiles/split_wide_gemm_tune.log): from three rounds of the chip's 512 workgroup slots on it wins at all three
-// widths (time ratio 0.93-0.98); at two rounds it ties (0.99-1.01), at one round and below the narrow grid's twice as many, half as
-// long workgroups win by 6-15 %.  tile_n = 128 / 256 forces a tiling (the unit entry iefvad_gemm_split_unit, IEFVAD_SPLIT_TILE);
-// the fp16x3 arithmetic has the narrow tiling only.
-static const int kSplitWideMinWgs = 1536;     // 3 x 512
 static std::atomic<unsigned long long> g_split_wide_launches{0};     // iefvad_gemm_split_wide_launches: which tiling ran is otherwise invisible
 static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false, int tile_n = 0) {
-    if (a.M % GS_BM || a.N % kSplitBN || a.K % 64 || a.K < 64)
-        return fail("gemm(bf16x6): shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", a.M, a.N, a.K, GS_BM, kSplitBN);
-    if (tile_n != 0 && tile_n != 128 && tile_n != 256) return fail("gemm(bf16x6): tile_n = %d (128, 256 or 0 for the launch rule)", tile_n);
-    if (tile_n == 256 && (f16 || a.N % 256))
+    const GemmPlan pl = plan_gemm_split(a.M, a.N, a.K, nz, f16, tile_n, a.epi == EPI_BIAS_RELU_DOT, a.p[0].R && a.p[0].C2);
+    switch (pl.reject) {
+    case GEMM_OK: break;
+    case GEMM_BAD_SHAPE: return fail("gemm(bf16x6): shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", a.M, a.N, a.K, GS_BM, kSplitBN);
+    case GEMM_BAD_TILE_N: return fail("gemm(bf16x6): tile_n = %d (128, 256 or 0 for the launch rule)", tile_n);
+    case GEMM_NO_WIDE_TILING:
         return fail("gemm(bf16x6): the 128 x 256 tiling takes bf16x6 problems with N %% 256 == 0 (N = %d%s)", a.N, f16 ? ", fp16x3" : "");
-    const bool wide = !f16 && a.N % 256 == 0 && (tile_n == 256 || (tile_n == 0 && (a.M / GS_BM) * (a.N / 256) * nz >= kSplitWideMinWgs));
-    if (a.epi == EPI_BIAS_RELU_DOT && (f16 || nz != 1 || !a.p[0].R || !a.p[0].C2))
+    case GEMM_BAD_DOT_EPILOGUE:
         return fail("gemm(bf16x6): the dot-product epilogue takes one bf16x6 problem with its vector (R) and its partial sums (C2)");
-    dim3 grid((a.M / GS_BM) * (a.N / (wide ? 256 : kSplitBN)), 1, nz);
+    }
+    const dim3 grid(pl.wgs, 1, nz);
     hipEvent_t e = tm.begin(stage);
-    if (wide) {
+    switch (pl.kernel) {
+    case GEMM_SPLIT_N128X2:
         hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
         g_split_wide_launches.fetch_add(1, std::memory_order_relaxed);
+        break;
+    case GEMM_SPLIT_F16_N128: hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a); break;
+    case GEMM_SPLIT_N128: hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a); break;
+    default: break;
     }
-    else if (f16) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
-    else hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
     tm.end(e);
     tm.gemm_launches += 1;
     HIP_TRY(hipGetLastError());
@@ -868,8 +779,7 @@ static int launch_proj(const Proj& p, int compute, bool use_split, int D, int ro
                 g.p[m].amaxA = p.amaxA[m]; g.p[m].amaxW = p.amaxW[m]; g.p[m].amaxC = p.amaxC[m];
             }
         }
-        // IEFVAD_SPLIT_TILE is a preference: a projection the wide tiling cannot take (fp16x3, N % 256 != 0) runs on the narrow one
-        return launch_gemm_split(g, p.nz, stream, tm, stage, f16, (f16 || (split_tile == 256 && p.N % 256)) ? (f16 ? 0 : 128) : split_tile);
+        return launch_gemm_split(g, p.nz, stream, tm, stage, f16, split_tile_for(split_tile, p.N, f16));
     }
     if (!bf16) {
         GemmArgs g;
@@ -924,17 +834,16 @@ static int launch_outproj_ln_chain(iefvad_handle* h, int l, bool whiten, const b
         q.yb = yb[m];
     }
     oa.M = rows; oa.eps = 1e-5f; oa.wave_stride = (unsigned)wstream_wave_stride_bytes();
-    // From two blocks per workgroup on: the persistent kernel, one workgroup per CU, the next block's image fetched during the LayerNorm
-    // epilogue (outproj_ln_pchain_bf16.h; same bits); IEFVAD_PERSIST=0 keeps the one-block-per-workgroup kernels (A/B).
-    const int gx = h->num_cus / 2;
-    const int nblk = rows / OC_BM;
+    const bool uniform = (y[0] != nullptr) == (y[1] != nullptr) && (yb[0] != nullptr) == (yb[1] != nullptr) && (y[0] || yb[0]);
+    const StagePlan pl = plan_outproj_ln(h->policy, h->num_cus, rows, uniform);
+    const dim3 grid(pl.gx, pl.gy);
     hipEvent_t e = tm.begin(ST_OUT);
-    if (h->persist && nblk >= 2 * gx && (y[0] != nullptr) == (y[1] != nullptr) && (yb[0] != nullptr) == (yb[1] != nullptr) && (y[0] || yb[0])) {
-        if (y[0] && yb[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, true>), dim3(gx, 2), dim3(512), OP_LDS_BYTES, stream, oa);
-        else if (y[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, false>), dim3(gx, 2), dim3(512), OP_LDS_BYTES, stream, oa);
-        else hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<false, true>), dim3(gx, 2), dim3(512), OP_LDS_BYTES, stream, oa);
+    if (pl.kernel == STAGE_OUTLN_PCHAIN) {    // the persistent kernel is compiled per set of stored results
+        if (y[0] && yb[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, true>), grid, dim3(512), OP_LDS_BYTES, stream, oa);
+        else if (y[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, false>), grid, dim3(512), OP_LDS_BYTES, stream, oa);
+        else hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<false, true>), grid, dim3(512), OP_LDS_BYTES, stream, oa);
     } else
-        hipLaunchKernelGGL(iefvad_outproj_ln_chain_bf16_kernel, dim3(rows / OC_BM, 2), dim3(512), OC_LDS_BYTES, stream, oa);
+        hipLaunchKernelGGL(iefvad_outproj_ln_chain_bf16_kernel, grid, dim3(512), OC_LDS_BYTES, stream, oa);
     tm.end(e);
     tm.gemm_launches += 1;
     HIP_TRY(hipGetLastError());
@@ -950,14 +859,15 @@ static void launch_attention_bf16(iefvad_handle* h, const bf16_t* const qkv[2], 
     ab.chunks = chunks;
     ab.head_major = head_major ? 1 : 0;
     ab.nrows = rows;
-    // from two items per CU on: the persistent kernel (attention_pbf16.h: one 8-wave workgroup per CU, K / V staged once for
-    // both query halves by LDS-DMA, the next item's K in flight under the current item); bit-identical to the one below
-    const int items = 2 * nb * IEF_H;
-    if (h->persist && items >= 2 * h->num_cus) {
-        if (chunks) hipLaunchKernelGGL(iefvad_attention_pbf16_rows_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
-        else hipLaunchKernelGGL(iefvad_attention_pbf16_kernel, dim3(h->num_cus), dim3(512), APB_LDS_BYTES, stream, ab);
-    } else if (chunks) hipLaunchKernelGGL(iefvad_attention_bf16_rows_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);
-    else hipLaunchKernelGGL(iefvad_attention_bf16_kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), 0, stream, ab);
+    const StagePlan pl = plan_attention_bf16(h->policy, h->num_cus, nb, chunks != nullptr);
+    const dim3 grid(pl.gx, pl.gy, pl.gz);
+    switch (pl.kernel) {
+    case STAGE_ATTN_PBF16_ROWS: hipLaunchKernelGGL(iefvad_attention_pbf16_rows_kernel, grid, dim3(512), APB_LDS_BYTES, stream, ab); break;
+    case STAGE_ATTN_PBF16: hipLaunchKernelGGL(iefvad_attention_pbf16_kernel, grid, dim3(512), APB_LDS_BYTES, stream, ab); break;
+    case STAGE_ATTN_BF16_ROWS: hipLaunchKernelGGL(iefvad_attention_bf16_rows_kernel, grid, dim3(256), 0, stream, ab); break;
+    case STAGE_ATTN_BF16: hipLaunchKernelGGL(iefvad_attention_bf16_kernel, grid, dim3(256), 0, stream, ab); break;
+    default: break;
+    }
 }
 
 // `ha` arrives with its tensors filled in; the stream, scalars and the kernel choice are set here
@@ -965,14 +875,11 @@ static int launch_heads_chain(iefvad_handle* h, HeadsChainArgs& ha, int rows, fl
     for (int m = 0; m < 2; ++m) ha.bias[m] = h->head[m].b;
     ha.stream = h->heads_stream;
     ha.M = rows; ha.factor = factor; ha.eps = h->cfg.epsilon; ha.wave_stride = (unsigned)heads_stream_wave_stride_bytes();
-    // from two blocks per workgroup on: the persistent kernel (heads_pchain_bf16.h: one workgroup per CU and column third, both
-    // images by LDS-DMA under the previous block's epilogue / the first part of phase 2; same bits); IEFVAD_PERSIST=0: A/B
-    const int gx = h->num_cus / HC_THIRDS;
+    const StagePlan pl = plan_heads(h->policy, h->num_cus, rows);
+    const dim3 grid(pl.gx, pl.gy);
     hipEvent_t e = tm.begin(ST_HEAD);
-    if (h->persist && rows / HC_BM >= 2 * gx)
-        hipLaunchKernelGGL(iefvad_heads_pchain_bf16_kernel, dim3(gx, HC_THIRDS), dim3(512), HP_LDS_BYTES, stream, ha);
-    else
-        hipLaunchKernelGGL(iefvad_heads_chain_bf16_kernel, dim3(rows / HC_BM, HC_THIRDS), dim3(512), HC_LDS_BYTES, stream, ha);
+    if (pl.kernel == STAGE_HEADS_PCHAIN) hipLaunchKernelGGL(iefvad_heads_pchain_bf16_kernel, grid, dim3(512), HP_LDS_BYTES, stream, ha);
+    else hipLaunchKernelGGL(iefvad_heads_chain_bf16_kernel, grid, dim3(512), HC_LDS_BYTES, stream, ha);
     tm.end(e);
     tm.gemm_launches += 1;
     HIP_TRY(hipGetLastError());
@@ -1010,15 +917,13 @@ struct RaggedPass {
     float* w_e_mean;
 };
 
-// The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it.
-struct PassBuffers {
+// The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it
+// (PassFlags from pass_buffers on, TailFlags from pass_compact_rows on: launch_rules.h).
+struct PassBuffers : PassFlags, TailFlags {
     int nb, rows;             // chunks; rows of the current row set (the compaction step shrinks it)
     size_t R;                 // region stride in rows: the dense capacity nb * 256
     bool enc_rows_mode;       // row-compressed chunks: valid rows + one pad row each
-    bool ip_chain;            // bf16 mode, full grids: in_proj on the row-block kernel (inproj_chain_bf16.h); its first layer reads the fp32 rows
-    bool need_xb0;            // bf16 mode also needs the bf16 copy of the inputs (unless ip_chain)
-    bool splitmb, f16mb;      // the split kernels take this micro-batch's projections; ... in the fp16x3 arithmetic
-    bool compacted, tail_split;
+    bool compacted;           // the tail runs on the gathered valid rows (pass_compact_rows)
     // workspace regions, in units of R*D floats: xin 0..2 | qkv 2..8 | att 8..10 | y 10..12 | x 12..14 | logits
     float *xin[2], *qkv[2], *att[2], *ybuf[2], *xbuf[2];
     bf16_t *qkvb[2], *attb[2], *xb[2];      // bf16 mode: q|k|v as bf16 in the qkv region; the att region holds attb | xb
@@ -1081,10 +986,7 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
         b.wim_out = rg->w_i_mean ? b.lg_scratch + R : nullptr;
         b.wem_out = rg->w_e_mean ? b.lg_scratch + 2 * R : nullptr;
     }
-    b.ip_chain = c.compute == IEFVAD_COMPUTE_BF16 && !h->no_inproj_chain && b.rows % IC_BM == 0 && (b.rows / IC_BM) * 2 >= h->rowblock_min_wgs;
-    b.need_xb0 = c.compute == IEFVAD_COMPUTE_BF16 && !b.ip_chain;
-    b.splitmb = (c.compute == IEFVAD_COMPUTE_BF16X6 || c.compute == IEFVAD_COMPUTE_FP16X3) && split_eligible(b.rows, IEF_D, IEF_D, 1);
-    b.f16mb = b.splitmb && c.compute == IEFVAD_COMPUTE_FP16X3;
+    static_cast<PassFlags&>(b) = plan_pass(h->policy, c.compute, b.rows);
     b.am = h->amax_dev ? h->amax_dev + kAmaxActBase * IEF_AMAX_FLOATS : nullptr;
     b.mbs = (size_t)micro_batch(h) * IEF_AMAX_PARTS;
     b.L = c.num_layers; b.K = c.num_steps;
@@ -1178,7 +1080,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             p.amaxC[m] = b.am_qkv(l, m);
             if (bf) p.Cb[m] = b.qkvb[m]; else p.C[m] = b.qkv[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV, h->policy.split_tile)) return rc;
     }
 
     hipEvent_t e = tm.begin(ST_ATT);
@@ -1202,10 +1104,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
     tm.end(e);
     HIP_TRY(hipGetLastError());
 
-    // out_proj + residual + LayerNorm(s) in one row-owning kernel (bf16 mode, full grids): 64-row blocks on the refinement chain's
-    // structure (outproj_ln_chain_bf16.h); same bits as the GEMM + LayerNorm kernels
-    const bool ln_fused = bf && !h->no_ln_fusion && rows % OC_BM == 0 && (rows / OC_BM) * 2 >= h->rowblock_min_wgs;
-    if (ln_fused) {
+    if (b.ln_fused) {      // out_proj + residual + LayerNorm(s) in one row-owning kernel
         float* oy[2] = {(l < L - 1) ? b.xbuf[0] : nullptr, (l < L - 1) ? b.xbuf[1] : nullptr};      // fp32 rows are only the next layer's residual
         if (int rc = launch_outproj_ln_chain(h, l, l == L - 1, b.attb, b.cur, oy, b.xb, rows, stream, tm)) return rc;
     } else {
@@ -1216,7 +1115,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             p.A32[m] = b.att[m]; p.A16[m] = b.attb[m]; p.amaxA[m] = b.am_att(l, m);
             p.C[m] = b.ybuf[m]; p.R[m] = b.cur[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT, h->policy.split_tile)) return rc;
 
         LnArgs la;
         memset(&la, 0, sizeof(la));
@@ -1274,7 +1173,8 @@ static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass*
             b.compacted = true;
         }
     }
-    b.tail_split = b.splitmb && (!b.compacted || split_eligible(b.rows, IEF_D, IEF_D, 1));   // bf16x6: a small compact set runs on the fp32 kernels
+    static_cast<TailFlags&>(b) = plan_tail(h->policy, h->cfg.compute, b.rows, h->cfg.num_steps, b.splitmb, b.compacted, h->heads_stream != nullptr,
+                                           h->chain_stream != nullptr);
     return 0;
 }
 
@@ -1288,12 +1188,9 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
     float* const z = b.z;
 
-    // 2 + 3 in one kernel (bf16 mode, full grids): heads of both modalities + fusion on the row-block structure (heads_chain_bf16.h).
-    // The four head tensors are stored only if the caller asked for them.
-    const bool heads_rows = bf && !h->no_heads_fusion && h->heads_stream && rows % HC_BM == 0 && (rows / HC_BM) * HC_THIRDS >= h->rowblock_min_wgs;
-    // 4 + 5 in one kernel (bf16 mode): the K refinement steps and the scorer with the state on chip, refine_chain_bf16.h
-    const bool chain = bf && K > 0 && !h->no_chain && h->chain_stream && rows % RC_BM == 0 && rows / RC_BM >= h->chain_min_blocks;
-    if (heads_rows) {
+    const bool chain = b.chain, fold = b.fold;
+    // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
+    if (b.heads_rows) {
         HeadsChainArgs ha;
         memset(&ha, 0, sizeof(ha));
         for (int m = 0; m < 2; ++m) ha.A[m] = b.xtb[m];
@@ -1322,7 +1219,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             p.A32[m] = b.xt[m]; p.A16[m] = b.xtb[m]; p.amaxA[m] = b.am_x(L - 1, m);
         }
         p.C[0] = b.mu_i; p.C2[0] = b.lv_i; p.C[1] = b.mu_e; p.C2[1] = b.lv_e;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD, h->policy.split_tile)) return rc;
 
         // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
         FusionArgs fa;
@@ -1348,7 +1245,6 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     // region, dead since the last LayerNorm).  Without `fused` in the outputs that projection stores no h and the last W2 launch
     // does not run; with it, h is stored and z_K is formed as always, after the scorer has read z_{K-1} (EPI_REFINE updates z
     // in place) -- so the logits of both output sets are the same bits.
-    const bool fold = b.tail_split && c.compute == IEFVAD_COMPUTE_BF16X6 && K >= 1;
     float* const fold_part = b.ybuf[0];
 
     // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
@@ -1364,7 +1260,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
             if (!out->fused) p.C[0] = nullptr;
         }
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
         if (dot) {
             hipEvent_t e = tm.begin(ST_SCORER);
             hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
@@ -1378,7 +1274,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         p.set_w(0, h->ref2[k]);
         p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
         p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
     }
 
     // 5. scorer (imf_vad.py:150)
@@ -1531,7 +1427,7 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
     RaggedChunk* hc = (RaggedChunk*)mr.host[slot];
     const int mb = micro_batch(h);
     // fp16x3 carries one operand scale per 256-row chunk of the row set: it keeps whole chunks
-    const bool enc_rows_mode = !h->dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
+    const bool enc_rows_mode = !h->policy.dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
     {
         // chunk table; src_row and enc_row are relative to the chunk's PASS (passes are runs of <= mb chunks)
         long long row = 0, pass_row0 = 0;
@@ -2383,10 +2279,8 @@ extern "C" int iefvad_gemm_bias(const void* A, const void* W, const float* bias,
         memset(&g, 0, sizeof(g));
         g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = N; g.epi = EPI_BIAS; g.wplane = N * K * 2;
         g.p[0].A = (const bf16_t*)A; g.p[0].W = (const bf16_t*)W; g.p[0].bias = bias; g.p[0].C = C;
-        hipError_t e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           GS_LDS_BYTES_OF(2));
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2));
+        hipError_t e = raise_lds_limit((const void*)iefvad_gemm_split_n128_kernel);
+        if (e == hipSuccess) e = raise_lds_limit((const void*)iefvad_gemm_split_n128x2_kernel);
         if (e != hipSuccess) return fail("iefvad_gemm_bias: %s", hipGetErrorString(e));
         return launch_gemm_split(g, 1, (hipStream_t)stream, tm, ST_QKV);
     }
@@ -2423,9 +2317,8 @@ extern "C" int iefvad_gemm_split_unit(const iefvad_gemm_split_io* io, int32_t M,
         g.p[m].R = (resid || dot) ? io->R[m] : nullptr;
         g.p[m].C2 = (heads || dot) ? io->C2[m] : nullptr;
     }
-    hipError_t e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2));
+    hipError_t e = raise_lds_limit((const void*)iefvad_gemm_split_n128_kernel);
+    if (e == hipSuccess) e = raise_lds_limit((const void*)iefvad_gemm_split_n128x2_kernel);
     if (e != hipSuccess) return fail("iefvad_gemm_split_unit: %s", hipGetErrorString(e));
     Timer tm;
     return launch_gemm_split(g, nz, (hipStream_t)stream, tm, ST_QKV, false, tile_n);

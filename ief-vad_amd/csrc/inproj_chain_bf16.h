@@ -16,7 +16,7 @@
 #pragma once
 #include "outproj_ln_chain_bf16.h"
 
-#define IC_BM 64
+#include "launch_rules.h"   // IC_BM
 #define IC_NPASS 3
 #define IC_STAGE_LD 104                                   // bf16 per staged row (208 B)
 #define IC_STAGE_BYTES (16 * IC_STAGE_LD * 2)             // 3,328 B per wave

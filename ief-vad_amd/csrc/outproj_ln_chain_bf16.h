@@ -17,7 +17,7 @@
 #include "gemm_bf16.h"
 #include "rowops.h"
 
-#define OC_BM 64
+#include "launch_rules.h"   // OC_BM
 #define OC_IMG_BYTES (OC_BM * IEF_D * 2)            // 98,304
 #define OC_PARK_LD 772                               // floats per parked row (768 + 4: conflict-free 16-byte tile stores)
 #define OC_PARK_BYTES (32 * OC_PARK_LD * 4)          // 98,816

@@ -28,7 +28,7 @@
 #include "gemm_bf16.h"
 #include "rowops.h"
 
-#define RC_BM 64
+#include "launch_rules.h"   // RC_BM
 #define RC_IMG_BYTES (RC_BM * IEF_D * 2)                    // 98,304 B: [64 rows][768 k] bf16, 16-byte chunks XOR-swizzled
 #define RC_NW 8                                             // waves per workgroup
 #define RC_KT (IEF_D / 32)                                  // 24 k-steps of 32

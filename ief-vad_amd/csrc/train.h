@@ -171,7 +171,7 @@ static int launch_dx(iefvad_handle* h, const bf16_t* planes_t, const float* dY, 
         g.p[0].A = (const bf16_t*)dY;            // fp32 data behind the typed pointer
         g.p[0].W = planes_t; g.p[0].bias = h->zero_bias; g.p[0].C = dX; g.p[0].R = G ? G : R;
         Timer tm;
-        return launch_gemm_split(g, 1, stream, tm, ST_REFINE, false, h->split_tile);      // N = 768: either tiling takes it
+        return launch_gemm_split(g, 1, stream, tm, ST_REFINE, false, h->policy.split_tile);      // N = 768: either tiling takes it
     }
     BgemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -424,7 +424,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             p.set_w(m, h->in[m][l]);
             p.A32[m] = xin(m, l); p.C[m] = ws + t.qkv[m][l];
         }
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_QKV, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_QKV, h->policy.split_tile)) return rc;
 
         // bf16x6: S = q k^T -> softmax -> dropout -> Pd v in ONE launch for both modalities (attention_split.h, TRAIN: the eval kernel
         // with the sign-carrying P stored for the backward); IEFVAD_TRAIN_ATTN=unfused keeps the three launches below (A/B: the test
@@ -489,7 +489,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             p.set_w(m, h->out[m][l]);
             p.A32[m] = ws + t.att[m][l]; p.C[m] = ws + t.s[m][l]; p.R[m] = xin(m, l);
         }
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_OUT, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_OUT, h->policy.split_tile)) return rc;
 
         LnArgs la;
         memset(&la, 0, sizeof(la));
@@ -518,7 +518,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             p.set_w(m, h->head[m]);
             p.A32[m] = ws + t.E[m]; p.C[m] = rec->mu[m]; p.C2[m] = rec->lv[m];
         }
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_HEAD, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_HEAD, h->policy.split_tile)) return rc;
     }
     {
         FusionArgs fa;
@@ -536,12 +536,12 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RELU; p.nz = 1;
         p.set_w(0, h->ref1[k]);
         p.A32[0] = zst(k); p.C[0] = ws + t.hid[k];
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
         memset(&p, 0, sizeof(p));
         p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
         p.set_w(0, h->ref2[k]);
         p.A32[0] = ws + t.hid[k]; p.C[0] = zst(k + 1); p.R[0] = zst(k);
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE, h->split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
     }
     float* logits = out->logits ? out->logits : ws + t.logits;
     hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, rec->zK, h->cls_w, h->cls_b,

@@ -54,7 +54,7 @@ def test_bf16_w256_gemm_kernel_matches_fp64_and_the_pipe_kernel(M, N):
     """`iefvad_gemm_bf16_w256_kernel` (256 x 256 tiles, 8 waves) carries in_proj, out_proj and the heads of every full-size
     micro-batch; `iefvad_gemm_bias` selects it once (M / 256)(N / 256) >= 256.  Against an fp64 product of the same
     bf16-rounded operands on sampled rows, and BIT-IDENTICAL to the 128 x 256 pipe kernel (what a 512-row problem runs on:
-    the "two bit-identical tilings" of launch_gemm_b) on the first and last 512 rows."""
+    the "two bit-identical tilings" of plan_gemm_bf16, csrc/launch_rules.h) on the first and last 512 rows."""
     lib = iefvad_amd.lib.load_library()
     g = torch.Generator().manual_seed(5)
     K = 768

@@ -163,8 +163,8 @@ def test_small_batches_run_on_the_fp32_kernels():
 
 @pytest.mark.parametrize("B", [5, 6, 9, 20])
 def test_mid_size_batches_meet_the_fp32_gates_on_either_side_of_the_dispatch_rule(B):
-    """The split kernels take a micro-batch from 6 chunks on (72 workgroups of a 768-wide projection: the measured crossover,
-    profiles/r03_kernel_selection_thresholds.log); B = 5 still runs on the fp32 kernels (bit-identical to compute="f32"), B = 6, 9, 20 on
+    """The split kernels take a micro-batch from 6 chunks on (kSplitMinWgs = 72 workgroups of a 768-wide projection in csrc/launch_rules.h: the
+    measured crossover, profiles/r03_kernel_selection_thresholds.log); B = 5 still runs on the fp32 kernels (bit-identical to compute="f32"), B = 6, 9, 20 on
     partially filled split grids.  All against the CPU oracle at the fp32 gates."""
     sd = synth.make_state_dict(4)
     img, ev = synth.make_inputs(21, B)

@@ -1,7 +1,7 @@
 """The two tilings of the bf16x6 split projection (csrc/gemm_split.h): 128 x 128 (iefvad_gemm_split_n128_kernel) and 128 x 256 as two
 column halves that share a wave's A planes (iefvad_gemm_split_n128x2_kernel).  Both sum every output element over its k-tiles in
 ascending order and over the six products of a k-tile in one order, so they must agree BIT FOR BIT -- which is what lets the launch
-rule (launch_gemm_split in csrc/iefvad.hip) choose a tiling by grid size alone.  The unit entry iefvad_gemm_split_unit names the
+rule (plan_gemm_split in csrc/launch_rules.h) choose a tiling by grid size alone.  The unit entry iefvad_gemm_split_unit names the
 tiling; whole forwards take it from IEFVAD_SPLIT_TILE at iefvad_create.  Needs a real MI355X: run with `-m gpu`."""
 import argparse
 import ctypes as C

@@ -5,7 +5,7 @@ one.  A model that was given state dict A, ran, and was then given state dict B 
 fresh model given B computes, bit for bit: nothing of A may survive in a reused arena, a weight stream, a captured graph or a plane
 that is rebuilt lazily.
 
-Batch sizes: 6 chunks is the smallest batch at which the split kernels take the projections (kSplitMinWgs = 72 workgroups), and a
+Batch sizes: 6 chunks is the smallest batch at which the split kernels take the projections (kSplitMinWgs = 72 workgroups, csrc/launch_rules.h), and a
 batch the library replays from a captured hipGraph; the bf16 mode runs once more at 8 chunks = 2,048 rows, the row count
 tests/test_gpu_rowblock_units.py gives the one-block row-block kernels, with the forward's own threshold lowered to that grid
 (IEFVAD_ROWBLOCK_MIN_WGS) so that all four of them read their re-packed streams.  Needs a real MI355X: run with `-m gpu`."""

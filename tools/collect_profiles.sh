@@ -42,7 +42,7 @@ python3 "$R/tools/hbm_traffic.py" "$(find "$O/pmc_fetch_bf16" -name '*counter_co
     "$K" 262144 "$O/gemm_bf16_hbm_traffic.json" "$SRC --compute bf16 (one micro-batch of 1024 chunks = 262144 rows per launch), MI355X, $RND, head $HEAD" \
     $(python3 -c "print(262144*1024*(6+3+3+6+3+6+3+3)/6, 262144*1024*(9+9+9+3+3.2+0.004)/6)") \
     "mean over the 6 projection launches of one pass: 2 x in_proj (6 / 3 KB/row read, 9 written), 2 x out_proj+LayerNorm (9 read; 9 / 3 written), heads+fusion (3 / 3.2), refinement chain of 2K projections + scorer (3 / 0.004); weights <= 24 MB per launch" > /dev/null 2>&1
-# the bf16x6 projections of a 262144-row pass run on the 128 x 256 two-half tiling (launch_gemm_split's rule); the file carries the
+# the bf16x6 projections of a 262144-row pass run on the 128 x 256 two-half tiling (plan_gemm_split's rule, csrc/launch_rules.h); the file carries the
 # kernel's name so that bench.py's lookup (which names the 128 x 128 kernel) never attaches it to another kernel's timings
 K=iefvad_gemm_split_n128x2_kernel
 python3 "$R/tools/hbm_traffic.py" "$(find "$O/pmc_fetch_bf16x6" -name '*counter_collection.csv' | head -1)" "$(find "$O/pmc_write_bf16x6" -name '*counter_collection.csv' | head -1)" \

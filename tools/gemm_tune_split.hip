@@ -43,7 +43,7 @@ static float run(const Variant& v, GemmBArgs gs, GemmBArgs gf, int iters) {
     return ms / iters;
 }
 
-// `gemm_tune_split sweep`: the crossover of the two bf16x6 tilings (launch_gemm_split's kSplitWideMinWgs): 128 x 128 (kind 2) against
+// `gemm_tune_split sweep`: the crossover of the two bf16x6 tilings (kSplitWideMinWgs, csrc/launch_rules.h): 128 x 128 (kind 2) against
 // 128 x 256 in two halves (kind 5) at N = 768, 1536, 2304 over grids from a fraction of one round of the chip's 512 workgroup slots
 // up to M = 262,144 rows; bias and refine epilogues, fp32 stores; medians of 5 alternating rounds.
 static int sweep(float* A, bf16_t* Wp, float* bias, float* C, float* R, const std::vector<float>& hW, int K, int Mmax) {
