@@ -915,6 +915,13 @@ struct RaggedPass {
     float* logits;                   // packed outputs at the pass's first row, nullable
     float* w_i_mean;
     float* w_e_mean;
+    // iefvad_forward_videos_scaled (all null / zero otherwise)
+    const float* scale[2];           // per-row input scales at the pass's first packed row (image, event), nullable
+    int nan_all;                     // torch.nan_to_num on every video and modality (test2.py:59-60): no flag words
+    double* w_colsum;                // [2, D]: the call's column sums of w_i / w_e over its valid rows, nullable
+    float* w_rows[2];                // home of the pass's w_i / w_e rows ([R, D] each, behind the base workspace); set with w_colsum
+    double* colsum_part;             // [nb, 2, D] slab partials of the pass; set with w_colsum
+    int first_pass;                  // the pass overwrites w_colsum, later ones add to it
 };
 
 // The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it
@@ -985,6 +992,8 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
         b.logits = b.lg_scratch;
         b.wim_out = rg->w_i_mean ? b.lg_scratch + R : nullptr;
         b.wem_out = rg->w_e_mean ? b.lg_scratch + 2 * R : nullptr;
+        b.n_i = rg->w_rows[0];                    // only with w_colsum: the fusion stage stores its weights for the column sums
+        b.n_e = rg->w_rows[1];
     }
     static_cast<PassFlags&>(b) = plan_pass(h->policy, c.compute, b.rows);
     b.am = h->amax_dev ? h->amax_dev + kAmaxActBase * IEF_AMAX_FLOATS : nullptr;
@@ -1013,11 +1022,13 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const void* pi, co
         hipEvent_t e = tm.begin(ST_CAST);
         // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
         // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
+        const bool scaled = rg->scale[0] || rg->scale[1] || rg->nan_all;
         dispatch_in(in_dtype, d512, [&](auto t, auto w) {
             using T = typename decltype(t)::type;
-            hipLaunchKernelGGL((iefvad_scatter_rows_kernel<T, decltype(w)::value>), dim3(b.nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream,
-                               (const T*)rg->img_rows, (const T*)rg->ev_rows, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p,
-                               b.enc_rows_mode ? 0 : IEF_T);
+            constexpr int W = decltype(w)::value;
+            hipLaunchKernelGGL((scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>),
+                               dim3(b.nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)rg->img_rows, (const T*)rg->ev_rows, rg->d_chunks,
+                               rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, b.enc_rows_mode ? 0 : IEF_T, rg->scale[0], rg->scale[1], rg->nan_all);
             return 0;
         });
         tm.end(e);
@@ -1295,6 +1306,20 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
                            b.wem_out, rg->logits, rg->w_i_mean, rg->w_e_mean, b.compacted ? nullptr : rg->d_chunks, rg->valid_rows);
         tm.end(e);
         HIP_TRY(hipGetLastError());
+        if (rg->w_colsum) {
+            // column sums of the stored weights over the valid rows: the chunk table on the row-compressed / whole-chunk set, 256-row
+            // slabs of the packed order on the compacted one (ragged.h)
+            const int nslabs = b.compacted ? (rg->valid_rows + 255) / 256 : b.nb;
+            e = tm.begin(ST_FUSION);
+            dispatch_d(d512, [&](auto w) {
+                hipLaunchKernelGGL(iefvad_colsum_rows_kernel<decltype(w)::value>, dim3(nslabs, 2), dim3(256), 0, stream, b.n_i, b.n_e,
+                                   b.compacted ? nullptr : rg->d_chunks, rg->valid_rows, rg->colsum_part);
+            });
+            hipLaunchKernelGGL(iefvad_colsum_finish_kernel, dim3(2 * D / 16), dim3(256), 0, stream, rg->colsum_part, nslabs, 2 * D,
+                               rg->first_pass, rg->w_colsum);
+            tm.end(e);
+            HIP_TRY(hipGetLastError());
+        }
     }
     return 0;
 }
@@ -1364,10 +1389,11 @@ static void release_meta(iefvad_handle* h) {
     h->meta = nullptr;
 }
 
-static int videos_layout(const int32_t* lengths, int32_t nvideos, long long* total_rows, long long* total_chunks) {
+static int videos_layout(const int32_t* lengths, int32_t nvideos, long long* total_rows, long long* total_chunks,
+                         const char* who = "iefvad_forward_videos") {
     long long rows = 0, chunks = 0;
     for (int v = 0; v < nvideos; ++v) {
-        if (lengths[v] <= 0) return fail("iefvad_forward_videos: lengths[%d] = %d", v, lengths[v]);
+        if (lengths[v] <= 0) return fail("%s: lengths[%d] = %d", who, v, lengths[v]);
         rows += lengths[v];
         chunks += video_chunks(lengths[v]);
     }
@@ -1383,30 +1409,61 @@ extern "C" size_t iefvad_videos_workspace_bytes(const iefvad_handle* h, const in
     return iefvad_workspace_bytes(h, (int32_t)chunks);
 }
 
+// What iefvad_forward_videos_scaled adds to a whole-video call.  With w_colsum the fusion stage stores w_i / w_e of the pass's row
+// set, and they need a home: no region of the base workspace is dead in every arithmetic while the tail runs (bf16 mode keeps its A
+// operand in the att region, mu / lv / z / h fill the qkv region, y holds the row-mean and scorer partial sums), so the scaled
+// entry's workspace is the base one plus [2, R, D] floats and the [nb, 2, D] slab partials of the column sums, nb = chunks of a pass.
+struct VideosExtras {
+    const float* scale[2];           // [sum(lengths)] each, indexed by the packed row of the call, nullable
+    double* w_colsum;                // [2, D], nullable
+};
+static size_t colsum_extra_bytes(const iefvad_handle* h, long long chunks) {
+    const int mb = micro_batch(h);
+    const size_t nb = (size_t)(chunks < mb ? chunks : mb);
+    return 2 * nb * IEF_T * (size_t)h->D * sizeof(float) + nb * 2 * (size_t)h->D * sizeof(double);
+}
+
+extern "C" size_t iefvad_videos_scaled_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t with_colsum) {
+    const size_t base = iefvad_videos_workspace_bytes(h, lengths, nvideos);
+    if (!base || !with_colsum) return base;
+    long long rows, chunks;
+    if (videos_layout(lengths, nvideos, &rows, &chunks)) return 0;
+    return base + colsum_extra_bytes(h, chunks);
+}
+
+// nan_to_num: 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 (the scaled entry only) = every video and modality
 static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
                                int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes, float* logits,
-                               float* w_i_mean, float* w_e_mean, hipStream_t stream, Timer& tm) {
-    if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("iefvad_forward_videos: null argument");
-    if (!h->weights_set) return fail("iefvad_forward_videos: weights not set");
-    if (nvideos <= 0) return fail("iefvad_forward_videos: nvideos must be positive (got %d)", nvideos);
-    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16)
-        return fail("iefvad_forward_videos: unknown in_dtype %d", in_dtype);
+                               float* w_i_mean, float* w_e_mean, hipStream_t stream, Timer& tm, const VideosExtras* ex = nullptr,
+                               const char* who = "iefvad_forward_videos") {
+    if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("%s: null argument", who);
+    if (!h->weights_set) return fail("%s: weights not set", who);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
+    if (nan_to_num < 0 || nan_to_num > (ex ? 2 : 1)) {
+        if (ex) return fail("%s: unknown nan_to_num %d (0: off, 1: per video with a NaN, 2: always)", who, nan_to_num);
+        nan_to_num = 1;       // iefvad_forward_videos: any non-zero value is the per-video rule
+    }
+    if (ex && ex->w_colsum && ((uintptr_t)ex->w_colsum & 7)) return fail("%s: w_colsum must be 8-byte aligned", who);
+    if (ex && (((uintptr_t)ex->scale[0] | (uintptr_t)ex->scale[1]) & 3)) return fail("%s: row scale vectors must be 4-byte aligned", who);
     long long total_rows, total_chunks;
-    if (int rc = videos_layout(lengths, nvideos, &total_rows, &total_chunks)) return rc;
-    if (total_chunks > 0x7fffffffLL / IEF_T) return fail("iefvad_forward_videos: too many chunks");
-    const size_t need = iefvad_workspace_bytes(h, (int32_t)total_chunks);
-    if (!workspace || workspace_bytes < need) return fail("iefvad_forward_videos: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
-    if (((uintptr_t)workspace & 15) || ((uintptr_t)img_rows & 15) || ((uintptr_t)ev_rows & 15))
-        return fail("iefvad_forward_videos: buffers must be 16-byte aligned");
+    if (int rc = videos_layout(lengths, nvideos, &total_rows, &total_chunks, who)) return rc;
+    if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
+    const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
+    const bool colsum = ex && ex->w_colsum;
+    const size_t need = base + (colsum ? colsum_extra_bytes(h, total_chunks) : 0);
+    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)img_rows & 15) || ((uintptr_t)ev_rows & 15)) return fail("%s: buffers must be 16-byte aligned", who);
+    const bool nan_all = nan_to_num == 2;
 
     // ---- metadata: the chunk table of the whole call (src_row relative to its pass, filled below) + the flag words
     const size_t chunk_bytes = (size_t)total_chunks * sizeof(RaggedChunk);
     const size_t flag_off = (chunk_bytes + 255) & ~(size_t)255;
-    const size_t flag_bytes = nan_to_num ? (size_t)nvideos * 2 * sizeof(int) : 0;
+    const size_t flag_bytes = (nan_to_num && !nan_all) ? (size_t)nvideos * 2 * sizeof(int) : 0;
     const size_t meta_bytes = flag_off + flag_bytes;
     if (!h->meta) {
         h->meta = new (std::nothrow) MetaRing();
-        if (!h->meta) return fail("iefvad_forward_videos: out of host memory");
+        if (!h->meta) return fail("%s: out of host memory", who);
     }
     MetaRing& mr = *h->meta;
     const int slot = mr.turn;
@@ -1496,6 +1553,20 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
         rg.logits = logits + row0;
         rg.w_i_mean = w_i_mean ? w_i_mean + row0 : nullptr;
         rg.w_e_mean = w_e_mean ? w_e_mean + row0 : nullptr;
+        for (int m = 0; m < 2; ++m) {
+            rg.scale[m] = (ex && ex->scale[m]) ? ex->scale[m] + row0 : nullptr;       // pass-relative, like src_row
+            rg.w_rows[m] = nullptr;
+        }
+        rg.nan_all = nan_all;
+        rg.w_colsum = nullptr; rg.colsum_part = nullptr;
+        rg.first_pass = c0 == 0;
+        if (colsum) {
+            const size_t per = (size_t)(total_chunks < mb ? total_chunks : mb) * IEF_T * h->D;
+            rg.w_colsum = ex->w_colsum;
+            rg.w_rows[0] = (float*)((char*)workspace + base);
+            rg.w_rows[1] = rg.w_rows[0] + per;
+            rg.colsum_part = (double*)(rg.w_rows[1] + per);
+        }
         rc = forward_pass(h, nullptr, nullptr, in_dtype, nb, 0, workspace, &none, &rg, stream, tm);
         row0 += vrows;
     }
@@ -1509,6 +1580,18 @@ extern "C" int iefvad_forward_videos(iefvad_handle* h, const void* img_rows, con
     Timer tm;
     return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
                                w_e_mean, (hipStream_t)stream, tm);
+}
+
+extern "C" int iefvad_forward_videos_scaled(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                            const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const float* img_row_scale,
+                                            const float* ev_row_scale, void* workspace, size_t workspace_bytes, float* logits,
+                                            float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream) {
+    Timer tm;
+    VideosExtras ex;
+    ex.scale[0] = img_row_scale; ex.scale[1] = ev_row_scale;
+    ex.w_colsum = w_colsum;
+    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
+                               w_e_mean, (hipStream_t)stream, tm, &ex, "iefvad_forward_videos_scaled");
 }
 
 

@@ -19,6 +19,9 @@
 //     row-wise) runs on the same row set; iefvad_rows_out_kernel picks the valid rows' results (test.py:121).
 //   fp16x3 (per-chunk operand scales) and IEFVAD_DENSE_ENCODER=1 keep whole chunks in the encoder;
 //   iefvad_compact_rows_kernel then gathers the valid rows of the last LayerNorm's output for the tail.
+// The robustness sweep (/root/reference/test2.py:35-123) runs on the same route through iefvad_forward_videos_scaled: the chunker's
+// scaled instantiation applies the unconditional nan_to_num (test2.py:59-60) and a per-row scale (test2.py:70-77), and
+// iefvad_colsum_rows_kernel / iefvad_colsum_finish_kernel reduce w_i / w_e over the valid rows to 768 sums per modality (test2.py:102-103).
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
@@ -53,10 +56,15 @@ __global__ __launch_bounds__(256) void iefvad_nanflag_kernel(const T* img, const
 }
 
 // gridDim.z workgroups per (chunk, modality), 16-row groups dealt round-robin: valid rows from the packed input (fixed up if the
-// video's flag is set), zeros behind them (nrows = 256: whole chunks; nrows = 0: row-compressed, one zero row)
-template <typename T, int D>
+// video's flag is set), zeros behind them (nrows = 256: whole chunks; nrows = 0: row-compressed, one zero row).
+// SC (iefvad_forward_videos_scaled): `fix_all` replaces in every video (test2.py:59-60, no flag words), and packed row r of the pass
+// is multiplied by sc0[r] / sc1[r] (nullable) AFTER the replacement (test2.py:70-77) with the semantics of
+// iefvad_cast_scaled_kernel (rowops.h): fp32 product, rounded to T before the widening, a scale of exactly 1 leaves the bits
+// alone.  Pad rows are the zeros written here, never scaled.  SC = false is the kernel of iefvad_forward_videos, unchanged.
+template <typename T, int D, bool SC = false>
 __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, const T* ev, const RaggedChunk* chunks, const int* flags,
-                                                                  float* out0, float* out1, __bf16* ob0, __bf16* ob1, int nrows) {
+                                                                  float* out0, float* out1, __bf16* ob0, __bf16* ob1, int nrows,
+                                                                  const float* sc0, const float* sc1, int fix_all) {
     constexpr int NJ = D / 256;
     const RaggedChunk c = chunks[blockIdx.x];
     const int m = blockIdx.y;
@@ -64,7 +72,9 @@ __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, 
     float* out = (m ? out1 : out0) + (size_t)c.enc_row * D;
     __bf16* ob = m ? ob1 : ob0;
     if (ob) ob += (size_t)c.enc_row * D;
-    const bool fix = flags && flags[2 * c.video + m] != 0;
+    const bool fix = (SC && fix_all) || (flags && flags[2 * c.video + m] != 0);
+    const float* sc = SC ? (m ? sc1 : sc0) : nullptr;
+    if (sc) sc += c.src_row;
     const float big = RaggedLimits<T>::max();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nr = nrows ? nrows : ragged_rows(c.valid);
@@ -97,6 +107,17 @@ __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, 
                     for (int e = 0; e < 4; ++e) {
                         const float x = w[e];
                         w[e] = (x != x) ? 0.f : (x > big ? big : (x < -big ? -big : x));     // torch.nan_to_num(nan=0.0)
+                    }
+                }
+                if (SC && sc && r < c.valid) {
+                    const float f = sc[r];
+                    if (f != 1.0f) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float prod = w[e] * f;
+                            asm volatile("" : "+v"(prod));       // keep the fp32 product: no fpext -> fmul -> fptrunc fold (rowops.h)
+                            w[e] = (float)(T)prod;
+                        }
                     }
                 }
                 *(f32x4*)(out + (size_t)r * D + col) = w;
@@ -153,4 +174,83 @@ __global__ __launch_bounds__(256) void iefvad_rows_out_kernel(const float* s0, c
         if (d1) d1[d] = s1[s];
         if (d2) d2[d] = s2[s];
     }
+}
+
+// ---- column sums of the fusion weights over the VALID rows of a pass (iefvad_forward_videos_scaled, w_colsum): the 768 sums per
+// modality behind the robustness sweep's w_img_change / w_ev_change (test2.py:86-87,102-103), without a [rows, D] tensor
+// crossing the boundary.  One workgroup per (slab, modality): slab = chunk c of the table (rows enc_row .. enc_row + valid - 1
+// of the tail's row set), or, chunks == nullptr (the compacted set: packed order), rows 256 slab .. of the first valid_rows rows.
+// The scatter kernel's lane map: a lane owns columns 4 lane + 256 j, wave w takes rows w, w + 4, ... in ascending order into fp64
+// registers; the four waves' sums meet in LDS and are added in wave order.  part[(slab * 2 + m) * D + col]: no atomics, the same
+// bits on every run.
+template <int D>
+__global__ __launch_bounds__(256) void iefvad_colsum_rows_kernel(const float* n0, const float* n1, const RaggedChunk* chunks, int valid_rows,
+                                                                 double* part) {
+    constexpr int NJ = D / 256;
+    __shared__ double lds[4][D];
+    const int m = blockIdx.y;
+    int first, nr;
+    if (chunks) {
+        const RaggedChunk c = chunks[blockIdx.x];
+        first = c.enc_row; nr = c.valid;
+    } else {
+        first = blockIdx.x * 256;
+        nr = valid_rows - first < 256 ? valid_rows - first : 256;
+    }
+    const float* src = (m ? n1 : n0) + (size_t)first * D;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double acc[NJ][4];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[j][e] = 0.0;
+    // four rows of the wave per trip, all their loads issued before the first add
+    for (int r0 = wave; r0 < nr; r0 += 16) {
+        f32x4 v[4][NJ];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = r0 + 4 * u;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                v[u][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (r < nr) v[u][j] = *(const f32x4*)(src + (size_t)r * D + 4 * lane + 256 * j);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (r0 + 4 * u >= nr) break;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[j][e] += (double)v[u][j][e];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) lds[wave][4 * lane + 256 * j + e] = acc[j][e];
+    __syncthreads();
+    double* dst = part + ((size_t)blockIdx.x * 2 + m) * D;
+    for (int col = threadIdx.x; col < D; col += 256) dst[col] = ((lds[0][col] + lds[1][col]) + lds[2][col]) + lds[3][col];
+}
+
+// the slab partials of a pass onto the call's running total: out[m][d] (the caller's w_colsum) is overwritten by the first pass of a
+// call (first != 0) and carried by the later ones.  A workgroup takes 16 of the 2 D (modality, column) sums; thread (seg, jj) adds the
+// slabs of its sixteenth of the index range in ascending order, thread (0, jj) then adds the 16 segment sums in ascending order -- an
+// order fixed by nslabs alone (a 256-slab pass would otherwise be one chain of 256 dependent adds per thread on six workgroups).
+#define COLSUM_SEGS 16
+__global__ __launch_bounds__(256) void iefvad_colsum_finish_kernel(const double* part, int nslabs, int twoD, int first, double* out) {
+    __shared__ double seg_sum[COLSUM_SEGS][16];
+    const int seg = threadIdx.x >> 4, jj = threadIdx.x & 15;
+    const int i = blockIdx.x * 16 + jj;                // m * D + d; twoD is a multiple of 16
+    const int len = (nslabs + COLSUM_SEGS - 1) / COLSUM_SEGS;
+    const int k1 = (seg + 1) * len < nslabs ? (seg + 1) * len : nslabs;
+    double s = 0.0;
+    for (int k = seg * len; k < k1; ++k) s += part[(size_t)k * twoD + i];
+    seg_sum[seg][jj] = s;
+    __syncthreads();
+    if (seg != 0) return;
+    double t = first ? 0.0 : out[i];
+    for (int g = 0; g < COLSUM_SEGS; ++g) t += seg_sum[g][jj];
+    out[i] = t;
 }

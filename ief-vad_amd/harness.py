@@ -1296,6 +1296,26 @@ class SweepResult(tuple):
             raise AttributeError(name) from None
 
 
+def sweep_row_scales(lengths: Sequence[int], draws, T: int):
+    """The two packed row-scale vectors (image, event; fp32 host tensors of sum(lengths) elements) of one level of the sweep on the
+    valid-row route: row r of video v gets 0.01 if `r % T` is among the time steps `draws[v][m]` drawn for that video and modality,
+    1 otherwise -- the `x[:, idx]` of test2.py:73,77 (every chunk of the video, the drawn time steps) restricted to the valid rows.
+    A modality with no draw in any video gives None."""
+    out = []
+    for m in (0, 1):
+        if all(d[m] is None or d[m].numel() == 0 for d in draws):
+            out.append(None)
+            continue
+        parts = []
+        for n, d in zip(lengths, draws):
+            step = torch.ones(T)
+            if d[m] is not None and d[m].numel():
+                step[d[m]] = 0.01
+            parts.append(step.repeat(-(-int(n) // T))[:int(n)])
+        out.append(torch.cat(parts).contiguous())
+    return out
+
+
 class PerturbationSweep:
     """Robustness sweep over one test list, organised for the device instead of per video:
 
@@ -1315,11 +1335,25 @@ class PerturbationSweep:
         from per-snippet values and the 16-frames-per-snippet ground truth, never materialising the x16 repeat.
 
     On a HIP device `model` should be built with outputs="weights" (or "full").  With a CPU `device` (plumbing runs with a CPU
-    model) the scale is applied to a copy with torch ops and the metrics come from sklearn as in test2.py:105-106."""
+    model) the scale is applied to a copy with torch ops and the metrics come from sklearn as in test2.py:105-106.
 
-    def __init__(self, args, model, loader, gt, device, batch_chunks: int = 64, repeat: int = 16):
+    `ragged=True` (HIP only; the default is the padded route above) is the valid-row route of the evaluation loops
+    (`MMFMIL.forward_videos`, csrc/ragged.h): only the VALID rows of every item are kept, concatenated in list order and uploaded
+    once (`self.rows`); no padding crosses the boundary or is computed behind the encoder.  The unconditional `nan_to_num` is the
+    library's mode "always", a level's draws become two packed scale vectors (`sweep_row_scales`), ONE `forward_videos` call per
+    level serves the whole list, and the per-dimension weight sums come from the library's column-sum kernels (`w_colsum`), so a
+    model built with outputs="scores" is enough.  The draws and the statistics are those of the padded route."""
+
+    def __init__(self, args, model, loader, gt, device, batch_chunks: int = 64, repeat: int = 16, ragged: bool = False):
         self.model, self.device, self.repeat = model, torch.device(device), repeat
         self.T = T = args.visual_length
+        self.ragged = bool(ragged)
+        if self.ragged:
+            if self.device.type != 'cuda':
+                raise ValueError("PerturbationSweep(ragged=True) is the valid-row route of the HIP library (iefvad_forward_videos_scaled): "
+                                 f"it runs on a HIP device only, not on {self.device}")
+            self._init_rows(loader, gt)
+            return
         videos: List[Tuple[torch.Tensor, torch.Tensor, int]] = []
         for item in loader:
             img, ev, n = item[0].squeeze(0), item[1].squeeze(0), int(item[3])
@@ -1348,12 +1382,42 @@ class PerturbationSweep:
                 valid.append(torch.arange(off * T, off * T + self.lengths[v]))
                 off += self.nchunks[v]
             self.packed.append((img, ev, torch.cat(valid).to(self.device)))
+        self._init_gt(gt)
+
+    def _init_gt(self, gt):
         self.total = sum(self.lengths)
-        g = torch.as_tensor(np.asarray(gt)[: repeat * self.total], dtype=torch.float64).reshape(self.total, repeat)
+        g = torch.as_tensor(np.asarray(gt)[: self.repeat * self.total], dtype=torch.float64).reshape(self.total, self.repeat)
         self.gt = g.to(self.device)
         self.pos = self.gt.sum(dim=1)                        # anomalous frames of each snippet
         self.clean_passes = 0
         self._clean = None
+
+    def _init_rows(self, loader, gt):
+        """Valid-row route: the first `n` rows of every item, concatenated in list order, one upload per modality."""
+        imgs, evs, self.lengths = [], [], []
+        for item in loader:
+            n = int(item[3])
+            D = item[0].shape[-1]
+            imgs.append(item[0].reshape(-1, D)[:n])
+            evs.append(item[1].reshape(-1, D)[:n])
+            self.lengths.append(n)
+        dts = {t.dtype for t in imgs + evs}
+        dt = torch.float32 if len(dts) > 1 else next(iter(dts))       # fp16 stays fp16, mixed dtypes widen to fp32
+        self.rows = tuple(torch.cat([t.to(dt) for t in parts]).contiguous().to(self.device) for parts in (imgs, evs))
+        self._init_gt(gt)
+
+    def _pass_rows(self, draws=None):
+        """One `forward_videos` call over the whole list: mode "always" of the NaN rule, the level's packed scale vectors, the
+        column sums of the fusion weights from the device."""
+        scale = None
+        if draws is not None:
+            si, se = sweep_row_scales(self.lengths, draws, self.T)
+            scale = (si.to(self.device) if si is not None else None, se.to(self.device) if se is not None else None)
+        with torch.no_grad():
+            out = self.model.forward_videos(self.rows[0], self.rows[1], self.lengths, nan_to_num="always", row_scale=scale,
+                                            weight_sums=True)
+        return {"p": torch.sigmoid(out["logits"]).float(), "wi_row": out["w_i_mean"], "we_row": out["w_e_mean"],
+                "wi_dim": out["w_colsum"][0] / self.total, "we_dim": out["w_colsum"][1] / self.total}
 
     def _scales(self, batch, draws):
         """Row-scale vectors [C * T] (image, event) of one packed batch for one level's draws; None for an untouched modality."""
@@ -1375,6 +1439,8 @@ class PerturbationSweep:
 
     # one packed pass over the list; `draws[v]` = (image time steps, event time steps) to attenuate in video v, or None
     def _pass(self, draws=None):
+        if self.ragged:
+            return self._pass_rows(draws)
         probs, wi_rows, we_rows = [], [], []
         wi_dim = we_dim = None
         on_gpu = self.device.type == 'cuda'
@@ -1441,14 +1507,15 @@ class PerturbationSweep:
 
 
 def run_perturbation_test(args, model, loader, gt, device, sigma_img=0, sigma_ev=0, clean_cache: Optional[dict] = None,
-                          batch_chunks: int = 64) -> SweepResult:
+                          batch_chunks: int = 64, ragged: bool = False) -> SweepResult:
     """One level of the sweep with the call shape of the reference's `run_test(args, model, loader, gt, device,
     sigma_img, sigma_ev)` (test2.py:35) and its 12-tuple.  `clean_cache` (a dict the caller keeps across levels) holds
-    the `PerturbationSweep`, so the unpacked list and the clean pass are shared by all levels."""
+    the `PerturbationSweep`, so the unpacked list and the clean pass are shared by all levels.  `ragged=True`: the sweep's
+    valid-row route (HIP only; `PerturbationSweep`)."""
     model.eval()
     sweep = clean_cache.get("sweep") if clean_cache is not None else None
     if sweep is None:
-        sweep = PerturbationSweep(args, model, loader, gt, device, batch_chunks)
+        sweep = PerturbationSweep(args, model, loader, gt, device, batch_chunks, ragged=ragged)
         if clean_cache is not None:
             clean_cache["sweep"] = sweep
     return sweep.level(sigma_img, sigma_ev)

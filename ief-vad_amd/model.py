@@ -531,15 +531,35 @@ class MMFMIL(nn.Module):
         outs = _TrainForward.apply(self, img_visual.detach(), ev_visual.detach(), *params)
         return dict(zip(OUTPUT_KEYS, outs))
 
-    def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num: bool = True
-                       ) -> Dict[str, torch.Tensor]:
+    def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
+                       weight_sums: bool = False) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
-        test.py:119-121,131-138 happen on the device.  Returns `logits`, `w_i_mean`, `w_e_mean`, each [sum(lengths)]."""
+        test.py:119-121,131-138 happen on the device.  Returns `logits`, `w_i_mean`, `w_e_mean`, each [sum(lengths)].
+        The robustness sweep's extras (`iefvad_forward_videos_scaled`; with none of them the entry above is called, unchanged):
+        `nan_to_num="always"` replaces in every video and modality (test2.py:59-60); `row_scale=(s_img, s_ev)`, contiguous fp32
+        DEVICE vectors of sum(lengths) elements (either may be None), multiply the packed rows inside the library's input load,
+        after the NaN rule (test2.py:70-77 on valid rows); `weight_sums=True` adds `w_colsum`, a [2, D] float64 device tensor: the
+        sums over all valid rows of w_i / w_e (test2.py:86-87), reduced on the device."""
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos is an evaluation entry point; call model.eval() first")
         self._noise_code()
+        if isinstance(nan_to_num, str):
+            if nan_to_num != "always":
+                raise ValueError(f"nan_to_num must be True, False or 'always' (got {nan_to_num!r})")
+            nan_mode = 2
+        else:
+            nan_mode = 1 if nan_to_num else 0
+        scales = (None, None) if row_scale is None else tuple(row_scale)
+        if len(scales) != 2:
+            raise ValueError("row_scale must be a pair (image vector, event vector), either may be None")
+        nrows = sum(int(n) for n in lengths)
+        for sv in scales:
+            if sv is not None and (not isinstance(sv, torch.Tensor) or sv.dtype != torch.float32 or sv.device != img_rows.device
+                                   or sv.numel() != nrows or not sv.is_contiguous()):
+                raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {nrows} elements (sum of lengths) on {img_rows.device}")
+        extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None
         if not (img_rows.is_cuda and ev_rows.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         lens = [int(n) for n in lengths]
@@ -561,14 +581,31 @@ class MMFMIL(nn.Module):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._ensure_handle(device)
             self._ensure_weights(device, stream)
-            need = lib.iefvad_videos_workspace_bytes(self._handle, larr, len(lens))
+            if extras:
+                need = lib.iefvad_videos_scaled_workspace_bytes(self._handle, larr, len(lens), 1 if weight_sums else 0)
+            else:
+                need = lib.iefvad_videos_workspace_bytes(self._handle, larr, len(lens))
             if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
                 self._workspace = None
                 self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
             f32 = dict(dtype=torch.float32, device=device)
             res = {"logits": torch.empty(total, **f32), "w_i_mean": torch.empty(total, **f32), "w_e_mean": torch.empty(total, **f32)}
+            if extras:
+                if weight_sums:
+                    res["w_colsum"] = torch.empty(2, D, dtype=torch.float64, device=device)
+                rc = lib.iefvad_forward_videos_scaled(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()),
+                                                      _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
+                                                      C.c_void_p(scales[0].data_ptr()) if scales[0] is not None else None,
+                                                      C.c_void_p(scales[1].data_ptr()) if scales[1] is not None else None,
+                                                      C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(),
+                                                      C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
+                                                      C.c_void_p(res["w_e_mean"].data_ptr()),
+                                                      C.c_void_p(res["w_colsum"].data_ptr()) if weight_sums else None, C.c_void_p(stream))
+                if rc != 0:
+                    raise RuntimeError("iefvad_forward_videos_scaled: " + _lib.last_error())
+                return res
             rc = lib.iefvad_forward_videos(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()),
-                                           _IN_DTYPES[img.dtype], larr, len(lens), 1 if nan_to_num else 0,
+                                           _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
                                            C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(),
                                            C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
                                            C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))

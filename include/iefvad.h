@@ -189,6 +189,31 @@ int iefvad_forward_videos(iefvad_handle* h, const void* img_rows, const void* ev
                           const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
                           size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, void* stream);
 
+/* iefvad_forward_videos for the robustness sweep (/root/reference/test2.py:35-123: twelve levels over one list): the same call, plus
+ *   nan_to_num          gains the value 2: torch.nan_to_num on EVERY video and modality (test2.py:59-60; NaN -> 0, +-inf -> the
+ *                       largest / smallest finite value of `in_dtype`), with no scan and no flag words.  0 and 1 as above; any other
+ *                       value is refused
+ *   img_row_scale, ev_row_scale   DEVICE fp32 [sum(lengths)], each nullable, indexed by the packed row of the CALL: packed row r of
+ *                       modality m enters the model as x[r] * scale_m[r] (test2.py:70-77's `x[:, idx] * 0.01` on valid rows), the
+ *                       product formed as iefvad_forward_scaled forms it (fp32, rounded to `in_dtype` before the widening; a scale
+ *                       of exactly 1, or a NULL vector, leaves the row's bits alone) and AFTER the NaN rule; pad rows are the zeros
+ *                       the library writes and are not scaled
+ *   w_colsum            DEVICE [2, D] doubles (8-byte aligned), nullable: on return (stream-ordered) w_colsum[0][d] is the sum over
+ *                       all valid rows of the call of w_i[r][d], w_colsum[1][d] the same for w_e (test2.py:86-87,102-103): the fp32
+ *                       values the fusion stage stores, added in fp64, per-slab partial sums finished in a fixed order without
+ *                       atomics (the same call gives the same bits).  Pad rows and tile-rounding rows are not included.  The buffer
+ *                       is overwritten.
+ * Workspace: iefvad_videos_scaled_workspace_bytes(h, lengths, nvideos, with_colsum) -- with_colsum != 0 adds a home for the w_i / w_e
+ * rows of one pass and the slab partials; with w_colsum == NULL the size of iefvad_videos_workspace_bytes is enough.  With
+ * w_colsum == NULL and both scale vectors NULL (and nan_to_num 0 or 1) the call launches exactly what iefvad_forward_videos launches.
+ * Per-snippet results equal those of iefvad_forward_scaled on the host-padded chunks, as above.  D = 512 handles are served.
+ * Added without a change to any other entry or struct: IEFVAD_ABI_VERSION stays. */
+size_t iefvad_videos_scaled_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t with_colsum);
+int iefvad_forward_videos_scaled(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                 const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const float* img_row_scale,
+                                 const float* ev_row_scale, void* workspace, size_t workspace_bytes, float* logits,
+                                 float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream);
+
 /* The whole evaluation LIST in one call: host rows in, per-snippet results on the device.  Replaces the Python loop around
  * iefvad_forward_videos (one iteration per video in the reference, /root/reference/test.py:76-121; one per packed batch in this
  * package until round 3): the library cuts the list into passes of >= batch_chunks chunks (whole videos; 0 = 128), a worker thread
