@@ -64,21 +64,24 @@ static void release_hostpipe(iefvad_handle* h) {
     h->hostpipe = nullptr;
 }
 
-extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
-                                          int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
-                                          int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream_) {
-    if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("iefvad_forward_videos_host: null argument");
-    if (!h->weights_set) return fail("iefvad_forward_videos_host: weights not set");
-    if (nvideos <= 0) return fail("iefvad_forward_videos_host: nvideos must be positive (got %d)", nvideos);
+// `similarity` (iefvad_forward_videos_host_similarity; null for the plain entry): [4, sum(lengths)] on the device -- every pass reduces
+// its own rows and writes at its row offset with the list's total as the stride (VideosExtras).
+static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
+                                    int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
+                                    int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream_, float* similarity,
+                                    const char* who) {
+    if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("%s: null argument", who);
+    if (!h->weights_set) return fail("%s: weights not set", who);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
     if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16)
-        return fail("iefvad_forward_videos_host: unknown in_dtype %d", in_dtype);
+        return fail("%s: unknown in_dtype %d", who, in_dtype);
     if (wire_dtype != in_dtype && !(in_dtype == IEFVAD_IN_F32 && wire_dtype == IEFVAD_IN_BF16))
-        return fail("iefvad_forward_videos_host: wire_dtype %d with in_dtype %d (the wire type is in_dtype, or BF16 for F32 rows)", wire_dtype, in_dtype);
+        return fail("%s: wire_dtype %d with in_dtype %d (the wire type is in_dtype, or BF16 for F32 rows)", who, wire_dtype, in_dtype);
     if (wire_dtype != in_dtype && h->cfg.compute != IEFVAD_COMPUTE_BF16)
-        return fail("iefvad_forward_videos_host: a narrowed wire type belongs to the bf16 mode (compute = %d)", h->cfg.compute);
+        return fail("%s: a narrowed wire type belongs to the bf16 mode (compute = %d)", who, h->cfg.compute);
     for (int v = 0; v < nvideos; ++v) {
-        if (lengths[v] <= 0) return fail("iefvad_forward_videos_host: lengths[%d] = %d", v, lengths[v]);
-        if (!img_rows[v] || !ev_rows[v]) return fail("iefvad_forward_videos_host: null row pointer (video %d)", v);
+        if (lengths[v] <= 0) return fail("%s: lengths[%d] = %d", who, v, lengths[v]);
+        if (!img_rows[v] || !ev_rows[v]) return fail("%s: null row pointer (video %d)", who, v);
     }
     hipStream_t stream = (hipStream_t)stream_;
     const bool narrow = wire_dtype != in_dtype;
@@ -95,8 +98,8 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
     // second round on 256 CUs, i.e. as much as the first 256.
     struct Batch { int v0, v1; long long rows, chunks, enc; };
     std::vector<Batch> batches;
-    long long max_rows = 0, max_chunks = 0, total_chunks = 0;
-    for (int v = 0; v < nvideos; ++v) total_chunks += video_chunks(lengths[v]);
+    long long max_rows = 0, max_chunks = 0, total_chunks = 0, total_rows = 0;
+    for (int v = 0; v < nvideos; ++v) { total_chunks += video_chunks(lengths[v]); total_rows += lengths[v]; }
     const bool compressed = !h->policy.dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
     const long long round_rows = (long long)(h->num_cus > 0 ? h->num_cus : 256) * 64;
     const long long row_cap = compressed ? round_rows * ((want + 64) / 128 > 1 ? (want + 64) / 128 : 1) : (1LL << 60);
@@ -125,13 +128,13 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
             if (b.chunks >= target || v == nvideos - 1) close(v + 1);
         }
     }
-    if (max_chunks > 0x7fffffffLL / IEF_T) return fail("iefvad_forward_videos_host: batch too large");
+    if (max_chunks > 0x7fffffffLL / IEF_T) return fail("%s: batch too large", who);
 
     HIP_TRY(hipSetDevice(h->device));
     if (!h->hostpipe) {
         // built completely or not at all: a handle never keeps a HostPipe with missing streams / events
         h->hostpipe = new (std::nothrow) HostPipe();
-        if (!h->hostpipe) return fail("iefvad_forward_videos_host: out of host memory");
+        if (!h->hostpipe) return fail("%s: out of host memory", who);
         HostPipe& np = *h->hostpipe;
         hipError_t ce = hipStreamCreateWithFlags(&np.copy_stream, hipStreamNonBlocking);
         for (int s = 0; s < HostPipe::kSlots && ce == hipSuccess; ++s) {
@@ -145,7 +148,7 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
         }
         if (ce != hipSuccess) {
             release_hostpipe(h);
-            return fail("iefvad_forward_videos_host: creating the internal streams / events failed: %s", hipGetErrorString(ce));
+            return fail("%s: creating the internal streams / events failed: %s", who, hipGetErrorString(ce));
         }
     }
     HostPipe& p = *h->hostpipe;
@@ -190,7 +193,7 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
     bool abort_all = false;
     const int nthreads = host_threads > 0 ? (host_threads > 16 ? 16 : host_threads) : 8;
     if (!p.pool) p.pool = new (std::nothrow) GatherPool();
-    if (!p.pool) return fail("iefvad_forward_videos_host: out of host memory");
+    if (!p.pool) return fail("%s: out of host memory", who);
     p.pool->start(nthreads);
     std::vector<const void*> srcs;
     std::vector<size_t> offs;
@@ -286,9 +289,12 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
         hipStream_t cs = p.lane[ln];
         he = hipStreamWaitEvent(cs, p.sent[s], 0);
         if (he != hipSuccess) break;
+        VideosExtras ex;
+        memset(&ex, 0, sizeof(ex));
+        ex.similarity = similarity; ex.sim_stride = total_rows; ex.sim_row0 = row0;
         rc = forward_videos_impl(h, p.dev_in[s][0], p.dev_in[s][1], wire_dtype, lengths + b.v0, b.v1 - b.v0, nan_to_num,
                                  p.workspace[ln], p.workspace_bytes, logits + row0, w_i_mean ? w_i_mean + row0 : nullptr,
-                                 w_e_mean ? w_e_mean + row0 : nullptr, cs, tm);
+                                 w_e_mean ? w_e_mean + row0 : nullptr, cs, tm, similarity ? &ex : nullptr, who);
         if (rc == 0) he = hipEventRecord(p.used[s], cs);
         if (trace)
             fprintf(stderr, "[hostpipe] pass %d: %lld chunks %lld rows | waited for staging %.0f us | enqueue copies + forward %.0f us | t = %.0f us\n", k,
@@ -309,9 +315,26 @@ extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* i
         if (he == hipSuccess) he = e2;
     }
     if (rc) return rc;
-    if (he != hipSuccess) return fail("iefvad_forward_videos_host: %s", hipGetErrorString(he));
+    if (he != hipSuccess) return fail("%s: %s", who, hipGetErrorString(he));
     return 0;
     } catch (const std::exception& e) {      // nothing throws across the ABI (allocation failures of the host-side tables)
-        return fail("iefvad_forward_videos_host: %s", e.what());
+        return fail("%s: %s", who, e.what());
     }
+}
+
+extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
+                                          int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
+                                          int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream_) {
+    return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads, logits,
+                                    w_i_mean, w_e_mean, stream_, nullptr, "iefvad_forward_videos_host");
+}
+
+extern "C" int iefvad_forward_videos_host_similarity(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
+                                                     int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num,
+                                                     int32_t batch_chunks, int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean,
+                                                     void* stream_, float* similarity) {
+    static const char* const who = "iefvad_forward_videos_host_similarity";
+    if (int rc = similarity_args(who, similarity, in_dtype, nvideos)) return rc;
+    return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads, logits,
+                                    w_i_mean, w_e_mean, stream_, similarity, who);
 }

@@ -922,6 +922,10 @@ struct RaggedPass {
     float* w_rows[2];                // home of the pass's w_i / w_e rows ([R, D] each, behind the base workspace); set with w_colsum
     double* colsum_part;             // [nb, 2, D] slab partials of the pass; set with w_colsum
     int first_pass;                  // the pass overwrites w_colsum, later ones add to it
+    // iefvad_forward_videos_similarity / _host_similarity (null otherwise): the call's [4, sim_stride] series; the pass's packed row r
+    // is column sim_row0 + r.  With it the tail keeps fused (= z_K) and both mu of its row set (pass_tail).
+    float* similarity;
+    long long sim_stride, sim_row0;
 };
 
 // The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it
@@ -1200,13 +1204,17 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     float* const z = b.z;
 
     const bool chain = b.chain, fold = b.fold;
+    // keep fused / mu: the caller asked for the tensor, or the pass reduces it to the similarity series before it ends (then it stays
+    // in the workspace alias of pass_buffers).  Kernel selection does not look at these.
+    const bool sim = rg && rg->similarity;
+    const bool keep_fused = out->fused || sim, keep_mu_i = out->image_mu || sim, keep_mu_e = out->event_mu || sim;
     // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
     if (b.heads_rows) {
         HeadsChainArgs ha;
         memset(&ha, 0, sizeof(ha));
         for (int m = 0; m < 2; ++m) ha.A[m] = b.xtb[m];
-        ha.mu[0] = out->image_mu ? b.mu_i : nullptr; ha.lv[0] = out->image_logvar ? b.lv_i : nullptr;
-        ha.mu[1] = out->event_mu ? b.mu_e : nullptr; ha.lv[1] = out->event_logvar ? b.lv_e : nullptr;
+        ha.mu[0] = keep_mu_i ? b.mu_i : nullptr; ha.lv[0] = out->image_logvar ? b.lv_i : nullptr;
+        ha.mu[1] = keep_mu_e ? b.mu_e : nullptr; ha.lv[1] = out->event_logvar ? b.lv_e : nullptr;
         ha.n[0] = b.n_i; ha.n[1] = b.n_e;
         ha.z = z;
         ha.zb = chain ? nullptr : b.zb;
@@ -1248,14 +1256,14 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     }
 
     if (chain)
-        if (int rc = launch_refine_chain(h, z, out->fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
+        if (int rc = launch_refine_chain(h, z, keep_fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
 
     // bf16x6 on the split kernels: the last step's second projection is folded into the scorer,
     //   logits = c . z_K + b_c = c . z_{K-1} + v . h + s0     (v, s0: iefvad_set_weights; rowops.h),
     // v . h taken in the epilogue of the last step's FIRST projection (EPI_BIAS_RELU_DOT: six partial sums per row, into the y
-    // region, dead since the last LayerNorm).  Without `fused` in the outputs that projection stores no h and the last W2 launch
-    // does not run; with it, h is stored and z_K is formed as always, after the scorer has read z_{K-1} (EPI_REFINE updates z
-    // in place) -- so the logits of both output sets are the same bits.
+    // region, dead since the last LayerNorm).  Without `fused` in the outputs (and no similarity reduction behind the pass:
+    // keep_fused) that projection stores no h and the last W2 launch does not run; with it, h is stored and z_K is formed as always,
+    // after the scorer has read z_{K-1} (EPI_REFINE updates z in place) -- so the logits of both output sets are the same bits.
     float* const fold_part = b.ybuf[0];
 
     // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
@@ -1269,7 +1277,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         p.C[0] = bf ? nullptr : b.hbuf; p.Cb[0] = bf ? b.hb : nullptr;
         if (dot) {
             p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
-            if (!out->fused) p.C[0] = nullptr;
+            if (!keep_fused) p.C[0] = nullptr;
         }
         if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
         if (dot) {
@@ -1278,7 +1286,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
                                h->score_fold, b.logits, rows);
             tm.end(e);
             HIP_TRY(hipGetLastError());
-            if (!out->fused) break;
+            if (!keep_fused) break;
         }
         memset(&p, 0, sizeof(p));
         p.N = D; p.ldc = D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
@@ -1306,6 +1314,17 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
                            b.wem_out, rg->logits, rg->w_i_mean, rg->w_e_mean, b.compacted ? nullptr : rg->d_chunks, rg->valid_rows);
         tm.end(e);
         HIP_TRY(hipGetLastError());
+        if (sim) {
+            // the four series of the pass's valid rows from z_K / mu_i / mu_e where the tail left them (similarity.h)
+            const int nslabs = b.compacted ? (rg->valid_rows + 255) / 256 : b.nb;
+            e = tm.begin(ST_SCORER);
+            dispatch_d(d512, [&](auto w) {
+                hipLaunchKernelGGL(iefvad_similarity_rowset_kernel<decltype(w)::value>, dim3(nslabs, SIM_SLICES), dim3(256), 0, stream, z, b.mu_i,
+                                   b.mu_e, b.compacted ? nullptr : rg->d_chunks, rg->valid_rows, rg->similarity, rg->sim_stride, rg->sim_row0);
+            });
+            tm.end(e);
+            HIP_TRY(hipGetLastError());
+        }
         if (rg->w_colsum) {
             // column sums of the stored weights over the valid rows: the chunk table on the row-compressed / whole-chunk set, 256-row
             // slabs of the packed order on the compacted one (ragged.h)
@@ -1416,6 +1435,10 @@ extern "C" size_t iefvad_videos_workspace_bytes(const iefvad_handle* h, const in
 struct VideosExtras {
     const float* scale[2];           // [sum(lengths)] each, indexed by the packed row of the call, nullable
     double* w_colsum;                // [2, D], nullable
+    // iefvad_forward_videos_similarity / _host_similarity (the scaled entry leaves it null): [4, sim_stride] fp32 on the device; the
+    // call's packed row r is column sim_row0 + r (the host-list entry: the row offset of the pass within the whole list)
+    float* similarity;
+    long long sim_stride, sim_row0;
 };
 static size_t colsum_extra_bytes(const iefvad_handle* h, long long chunks) {
     const int mb = micro_batch(h);
@@ -1440,12 +1463,14 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
     if (!h->weights_set) return fail("%s: weights not set", who);
     if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
     if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
-    if (nan_to_num < 0 || nan_to_num > (ex ? 2 : 1)) {
-        if (ex) return fail("%s: unknown nan_to_num %d (0: off, 1: per video with a NaN, 2: always)", who, nan_to_num);
+    const bool sweep = ex && !ex->similarity;      // the scaled entry's nan_to_num codes; the similarity entries keep the plain ones
+    if (nan_to_num < 0 || nan_to_num > (sweep ? 2 : 1)) {
+        if (sweep) return fail("%s: unknown nan_to_num %d (0: off, 1: per video with a NaN, 2: always)", who, nan_to_num);
         nan_to_num = 1;       // iefvad_forward_videos: any non-zero value is the per-video rule
     }
     if (ex && ex->w_colsum && ((uintptr_t)ex->w_colsum & 7)) return fail("%s: w_colsum must be 8-byte aligned", who);
     if (ex && (((uintptr_t)ex->scale[0] | (uintptr_t)ex->scale[1]) & 3)) return fail("%s: row scale vectors must be 4-byte aligned", who);
+    if (ex && ex->similarity && ((uintptr_t)ex->similarity & 3)) return fail("%s: similarity must be 4-byte aligned", who);
     long long total_rows, total_chunks;
     if (int rc = videos_layout(lengths, nvideos, &total_rows, &total_chunks, who)) return rc;
     if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
@@ -1560,6 +1585,9 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
         rg.nan_all = nan_all;
         rg.w_colsum = nullptr; rg.colsum_part = nullptr;
         rg.first_pass = c0 == 0;
+        rg.similarity = ex ? ex->similarity : nullptr;
+        rg.sim_stride = ex ? ex->sim_stride : 0;
+        rg.sim_row0 = ex ? ex->sim_row0 + row0 : 0;
         if (colsum) {
             const size_t per = (size_t)(total_chunks < mb ? total_chunks : mb) * IEF_T * h->D;
             rg.w_colsum = ex->w_colsum;
@@ -1588,10 +1616,37 @@ extern "C" int iefvad_forward_videos_scaled(iefvad_handle* h, const void* img_ro
                                             float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream) {
     Timer tm;
     VideosExtras ex;
+    memset(&ex, 0, sizeof(ex));
     ex.scale[0] = img_row_scale; ex.scale[1] = ev_row_scale;
     ex.w_colsum = w_colsum;
     return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
                                w_e_mean, (hipStream_t)stream, tm, &ex, "iefvad_forward_videos_scaled");
+}
+
+// The checks the two similarity entries make before they look at the handle: each names the entry, none makes a HIP call.
+static int similarity_args(const char* who, const float* similarity, int32_t in_dtype, int32_t nvideos) {
+    if (!similarity) return fail("%s: null similarity", who);
+    if ((uintptr_t)similarity & 3) return fail("%s: similarity must be 4-byte aligned", who);
+    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    return 0;
+}
+
+extern "C" int iefvad_forward_videos_similarity(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                                const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                                size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, void* stream,
+                                                float* similarity) {
+    static const char* const who = "iefvad_forward_videos_similarity";
+    if (int rc = similarity_args(who, similarity, in_dtype, nvideos)) return rc;
+    if (!h || !lengths) return fail("%s: null argument", who);
+    long long rows, chunks;
+    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
+    Timer tm;
+    VideosExtras ex;
+    memset(&ex, 0, sizeof(ex));
+    ex.similarity = similarity; ex.sim_stride = rows; ex.sim_row0 = 0;
+    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
+                               w_e_mean, (hipStream_t)stream, tm, &ex, who);
 }
 
 

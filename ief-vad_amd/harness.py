@@ -732,10 +732,11 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
                '(outputs="scores" / "weights" do not return them)')
 
 
-def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks):
+def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False):
     """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
-    while this thread sends batch k and enqueues its forward; batches complete in order."""
+    while this thread sends batch k and enqueues its forward; batches complete in order.
+    `similarity`: every forward also returns its [4, n] block of series (`forward_videos(similarity=True)`) for the sink."""
     def stage(pend, k):
         dt, widened = _batch_dtype(pend)
         if widened:               # a narrower video is widened at staging: its own dtype's inf -> max rule applies first (test.py:90-95)
@@ -748,8 +749,10 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
         staged = fut.result()
         with _lane_stream(streams[k]):
             img, ev = stagers[k].send(staged)
-            out = models[k].forward_videos(img, ev, lens, nan_to_num=True)
-        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens)
+            out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'))
+
+    sim_kw = dict(similarity=True) if similarity else {}
 
     stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
@@ -773,7 +776,7 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
         stage_pool.shutdown(wait=True)              # also when a forward raised: the worker thread must not outlive the call
 
 
-def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16):
+def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, similarity=False):
     """Valid-row route with the walk inside the library (`MMFMIL.forward_videos_host`, csrc/hostpipe.h): this thread only collects
     each video's host tensor and length; one library call per `host_list_bytes` of features stages, sends and scores them pass by
     pass.  Same batches, same kernels as `_score_rows_loop` (which remains for models without the entry, lanes > 1 callers that
@@ -782,8 +785,10 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
         wire = torch.bfloat16 if (wire_bf16 and group[0][0].dtype == torch.float32) else None
         lens = [g[2] for g in group]
         out = model.forward_videos_host([g[0] for g in group], [g[1] for g in group], lens, nan_to_num=True,
-                                        batch_chunks=batch_chunks, wire_dtype=wire)
-        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens)
+                                        batch_chunks=batch_chunks, wire_dtype=wire, **sim_kw)
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'))
+
+    sim_kw = dict(similarity=True) if similarity else {}
 
     group, gbytes = [], 0
     for item in loader:
@@ -810,7 +815,7 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
-                 return_device: bool = False, similarity: bool = False):
+                 return_device: bool = False, similarity=False):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -842,9 +847,22 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     every snippet's `fused` row to its `image_mu` / `event_mu` rows (`similarity_rows`; the series of test.py:235-238).  The padded route
     is taken with the caller's `batch_chunks` -- the valid-row entries return no 768-wide tensors; in f32 and bf16 both routes give the
     same bits, so the scores do not move -- and the model must return the full dict (`outputs="full"`).  The series stay on the device
-    and come back with the scores' one copy."""
+    and come back with the scores' one copy.
+    `similarity="rows"` (opt-in): the same last result from the valid-row routes -- the host-list walk, or the `forward_videos` loop
+    (`host_list=False`, `lanes > 1` included): every library call reduces the series of its valid rows from the pass's own fused / mu
+    rows (`MMFMIL.forward_videos(similarity=True)`, csrc/similarity.h), no padding is computed and the model may be built with any
+    `outputs=`.  Needs a HIP device, a model with `forward_videos` and batch_chunks > 0 (ValueError otherwise).  In f32 and bf16 the
+    series are the bits of `similarity=True`."""
     on_gpu = torch.device(device).type == 'cuda'
-    if similarity:
+    sim_rows = isinstance(similarity, str)
+    if sim_rows:
+        if similarity != "rows":
+            raise ValueError(f'similarity must be False, True (the padded route) or "rows" (the valid-row routes), got {similarity!r}')
+        if not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos')) or ragged is False:
+            raise ValueError('similarity="rows" takes the valid-row routes: it needs a HIP device, batch_chunks > 0 and a model with '
+                             'forward_videos (and not ragged=False)')
+        ragged = True
+    elif similarity:
         if ragged:
             raise ValueError("similarity=True takes the padded route: ragged=True returns no fused / image_mu / event_mu")
         if getattr(model, 'outputs', 'full') != 'full':
@@ -873,12 +891,12 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         for s in streams if nl > 1 else ():
             s.wait_stream(torch.cuda.current_stream(device))         # e.g. a `model.to(device)` still in flight
         if use_list:
-            _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16)
+            _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, sim_rows)
         elif ragged:
-            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks)
+            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows)
         else:
             _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                          similarity)
+                          bool(similarity))
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
         return sink.finish(device, return_device)
@@ -1186,7 +1204,7 @@ def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 
 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
-              batch_chunks, lanes, metric_tail="host", vis_flavour="test"):
+              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded"):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
@@ -1195,9 +1213,15 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     on the device (`evaluate_scores_device`).
     `vis`: the plots of the file named by `vis_flavour` (`vis_series` / `draw_vis`) under vis/{args.exp_name}/, at `args.vis_dpi` dots
     per inch where the namespace has one (100 otherwise); the result dict gains "similarity" (the four series of `similarity_rows`,
-    per video) and "vis_files" (the PNG paths written)."""
+    per video) and "vis_files" (the PNG paths written).
+    `vis_route` (read with vis=True only): "padded" = `score_loader(similarity=True)`, whole chunks through an outputs="full" model;
+    "rows" = `score_loader(similarity="rows")`, the valid-row routes, any `outputs=`.  A vis evaluation is for plots, so with
+    `batch_chunks` unset "rows" packs 64 chunks in EVERY arithmetic (bf16x6 / fp16x3: the scores move inside the fp32 gates, as below)."""
     if metric_tail not in ("host", "device"):
         raise ValueError('metric_tail must be "host" or "device"')
+    if vis_route not in ("padded", "rows"):
+        raise ValueError(f'vis_route must be "padded" or "rows" (got {vis_route!r})')
+    vis_rows = bool(vis) and vis_route == "rows"
     model.to(device)
     model.eval()
     if batch_chunks is None:
@@ -1207,10 +1231,10 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
         # the caller asks (batch_chunks=64: scores move at the 1e-7 level, inside the fp32 gates).  Five times the per-video rate on a
         # UCF-sized list.
         packed_same_bits = (getattr(model, "compute", None) in ("f32", "bf16") and torch.device(device).type == "cuda" and lanes == 1)
-        batch_chunks = 64 if packed_same_bits else 0
+        batch_chunks = 64 if (packed_same_bits or vis_rows) else 0
     # vis=True: the same loop with the four similarity series collected on the device (`score_loader(similarity=True)`, a last result)
     got = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks, lanes=lanes,
-                       return_device=metric_tail == "device", similarity=bool(vis))
+                       return_device=metric_tail == "device", similarity="rows" if vis_rows else bool(vis))
     scores, classes, wi, we = got[:4]
     if metric_tail == "device":
         res = evaluate_scores_device((got[4], [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
@@ -1229,32 +1253,33 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
-         batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host"):
+         batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded"):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
     (ROC1, AP1, attn_weights, labels) when attn=True.  For `train/ucf_test.py` and `train/xd_test.py` -- whose
     positional orders differ from this one and from each other -- use `ucf_test` / `xd_test` below.
     `metric_tail="device"` (opt-in, here and in `ucf_test` / `xd_test`): the whole metric tail -- global, Ano-AUC and per-class --
-    through the library on the device-resident scores (`evaluate_scores_device`) instead of sklearn on the host."""
+    through the library on the device-resident scores (`evaluate_scores_device`) instead of sklearn on the host.
+    `vis_route="rows"` (opt-in, here and in `ucf_test` / `xd_test`): a vis=True evaluation on the valid-row routes (`_run_test`)."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
-                                      False, None, batch_chunks, lanes, metric_tail)
+                                      False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
-             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host"):
+             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded"):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
-                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test")
+                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
-            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host"):
+            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded"):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -1262,7 +1287,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
     if label_map is None:
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
-                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test")
+                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route)
     test.last_result = xd_test.last_result
     return ret
 

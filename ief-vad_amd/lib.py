@@ -33,7 +33,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_gcn_workspace_bytes", "iefvad_gat_forward", "iefvad_gat_workspace_bytes", "iefvad_resblock_forward",
            "iefvad_resblock_workspace_bytes", "iefvad_adamw_step_multi", "iefvad_resample_workspace_bytes", "iefvad_resample_videos",
            "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows", "iefvad_gemm_split_unit", "iefvad_gemm_split_wide_launches",
-           "iefvad_forward_videos_scaled", "iefvad_videos_scaled_workspace_bytes"]
+           "iefvad_forward_videos_scaled", "iefvad_videos_scaled_workspace_bytes", "iefvad_forward_videos_similarity",
+           "iefvad_forward_videos_host_similarity"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -166,6 +167,10 @@ def load_library() -> C.CDLL:
     lib.iefvad_forward_videos_host.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.iefvad_forward_videos_host.restype = C.c_int
+    lib.iefvad_forward_videos_similarity.argtypes = lib.iefvad_forward_videos.argtypes + [C.c_void_p]
+    lib.iefvad_forward_videos_similarity.restype = C.c_int
+    lib.iefvad_forward_videos_host_similarity.argtypes = lib.iefvad_forward_videos_host.argtypes + [C.c_void_p]
+    lib.iefvad_forward_videos_host_similarity.restype = C.c_int
     lib.iefvad_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.iefvad_loss_workspace_bytes.restype = C.c_size_t
     lib.iefvad_loss_forward.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,

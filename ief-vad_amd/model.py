@@ -453,14 +453,15 @@ class MMFMIL(nn.Module):
         return res
 
     def forward_videos_host(self, imgs, evs, lengths, nan_to_num: bool = True, batch_chunks: int = 128, host_threads: int = 0,
-                            wire_dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
+                            wire_dtype: Optional[torch.dtype] = None, similarity: bool = False) -> Dict[str, torch.Tensor]:
         """A whole list of videos in ONE library call (`iefvad_forward_videos_host`): `imgs[v]`, `evs[v]` are contiguous HOST tensors
         of one dtype whose first `lengths[v]` rows ([..., D]) are video v's features -- e.g. the padded tensors a DataLoader
         delivers (data/dataset.py:34-52).  The library packs whole videos into passes of >= `batch_chunks` chunks, stages and sends
         pass k + 1 while pass k computes, and returns DEVICE vectors `logits`, `w_i_mean`, `w_e_mean` of [sum(lengths)] in list
         order (stream-ordered on the current stream).  Same results as `forward_videos` on the same batches.
         `wire_dtype=torch.bfloat16` (fp32 features, compute="bf16" only): the gather threads round the rows to bf16 while staging, so
-        half the bytes cross PCIe; same results as `forward_videos` on `rows.to(torch.bfloat16)` (include/iefvad.h)."""
+        half the bytes cross PCIe; same results as `forward_videos` on `rows.to(torch.bfloat16)` (include/iefvad.h).
+        `similarity=True` (`iefvad_forward_videos_host_similarity`) adds "similarity" as `forward_videos` does."""
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos_host is an evaluation entry point; call model.eval() first")
         self._noise_code()
@@ -494,12 +495,16 @@ class MMFMIL(nn.Module):
             self._ensure_weights(device, stream)
             f32 = dict(dtype=torch.float32, device=device)
             res = {"logits": torch.empty(total, **f32), "w_i_mean": torch.empty(total, **f32), "w_e_mean": torch.empty(total, **f32)}
-            rc = lib.iefvad_forward_videos_host(self._handle, pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], larr, n, 1 if nan_to_num else 0, int(batch_chunks),
-                                                int(host_threads), C.c_void_p(res["logits"].data_ptr()),
-                                                C.c_void_p(res["w_i_mean"].data_ptr()), C.c_void_p(res["w_e_mean"].data_ptr()),
-                                                C.c_void_p(stream))
+            head = (self._handle, pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], larr, n, 1 if nan_to_num else 0, int(batch_chunks),
+                    int(host_threads), C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
+                    C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
+            if similarity:
+                res["similarity"] = torch.empty(4, total, **f32)
+                rc = lib.iefvad_forward_videos_host_similarity(*head, C.c_void_p(res["similarity"].data_ptr()))
+            else:
+                rc = lib.iefvad_forward_videos_host(*head)
         if rc != 0:
-            raise RuntimeError("iefvad_forward_videos_host: " + _lib.last_error())
+            raise RuntimeError(("iefvad_forward_videos_host_similarity: " if similarity else "iefvad_forward_videos_host: ") + _lib.last_error())
         return res
 
     # ------------------------------------------------------------------ train mode
@@ -532,7 +537,7 @@ class MMFMIL(nn.Module):
         return dict(zip(OUTPUT_KEYS, outs))
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
-                       weight_sums: bool = False) -> Dict[str, torch.Tensor]:
+                       weight_sums: bool = False, similarity: bool = False) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
@@ -541,7 +546,11 @@ class MMFMIL(nn.Module):
         `nan_to_num="always"` replaces in every video and modality (test2.py:59-60); `row_scale=(s_img, s_ev)`, contiguous fp32
         DEVICE vectors of sum(lengths) elements (either may be None), multiply the packed rows inside the library's input load,
         after the NaN rule (test2.py:70-77 on valid rows); `weight_sums=True` adds `w_colsum`, a [2, D] float64 device tensor: the
-        sums over all valid rows of w_i / w_e (test2.py:86-87), reduced on the device."""
+        sums over all valid rows of w_i / w_e (test2.py:86-87), reduced on the device.
+        `similarity=True` (`iefvad_forward_videos_similarity`) adds "similarity", a [4, sum(lengths)] fp32 device tensor: the series of
+        `harness.SIMILARITY_KEYS` (test.py:235-238) of every valid snippet, reduced inside the library from the pass's own fused / mu
+        rows -- whatever `outputs=` the model was built with; the other three results keep their bits.  The sweep's extras do not
+        combine with it (ValueError)."""
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos is an evaluation entry point; call model.eval() first")
         self._noise_code()
@@ -560,6 +569,9 @@ class MMFMIL(nn.Module):
                                    or sv.numel() != nrows or not sv.is_contiguous()):
                 raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {nrows} elements (sum of lengths) on {img_rows.device}")
         extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None
+        if similarity and extras:
+            raise ValueError("similarity=True does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
+                             "iefvad_forward_videos_scaled takes no similarity buffer")
         if not (img_rows.is_cuda and ev_rows.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         lens = [int(n) for n in lengths]
@@ -604,11 +616,14 @@ class MMFMIL(nn.Module):
                 if rc != 0:
                     raise RuntimeError("iefvad_forward_videos_scaled: " + _lib.last_error())
                 return res
-            rc = lib.iefvad_forward_videos(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()),
-                                           _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
-                                           C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(),
-                                           C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
-                                           C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
+            head = (self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
+                    C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), C.c_void_p(res["logits"].data_ptr()),
+                    C.c_void_p(res["w_i_mean"].data_ptr()), C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
+            if similarity:
+                res["similarity"] = torch.empty(4, total, **f32)
+                rc = lib.iefvad_forward_videos_similarity(*head, C.c_void_p(res["similarity"].data_ptr()))
+            else:
+                rc = lib.iefvad_forward_videos(*head)
             if rc != 0:
-                raise RuntimeError("iefvad_forward_videos: " + _lib.last_error())
+                raise RuntimeError(("iefvad_forward_videos_similarity: " if similarity else "iefvad_forward_videos: ") + _lib.last_error())
         return res

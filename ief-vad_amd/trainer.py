@@ -116,20 +116,25 @@ def _finish(path):
             torch.save(ck['model_state_dict'], path)
 
 
-def _check_vis_model(model, vis):
+def _check_vis_model(model, vis, vis_route="padded"):
     """The plots of a vis=True evaluation read `fused`, `image_mu` and `event_mu`: refuse a model that does not return them before
-    the first step, not at the fifth epoch."""
-    if vis and getattr(model, "outputs", "full") != "full":
+    the first step, not at the fifth epoch.  `vis_route="rows"` reduces the series inside the library (`harness.test`): any model."""
+    if vis_route not in ("padded", "rows"):
+        raise ValueError(f'vis_route must be "padded" or "rows" (got {vis_route!r})')
+    if vis and vis_route == "padded" and getattr(model, "outputs", "full") != "full":
         raise ValueError(f'vis=True needs a model built with outputs="full" (this one has outputs="{model.outputs}")')
 
 
 def train_paired(args, model, normal_loader, abnormal_loader, test_loader, label_map, device, gt: Optional[np.ndarray] = None,
-                 log: Optional[Callable[[dict], None]] = None, optimizer=None, eval_batch_chunks: int = 64, vis: bool = False):
+                 log: Optional[Callable[[dict], None]] = None, optimizer=None, eval_batch_chunks: int = 64, vis: bool = False,
+                 vis_route: str = "padded"):
     """Counterpart of /root/reference/train/ucf_train.py:train (same positional arguments; `gt` defaults to np.load(args.gt_path)).
     Each step concatenates a normal and an abnormal batch (:44-48), lambda_reg = lambda_kl = 1 (:100-101); the model is evaluated
     every `args.print_steps` samples and kept when its AUC improves.  Returns the best AUC.
-    `vis=True`: an evaluation draws the reference's plots on its schedule (:138: every fifth epoch, past `args.vis_steps` samples)."""
-    _check_vis_model(model, vis)
+    `vis=True`: an evaluation draws the reference's plots on its schedule (:138: every fifth epoch, past `args.vis_steps` samples);
+    `vis_route="rows"` is passed on to `harness.ucf_test` (the valid-row routes; the model need not return the full dict)."""
+    _check_vis_model(model, vis, vis_route)
+    route_kw = {} if vis_route == "padded" else {"vis_route": vis_route}
     model.to(device)
     if gt is None:
         gt = np.load(args.gt_path)
@@ -154,7 +159,7 @@ def train_paired(args, model, normal_loader, abnormal_loader, test_loader, label
                 rec = {f'train/loss_{k}' if k != 'total' else 'train/loss': float(v) for k, v in terms.items()}
                 auc, ap = harness.ucf_test(args, model, test_loader, args.visual_length, prompt_text, gt, device,   # ucf_train.py:130-139
                                            vis=bool(vis and (e + 1) % 5 == 0 and e > 0 and step > args.vis_steps),      # :138
-                                           batch_chunks=eval_batch_chunks)
+                                           batch_chunks=eval_batch_chunks, **route_kw)
                 rec.update(epoch=e, step=step, auc=auc, ap=ap)
                 if log:
                     log(rec)
@@ -167,11 +172,14 @@ def train_paired(args, model, normal_loader, abnormal_loader, test_loader, label
 
 
 def train_single(args, model, train_loader, test_loader, label_map, device, gt: Optional[np.ndarray] = None,
-                 log: Optional[Callable[[dict], None]] = None, optimizer=None, eval_batch_chunks: int = 64, vis: bool = False):
+                 log: Optional[Callable[[dict], None]] = None, optimizer=None, eval_batch_chunks: int = 64, vis: bool = False,
+                 vis_route: str = "padded"):
     """Counterpart of /root/reference/train/xd_train.py:train: one loader, lambda_reg = lambda_kl = 0.01 (:73-74), the Student-t
     shift of the KL terms whatever `args.noise_model` says (:67-70 apply it unconditionally), best checkpoint by AP (:114).
-    `vis=True`: an evaluation draws the reference's plots on its schedule (:111: every fifth epoch, past 33,000 samples)."""
-    _check_vis_model(model, vis)
+    `vis=True`: an evaluation draws the reference's plots on its schedule (:111: every fifth epoch, past 33,000 samples);
+    `vis_route="rows"` is passed on to `harness.xd_test`."""
+    _check_vis_model(model, vis, vis_route)
+    route_kw = {} if vis_route == "padded" else {"vis_route": vis_route}
     model.to(device)
     if gt is None:
         gt = np.load(args.gt_path)
@@ -191,7 +199,7 @@ def train_single(args, model, train_loader, test_loader, label_map, device, gt: 
                 rec = {f'train/loss_{k}' if k != 'total' else 'train/loss': float(v) for k, v in terms.items()}
                 auc, ap = harness.xd_test(args, model, test_loader, args.visual_length, prompt_text, gt, device, label_map,   # xd_train.py:102-112
                                           vis=bool(vis and (e + 1) % 5 == 0 and e > 0 and step > 33000),      # :111
-                                          batch_chunks=eval_batch_chunks)
+                                          batch_chunks=eval_batch_chunks, **route_kw)
                 rec.update(epoch=e, step=step, auc=auc, ap=ap)
                 if log:
                     log(rec)

@@ -237,6 +237,31 @@ int iefvad_forward_videos_host(iefvad_handle* h, const void* const* img_rows, co
                                int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
                                int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream);
 
+/* The two whole-video entries above with the four similarity series of the reference's plots (test.py:235-238; iefvad_similarity_rows
+ * below) of every valid snippet as a further result -- what a vis=True evaluation needs, without a D-wide tensor leaving the library
+ * and without computing the padding.  The arguments of iefvad_forward_videos / iefvad_forward_videos_host, then
+ *   similarity          DEVICE [4, sum(lengths)] fp32, series-major (cos_i, cos_e, dist_i, dist_e: the layout iefvad_similarity_rows
+ *                       writes with nout = sum(lengths)), 4-byte aligned, not NULL; column r is packed row r of the call (of the whole
+ *                       list for the host entry: every pass writes at its own row offset).  Valid once `stream` has run.
+ * A pass keeps fused (= z_K), image_mu and event_mu of its row set in its workspace -- the heads stage stores mu where a score-only
+ * pass would not, the last refinement step forms z_K where a score-only pass folds it into the scorer -- and one launch of
+ * iefvad_similarity_rowset_kernel (csrc/similarity.h) reduces the valid rows before the pass ends; pad rows and tile-rounding rows are
+ * not read.  The kernel shares its row arithmetic with iefvad_similarity_rows: in the f32, bf16 and fp16x3 arithmetics the series
+ * equal, bit for bit, those of iefvad_similarity_rows on the outputs of iefvad_forward on the host-padded chunks.  logits, w_i_mean
+ * and w_e_mean are the bits of the entry without `similarity`, in every arithmetic.  Workspace: iefvad_videos_workspace_bytes, no
+ * more.  Served: every arithmetic, D = 768 and 512, the three input dtypes, videos that straddle micro-batch passes,
+ * IEFVAD_DENSE_ENCODER=1.  A NULL or misaligned `similarity`, an unknown in_dtype and nvideos <= 0 are refused by name before the
+ * handle is looked at.  NOT covered: iefvad_forward_videos_scaled (row scales, w_colsum) takes no `similarity`.
+ * Added without a change to any other entry or struct: IEFVAD_ABI_VERSION stays. */
+int iefvad_forward_videos_similarity(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                     const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                     size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, void* stream,
+                                     float* similarity);
+int iefvad_forward_videos_host_similarity(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
+                                          int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num,
+                                          int32_t batch_chunks, int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean,
+                                          void* stream, float* similarity);
+
 /* ---- training-side loss head: forward, and its gradients w.r.t. the model's outputs -----------------
  * The three terms the reference's trainers add up (/root/reference/train/ucf_train.py:68-101, train/xd_train.py:60-75), as
  * device reductions over tensors iefvad_forward already produces:
