@@ -66,10 +66,12 @@ static void release_hostpipe(iefvad_handle* h) {
 
 // `similarity` (iefvad_forward_videos_host_similarity; null for the plain entry): [4, sum(lengths)] on the device -- every pass reduces
 // its own rows and writes at its row offset with the list's total as the stride (VideosExtras).
+// `wide` (iefvad_forward_videos_host_full; null otherwise): the caller's [sum(lengths), D] tensors -- every pass copies the valid rows of
+// what it kept to its row offset; with w_i / w_e each lane's workspace carries the weights' home behind the base size.
 static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
                                     int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
                                     int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream_, float* similarity,
-                                    const char* who) {
+                                    const char* who, const iefvad_outputs* wide = nullptr) {
     if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("%s: null argument", who);
     if (!h->weights_set) return fail("%s: weights not set", who);
     if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
@@ -172,7 +174,7 @@ static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_row
             }
         p.slot_bytes = cap;
     }
-    const size_t need_ws = iefvad_workspace_bytes(h, (int32_t)max_chunks);
+    const size_t need_ws = iefvad_workspace_bytes(h, (int32_t)max_chunks) + (wide_has_w(wide) ? wide_extra_bytes(h, max_chunks) : 0);
     if (p.workspace_bytes < need_ws) {
         HIP_TRY(hipDeviceSynchronize());                   // a forward of an earlier call may still use the old workspaces
         p.workspace_bytes = 0;
@@ -292,9 +294,10 @@ static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_row
         VideosExtras ex;
         memset(&ex, 0, sizeof(ex));
         ex.similarity = similarity; ex.sim_stride = total_rows; ex.sim_row0 = row0;
+        ex.wide = wide; ex.wide_row0 = row0;
         rc = forward_videos_impl(h, p.dev_in[s][0], p.dev_in[s][1], wire_dtype, lengths + b.v0, b.v1 - b.v0, nan_to_num,
                                  p.workspace[ln], p.workspace_bytes, logits + row0, w_i_mean ? w_i_mean + row0 : nullptr,
-                                 w_e_mean ? w_e_mean + row0 : nullptr, cs, tm, similarity ? &ex : nullptr, who);
+                                 w_e_mean ? w_e_mean + row0 : nullptr, cs, tm, (similarity || wide) ? &ex : nullptr, who);
         if (rc == 0) he = hipEventRecord(p.used[s], cs);
         if (trace)
             fprintf(stderr, "[hostpipe] pass %d: %lld chunks %lld rows | waited for staging %.0f us | enqueue copies + forward %.0f us | t = %.0f us\n", k,
@@ -337,4 +340,13 @@ extern "C" int iefvad_forward_videos_host_similarity(iefvad_handle* h, const voi
     if (int rc = similarity_args(who, similarity, in_dtype, nvideos)) return rc;
     return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads, logits,
                                     w_i_mean, w_e_mean, stream_, similarity, who);
+}
+
+extern "C" int iefvad_forward_videos_host_full(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
+                                               int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num,
+                                               int32_t batch_chunks, int32_t host_threads, const iefvad_outputs* out, void* stream_) {
+    static const char* const who = "iefvad_forward_videos_host_full";
+    if (int rc = full_args(who, h, out, in_dtype, nvideos)) return rc;
+    return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads,
+                                    out->logits, out->w_i_mean, out->w_e_mean, stream_, nullptr, who, out);
 }

@@ -926,7 +926,12 @@ struct RaggedPass {
     // is column sim_row0 + r.  With it the tail keeps fused (= z_K) and both mu of its row set (pass_tail).
     float* similarity;
     long long sim_stride, sim_row0;
+    // iefvad_forward_videos_full / _host_full (all null otherwise): the caller's packed [rows, D] tensors at the pass's first packed row,
+    // in the order of kWideFused .. kWideWe.  The tail keeps the asked-for tensors of its row set (mu / lv / z in the workspace aliases of
+    // pass_buffers, the weights in w_rows) and iefvad_rows_out_wide_kernel copies the valid rows out (pass_tail).
+    float* wide[ROWS_OUT_WIDE_MAX];
 };
+enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 
 // The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it
 // (PassFlags from pass_buffers on, TailFlags from pass_compact_rows on: launch_rules.h).
@@ -996,7 +1001,7 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
         b.logits = b.lg_scratch;
         b.wim_out = rg->w_i_mean ? b.lg_scratch + R : nullptr;
         b.wem_out = rg->w_e_mean ? b.lg_scratch + 2 * R : nullptr;
-        b.n_i = rg->w_rows[0];                    // only with w_colsum: the fusion stage stores its weights for the column sums
+        b.n_i = rg->w_rows[0];                    // only with w_colsum or a wide w_i / w_e: the fusion stage stores its weights there
         b.n_e = rg->w_rows[1];
     }
     static_cast<PassFlags&>(b) = plan_pass(h->policy, c.compute, b.rows);
@@ -1207,14 +1212,18 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     // keep fused / mu: the caller asked for the tensor, or the pass reduces it to the similarity series before it ends (then it stays
     // in the workspace alias of pass_buffers).  Kernel selection does not look at these.
     const bool sim = rg && rg->similarity;
-    const bool keep_fused = out->fused || sim, keep_mu_i = out->image_mu || sim, keep_mu_e = out->event_mu || sim;
+    float* const none7[ROWS_OUT_WIDE_MAX] = {};
+    float* const* const wide = rg ? rg->wide : none7;      // the full entries: what the pass copies out of its row set at its end
+    const bool keep_fused = out->fused || sim || wide[kWideFused];
+    const bool keep_mu_i = out->image_mu || sim || wide[kWideMuI], keep_mu_e = out->event_mu || sim || wide[kWideMuE];
+    const bool keep_lv_i = out->image_logvar || wide[kWideLvI], keep_lv_e = out->event_logvar || wide[kWideLvE];
     // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
     if (b.heads_rows) {
         HeadsChainArgs ha;
         memset(&ha, 0, sizeof(ha));
         for (int m = 0; m < 2; ++m) ha.A[m] = b.xtb[m];
-        ha.mu[0] = keep_mu_i ? b.mu_i : nullptr; ha.lv[0] = out->image_logvar ? b.lv_i : nullptr;
-        ha.mu[1] = keep_mu_e ? b.mu_e : nullptr; ha.lv[1] = out->event_logvar ? b.lv_e : nullptr;
+        ha.mu[0] = keep_mu_i ? b.mu_i : nullptr; ha.lv[0] = keep_lv_i ? b.lv_i : nullptr;
+        ha.mu[1] = keep_mu_e ? b.mu_e : nullptr; ha.lv[1] = keep_lv_e ? b.lv_e : nullptr;
         ha.n[0] = b.n_i; ha.n[1] = b.n_e;
         ha.z = z;
         ha.zb = chain ? nullptr : b.zb;
@@ -1324,6 +1333,26 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             });
             tm.end(e);
             HIP_TRY(hipGetLastError());
+        }
+        {
+            // the full entries: the valid rows of the kept tensors -> the caller's packed tensors, at the pass's own row offset
+            RowsOutWideArgs wa;
+            memset(&wa, 0, sizeof(wa));
+            const float* const home[ROWS_OUT_WIDE_MAX] = {z, b.mu_i, b.mu_e, b.lv_i, b.lv_e, b.n_i, b.n_e};
+            int nt = 0;
+            for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
+                if (wide[t]) { wa.src[nt] = home[t]; wa.dst[nt] = wide[t]; ++nt; }
+            if (nt) {
+                wa.chunks = b.compacted ? nullptr : rg->d_chunks;
+                wa.valid_rows = rg->valid_rows;
+                const int nslabs = b.compacted ? (rg->valid_rows + 255) / 256 : b.nb;
+                e = tm.begin(ST_SCORER);
+                dispatch_d(d512, [&](auto w) {
+                    hipLaunchKernelGGL(iefvad_rows_out_wide_kernel<decltype(w)::value>, dim3(nslabs, nt, IEF_RAGGED_SLICES), dim3(256), 0, stream, wa);
+                });
+                tm.end(e);
+                HIP_TRY(hipGetLastError());
+            }
         }
         if (rg->w_colsum) {
             // column sums of the stored weights over the valid rows: the chunk table on the row-compressed / whole-chunk set, 256-row
@@ -1439,7 +1468,19 @@ struct VideosExtras {
     // call's packed row r is column sim_row0 + r (the host-list entry: the row offset of the pass within the whole list)
     float* similarity;
     long long sim_stride, sim_row0;
+    // iefvad_forward_videos_full / _host_full (null otherwise): the caller's outputs; the call's packed row r is row wide_row0 + r of
+    // the seven [rows, D] tensors (the host-list entry: the row offset of the pass within the whole list)
+    const iefvad_outputs* wide;
+    long long wide_row0;
 };
+// The full entries' w_i / w_e: the fusion stage stores the weights of the pass's row set, and they need the home the column sums'
+// weights have -- [2, R, D] floats behind the base workspace (nothing behind them: w_colsum does not combine with the full entries).
+static bool wide_has_w(const iefvad_outputs* o) { return o && (o->w_i || o->w_e); }
+static size_t wide_extra_bytes(const iefvad_handle* h, long long chunks) {
+    const int mb = micro_batch(h);
+    const size_t nb = (size_t)(chunks < mb ? chunks : mb);
+    return 2 * nb * IEF_T * (size_t)h->D * sizeof(float);
+}
 static size_t colsum_extra_bytes(const iefvad_handle* h, long long chunks) {
     const int mb = micro_batch(h);
     const size_t nb = (size_t)(chunks < mb ? chunks : mb);
@@ -1463,7 +1504,7 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
     if (!h->weights_set) return fail("%s: weights not set", who);
     if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
     if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
-    const bool sweep = ex && !ex->similarity;      // the scaled entry's nan_to_num codes; the similarity entries keep the plain ones
+    const bool sweep = ex && !ex->similarity && !ex->wide;      // the scaled entry's nan_to_num codes; the similarity entries keep the plain ones
     if (nan_to_num < 0 || nan_to_num > (sweep ? 2 : 1)) {
         if (sweep) return fail("%s: unknown nan_to_num %d (0: off, 1: per video with a NaN, 2: always)", who, nan_to_num);
         nan_to_num = 1;       // iefvad_forward_videos: any non-zero value is the per-video rule
@@ -1476,7 +1517,8 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
     if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
     const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
     const bool colsum = ex && ex->w_colsum;
-    const size_t need = base + (colsum ? colsum_extra_bytes(h, total_chunks) : 0);
+    const bool wide_w = ex && wide_has_w(ex->wide);
+    const size_t need = base + (colsum ? colsum_extra_bytes(h, total_chunks) : 0) + (wide_w ? wide_extra_bytes(h, total_chunks) : 0);
     if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     if (((uintptr_t)workspace & 15) || ((uintptr_t)img_rows & 15) || ((uintptr_t)ev_rows & 15)) return fail("%s: buffers must be 16-byte aligned", who);
     const bool nan_all = nan_to_num == 2;
@@ -1588,6 +1630,18 @@ static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const voi
         rg.similarity = ex ? ex->similarity : nullptr;
         rg.sim_stride = ex ? ex->sim_stride : 0;
         rg.sim_row0 = ex ? ex->sim_row0 + row0 : 0;
+        for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t) rg.wide[t] = nullptr;
+        if (ex && ex->wide) {
+            const iefvad_outputs& o = *ex->wide;
+            float* const dst[ROWS_OUT_WIDE_MAX] = {o.fused, o.image_mu, o.event_mu, o.image_logvar, o.event_logvar, o.w_i, o.w_e};
+            for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
+                if (dst[t]) rg.wide[t] = dst[t] + (size_t)(ex->wide_row0 + row0) * h->D;
+        }
+        if (wide_w) {
+            const size_t per = (size_t)(total_chunks < mb ? total_chunks : mb) * IEF_T * h->D;
+            rg.w_rows[0] = (float*)((char*)workspace + base);
+            rg.w_rows[1] = rg.w_rows[0] + per;
+        }
         if (colsum) {
             const size_t per = (size_t)(total_chunks < mb ? total_chunks : mb) * IEF_T * h->D;
             rg.w_colsum = ex->w_colsum;
@@ -1647,6 +1701,40 @@ extern "C" int iefvad_forward_videos_similarity(iefvad_handle* h, const void* im
     ex.similarity = similarity; ex.sim_stride = rows; ex.sim_row0 = 0;
     return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
                                w_e_mean, (hipStream_t)stream, tm, &ex, who);
+}
+
+// The checks the two full entries make before they look at the handle's contents: each names the entry, none makes a HIP call.
+static int full_args(const char* who, const iefvad_handle* h, const iefvad_outputs* out, int32_t in_dtype, int32_t nvideos) {
+    if (!h) return fail("%s: null handle", who);
+    if (!out) return fail("%s: null out", who);
+    if (!out->logits) return fail("%s: null logits (out->logits is required)", who);
+    float* const wide[ROWS_OUT_WIDE_MAX] = {out->fused, out->image_mu, out->event_mu, out->image_logvar, out->event_logvar, out->w_i, out->w_e};
+    for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
+        if ((uintptr_t)wide[t] & 15) return fail("%s: the [rows, D] outputs must be 16-byte aligned", who);
+    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    return 0;
+}
+
+extern "C" size_t iefvad_videos_full_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, const iefvad_outputs* out) {
+    const size_t base = iefvad_videos_workspace_bytes(h, lengths, nvideos);
+    if (!base || !wide_has_w(out)) return base;
+    long long rows, chunks;
+    if (videos_layout(lengths, nvideos, &rows, &chunks)) return 0;
+    return base + wide_extra_bytes(h, chunks);
+}
+
+extern "C" int iefvad_forward_videos_full(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
+                                          int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes,
+                                          const iefvad_outputs* out, void* stream) {
+    static const char* const who = "iefvad_forward_videos_full";
+    if (int rc = full_args(who, h, out, in_dtype, nvideos)) return rc;
+    Timer tm;
+    VideosExtras ex;
+    memset(&ex, 0, sizeof(ex));
+    ex.wide = out; ex.wide_row0 = 0;
+    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, out->logits,
+                               out->w_i_mean, out->w_e_mean, (hipStream_t)stream, tm, &ex, who);
 }
 
 

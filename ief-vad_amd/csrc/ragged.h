@@ -22,6 +22,8 @@
 // The robustness sweep (/root/reference/test2.py:35-123) runs on the same route through iefvad_forward_videos_scaled: the chunker's
 // scaled instantiation applies the unconditional nan_to_num (test2.py:59-60) and a per-row scale (test2.py:70-77), and
 // iefvad_colsum_rows_kernel / iefvad_colsum_finish_kernel reduce w_i / w_e over the valid rows to 768 sums per modality (test2.py:102-103).
+// The reference's whole return dict (imf_vad.py:152-161) leaves the same route through iefvad_forward_videos_full / _host_full: the pass keeps
+// the asked-for [rows, D] tensors of its row set and iefvad_rows_out_wide_kernel copies the valid rows to the caller's packed tensors.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_bf16.h>
@@ -173,6 +175,54 @@ __global__ __launch_bounds__(256) void iefvad_rows_out_kernel(const float* s0, c
         if (d0) d0[d] = s0[s];
         if (d1) d1[d] = s1[s];
         if (d2) d2[d] = s2[s];
+    }
+}
+
+// The D-wide counterpart (iefvad_forward_videos_full / _host_full): the valid rows of up to seven [rows, D] tensors of a pass's row set
+// (z = fused, mu_i, mu_e, lv_i, lv_e, n_i, n_e where the tail left them) -> the caller's packed tensors, the row map of the kernel
+// above: row-set row enc_row + r of chunk c -> packed row src_row + r of the pass (dst points at the pass's first packed row), r <
+// valid; chunks == nullptr: the compacted set, identity over the first valid_rows rows in 256-row slabs.  The host lists only the
+// tensors the caller asked for: gridDim.z workgroups per (chunk or slab, listed tensor), 16-row groups dealt round-robin as in the
+// chunker (a 40-row chunk on one workgroup is three dependent trips of pure latency), one wavefront per row, 16 bytes per lane and
+// 256-column group, four rows of the wave in flight.  Pad rows and tile-rounding rows are never read; no LDS, no atomics.
+#define ROWS_OUT_WIDE_MAX 7
+struct RowsOutWideArgs {
+    const float* src[ROWS_OUT_WIDE_MAX];
+    float* dst[ROWS_OUT_WIDE_MAX];
+    const RaggedChunk* chunks;
+    int valid_rows;
+};
+template <int D>
+__global__ __launch_bounds__(256) void iefvad_rows_out_wide_kernel(RowsOutWideArgs a) {
+    constexpr int NJ = D / 256;
+    int first_s, first_d, nr;
+    if (a.chunks) {
+        const RaggedChunk c = a.chunks[blockIdx.x];
+        first_s = c.enc_row; first_d = c.src_row; nr = c.valid;
+    } else {
+        first_s = first_d = blockIdx.x * 256;
+        nr = a.valid_rows - first_s < 256 ? a.valid_rows - first_s : 256;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* src = a.src[blockIdx.y] + (size_t)first_s * D + 4 * lane;
+    float* dst = a.dst[blockIdx.y] + (size_t)first_d * D + 4 * lane;
+    for (int r0 = wave + 16 * blockIdx.z; r0 < nr; r0 += 16 * gridDim.z) {
+        f32x4 v[4][NJ];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = r0 + 4 * u;
+            if (r < nr) {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) v[u][j] = *(const f32x4*)(src + (size_t)r * D + 256 * j);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = r0 + 4 * u;
+            if (r >= nr) break;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) *(f32x4*)(dst + (size_t)r * D + 256 * j) = v[u][j];
+        }
     }
 }
 

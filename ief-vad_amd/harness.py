@@ -623,13 +623,18 @@ class _ScoreSink:
         self.spans: List[Tuple[int, int]] = []     # (offset into the concatenated device vectors, valid length) per video
         self.total = 0
         self.dev_sim: Optional[List[torch.Tensor]] = None     # score_loader(similarity=True): per forward [4, valid snippets of its videos]
+        self.dev_rows: Optional[Dict[str, List[torch.Tensor]]] = None   # score_loader(row_outputs=...): per key, per forward [valid snippets, D]
 
-    def add(self, logits, wi, we, lens, stride=None, sim=None):
+    def add(self, logits, wi, we, lens, stride=None, sim=None, rows=None):
         """One forward's flat fp32 vectors over videos of `lens` snippets: back to back (the valid-row routes), or video i in
         stride[i] slots of which the first lens[i] count (the padded route: its chunks * maxlen).  `sim`: the forward's
-        `similarity_rows` over the valid snippets of its videos, back to back."""
+        `similarity_rows` over the valid snippets of its videos, back to back.  `rows`: the forward's dict, from which the
+        [valid snippets, D] tensors of `dev_rows` are kept (on the device, as they are)."""
         if sim is not None:
             self.dev_sim.append(sim)
+        if self.dev_rows is not None and rows is not None:
+            for k, v in self.dev_rows.items():
+                v.append(rows[k])
         self.dev_prob.append(logits)
         self.dev_wi.append(wi)
         self.dev_we.append(we)
@@ -732,11 +737,12 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
                '(outputs="scores" / "weights" do not return them)')
 
 
-def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False):
+def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=()):
     """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
     while this thread sends batch k and enqueues its forward; batches complete in order.
-    `similarity`: every forward also returns its [4, n] block of series (`forward_videos(similarity=True)`) for the sink."""
+    `similarity`: every forward also returns its [4, n] block of series (`forward_videos(similarity=True)`) for the sink.
+    `row_outputs`: every forward also returns those [n, D] tensors (`forward_videos(outputs=...)`); the sink keeps them on the device."""
     def stage(pend, k):
         dt, widened = _batch_dtype(pend)
         if widened:               # a narrower video is widened at staging: its own dtype's inf -> max rule applies first (test.py:90-95)
@@ -750,9 +756,9 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
         with _lane_stream(streams[k]):
             img, ev = stagers[k].send(staged)
             out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
-        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'))
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out)
 
-    sim_kw = dict(similarity=True) if similarity else {}
+    sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else {}
 
     stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
@@ -776,7 +782,8 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
         stage_pool.shutdown(wait=True)              # also when a forward raised: the worker thread must not outlive the call
 
 
-def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, similarity=False):
+def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, similarity=False,
+                     row_outputs=()):
     """Valid-row route with the walk inside the library (`MMFMIL.forward_videos_host`, csrc/hostpipe.h): this thread only collects
     each video's host tensor and length; one library call per `host_list_bytes` of features stages, sends and scores them pass by
     pass.  Same batches, same kernels as `_score_rows_loop` (which remains for models without the entry, lanes > 1 callers that
@@ -786,9 +793,9 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
         lens = [g[2] for g in group]
         out = model.forward_videos_host([g[0] for g in group], [g[1] for g in group], lens, nan_to_num=True,
                                         batch_chunks=batch_chunks, wire_dtype=wire, **sim_kw)
-        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'))
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out)
 
-    sim_kw = dict(similarity=True) if similarity else {}
+    sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else {}
 
     group, gbytes = [], 0
     for item in loader:
@@ -815,7 +822,7 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
-                 return_device: bool = False, similarity=False):
+                 return_device: bool = False, similarity=False, row_outputs=None):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -845,15 +852,31 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
 
     `similarity`: a last result, {"cos_i", "cos_e", "dist_i", "dist_e"} -> per-video arrays: cosine similarity and Euclidean distance of
     every snippet's `fused` row to its `image_mu` / `event_mu` rows (`similarity_rows`; the series of test.py:235-238).  The padded route
-    is taken with the caller's `batch_chunks` -- the valid-row entries return no 768-wide tensors; in f32 and bf16 both routes give the
-    same bits, so the scores do not move -- and the model must return the full dict (`outputs="full"`).  The series stay on the device
+    is taken with the caller's `batch_chunks` -- in f32 and bf16 both routes give the same bits, so the scores do not move (the valid-row
+    routes: `similarity="rows"` and `row_outputs` below) -- and the model must return the full dict (`outputs="full"`).  The series stay on the device
     and come back with the scores' one copy.
     `similarity="rows"` (opt-in): the same last result from the valid-row routes -- the host-list walk, or the `forward_videos` loop
     (`host_list=False`, `lanes > 1` included): every library call reduces the series of its valid rows from the pass's own fused / mu
     rows (`MMFMIL.forward_videos(similarity=True)`, csrc/similarity.h), no padding is computed and the model may be built with any
     `outputs=`.  Needs a HIP device, a model with `forward_videos` and batch_chunks > 0 (ValueError otherwise).  In f32 and bf16 the
-    series are the bits of `similarity=True`."""
+    series are the bits of `similarity=True`.
+
+    `row_outputs` ("full", or names from `iefvad_amd.OUTPUT_KEYS`; opt-in): the valid-row routes -- the host-list walk, or the
+    `forward_videos` loop -- with `outputs=row_outputs` on every library call (`iefvad_forward_videos_full` / `_host_full`): the
+    [rows, D] tensors of the reference's dict for the VALID snippets only, whatever `outputs=` the model was built with.  The returned
+    tuple does not change; `score_loader.last_result` becomes {"row_outputs": {name: ONE [N, D] fp32 device tensor, the videos in
+    list order}, "row_offsets": int64 array of len(videos) + 1 offsets into N}.  Nothing D-wide is copied to the host here.  Needs what
+    `similarity="rows"` needs; it does not combine with `similarity` (ValueError)."""
     on_gpu = torch.device(device).type == 'cuda'
+    from .model import _row_output_keys
+    row_keys = _row_output_keys(row_outputs)
+    if row_outputs is not None:
+        if similarity:
+            raise ValueError('row_outputs does not combine with similarity: reduce the returned rows with similarity_rows')
+        if not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos')) or ragged is False:
+            raise ValueError('row_outputs takes the valid-row routes: it needs a HIP device, batch_chunks > 0 and a model with '
+                             'forward_videos (and not ragged=False)')
+        ragged = True
     sim_rows = isinstance(similarity, str)
     if sim_rows:
         if similarity != "rows":
@@ -887,18 +910,28 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     sink = _ScoreSink()
     if similarity:
         sink.dev_sim = []
+    if row_outputs is not None:
+        sink.dev_rows = {k: [] for k in row_keys}
     with torch.no_grad():
         for s in streams if nl > 1 else ():
             s.wait_stream(torch.cuda.current_stream(device))         # e.g. a `model.to(device)` still in flight
         if use_list:
-            _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, sim_rows)
+            _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, sim_rows,
+                             row_keys)
         elif ragged:
-            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows)
+            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys)
         else:
             _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
                           bool(similarity))
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
+        if sink.dev_rows is not None:
+            D = getattr(getattr(model, 'temporal', None), 'embed_dim', 0)
+            score_loader.last_result = {
+                # one library call (the host-list walk's usual case): its tensors as they are, no second copy
+                "row_outputs": {k: v[0] if len(v) == 1 else torch.cat(v) if v else torch.zeros(0, D, device=device)
+                                for k, v in sink.dev_rows.items()},
+                "row_offsets": np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)}
         return sink.finish(device, return_device)
 
 

@@ -34,7 +34,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_resblock_workspace_bytes", "iefvad_adamw_step_multi", "iefvad_resample_workspace_bytes", "iefvad_resample_videos",
            "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows", "iefvad_gemm_split_unit", "iefvad_gemm_split_wide_launches",
            "iefvad_forward_videos_scaled", "iefvad_videos_scaled_workspace_bytes", "iefvad_forward_videos_similarity",
-           "iefvad_forward_videos_host_similarity"]
+           "iefvad_forward_videos_host_similarity", "iefvad_videos_full_workspace_bytes", "iefvad_forward_videos_full",
+           "iefvad_forward_videos_host_full"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -171,6 +172,13 @@ def load_library() -> C.CDLL:
     lib.iefvad_forward_videos_similarity.restype = C.c_int
     lib.iefvad_forward_videos_host_similarity.argtypes = lib.iefvad_forward_videos_host.argtypes + [C.c_void_p]
     lib.iefvad_forward_videos_host_similarity.restype = C.c_int
+    # the full entries: the three result pointers replaced by one `const iefvad_outputs*` (POINTER(Outputs))
+    lib.iefvad_videos_full_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Outputs)]
+    lib.iefvad_videos_full_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_videos_full.argtypes = lib.iefvad_forward_videos.argtypes[:9] + [C.POINTER(Outputs), C.c_void_p]
+    lib.iefvad_forward_videos_full.restype = C.c_int
+    lib.iefvad_forward_videos_host_full.argtypes = lib.iefvad_forward_videos_host.argtypes[:10] + [C.POINTER(Outputs), C.c_void_p]
+    lib.iefvad_forward_videos_host_full.restype = C.c_int
     lib.iefvad_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.iefvad_loss_workspace_bytes.restype = C.c_size_t
     lib.iefvad_loss_forward.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,

@@ -29,6 +29,21 @@ from . import lib as _lib
 
 _IN_DTYPES = {torch.float32: _lib.IN_F32, torch.float16: _lib.IN_F16, torch.bfloat16: _lib.IN_BF16}
 OUTPUT_KEYS = ("fused", "logits", "image_mu", "event_mu", "image_logvar", "event_logvar", "w_i", "w_e")
+WIDE_KEYS = tuple(k for k in OUTPUT_KEYS if k != "logits")      # the seven [rows, D] tensors
+
+
+def _row_output_keys(outputs) -> tuple:
+    """`outputs=` of the valid-row calls -> the [rows, D] keys asked for, in OUTPUT_KEYS order: None -> none, "full" -> all seven, else a
+    key or an iterable of keys from OUTPUT_KEYS ("logits" is returned anyway)."""
+    if outputs is None:
+        return ()
+    if outputs == "full":
+        return WIDE_KEYS
+    names = [outputs] if isinstance(outputs, str) else list(outputs)
+    bad = [k for k in names if k not in OUTPUT_KEYS]
+    if bad:
+        raise ValueError(f'unknown output key(s) {bad}: outputs= takes "full" or names from OUTPUT_KEYS {OUTPUT_KEYS}')
+    return tuple(k for k in WIDE_KEYS if k in names)
 
 
 class _LinearParams(nn.Module):
@@ -453,7 +468,7 @@ class MMFMIL(nn.Module):
         return res
 
     def forward_videos_host(self, imgs, evs, lengths, nan_to_num: bool = True, batch_chunks: int = 128, host_threads: int = 0,
-                            wire_dtype: Optional[torch.dtype] = None, similarity: bool = False) -> Dict[str, torch.Tensor]:
+                            wire_dtype: Optional[torch.dtype] = None, similarity: bool = False, *, outputs=None) -> Dict[str, torch.Tensor]:
         """A whole list of videos in ONE library call (`iefvad_forward_videos_host`): `imgs[v]`, `evs[v]` are contiguous HOST tensors
         of one dtype whose first `lengths[v]` rows ([..., D]) are video v's features -- e.g. the padded tensors a DataLoader
         delivers (data/dataset.py:34-52).  The library packs whole videos into passes of >= `batch_chunks` chunks, stages and sends
@@ -461,10 +476,16 @@ class MMFMIL(nn.Module):
         order (stream-ordered on the current stream).  Same results as `forward_videos` on the same batches.
         `wire_dtype=torch.bfloat16` (fp32 features, compute="bf16" only): the gather threads round the rows to bf16 while staging, so
         half the bytes cross PCIe; same results as `forward_videos` on `rows.to(torch.bfloat16)` (include/iefvad.h).
-        `similarity=True` (`iefvad_forward_videos_host_similarity`) adds "similarity" as `forward_videos` does."""
+        `similarity=True` (`iefvad_forward_videos_host_similarity`) adds "similarity" as `forward_videos` does.
+        `outputs="full"` or an iterable of OUTPUT_KEYS names (`iefvad_forward_videos_host_full`) adds those keys as [sum(lengths), D]
+        fp32 device tensors in list order, as `forward_videos` does; it does not combine with `similarity=True` (ValueError)."""
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos_host is an evaluation entry point; call model.eval() first")
         self._noise_code()
+        wide = _row_output_keys(outputs)
+        if wide and similarity:
+            raise ValueError("outputs= does not combine with similarity=True: iefvad_forward_videos_host_full takes no similarity buffer "
+                             "(reduce the returned rows with harness.similarity_rows)")
         lens = [int(n) for n in lengths]
         if not lens or min(lens) < 1 or len(imgs) != len(lens) or len(evs) != len(lens):
             raise ValueError("imgs, evs and lengths must list the same videos, every video at least one snippet")
@@ -498,14 +519,28 @@ class MMFMIL(nn.Module):
             head = (self._handle, pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], larr, n, 1 if nan_to_num else 0, int(batch_chunks),
                     int(host_threads), C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
                     C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
-            if similarity:
+            if wide:
+                rc = lib.iefvad_forward_videos_host_full(*head[:10], C.byref(self._rows_outputs(res, wide, total, D, f32)), head[13])
+            elif similarity:
                 res["similarity"] = torch.empty(4, total, **f32)
                 rc = lib.iefvad_forward_videos_host_similarity(*head, C.c_void_p(res["similarity"].data_ptr()))
             else:
                 rc = lib.iefvad_forward_videos_host(*head)
         if rc != 0:
-            raise RuntimeError(("iefvad_forward_videos_host_similarity: " if similarity else "iefvad_forward_videos_host: ") + _lib.last_error())
+            who = "iefvad_forward_videos_host_full: " if wide else "iefvad_forward_videos_host_similarity: " if similarity else "iefvad_forward_videos_host: "
+            raise RuntimeError(who + _lib.last_error())
         return res
+
+    @staticmethod
+    def _rows_outputs(res, wide, total, D, f32):
+        """The `iefvad_outputs` of a full valid-row call: the three vectors already in `res`, plus a new [total, D] tensor per key of
+        `wide`, added to `res`."""
+        o = _lib.Outputs()
+        o.logits, o.w_i_mean, o.w_e_mean = res["logits"].data_ptr(), res["w_i_mean"].data_ptr(), res["w_e_mean"].data_ptr()
+        for k in wide:
+            res[k] = torch.empty(total, D, **f32)
+            setattr(o, k, res[k].data_ptr())
+        return o
 
     # ------------------------------------------------------------------ train mode
     def _forward_train(self, img_visual, ev_visual) -> Dict[str, torch.Tensor]:
@@ -537,7 +572,7 @@ class MMFMIL(nn.Module):
         return dict(zip(OUTPUT_KEYS, outs))
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
-                       weight_sums: bool = False, similarity: bool = False) -> Dict[str, torch.Tensor]:
+                       weight_sums: bool = False, similarity: bool = False, outputs=None) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
@@ -550,7 +585,11 @@ class MMFMIL(nn.Module):
         `similarity=True` (`iefvad_forward_videos_similarity`) adds "similarity", a [4, sum(lengths)] fp32 device tensor: the series of
         `harness.SIMILARITY_KEYS` (test.py:235-238) of every valid snippet, reduced inside the library from the pass's own fused / mu
         rows -- whatever `outputs=` the model was built with; the other three results keep their bits.  The sweep's extras do not
-        combine with it (ValueError)."""
+        combine with it (ValueError).
+        `outputs="full"`, or an iterable of names from OUTPUT_KEYS (`iefvad_forward_videos_full`), adds those keys of the reference's
+        dict (imf_vad.py:152-161) as [sum(lengths), D] fp32 device tensors in packed order: the pass keeps them for its row set and
+        copies the valid rows out -- whatever `outputs=` the model was built with; no padding is computed or written, and the other
+        three results keep their bits.  An unknown key, `similarity=True` and the sweep's extras are each refused (ValueError)."""
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos is an evaluation entry point; call model.eval() first")
         self._noise_code()
@@ -572,6 +611,13 @@ class MMFMIL(nn.Module):
         if similarity and extras:
             raise ValueError("similarity=True does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
                              "iefvad_forward_videos_scaled takes no similarity buffer")
+        wide = _row_output_keys(outputs)
+        if wide and similarity:
+            raise ValueError("outputs= does not combine with similarity=True: iefvad_forward_videos_full takes no similarity buffer "
+                             "(reduce the returned rows with harness.similarity_rows)")
+        if wide and extras:
+            raise ValueError("outputs= does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
+                             "iefvad_forward_videos_scaled returns no [rows, D] tensor")
         if not (img_rows.is_cuda and ev_rows.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         lens = [int(n) for n in lengths]
@@ -593,15 +639,18 @@ class MMFMIL(nn.Module):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._ensure_handle(device)
             self._ensure_weights(device, stream)
+            f32 = dict(dtype=torch.float32, device=device)
+            res = {"logits": torch.empty(total, **f32), "w_i_mean": torch.empty(total, **f32), "w_e_mean": torch.empty(total, **f32)}
+            o = self._rows_outputs(res, wide, total, D, f32) if wide else None
             if extras:
                 need = lib.iefvad_videos_scaled_workspace_bytes(self._handle, larr, len(lens), 1 if weight_sums else 0)
+            elif wide:
+                need = lib.iefvad_videos_full_workspace_bytes(self._handle, larr, len(lens), C.byref(o))
             else:
                 need = lib.iefvad_videos_workspace_bytes(self._handle, larr, len(lens))
             if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
                 self._workspace = None
                 self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            f32 = dict(dtype=torch.float32, device=device)
-            res = {"logits": torch.empty(total, **f32), "w_i_mean": torch.empty(total, **f32), "w_e_mean": torch.empty(total, **f32)}
             if extras:
                 if weight_sums:
                     res["w_colsum"] = torch.empty(2, D, dtype=torch.float64, device=device)
@@ -619,11 +668,14 @@ class MMFMIL(nn.Module):
             head = (self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
                     C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), C.c_void_p(res["logits"].data_ptr()),
                     C.c_void_p(res["w_i_mean"].data_ptr()), C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
-            if similarity:
+            if wide:
+                rc = lib.iefvad_forward_videos_full(*head[:9], C.byref(o), head[12])
+            elif similarity:
                 res["similarity"] = torch.empty(4, total, **f32)
                 rc = lib.iefvad_forward_videos_similarity(*head, C.c_void_p(res["similarity"].data_ptr()))
             else:
                 rc = lib.iefvad_forward_videos(*head)
             if rc != 0:
-                raise RuntimeError(("iefvad_forward_videos_similarity: " if similarity else "iefvad_forward_videos: ") + _lib.last_error())
+                who = "iefvad_forward_videos_full: " if wide else "iefvad_forward_videos_similarity: " if similarity else "iefvad_forward_videos: "
+                raise RuntimeError(who + _lib.last_error())
         return res

@@ -262,6 +262,33 @@ int iefvad_forward_videos_host_similarity(iefvad_handle* h, const void* const* i
                                           int32_t batch_chunks, int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean,
                                           void* stream, float* similarity);
 
+/* The two whole-video entries with the reference's full output dict (imf_vad.py:152-161) of every valid snippet: what the padded route
+ * returns through an iefvad_outputs, without computing or writing the padding.  The arguments of iefvad_forward_videos /
+ * iefvad_forward_videos_host with the three result pointers replaced by
+ *   out                 device buffers in PACKED order (row r = packed row r of the call; of the whole list for the host entry, every
+ *                       pass writes at its own row offset): logits, w_i_mean, w_e_mean [sum(lengths)] fp32; fused, image_mu, event_mu,
+ *                       image_logvar, event_logvar, w_i, w_e [sum(lengths), D] fp32, 16-byte aligned.  logits is required, every other
+ *                       pointer is optional and any subset is valid; a NULL tensor is neither computed for the caller nor written.
+ * A pass keeps the asked-for tensors of its row set -- mu / logvar / fused (= z_K) in its workspace, as the similarity entries keep
+ * theirs, w_i / w_e behind the base workspace, where the scaled entry keeps them -- and one launch of iefvad_rows_out_wide_kernel
+ * (csrc/ragged.h) behind the pass's scores copies the valid rows to the caller's tensors; pad rows and tile-rounding rows are not read.
+ * In the f32, bf16 and fp16x3 arithmetics every tensor equals, bit for bit, the `[0:len]` rows of iefvad_forward on the host-padded
+ * chunks; logits, w_i_mean and w_e_mean are the bits of the plain entries in every arithmetic.  Workspace:
+ * iefvad_videos_full_workspace_bytes(h, lengths, nvideos, out) -- the plain size, plus [2, R, D] floats (R = rows of one pass's chunks)
+ * when out->w_i or out->w_e is set (out == NULL: the plain size); a smaller workspace is refused by name before anything is launched.
+ * The host entry's two lanes each own such a workspace.  Served: every arithmetic, D = 768 and 512, the three input dtypes, videos
+ * that straddle micro-batch passes, IEFVAD_DENSE_ENCODER=1.  A NULL handle, a NULL out, a NULL out->logits and a misaligned [rows, D]
+ * tensor are refused by name before any HIP call.  NOT covered: the full entries do not combine with iefvad_forward_videos_scaled
+ * (row scales, nan_to_num = 2, w_colsum) or with the similarity entries -- reduce the returned rows with iefvad_similarity_rows instead.
+ * Added without a change to any other entry or struct: IEFVAD_ABI_VERSION stays. */
+size_t iefvad_videos_full_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, const iefvad_outputs* out);
+int iefvad_forward_videos_full(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
+                               int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes, const iefvad_outputs* out,
+                               void* stream);
+int iefvad_forward_videos_host_full(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
+                                    int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num,
+                                    int32_t batch_chunks, int32_t host_threads, const iefvad_outputs* out, void* stream);
+
 /* ---- training-side loss head: forward, and its gradients w.r.t. the model's outputs -----------------
  * The three terms the reference's trainers add up (/root/reference/train/ucf_train.py:68-101, train/xd_train.py:60-75), as
  * device reductions over tensors iefvad_forward already produces:
