@@ -1,5 +1,6 @@
 // iefvad_forward_videos_host: a whole evaluation list in ONE library call (include/iefvad.h).  Included by iefvad.hip behind
-// forward_videos_impl and stream_copy.
+// videos.h (forward_videos_impl; the list's destinations are one VideosOut record, each pass gets its view `out.at(row offset)`) and
+// stream_copy.
 //
 // The reference's evaluation loop (/root/reference/test.py:76-121; data/dataset.py:34-52) loads, pads, uploads and scores one video
 // per Python iteration.  iefvad_forward_videos already takes only the valid rows of a packed batch of videos, but the loop around it
@@ -64,19 +65,24 @@ static void release_hostpipe(iefvad_handle* h) {
     h->hostpipe = nullptr;
 }
 
-// `similarity` (iefvad_forward_videos_host_similarity; null for the plain entry): [4, sum(lengths)] on the device -- every pass reduces
-// its own rows and writes at its row offset with the list's total as the stride (VideosExtras).
-// `wide` (iefvad_forward_videos_host_full; null otherwise): the caller's [sum(lengths), D] tensors -- every pass copies the valid rows of
-// what it kept to its row offset; with w_i / w_e each lane's workspace carries the weights' home behind the base size.
-static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
-                                    int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
-                                    int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream_, float* similarity,
-                                    const char* who, const iefvad_outputs* wide = nullptr) {
-    if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("%s: null argument", who);
+// The host rows of a list: one pointer per video and modality, `in_dtype` elements; `wire_dtype` is what crosses to the device
+struct HostRowsIn {
+    const void* const* img;
+    const void* const* ev;
+    int32_t in_dtype, wire_dtype;
+};
+
+// `out` (VideosOut, defined beside RaggedPass in iefvad.hip): the destinations of the whole list on the device.  Pass k gets the view
+// `out.at(rows before pass k)`: the vectors and the full entry's [sum(lengths), D] tensors at its row offset, the similarity entry's [4, sum(lengths)] series at its
+// column with the list's total as the stride; with a wide w_i / w_e each lane's workspace carries the weights' home behind the base size.
+static int forward_videos_host_impl(iefvad_handle* h, const HostRowsIn& in, const int32_t* lengths, int32_t nvideos, int32_t batch_chunks,
+                                    int32_t host_threads, VideosOut out, void* stream_, const char* who) {
+    const void* const* const img_rows = in.img;
+    const void* const* const ev_rows = in.ev;
+    const int32_t in_dtype = in.in_dtype, wire_dtype = in.wire_dtype;
+    if (!h || !img_rows || !ev_rows || !lengths || !out.logits) return fail("%s: null argument", who);
     if (!h->weights_set) return fail("%s: weights not set", who);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16)
-        return fail("%s: unknown in_dtype %d", who, in_dtype);
+    if (int rc = videos_args(who, out, in_dtype, nvideos)) return rc;
     if (wire_dtype != in_dtype && !(in_dtype == IEFVAD_IN_F32 && wire_dtype == IEFVAD_IN_BF16))
         return fail("%s: wire_dtype %d with in_dtype %d (the wire type is in_dtype, or BF16 for F32 rows)", who, wire_dtype, in_dtype);
     if (wire_dtype != in_dtype && h->cfg.compute != IEFVAD_COMPUTE_BF16)
@@ -102,6 +108,7 @@ static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_row
     std::vector<Batch> batches;
     long long max_rows = 0, max_chunks = 0, total_chunks = 0, total_rows = 0;
     for (int v = 0; v < nvideos; ++v) { total_chunks += video_chunks(lengths[v]); total_rows += lengths[v]; }
+    out.sim_stride = total_rows;
     const bool compressed = !h->policy.dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
     const long long round_rows = (long long)(h->num_cus > 0 ? h->num_cus : 256) * 64;
     const long long row_cap = compressed ? round_rows * ((want + 64) / 128 > 1 ? (want + 64) / 128 : 1) : (1LL << 60);
@@ -174,7 +181,7 @@ static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_row
             }
         p.slot_bytes = cap;
     }
-    const size_t need_ws = iefvad_workspace_bytes(h, (int32_t)max_chunks) + (wide_has_w(wide) ? wide_extra_bytes(h, max_chunks) : 0);
+    const size_t need_ws = iefvad_workspace_bytes(h, (int32_t)max_chunks) + videos_extra_bytes(h, max_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
     if (p.workspace_bytes < need_ws) {
         HIP_TRY(hipDeviceSynchronize());                   // a forward of an earlier call may still use the old workspaces
         p.workspace_bytes = 0;
@@ -291,13 +298,8 @@ static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_row
         hipStream_t cs = p.lane[ln];
         he = hipStreamWaitEvent(cs, p.sent[s], 0);
         if (he != hipSuccess) break;
-        VideosExtras ex;
-        memset(&ex, 0, sizeof(ex));
-        ex.similarity = similarity; ex.sim_stride = total_rows; ex.sim_row0 = row0;
-        ex.wide = wide; ex.wide_row0 = row0;
-        rc = forward_videos_impl(h, p.dev_in[s][0], p.dev_in[s][1], wire_dtype, lengths + b.v0, b.v1 - b.v0, nan_to_num,
-                                 p.workspace[ln], p.workspace_bytes, logits + row0, w_i_mean ? w_i_mean + row0 : nullptr,
-                                 w_e_mean ? w_e_mean + row0 : nullptr, cs, tm, (similarity || wide) ? &ex : nullptr, who);
+        rc = forward_videos_impl(h, RowsIn{p.dev_in[s][0], p.dev_in[s][1], wire_dtype}, lengths + b.v0, b.v1 - b.v0, p.workspace[ln],
+                                 p.workspace_bytes, out.at(row0, h->D), cs, tm, who);
         if (rc == 0) he = hipEventRecord(p.used[s], cs);
         if (trace)
             fprintf(stderr, "[hostpipe] pass %d: %lld chunks %lld rows | waited for staging %.0f us | enqueue copies + forward %.0f us | t = %.0f us\n", k,
@@ -328,8 +330,9 @@ static int forward_videos_host_impl(iefvad_handle* h, const void* const* img_row
 extern "C" int iefvad_forward_videos_host(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
                                           int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, int32_t batch_chunks,
                                           int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean, void* stream_) {
-    return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads, logits,
-                                    w_i_mean, w_e_mean, stream_, nullptr, "iefvad_forward_videos_host");
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    return forward_videos_host_impl(h, HostRowsIn{img_rows, ev_rows, in_dtype, wire_dtype}, lengths, nvideos, batch_chunks, host_threads, out,
+                                    stream_, "iefvad_forward_videos_host");
 }
 
 extern "C" int iefvad_forward_videos_host_similarity(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
@@ -337,16 +340,21 @@ extern "C" int iefvad_forward_videos_host_similarity(iefvad_handle* h, const voi
                                                      int32_t batch_chunks, int32_t host_threads, float* logits, float* w_i_mean, float* w_e_mean,
                                                      void* stream_, float* similarity) {
     static const char* const who = "iefvad_forward_videos_host_similarity";
-    if (int rc = similarity_args(who, similarity, in_dtype, nvideos)) return rc;
-    return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads, logits,
-                                    w_i_mean, w_e_mean, stream_, similarity, who);
+    if (!similarity) return fail("%s: null similarity", who);
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    out.similarity = similarity;
+    if (int rc = videos_args(who, out, in_dtype, nvideos)) return rc;
+    return forward_videos_host_impl(h, HostRowsIn{img_rows, ev_rows, in_dtype, wire_dtype}, lengths, nvideos, batch_chunks, host_threads, out,
+                                    stream_, who);
 }
 
 extern "C" int iefvad_forward_videos_host_full(iefvad_handle* h, const void* const* img_rows, const void* const* ev_rows, int32_t in_dtype,
                                                int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num,
                                                int32_t batch_chunks, int32_t host_threads, const iefvad_outputs* out, void* stream_) {
     static const char* const who = "iefvad_forward_videos_host_full";
-    if (int rc = full_args(who, h, out, in_dtype, nvideos)) return rc;
-    return forward_videos_host_impl(h, img_rows, ev_rows, in_dtype, wire_dtype, lengths, nvideos, nan_to_num, batch_chunks, host_threads,
-                                    out->logits, out->w_i_mean, out->w_e_mean, stream_, nullptr, who, out);
+    if (int rc = full_nulls(who, h, out)) return rc;
+    const VideosOut dst = full_out(*out, nan_to_num);
+    if (int rc = videos_args(who, dst, in_dtype, nvideos)) return rc;
+    return forward_videos_host_impl(h, HostRowsIn{img_rows, ev_rows, in_dtype, wire_dtype}, lengths, nvideos, batch_chunks, host_threads, dst,
+                                    stream_, who);
 }

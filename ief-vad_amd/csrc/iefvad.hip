@@ -116,7 +116,6 @@ struct iefvad_handle {
     bf16_t* arena_st; float* zero_bias; bool tplanes_valid;
     struct HostPipe* hostpipe;  // staging slots, copy stream and workspace of iefvad_forward_videos_host (hostpipe.h)
     struct TrainState* train;   // records of the train-mode forwards whose backward is outstanding (train.h)
-    const float* row_scale[2];  // set for the duration of one iefvad_forward_scaled call: per-row input scales (image, event), nullable
 };
 static const int kAmaxActBase = 256;   // running-max slots of the projection matrices (multi-way words); behind them the activations'
 static int amax_act_tensors(int L, int K) { return 2 + 6 * L + 2 * K + 1; }   // inputs, per layer att|x|qkv x 2 modalities, z_0..z_K, h_0..h_{K-1}
@@ -902,36 +901,68 @@ static int launch_refine_chain(iefvad_handle* h, const float* z_in, float* z_out
     return 0;
 }
 
-// One pass of the valid rows of whole videos (iefvad_forward_videos): where the packed rows of the pass's chunks come from and
-// where its per-row results go.
+// The feature rows a call or a pass reads, both modalities in one element type: [B, 256, D] blocks (dense) or packed valid rows
+struct RowsIn {
+    const void* img;
+    const void* ev;
+    int32_t in_dtype;
+    RowsIn at(size_t rows, int D) const {
+        const size_t o = rows * D * in_elem_bytes(in_dtype);
+        return RowsIn{(const char*)img + o, (const char*)ev + o, in_dtype};
+    }
+};
+static const float* const kNoScale[2] = {nullptr, nullptr};      // per-row input scales: only the two scaled entries carry them
+
+// Where the results of a whole-video call go: one record per call, filled by the entry (csrc/videos.h, csrc/hostpipe.h); it is defined
+// here because a pass (RaggedPass, below) holds the view of it at its own first packed row.  `at` is the one place where row offsets
+// are added: it advances the vectors and the [rows, D] tensors; the series keeps its base pointer and takes its column from row0, which
+// `at` advances by the same rows.  Everything is nullable except logits.
+enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
+struct VideosOut {
+    float* logits;                   // [rows] each
+    float* w_i_mean;
+    float* w_e_mean;
+    const float* scale[2];           // iefvad_forward_videos_scaled: per-row input scales (image, event), [rows] each
+    double* w_colsum;                // iefvad_forward_videos_scaled: [2, D], the call's column sums of w_i / w_e over its valid rows
+    // the similarity entries: the [4, sim_stride] series; packed row r of this view is column row0 + r.  With it the tail keeps fused
+    // (= z_K) and both mu of its row set (tail_keep).
+    float* similarity;
+    long long sim_stride;
+    // the full entries: the caller's packed [rows, D] tensors in the order of kWideFused .. kWideWe.  The tail keeps the asked-for
+    // tensors of its row set (mu / lv / z in the workspace aliases of pass_buffers, the weights in w_rows) and
+    // iefvad_rows_out_wide_kernel copies the valid rows out (pass_rows_out).
+    float* wide[ROWS_OUT_WIDE_MAX];
+    long long row0;                  // packed row of the call's list (the host entries: of the whole list) that this view's first row is
+    int nan_mode;                    // 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 = every video and modality (test2.py:59-60)
+    bool sweep_codes;                // the scaled entry: nan_mode outside 0..2 is refused (the other entries read any non-zero value as 1)
+
+    bool wants_w_rows() const { return w_colsum || wide[kWideWi] || wide[kWideWe]; }      // the fusion stage must store its weights
+    VideosOut at(long long rows, int D) const {
+        VideosOut o = *this;
+        o.logits += rows;
+        if (w_i_mean) o.w_i_mean += rows;
+        if (w_e_mean) o.w_e_mean += rows;
+        for (int m = 0; m < 2; ++m)
+            if (scale[m]) o.scale[m] += rows;
+        for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
+            if (wide[t]) o.wide[t] += rows * D;
+        o.row0 += rows;
+        return o;
+    }
+};
+
+// One pass of the valid rows of whole videos (forward_videos_impl, csrc/videos.h): the pass's packed rows are forward_pass's `in`
 struct RaggedPass {
-    const void* img_rows;            // first packed row of the pass, element type in_dtype
-    const void* ev_rows;
     const RaggedChunk* d_chunks;     // device: the pass's chunks (src_row relative to the pass's first packed row)
-    const int* d_flags;              // device: NaN flag per (video, modality); nullptr = no nan_to_num
+    const int* d_flags;              // device: NaN flag per (video, modality); nullptr unless out.nan_mode == 1
     int valid_rows;                  // packed rows of the pass
     int enc_used_rows;               // rows of the compressed set that belong to chunks
     int enc_rows;                    // > 0: the encoder's row set is row-compressed (RaggedChunk, common.h) and has this many rows (a multiple of 256)
-    float* logits;                   // packed outputs at the pass's first row, nullable
-    float* w_i_mean;
-    float* w_e_mean;
-    // iefvad_forward_videos_scaled (all null / zero otherwise)
-    const float* scale[2];           // per-row input scales at the pass's first packed row (image, event), nullable
-    int nan_all;                     // torch.nan_to_num on every video and modality (test2.py:59-60): no flag words
-    double* w_colsum;                // [2, D]: the call's column sums of w_i / w_e over its valid rows, nullable
-    float* w_rows[2];                // home of the pass's w_i / w_e rows ([R, D] each, behind the base workspace); set with w_colsum
-    double* colsum_part;             // [nb, 2, D] slab partials of the pass; set with w_colsum
-    int first_pass;                  // the pass overwrites w_colsum, later ones add to it
-    // iefvad_forward_videos_similarity / _host_similarity (null otherwise): the call's [4, sim_stride] series; the pass's packed row r
-    // is column sim_row0 + r.  With it the tail keeps fused (= z_K) and both mu of its row set (pass_tail).
-    float* similarity;
-    long long sim_stride, sim_row0;
-    // iefvad_forward_videos_full / _host_full (all null otherwise): the caller's packed [rows, D] tensors at the pass's first packed row,
-    // in the order of kWideFused .. kWideWe.  The tail keeps the asked-for tensors of its row set (mu / lv / z in the workspace aliases of
-    // pass_buffers, the weights in w_rows) and iefvad_rows_out_wide_kernel copies the valid rows out (pass_tail).
-    float* wide[ROWS_OUT_WIDE_MAX];
+    int first_pass;                  // the pass overwrites out.w_colsum, later ones add to it
+    float* w_rows[2];                // home of the pass's w_i / w_e rows ([R, D] each, behind the base workspace); set if out.wants_w_rows()
+    double* colsum_part;             // [nb, 2, D] slab partials of the pass; set with out.w_colsum
+    VideosOut out;                   // the call's destinations at the pass's first packed row
 };
-enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 
 // The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it
 // (PassFlags from pass_buffers on, TailFlags from pass_compact_rows on: launch_rules.h).
@@ -999,8 +1030,8 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
     b.wem_out = out->w_e_mean ? out->w_e_mean + row0 : nullptr;
     if (rg) {                                     // per-row results of the pass land in scratch, then in rg's packed vectors
         b.logits = b.lg_scratch;
-        b.wim_out = rg->w_i_mean ? b.lg_scratch + R : nullptr;
-        b.wem_out = rg->w_e_mean ? b.lg_scratch + 2 * R : nullptr;
+        b.wim_out = rg->out.w_i_mean ? b.lg_scratch + R : nullptr;
+        b.wem_out = rg->out.w_e_mean ? b.lg_scratch + 2 * R : nullptr;
         b.n_i = rg->w_rows[0];                    // only with w_colsum or a wide w_i / w_e: the fusion stage stores its weights there
         b.n_e = rg->w_rows[1];
     }
@@ -1012,9 +1043,12 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
 }
 
 // 0. inputs: `.to(torch.float)` (imf_vad.py:41-42) into b.cur; bf16 mode also gets the bf16 operand copy (b.need_xb0)
-static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const void* pi, const void* pe, int32_t in_dtype, size_t row0, const RaggedPass* rg,
+static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, const float* const scale[2], const RaggedPass* rg,
                             hipStream_t stream, Timer& tm) {
     const size_t D = h->D, n = b.R * D;
+    const void* const pi = in.img;
+    const void* const pe = in.ev;
+    const int32_t in_dtype = in.in_dtype;
     const bool d512 = h->D == IEF_D512;
     bf16_t* const b0p = b.need_xb0 ? b.xb[0] : nullptr;
     bf16_t* const b1p = b.need_xb0 ? b.xb[1] : nullptr;
@@ -1031,24 +1065,24 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const void* pi, co
         hipEvent_t e = tm.begin(ST_CAST);
         // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
         // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
-        const bool scaled = rg->scale[0] || rg->scale[1] || rg->nan_all;
+        const VideosOut& o = rg->out;
+        const int nan_all = o.nan_mode == 2;
+        const bool scaled = o.scale[0] || o.scale[1] || nan_all;
         dispatch_in(in_dtype, d512, [&](auto t, auto w) {
             using T = typename decltype(t)::type;
             constexpr int W = decltype(w)::value;
             hipLaunchKernelGGL((scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>),
-                               dim3(b.nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)rg->img_rows, (const T*)rg->ev_rows, rg->d_chunks,
-                               rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, b.enc_rows_mode ? 0 : IEF_T, rg->scale[0], rg->scale[1], rg->nan_all);
+                               dim3(b.nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)pi, (const T*)pe, rg->d_chunks,
+                               rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, b.enc_rows_mode ? 0 : IEF_T, o.scale[0], o.scale[1], nan_all);
             return 0;
         });
         tm.end(e);
         HIP_TRY(hipGetLastError());
-    } else if (h->row_scale[0] || h->row_scale[1]) {
+    } else if (scale[0] || scale[1]) {
         // iefvad_forward_scaled: the rows pass through the cast kernel whatever their type, scaled on the way (rowops.h)
         hipEvent_t e = tm.begin(ST_CAST);
-        const float* s0 = h->row_scale[0] ? h->row_scale[0] + row0 : nullptr;
-        const float* s1 = h->row_scale[1] ? h->row_scale[1] + row0 : nullptr;
         const int rc = dispatch_in(in_dtype, d512, [&](auto t, auto w) {
-            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, s0, s1, stream);
+            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, scale[0], scale[1], stream);
         });
         tm.end(e);
         if (rc) return rc;
@@ -1198,7 +1232,17 @@ static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass*
     return 0;
 }
 
-// 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer; a ragged pass then writes its rows out
+// What the tail stores of its row set: the caller of a dense pass asked for the tensor, or a ragged pass copies it out (the full
+// entries) or reduces it to the similarity series (fused and both mu) before it ends -- then it stays in the workspace alias of
+// pass_buffers.  Kernel selection does not look at these.
+struct TailKeep { bool fused, mu_i, mu_e, lv_i, lv_e; };
+static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg) {
+    auto rows = [&](int t, bool in_series) { return rg && (rg->out.wide[t] || (in_series && rg->out.similarity)); };
+    return TailKeep{out->fused || rows(kWideFused, true), out->image_mu || rows(kWideMuI, true), out->event_mu || rows(kWideMuE, true),
+                    out->image_logvar || rows(kWideLvI, false), out->event_logvar || rows(kWideLvE, false)};
+}
+
+// 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer
 static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
@@ -1209,21 +1253,15 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     float* const z = b.z;
 
     const bool chain = b.chain, fold = b.fold;
-    // keep fused / mu: the caller asked for the tensor, or the pass reduces it to the similarity series before it ends (then it stays
-    // in the workspace alias of pass_buffers).  Kernel selection does not look at these.
-    const bool sim = rg && rg->similarity;
-    float* const none7[ROWS_OUT_WIDE_MAX] = {};
-    float* const* const wide = rg ? rg->wide : none7;      // the full entries: what the pass copies out of its row set at its end
-    const bool keep_fused = out->fused || sim || wide[kWideFused];
-    const bool keep_mu_i = out->image_mu || sim || wide[kWideMuI], keep_mu_e = out->event_mu || sim || wide[kWideMuE];
-    const bool keep_lv_i = out->image_logvar || wide[kWideLvI], keep_lv_e = out->event_logvar || wide[kWideLvE];
+    const TailKeep keep = tail_keep(out, rg);
+    const bool keep_fused = keep.fused;
     // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
     if (b.heads_rows) {
         HeadsChainArgs ha;
         memset(&ha, 0, sizeof(ha));
         for (int m = 0; m < 2; ++m) ha.A[m] = b.xtb[m];
-        ha.mu[0] = keep_mu_i ? b.mu_i : nullptr; ha.lv[0] = keep_lv_i ? b.lv_i : nullptr;
-        ha.mu[1] = keep_mu_e ? b.mu_e : nullptr; ha.lv[1] = keep_lv_e ? b.lv_e : nullptr;
+        ha.mu[0] = keep.mu_i ? b.mu_i : nullptr; ha.lv[0] = keep.lv_i ? b.lv_i : nullptr;
+        ha.mu[1] = keep.mu_e ? b.mu_e : nullptr; ha.lv[1] = keep.lv_e ? b.lv_e : nullptr;
         ha.n[0] = b.n_i; ha.n[1] = b.n_e;
         ha.z = z;
         ha.zb = chain ? nullptr : b.zb;
@@ -1315,78 +1353,84 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         HIP_TRY(hipGetLastError());
     }
 
-    // ragged pass: the valid rows' results -> the caller's packed vectors (test.py:119-121: logits1[0:len_cur])
-    if (rg) {
-        hipEvent_t e = tm.begin(ST_SCORER);
-        // a compacted set is already in packed order: one thread per valid row, no chunk table
-        hipLaunchKernelGGL(iefvad_rows_out_kernel, dim3(b.compacted ? (rg->valid_rows + 255) / 256 : b.nb), dim3(256), 0, stream, b.logits, b.wim_out,
-                           b.wem_out, rg->logits, rg->w_i_mean, rg->w_e_mean, b.compacted ? nullptr : rg->d_chunks, rg->valid_rows);
+    return 0;
+}
+
+// 6. a ragged pass: the valid rows' results -> the caller's packed vectors and tensors (test.py:119-121: logits1[0:len_cur]), from
+// where the tail left them.  The row set is the chunk table on the row-compressed / whole-chunk set; a compacted set is already in
+// packed order (256-row slabs of it, no table).
+static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+    const VideosOut& o = rg->out;
+    const bool d512 = h->D == IEF_D512;
+    const RaggedChunk* const chunks = b.compacted ? nullptr : rg->d_chunks;
+    const int valid_rows = rg->valid_rows, nslabs = b.compacted ? (valid_rows + 255) / 256 : b.nb;
+    hipEvent_t e = tm.begin(ST_SCORER);
+    hipLaunchKernelGGL(iefvad_rows_out_kernel, dim3(nslabs), dim3(256), 0, stream, b.logits, b.wim_out, b.wem_out, o.logits, o.w_i_mean,
+                       o.w_e_mean, chunks, valid_rows);
+    tm.end(e);
+    HIP_TRY(hipGetLastError());
+    if (o.similarity) {
+        // the four series of the pass's valid rows from z_K / mu_i / mu_e (similarity.h)
+        e = tm.begin(ST_SCORER);
+        dispatch_d(d512, [&](auto w) {
+            hipLaunchKernelGGL(iefvad_similarity_rowset_kernel<decltype(w)::value>, dim3(nslabs, SIM_SLICES), dim3(256), 0, stream, b.z, b.mu_i,
+                               b.mu_e, chunks, valid_rows, o.similarity, o.sim_stride, o.row0);
+        });
         tm.end(e);
         HIP_TRY(hipGetLastError());
-        if (sim) {
-            // the four series of the pass's valid rows from z_K / mu_i / mu_e where the tail left them (similarity.h)
-            const int nslabs = b.compacted ? (rg->valid_rows + 255) / 256 : b.nb;
-            e = tm.begin(ST_SCORER);
-            dispatch_d(d512, [&](auto w) {
-                hipLaunchKernelGGL(iefvad_similarity_rowset_kernel<decltype(w)::value>, dim3(nslabs, SIM_SLICES), dim3(256), 0, stream, z, b.mu_i,
-                                   b.mu_e, b.compacted ? nullptr : rg->d_chunks, rg->valid_rows, rg->similarity, rg->sim_stride, rg->sim_row0);
-            });
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
-        {
-            // the full entries: the valid rows of the kept tensors -> the caller's packed tensors, at the pass's own row offset
-            RowsOutWideArgs wa;
-            memset(&wa, 0, sizeof(wa));
-            const float* const home[ROWS_OUT_WIDE_MAX] = {z, b.mu_i, b.mu_e, b.lv_i, b.lv_e, b.n_i, b.n_e};
-            int nt = 0;
-            for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
-                if (wide[t]) { wa.src[nt] = home[t]; wa.dst[nt] = wide[t]; ++nt; }
-            if (nt) {
-                wa.chunks = b.compacted ? nullptr : rg->d_chunks;
-                wa.valid_rows = rg->valid_rows;
-                const int nslabs = b.compacted ? (rg->valid_rows + 255) / 256 : b.nb;
-                e = tm.begin(ST_SCORER);
-                dispatch_d(d512, [&](auto w) {
-                    hipLaunchKernelGGL(iefvad_rows_out_wide_kernel<decltype(w)::value>, dim3(nslabs, nt, IEF_RAGGED_SLICES), dim3(256), 0, stream, wa);
-                });
-                tm.end(e);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (rg->w_colsum) {
-            // column sums of the stored weights over the valid rows: the chunk table on the row-compressed / whole-chunk set, 256-row
-            // slabs of the packed order on the compacted one (ragged.h)
-            const int nslabs = b.compacted ? (rg->valid_rows + 255) / 256 : b.nb;
-            e = tm.begin(ST_FUSION);
-            dispatch_d(d512, [&](auto w) {
-                hipLaunchKernelGGL(iefvad_colsum_rows_kernel<decltype(w)::value>, dim3(nslabs, 2), dim3(256), 0, stream, b.n_i, b.n_e,
-                                   b.compacted ? nullptr : rg->d_chunks, rg->valid_rows, rg->colsum_part);
-            });
-            hipLaunchKernelGGL(iefvad_colsum_finish_kernel, dim3(2 * D / 16), dim3(256), 0, stream, rg->colsum_part, nslabs, 2 * D,
-                               rg->first_pass, rg->w_colsum);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
+    }
+    // the full entries: the valid rows of the kept tensors -> the caller's packed tensors
+    RowsOutWideArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    const float* const home[ROWS_OUT_WIDE_MAX] = {b.z, b.mu_i, b.mu_e, b.lv_i, b.lv_e, b.n_i, b.n_e};
+    int nt = 0;
+    for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
+        if (o.wide[t]) { wa.src[nt] = home[t]; wa.dst[nt] = o.wide[t]; ++nt; }
+    if (nt) {
+        wa.chunks = chunks;
+        wa.valid_rows = valid_rows;
+        e = tm.begin(ST_SCORER);
+        dispatch_d(d512, [&](auto w) {
+            hipLaunchKernelGGL(iefvad_rows_out_wide_kernel<decltype(w)::value>, dim3(nslabs, nt, IEF_RAGGED_SLICES), dim3(256), 0, stream, wa);
+        });
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
+    if (o.w_colsum) {
+        // column sums of the stored weights over the valid rows (ragged.h)
+        e = tm.begin(ST_FUSION);
+        dispatch_d(d512, [&](auto w) {
+            hipLaunchKernelGGL(iefvad_colsum_rows_kernel<decltype(w)::value>, dim3(nslabs, 2), dim3(256), 0, stream, b.n_i, b.n_e, chunks,
+                               valid_rows, rg->colsum_part);
+        });
+        hipLaunchKernelGGL(iefvad_colsum_finish_kernel, dim3(2 * h->D / 16), dim3(256), 0, stream, rg->colsum_part, nslabs, 2 * h->D,
+                           rg->first_pass, o.w_colsum);
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
     }
     return 0;
 }
 
-// One micro-batch of `nb` chunks.  Dense (rg == nullptr): pi / pe are the pass's [nb, 256, 768] blocks of `in_dtype`, results go
-// to `out` at row offset row0.  Ragged: the chunks are built on the device from rg's packed rows, everything behind the encoder
-// runs on the valid rows only, results go to rg's packed vectors (`out` must be all-null).
-static int forward_pass(iefvad_handle* h, const void* pi, const void* pe, int32_t in_dtype, int nb, size_t row0, void* workspace,
+// One micro-batch of `nb` chunks.  Dense (rg == nullptr): `in` holds the pass's [nb, 256, 768] blocks, `scale` their per-row scales
+// (kNoScale but for iefvad_forward_scaled), results go to `out` at row offset row0.  Ragged: `in` holds the pass's packed rows, the
+// chunks are built from them on the device, everything behind the encoder runs on the valid rows only, results go to rg->out (`out`
+// must be all-null, `scale` kNoScale: rg->out carries the packed scales).
+static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
                         const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
-    if (int rc = pass_load_inputs(h, b, pi, pe, in_dtype, row0, rg, stream, tm)) return rc;
+    if (int rc = pass_load_inputs(h, b, in, scale, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
         if (int rc = pass_encoder_layer(h, b, l, rg, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
-    return pass_tail(h, b, out, rg, stream, tm);
+    if (int rc = pass_tail(h, b, out, rg, stream, tm)) return rc;
+    return rg ? pass_rows_out(h, b, rg, stream, tm) : 0;
 }
 
-static int forward_impl(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
-                        size_t workspace_bytes, const iefvad_outputs* out, hipStream_t stream, Timer& tm) {
+static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
+                        const iefvad_outputs* out, hipStream_t stream, Timer& tm) {
+    const void* const img = in.img;
+    const void* const ev = in.ev;
+    const int32_t in_dtype = in.in_dtype;
     if (!h || !img || !ev || !out) return fail("iefvad_forward: null argument");
     if (!h->weights_set) return fail("iefvad_forward: weights not set");
     if (B <= 0) return fail("iefvad_forward: B must be positive (got %d)", B);
@@ -1400,10 +1444,8 @@ static int forward_impl(iefvad_handle* h, const void* img, const void* ev, int32
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = (B - b0 < mb) ? (B - b0) : mb;
         const size_t row0 = (size_t)b0 * IEF_T;
-        const size_t in_off = row0 * (size_t)h->D * in_elem_bytes(in_dtype);
-        if (int rc = forward_pass(h, (const char*)img + in_off, (const char*)ev + in_off, in_dtype, nb, row0, workspace, out, nullptr,
-                                  stream, tm))
-            return rc;
+        const float* const pass_scale[2] = {scale[0] ? scale[0] + row0 : nullptr, scale[1] ? scale[1] + row0 : nullptr};
+        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm)) return rc;
     }
     return 0;
 }
@@ -1411,332 +1453,7 @@ static int forward_impl(iefvad_handle* h, const void* img, const void* ev, int32
 // ------------------------------------------------------------------------------------------------
 // whole videos: valid rows in, per-snippet results out (include/iefvad.h, csrc/ragged.h)
 // ------------------------------------------------------------------------------------------------
-// chunk count of a video as the evaluation loop needs it: process_split's len // 256 + 1 chunks (tools.py:105-112) minus the
-// all-zero one of a len % 256 == 0 video, whose rows test.py:121 slices away
-static int video_chunks(int n) { return n < IEF_T ? 1 : n / IEF_T + (n % IEF_T ? 1 : 0); }
-
-// per-call metadata (chunk table, NaN flags) travels through a small ring of pinned host / device buffer pairs: the copy is
-// asynchronous, so a slot is reused only after the event recorded behind its last use has completed
-struct MetaRing {
-    static const int kSlots = 4;
-    void* host[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    void* dev[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[kSlots] = {0, 0, 0, 0};
-    hipEvent_t done[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    int turn = 0;
-};
-
-static void release_meta(iefvad_handle* h) {
-    if (!h->meta) return;
-    for (int i = 0; i < MetaRing::kSlots; ++i) {
-        if (h->meta->host[i]) (void)hipHostFree(h->meta->host[i]);
-        if (h->meta->dev[i]) (void)hipFree(h->meta->dev[i]);
-        if (h->meta->done[i]) (void)hipEventDestroy(h->meta->done[i]);
-    }
-    delete h->meta;
-    h->meta = nullptr;
-}
-
-static int videos_layout(const int32_t* lengths, int32_t nvideos, long long* total_rows, long long* total_chunks,
-                         const char* who = "iefvad_forward_videos") {
-    long long rows = 0, chunks = 0;
-    for (int v = 0; v < nvideos; ++v) {
-        if (lengths[v] <= 0) return fail("%s: lengths[%d] = %d", who, v, lengths[v]);
-        rows += lengths[v];
-        chunks += video_chunks(lengths[v]);
-    }
-    *total_rows = rows;
-    *total_chunks = chunks;
-    return 0;
-}
-
-extern "C" size_t iefvad_videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
-    if (!h || !lengths || nvideos <= 0) return 0;
-    long long rows, chunks;
-    if (videos_layout(lengths, nvideos, &rows, &chunks) || chunks > 0x7fffffffLL) return 0;
-    return iefvad_workspace_bytes(h, (int32_t)chunks);
-}
-
-// What iefvad_forward_videos_scaled adds to a whole-video call.  With w_colsum the fusion stage stores w_i / w_e of the pass's row
-// set, and they need a home: no region of the base workspace is dead in every arithmetic while the tail runs (bf16 mode keeps its A
-// operand in the att region, mu / lv / z / h fill the qkv region, y holds the row-mean and scorer partial sums), so the scaled
-// entry's workspace is the base one plus [2, R, D] floats and the [nb, 2, D] slab partials of the column sums, nb = chunks of a pass.
-struct VideosExtras {
-    const float* scale[2];           // [sum(lengths)] each, indexed by the packed row of the call, nullable
-    double* w_colsum;                // [2, D], nullable
-    // iefvad_forward_videos_similarity / _host_similarity (the scaled entry leaves it null): [4, sim_stride] fp32 on the device; the
-    // call's packed row r is column sim_row0 + r (the host-list entry: the row offset of the pass within the whole list)
-    float* similarity;
-    long long sim_stride, sim_row0;
-    // iefvad_forward_videos_full / _host_full (null otherwise): the caller's outputs; the call's packed row r is row wide_row0 + r of
-    // the seven [rows, D] tensors (the host-list entry: the row offset of the pass within the whole list)
-    const iefvad_outputs* wide;
-    long long wide_row0;
-};
-// The full entries' w_i / w_e: the fusion stage stores the weights of the pass's row set, and they need the home the column sums'
-// weights have -- [2, R, D] floats behind the base workspace (nothing behind them: w_colsum does not combine with the full entries).
-static bool wide_has_w(const iefvad_outputs* o) { return o && (o->w_i || o->w_e); }
-static size_t wide_extra_bytes(const iefvad_handle* h, long long chunks) {
-    const int mb = micro_batch(h);
-    const size_t nb = (size_t)(chunks < mb ? chunks : mb);
-    return 2 * nb * IEF_T * (size_t)h->D * sizeof(float);
-}
-static size_t colsum_extra_bytes(const iefvad_handle* h, long long chunks) {
-    const int mb = micro_batch(h);
-    const size_t nb = (size_t)(chunks < mb ? chunks : mb);
-    return 2 * nb * IEF_T * (size_t)h->D * sizeof(float) + nb * 2 * (size_t)h->D * sizeof(double);
-}
-
-extern "C" size_t iefvad_videos_scaled_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t with_colsum) {
-    const size_t base = iefvad_videos_workspace_bytes(h, lengths, nvideos);
-    if (!base || !with_colsum) return base;
-    long long rows, chunks;
-    if (videos_layout(lengths, nvideos, &rows, &chunks)) return 0;
-    return base + colsum_extra_bytes(h, chunks);
-}
-
-// nan_to_num: 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 (the scaled entry only) = every video and modality
-static int forward_videos_impl(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
-                               int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes, float* logits,
-                               float* w_i_mean, float* w_e_mean, hipStream_t stream, Timer& tm, const VideosExtras* ex = nullptr,
-                               const char* who = "iefvad_forward_videos") {
-    if (!h || !img_rows || !ev_rows || !lengths || !logits) return fail("%s: null argument", who);
-    if (!h->weights_set) return fail("%s: weights not set", who);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
-    const bool sweep = ex && !ex->similarity && !ex->wide;      // the scaled entry's nan_to_num codes; the similarity entries keep the plain ones
-    if (nan_to_num < 0 || nan_to_num > (sweep ? 2 : 1)) {
-        if (sweep) return fail("%s: unknown nan_to_num %d (0: off, 1: per video with a NaN, 2: always)", who, nan_to_num);
-        nan_to_num = 1;       // iefvad_forward_videos: any non-zero value is the per-video rule
-    }
-    if (ex && ex->w_colsum && ((uintptr_t)ex->w_colsum & 7)) return fail("%s: w_colsum must be 8-byte aligned", who);
-    if (ex && (((uintptr_t)ex->scale[0] | (uintptr_t)ex->scale[1]) & 3)) return fail("%s: row scale vectors must be 4-byte aligned", who);
-    if (ex && ex->similarity && ((uintptr_t)ex->similarity & 3)) return fail("%s: similarity must be 4-byte aligned", who);
-    long long total_rows, total_chunks;
-    if (int rc = videos_layout(lengths, nvideos, &total_rows, &total_chunks, who)) return rc;
-    if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
-    const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
-    const bool colsum = ex && ex->w_colsum;
-    const bool wide_w = ex && wide_has_w(ex->wide);
-    const size_t need = base + (colsum ? colsum_extra_bytes(h, total_chunks) : 0) + (wide_w ? wide_extra_bytes(h, total_chunks) : 0);
-    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    if (((uintptr_t)workspace & 15) || ((uintptr_t)img_rows & 15) || ((uintptr_t)ev_rows & 15)) return fail("%s: buffers must be 16-byte aligned", who);
-    const bool nan_all = nan_to_num == 2;
-
-    // ---- metadata: the chunk table of the whole call (src_row relative to its pass, filled below) + the flag words
-    const size_t chunk_bytes = (size_t)total_chunks * sizeof(RaggedChunk);
-    const size_t flag_off = (chunk_bytes + 255) & ~(size_t)255;
-    const size_t flag_bytes = (nan_to_num && !nan_all) ? (size_t)nvideos * 2 * sizeof(int) : 0;
-    const size_t meta_bytes = flag_off + flag_bytes;
-    if (!h->meta) {
-        h->meta = new (std::nothrow) MetaRing();
-        if (!h->meta) return fail("%s: out of host memory", who);
-    }
-    MetaRing& mr = *h->meta;
-    const int slot = mr.turn;
-    mr.turn = (mr.turn + 1) % MetaRing::kSlots;
-    HIP_TRY(hipSetDevice(h->device));
-    if (mr.done[slot]) HIP_TRY(hipEventSynchronize(mr.done[slot]));
-    else HIP_TRY(hipEventCreateWithFlags(&mr.done[slot], hipEventDisableTiming));
-    if (mr.cap[slot] < meta_bytes) {
-        if (mr.host[slot]) (void)hipHostFree(mr.host[slot]);
-        if (mr.dev[slot]) (void)hipFree(mr.dev[slot]);
-        mr.host[slot] = mr.dev[slot] = nullptr;
-        mr.cap[slot] = 0;
-        const size_t cap = meta_bytes * 2 + 4096;
-        HIP_TRY(hipHostMalloc(&mr.host[slot], cap, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&mr.dev[slot], cap));
-        mr.cap[slot] = cap;
-    }
-    RaggedChunk* hc = (RaggedChunk*)mr.host[slot];
-    const int mb = micro_batch(h);
-    // fp16x3 carries one operand scale per 256-row chunk of the row set: it keeps whole chunks
-    const bool enc_rows_mode = !h->policy.dense_encoder && h->cfg.compute != IEFVAD_COMPUTE_FP16X3;
-    {
-        // chunk table; src_row and enc_row are relative to the chunk's PASS (passes are runs of <= mb chunks)
-        long long row = 0, pass_row0 = 0;
-        long long ci = 0;
-        int enc = 0;
-        for (int v = 0; v < nvideos; ++v) {
-            const int n = lengths[v], nch = video_chunks(n);
-            for (int j = 0; j < nch; ++j, ++ci) {
-                if (ci % mb == 0) { pass_row0 = row; enc = 0; }
-                const int valid = (n - j * IEF_T) < IEF_T ? (n - j * IEF_T) : IEF_T;
-                hc[ci].src_row = (int)(row - pass_row0);
-                hc[ci].valid = valid;
-                hc[ci].video = v;
-                hc[ci].enc_row = enc;
-                enc += enc_rows_mode ? ragged_rows(valid) : IEF_T;
-                row += valid;
-            }
-        }
-        if (flag_bytes) memset((char*)mr.host[slot] + flag_off, 0, flag_bytes);
-    }
-    HIP_TRY(hipMemcpyAsync(mr.dev[slot], mr.host[slot], meta_bytes, hipMemcpyHostToDevice, stream));
-    const RaggedChunk* dc = (const RaggedChunk*)mr.dev[slot];
-    const int* dflags = flag_bytes ? (const int*)((const char*)mr.dev[slot] + flag_off) : nullptr;
-
-    iefvad_outputs none;
-    memset(&none, 0, sizeof(none));
-    const size_t esz = in_elem_bytes(in_dtype);
-    long long row0 = 0;
-    int rc = 0;
-    if (dflags) {
-        // The conditional nan_to_num of test.py:90-95 is decided on the WHOLE video tensor, and a video may straddle micro-batch
-        // passes: every chunk of the call is scanned before the first pass lays out (and fixes up) its rows.  src_row is
-        // pass-relative, so the scan goes pass by pass too, with the pass's base pointers.
-        hipEvent_t e = tm.begin(ST_CAST);
-        long long r0 = 0;
-        for (long long c0 = 0; c0 < total_chunks; c0 += mb) {
-            const int nb = (int)((total_chunks - c0 < mb) ? (total_chunks - c0) : mb);
-            const void* pi = (const char*)img_rows + (size_t)r0 * h->D * esz;
-            const void* pe = (const char*)ev_rows + (size_t)r0 * h->D * esz;
-            dispatch_in(in_dtype, h->D == IEF_D512, [&](auto t, auto w) {
-                using T = typename decltype(t)::type;
-                hipLaunchKernelGGL((iefvad_nanflag_kernel<T, decltype(w)::value>), dim3(nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)pi,
-                                   (const T*)pe, dc + c0, (int*)dflags);
-                return 0;
-            });
-            for (int j = 0; j < nb; ++j) r0 += hc[c0 + j].valid;
-        }
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
-    }
-    for (long long c0 = 0; c0 < total_chunks && !rc; c0 += mb) {
-        const int nb = (int)((total_chunks - c0 < mb) ? (total_chunks - c0) : mb);
-        long long vrows = 0;
-        for (int j = 0; j < nb; ++j) vrows += hc[c0 + j].valid;
-        RaggedPass rg;
-        rg.img_rows = (const char*)img_rows + (size_t)row0 * h->D * esz;
-        rg.ev_rows = (const char*)ev_rows + (size_t)row0 * h->D * esz;
-        rg.d_chunks = dc + c0;
-        rg.d_flags = dflags;
-        rg.valid_rows = (int)vrows;
-        rg.enc_used_rows = rg.enc_rows = 0;
-        if (enc_rows_mode) {
-            rg.enc_used_rows = hc[c0 + nb - 1].enc_row + ragged_rows(hc[c0 + nb - 1].valid);
-            rg.enc_rows = (rg.enc_used_rows + IEF_T - 1) / IEF_T * IEF_T;        // <= nb * 256
-        }
-        rg.logits = logits + row0;
-        rg.w_i_mean = w_i_mean ? w_i_mean + row0 : nullptr;
-        rg.w_e_mean = w_e_mean ? w_e_mean + row0 : nullptr;
-        for (int m = 0; m < 2; ++m) {
-            rg.scale[m] = (ex && ex->scale[m]) ? ex->scale[m] + row0 : nullptr;       // pass-relative, like src_row
-            rg.w_rows[m] = nullptr;
-        }
-        rg.nan_all = nan_all;
-        rg.w_colsum = nullptr; rg.colsum_part = nullptr;
-        rg.first_pass = c0 == 0;
-        rg.similarity = ex ? ex->similarity : nullptr;
-        rg.sim_stride = ex ? ex->sim_stride : 0;
-        rg.sim_row0 = ex ? ex->sim_row0 + row0 : 0;
-        for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t) rg.wide[t] = nullptr;
-        if (ex && ex->wide) {
-            const iefvad_outputs& o = *ex->wide;
-            float* const dst[ROWS_OUT_WIDE_MAX] = {o.fused, o.image_mu, o.event_mu, o.image_logvar, o.event_logvar, o.w_i, o.w_e};
-            for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
-                if (dst[t]) rg.wide[t] = dst[t] + (size_t)(ex->wide_row0 + row0) * h->D;
-        }
-        if (wide_w) {
-            const size_t per = (size_t)(total_chunks < mb ? total_chunks : mb) * IEF_T * h->D;
-            rg.w_rows[0] = (float*)((char*)workspace + base);
-            rg.w_rows[1] = rg.w_rows[0] + per;
-        }
-        if (colsum) {
-            const size_t per = (size_t)(total_chunks < mb ? total_chunks : mb) * IEF_T * h->D;
-            rg.w_colsum = ex->w_colsum;
-            rg.w_rows[0] = (float*)((char*)workspace + base);
-            rg.w_rows[1] = rg.w_rows[0] + per;
-            rg.colsum_part = (double*)(rg.w_rows[1] + per);
-        }
-        rc = forward_pass(h, nullptr, nullptr, in_dtype, nb, 0, workspace, &none, &rg, stream, tm);
-        row0 += vrows;
-    }
-    (void)hipEventRecord(mr.done[slot], stream);       // the slot's buffers are free once everything enqueued above has run
-    return rc;
-}
-
-extern "C" int iefvad_forward_videos(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
-                                     const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
-                                     size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, void* stream) {
-    Timer tm;
-    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
-                               w_e_mean, (hipStream_t)stream, tm);
-}
-
-extern "C" int iefvad_forward_videos_scaled(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
-                                            const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const float* img_row_scale,
-                                            const float* ev_row_scale, void* workspace, size_t workspace_bytes, float* logits,
-                                            float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream) {
-    Timer tm;
-    VideosExtras ex;
-    memset(&ex, 0, sizeof(ex));
-    ex.scale[0] = img_row_scale; ex.scale[1] = ev_row_scale;
-    ex.w_colsum = w_colsum;
-    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
-                               w_e_mean, (hipStream_t)stream, tm, &ex, "iefvad_forward_videos_scaled");
-}
-
-// The checks the two similarity entries make before they look at the handle: each names the entry, none makes a HIP call.
-static int similarity_args(const char* who, const float* similarity, int32_t in_dtype, int32_t nvideos) {
-    if (!similarity) return fail("%s: null similarity", who);
-    if ((uintptr_t)similarity & 3) return fail("%s: similarity must be 4-byte aligned", who);
-    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    return 0;
-}
-
-extern "C" int iefvad_forward_videos_similarity(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
-                                                const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
-                                                size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, void* stream,
-                                                float* similarity) {
-    static const char* const who = "iefvad_forward_videos_similarity";
-    if (int rc = similarity_args(who, similarity, in_dtype, nvideos)) return rc;
-    if (!h || !lengths) return fail("%s: null argument", who);
-    long long rows, chunks;
-    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
-    Timer tm;
-    VideosExtras ex;
-    memset(&ex, 0, sizeof(ex));
-    ex.similarity = similarity; ex.sim_stride = rows; ex.sim_row0 = 0;
-    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean,
-                               w_e_mean, (hipStream_t)stream, tm, &ex, who);
-}
-
-// The checks the two full entries make before they look at the handle's contents: each names the entry, none makes a HIP call.
-static int full_args(const char* who, const iefvad_handle* h, const iefvad_outputs* out, int32_t in_dtype, int32_t nvideos) {
-    if (!h) return fail("%s: null handle", who);
-    if (!out) return fail("%s: null out", who);
-    if (!out->logits) return fail("%s: null logits (out->logits is required)", who);
-    float* const wide[ROWS_OUT_WIDE_MAX] = {out->fused, out->image_mu, out->event_mu, out->image_logvar, out->event_logvar, out->w_i, out->w_e};
-    for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
-        if ((uintptr_t)wide[t] & 15) return fail("%s: the [rows, D] outputs must be 16-byte aligned", who);
-    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    return 0;
-}
-
-extern "C" size_t iefvad_videos_full_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, const iefvad_outputs* out) {
-    const size_t base = iefvad_videos_workspace_bytes(h, lengths, nvideos);
-    if (!base || !wide_has_w(out)) return base;
-    long long rows, chunks;
-    if (videos_layout(lengths, nvideos, &rows, &chunks)) return 0;
-    return base + wide_extra_bytes(h, chunks);
-}
-
-extern "C" int iefvad_forward_videos_full(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
-                                          int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes,
-                                          const iefvad_outputs* out, void* stream) {
-    static const char* const who = "iefvad_forward_videos_full";
-    if (int rc = full_args(who, h, out, in_dtype, nvideos)) return rc;
-    Timer tm;
-    VideosExtras ex;
-    memset(&ex, 0, sizeof(ex));
-    ex.wide = out; ex.wide_row0 = 0;
-    return forward_videos_impl(h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, out->logits,
-                               out->w_i_mean, out->w_e_mean, (hipStream_t)stream, tm, &ex, who);
-}
-
+#include "videos.h"
 
 // ------------------------------------------------------------------------------------------------
 // small batches: replay a captured hipGraph of the forward
@@ -1835,7 +1552,7 @@ static int forward_graphed(iefvad_handle* h, const void* img, const void* ev, in
             gc.disabled = true;
             return -1;
         }
-        const int rc = forward_impl(h, s_img, s_ev, in_dtype, B, workspace, workspace_bytes, &so, gc.cap_stream, tm);
+        const int rc = forward_impl(h, RowsIn{s_img, s_ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, &so, gc.cap_stream, tm);
         hipGraph_t graph = nullptr;
         const hipError_t ce = hipStreamEndCapture(gc.cap_stream, &graph);      // always end the capture, also after a failed launch
         if (rc) {
@@ -1882,7 +1599,7 @@ extern "C" int iefvad_forward(iefvad_handle* h, const void* img, const void* ev,
         }
     }
     Timer tm;      // everything else, and every invalid argument (reported by forward_impl), takes the direct path
-    return forward_impl(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
 }
 
 extern "C" int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const float* img_row_scale,
@@ -1890,11 +1607,8 @@ extern "C" int iefvad_forward_scaled(iefvad_handle* h, const void* img, const vo
     if (!h) return fail("iefvad_forward_scaled: null argument");
     if (!img_row_scale && !ev_row_scale) return iefvad_forward(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream);
     Timer tm;      // direct launches: the scale vectors are per call, a cached graph would pin their addresses
-    h->row_scale[0] = img_row_scale;
-    h->row_scale[1] = ev_row_scale;
-    const int rc = forward_impl(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
-    h->row_scale[0] = h->row_scale[1] = nullptr;
-    return rc;
+    const float* const scale[2] = {img_row_scale, ev_row_scale};
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, scale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
 }
 
 extern "C" int iefvad_forward_timed(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B,
@@ -1915,7 +1629,7 @@ extern "C" int iefvad_forward_timed(iefvad_handle* h, const void* img, const voi
     hipEvent_t t0 = pool.take(), t1 = pool.take();
     if (!t0 || !t1) return fail("iefvad_forward_timed: hipEventCreate: %s", hipGetErrorString(pool.err));
     HIP_TRY(hipEventRecord(t0, stream));
-    int rc = forward_impl(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream, tm);
+    int rc = forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, stream, tm);
     (void)hipEventRecord(t1, stream);
     hipError_t se = hipStreamSynchronize(stream);
     if (rc) return rc;

@@ -46,6 +46,33 @@ def _row_output_keys(outputs) -> tuple:
     return tuple(k for k in WIDE_KEYS if k in names)
 
 
+# The valid-row entries by the suffix of their names (`iefvad_forward_videos<suffix>`, `iefvad_forward_videos_host<suffix>`), each with:
+# the device entry's workspace query (`iefvad_videos<query>_workspace_bytes`) and its arguments behind (handle, lengths, nvideos); the
+# entry's arguments behind the common head.  `r` holds the call's pointers (`MMFMIL._rows_call` sets every key; None = not asked for).
+_ROW_ENTRIES = {
+    "": ("", lambda r: (), lambda r: (*r["vectors"], r["stream"])),
+    "_similarity": ("", lambda r: (), lambda r: (*r["vectors"], r["stream"], r["similarity"])),
+    "_full": ("_full", lambda r: (r["out"],), lambda r: (r["out"], r["stream"])),
+    "_scaled": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
+}
+
+
+def _row_entry_suffix(similarity, outputs, full_entry: str, extras: bool = False):
+    """The exclusion rules between `similarity=`, `outputs=` and the sweep's extras of the valid-row calls -> (the [rows, D] keys asked
+    for, the suffix of the entry that serves the request).  `full_entry`: the full entry's name, for the message."""
+    if similarity and extras:
+        raise ValueError("similarity=True does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
+                         "iefvad_forward_videos_scaled takes no similarity buffer")
+    wide = _row_output_keys(outputs)
+    if wide and similarity:
+        raise ValueError(f"outputs= does not combine with similarity=True: {full_entry} takes no similarity buffer "
+                         "(reduce the returned rows with harness.similarity_rows)")
+    if wide and extras:
+        raise ValueError("outputs= does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
+                         "iefvad_forward_videos_scaled returns no [rows, D] tensor")
+    return wide, "_scaled" if extras else "_full" if wide else "_similarity" if similarity else ""
+
+
 class _LinearParams(nn.Module):
     """Parameter holder with nn.Linear's names, shapes and default init (kaiming-uniform a=sqrt(5))."""
 
@@ -482,10 +509,7 @@ class MMFMIL(nn.Module):
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos_host is an evaluation entry point; call model.eval() first")
         self._noise_code()
-        wide = _row_output_keys(outputs)
-        if wide and similarity:
-            raise ValueError("outputs= does not combine with similarity=True: iefvad_forward_videos_host_full takes no similarity buffer "
-                             "(reduce the returned rows with harness.similarity_rows)")
+        wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_host_full")
         lens = [int(n) for n in lengths]
         if not lens or min(lens) < 1 or len(imgs) != len(lens) or len(evs) != len(lens):
             raise ValueError("imgs, evs and lengths must list the same videos, every video at least one snippet")
@@ -507,40 +531,50 @@ class MMFMIL(nn.Module):
         device = next(self.temporal.parameters()).device
         if device.type != "cuda":
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback (call model.to('cuda'))")
-        total = sum(lens)
-        lib = _lib.load_library()
-        larr = (C.c_int32 * n)(*lens)
+        front = (pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], (C.c_int32 * n)(*lens), n, 1 if nan_to_num else 0, int(batch_chunks), int(host_threads))
+        return self._rows_call("iefvad_forward_videos_host", suffix, device, sum(lens), front, wide=wide)
+
+    def _rows_call(self, base, suffix, device, total, front, *, wide=(), weight_sums=False, workspace_for=None):
+        """One valid-row call, the entry `base + suffix` (`_ROW_ENTRIES`): allocates the results -- the three [total] vectors, a
+        [total, D] tensor per key of `wide`, the similarity entries' [4, total] series, `w_colsum` -- and calls the entry with
+        (handle, *front, [workspace, bytes,] the suffix's tail).  `workspace_for=(lengths array, nvideos)`: the device entries, whose
+        workspace the caller owns; it is sized by the suffix's query."""
+        lib, name = _lib.load_library(), base + suffix
+        query, query_tail, tail = _ROW_ENTRIES[suffix]
+        D = self.temporal.embed_dim
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._ensure_handle(device)
             self._ensure_weights(device, stream)
             f32 = dict(dtype=torch.float32, device=device)
-            res = {"logits": torch.empty(total, **f32), "w_i_mean": torch.empty(total, **f32), "w_e_mean": torch.empty(total, **f32)}
-            head = (self._handle, pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], larr, n, 1 if nan_to_num else 0, int(batch_chunks),
-                    int(host_threads), C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
-                    C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
-            if wide:
-                rc = lib.iefvad_forward_videos_host_full(*head[:10], C.byref(self._rows_outputs(res, wide, total, D, f32)), head[13])
-            elif similarity:
+            res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
+            r = {"vectors": tuple(C.c_void_p(t.data_ptr()) for t in res.values()), "stream": C.c_void_p(stream), "out": None,
+                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0}
+            if suffix == "_full":
+                o = _lib.Outputs()
+                for k in res:
+                    setattr(o, k, res[k].data_ptr())
+                for k in wide:
+                    res[k] = torch.empty(total, D, **f32)
+                    setattr(o, k, res[k].data_ptr())
+                r["out"] = C.byref(o)
+            if suffix == "_similarity":
                 res["similarity"] = torch.empty(4, total, **f32)
-                rc = lib.iefvad_forward_videos_host_similarity(*head, C.c_void_p(res["similarity"].data_ptr()))
-            else:
-                rc = lib.iefvad_forward_videos_host(*head)
+                r["similarity"] = C.c_void_p(res["similarity"].data_ptr())
+            if weight_sums:
+                res["w_colsum"] = torch.empty(2, D, dtype=torch.float64, device=device)
+                r["w_colsum"] = C.c_void_p(res["w_colsum"].data_ptr())
+            front = (self._handle, *front)
+            if workspace_for is not None:
+                need = getattr(lib, f"iefvad_videos{query}_workspace_bytes")(self._handle, *workspace_for, *query_tail(r))
+                if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
+                    self._workspace = None
+                    self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
+                front += (C.c_void_p(self._workspace.data_ptr()), self._workspace.numel())
+            rc = getattr(lib, name)(*front, *tail(r))
         if rc != 0:
-            who = "iefvad_forward_videos_host_full: " if wide else "iefvad_forward_videos_host_similarity: " if similarity else "iefvad_forward_videos_host: "
-            raise RuntimeError(who + _lib.last_error())
+            raise RuntimeError(name + ": " + _lib.last_error())
         return res
-
-    @staticmethod
-    def _rows_outputs(res, wide, total, D, f32):
-        """The `iefvad_outputs` of a full valid-row call: the three vectors already in `res`, plus a new [total, D] tensor per key of
-        `wide`, added to `res`."""
-        o = _lib.Outputs()
-        o.logits, o.w_i_mean, o.w_e_mean = res["logits"].data_ptr(), res["w_i_mean"].data_ptr(), res["w_e_mean"].data_ptr()
-        for k in wide:
-            res[k] = torch.empty(total, D, **f32)
-            setattr(o, k, res[k].data_ptr())
-        return o
 
     # ------------------------------------------------------------------ train mode
     def _forward_train(self, img_visual, ev_visual) -> Dict[str, torch.Tensor]:
@@ -608,16 +642,7 @@ class MMFMIL(nn.Module):
                                    or sv.numel() != nrows or not sv.is_contiguous()):
                 raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {nrows} elements (sum of lengths) on {img_rows.device}")
         extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None
-        if similarity and extras:
-            raise ValueError("similarity=True does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
-                             "iefvad_forward_videos_scaled takes no similarity buffer")
-        wide = _row_output_keys(outputs)
-        if wide and similarity:
-            raise ValueError("outputs= does not combine with similarity=True: iefvad_forward_videos_full takes no similarity buffer "
-                             "(reduce the returned rows with harness.similarity_rows)")
-        if wide and extras:
-            raise ValueError("outputs= does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
-                             "iefvad_forward_videos_scaled returns no [rows, D] tensor")
+        wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_full", extras)
         if not (img_rows.is_cuda and ev_rows.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         lens = [int(n) for n in lengths]
@@ -633,49 +658,9 @@ class MMFMIL(nn.Module):
         ev = self._prepare_input(ev_rows)
         if ev.dtype != img.dtype:
             img, ev = img.to(torch.float), ev.to(torch.float)
-        lib = _lib.load_library()
         larr = (C.c_int32 * len(lens))(*lens)
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            self._ensure_handle(device)
-            self._ensure_weights(device, stream)
-            f32 = dict(dtype=torch.float32, device=device)
-            res = {"logits": torch.empty(total, **f32), "w_i_mean": torch.empty(total, **f32), "w_e_mean": torch.empty(total, **f32)}
-            o = self._rows_outputs(res, wide, total, D, f32) if wide else None
-            if extras:
-                need = lib.iefvad_videos_scaled_workspace_bytes(self._handle, larr, len(lens), 1 if weight_sums else 0)
-            elif wide:
-                need = lib.iefvad_videos_full_workspace_bytes(self._handle, larr, len(lens), C.byref(o))
-            else:
-                need = lib.iefvad_videos_workspace_bytes(self._handle, larr, len(lens))
-            if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
-                self._workspace = None
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            if extras:
-                if weight_sums:
-                    res["w_colsum"] = torch.empty(2, D, dtype=torch.float64, device=device)
-                rc = lib.iefvad_forward_videos_scaled(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()),
-                                                      _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
-                                                      C.c_void_p(scales[0].data_ptr()) if scales[0] is not None else None,
-                                                      C.c_void_p(scales[1].data_ptr()) if scales[1] is not None else None,
-                                                      C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(),
-                                                      C.c_void_p(res["logits"].data_ptr()), C.c_void_p(res["w_i_mean"].data_ptr()),
-                                                      C.c_void_p(res["w_e_mean"].data_ptr()),
-                                                      C.c_void_p(res["w_colsum"].data_ptr()) if weight_sums else None, C.c_void_p(stream))
-                if rc != 0:
-                    raise RuntimeError("iefvad_forward_videos_scaled: " + _lib.last_error())
-                return res
-            head = (self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), nan_mode,
-                    C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), C.c_void_p(res["logits"].data_ptr()),
-                    C.c_void_p(res["w_i_mean"].data_ptr()), C.c_void_p(res["w_e_mean"].data_ptr()), C.c_void_p(stream))
-            if wide:
-                rc = lib.iefvad_forward_videos_full(*head[:9], C.byref(o), head[12])
-            elif similarity:
-                res["similarity"] = torch.empty(4, total, **f32)
-                rc = lib.iefvad_forward_videos_similarity(*head, C.c_void_p(res["similarity"].data_ptr()))
-            else:
-                rc = lib.iefvad_forward_videos(*head)
-            if rc != 0:
-                who = "iefvad_forward_videos_full: " if wide else "iefvad_forward_videos_similarity: " if similarity else "iefvad_forward_videos: "
-                raise RuntimeError(who + _lib.last_error())
-        return res
+        front = (C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), nan_mode)
+        if extras:      # the scaled entry alone takes the two scale vectors, behind nan_to_num
+            front += tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in scales)
+        return self._rows_call("iefvad_forward_videos", suffix, device, total, front, wide=wide, weight_sums=weight_sums,
+                               workspace_for=(larr, len(lens)))

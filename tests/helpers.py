@@ -146,3 +146,10 @@ def write_xd_set(tmp, golden_dir=GOLDEN):
     args = argparse.Namespace(dataset="xd", visual_length=256, test_list=str(csv), exp_name="t")
     label_map = {str(k): str(v) for k, v in zip(g["map_keys"], g["map_values"])}
     return g, args, gt, sd, label_map
+
+
+def with_nan(vids, video, row, col):
+    """A copy of a list of (image rows, event rows) numpy pairs with one NaN planted in the image rows of `video`."""
+    vids = [(v[0].copy(), v[1].copy()) for v in vids]
+    vids[video][0][row, col] = float("nan")
+    return vids

@@ -171,6 +171,25 @@ def test_host_list_entry_equals_the_device_entry(compute):
     assert "similarity" not in host_call(model, videos(np.float32), batch_chunks=3)
 
 
+@pytest.mark.parametrize("plant_nan", [False, True])
+def test_host_passes_cut_into_micro_batches_write_at_the_composed_column(plant_nan):
+    """4. micro_batch = 2 under batch_chunks = 3: the 1,500-row video starts at a non-zero row of the list and spans three micro-batch
+    passes of its host pass, so the series' column is (list offset of the host pass) + (offset of the micro-batch pass in it), both
+    above zero.  f32 is bit-identical across pass sizes (`micro_batch=3` above), so the device entry of a default-micro-batch model is
+    the reference.  With a NaN in the image rows of that video's third chunk, the per-video flag (scanned pass by pass) must reach
+    every pass of the video; `torch.equal` is false on a NaN that got through."""
+    vids = videos(np.float32)
+    if plant_nan:
+        vids = H.with_nan(vids, EDGE.index(1500), 2 * T + 88, 11)
+    rows = pack(vids)
+    with torch.no_grad():
+        want = make_model("f32", outputs="scores").forward_videos(rows[0], rows[1], EDGE, nan_to_num=True, similarity=True)
+    got = host_call(make_model("f32", outputs="scores", micro_batch=2), vids, nan_to_num=True, batch_chunks=3, similarity=True)
+    assert set(got) == set(want) == set(SCORE_KEYS) | {"similarity"}
+    for k in got:
+        assert torch.equal(got[k], want[k]), (plant_nan, k, float((got[k] - want[k]).abs().max()))
+
+
 def test_host_list_entry_on_the_bf16_wire():
     """4. fp32 host rows rounded to bf16 while they are staged: `forward_videos` on torch-rounded rows, as tests/test_gpu_videos.py
     compares the scores."""

@@ -247,6 +247,25 @@ def test_host_list_entry_equals_the_device_entry(compute):
     assert set(host_call(model, videos(np.float32), batch_chunks=3)) == set(SCORE_KEYS)
 
 
+@pytest.mark.parametrize("plant_nan", [False, True])
+def test_host_passes_cut_into_micro_batches_write_at_the_composed_offset(plant_nan):
+    """7. micro_batch = 2 under batch_chunks = 3: the 1,500-row video starts at a non-zero row of the list and spans three micro-batch
+    passes of its host pass, so every destination is written at (list offset of the host pass) + (offset of the micro-batch pass in
+    it), both above zero.  f32 is bit-identical across pass sizes (`micro_batch=3` above), so the device entry of a
+    default-micro-batch model is the reference.  With a NaN planted, the per-video flag (scanned pass by pass) must reach every pass
+    of the video; `torch.equal` is false on a NaN that got through."""
+    vids = videos(np.float32)
+    if plant_nan:          # in the image rows of the 1,500-row video's third chunk
+        vids = H.with_nan(vids, EDGE.index(1500), 2 * T + 88, 11)
+    rows = pack(vids)
+    with torch.no_grad():
+        want = make_model("f32", outputs="scores").forward_videos(rows[0], rows[1], EDGE, nan_to_num=True, outputs="full")
+    got = host_call(make_model("f32", outputs="scores", micro_batch=2), vids, nan_to_num=True, batch_chunks=3, outputs="full")
+    assert set(got) == set(want) == set(ALL_KEYS)
+    for k in ALL_KEYS:
+        assert torch.equal(got[k], want[k]), (plant_nan, k, float((got[k] - want[k]).abs().max()))
+
+
 def test_nan_rule_precedes_the_wide_outputs():
     """8. An fp16 video with a NaN and both infinities in its image rows (and clean event rows) among clean videos: test.py:90-95
     replaces in the whole image tensor of that video only (NaN -> 0, +-inf -> +-65504) -- on the host for the padded route, on the
