@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "attention_f32.h"
+#include "attention_maps.h"
 #include "attention_bf16.h"
 #include "attention_pbf16.h"
 #include "attention_split.h"
@@ -917,6 +918,25 @@ static const float* const kNoScale[2] = {nullptr, nullptr};      // per-row inpu
 // here because a pass (RaggedPass, below) holds the view of it at its own first packed row.  `at` is the one place where row offsets
 // are added: it advances the vectors and the [rows, D] tensors; the series keeps its base pointer and takes its column from row0, which
 // `at` advances by the same rows.  Everything is nullable except logits.
+// The head-averaged attention maps a call asked for (include/iefvad.h, csrc/attention_maps.h): [rows, 256] fp32 per modality and layer,
+// null where not asked for.  `at` moves every map to a later first row.
+struct AttnMaps {
+    float* p[2][IEFVAD_MAX_LAYERS];
+    bool any() const {
+        for (int m = 0; m < 2; ++m)
+            for (int l = 0; l < IEFVAD_MAX_LAYERS; ++l)
+                if (p[m][l]) return true;
+        return false;
+    }
+    AttnMaps at(long long rows) const {
+        AttnMaps o = *this;
+        for (int m = 0; m < 2; ++m)
+            for (int l = 0; l < IEFVAD_MAX_LAYERS; ++l)
+                if (p[m][l]) o.p[m][l] += rows * IEF_T;
+        return o;
+    }
+};
+
 enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 struct VideosOut {
     float* logits;                   // [rows] each
@@ -932,6 +952,7 @@ struct VideosOut {
     // tensors of its row set (mu / lv / z in the workspace aliases of pass_buffers, the weights in w_rows) and
     // iefvad_rows_out_wide_kernel copies the valid rows out (pass_rows_out).
     float* wide[ROWS_OUT_WIDE_MAX];
+    AttnMaps attn;                   // iefvad_forward_videos_attn: the packed [rows, 256] maps, written inside the encoder (pass_encoder_layer)
     long long row0;                  // packed row of the call's list (the host entries: of the whole list) that this view's first row is
     int nan_mode;                    // 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 = every video and modality (test2.py:59-60)
     bool sweep_codes;                // the scaled entry: nan_mode outside 0..2 is refused (the other entries read any non-zero value as 1)
@@ -946,6 +967,7 @@ struct VideosOut {
             if (scale[m]) o.scale[m] += rows;
         for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
             if (wide[t]) o.wide[t] += rows * D;
+        o.attn = attn.at(rows);
         o.row0 += rows;
         return o;
     }
@@ -1113,7 +1135,7 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
 }
 
 // 1. one layer of the temporal encoder (imf_vad.py:113-123): in_proj, attention, out_proj + residual, LayerNorm; b.cur moves to its output
-static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const RaggedPass* rg, const AttnMaps* maps, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const int D = h->D, L = c.num_layers, rows = b.rows, nb = b.nb;
@@ -1157,6 +1179,23 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
     }
     tm.end(e);
     HIP_TRY(hipGetLastError());
+
+    if (maps && (maps->p[0][l] || maps->p[1][l])) {
+        // the layer's head-averaged attention weights, from q | k | v while they are alive (attention_maps.h).  The entries refuse
+        // the bf16 arithmetic, whose q | k | v are bf16 planes in another layout.
+        if (bf) return fail("attention maps: compute = BF16 is not supported");
+        AttnMapArgs ma;
+        memset(&ma, 0, sizeof(ma));
+        for (int m = 0; m < 2; ++m) { ma.qkv[m] = b.qkv[m]; ma.out[m] = maps->p[m][l]; }
+        ma.nchunks = nb;
+        ma.chunks = rg ? rg->d_chunks : nullptr;
+        void (*const kernel)(AttnMapArgs) = d512 ? (enc_chunks ? iefvad_attention_maps_kernel<true, 64> : iefvad_attention_maps_kernel<false, 64>)
+                                                 : (enc_chunks ? iefvad_attention_maps_kernel<true, IEF_DH> : iefvad_attention_maps_kernel<false, IEF_DH>);
+        e = tm.begin(ST_ATT);
+        hipLaunchKernelGGL(kernel, dim3(2, 2 * nb), dim3(256), 0, stream, ma);
+        tm.end(e);
+        HIP_TRY(hipGetLastError());
+    }
 
     if (b.ln_fused) {      // out_proj + residual + LayerNorm(s) in one row-owning kernel
         float* oy[2] = {(l < L - 1) ? b.xbuf[0] : nullptr, (l < L - 1) ? b.xbuf[1] : nullptr};      // fp32 rows are only the next layer's residual
@@ -1416,18 +1455,19 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
 // chunks are built from them on the device, everything behind the encoder runs on the valid rows only, results go to rg->out (`out`
 // must be all-null, `scale` kNoScale: rg->out carries the packed scales).
 static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
-                        const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+                        const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
+    if (rg) maps = &rg->out.attn;                 // a whole-video pass: the maps at the pass's first packed row
     if (int rc = pass_load_inputs(h, b, in, scale, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
-        if (int rc = pass_encoder_layer(h, b, l, rg, stream, tm)) return rc;
+        if (int rc = pass_encoder_layer(h, b, l, rg, maps, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
     if (int rc = pass_tail(h, b, out, rg, stream, tm)) return rc;
     return rg ? pass_rows_out(h, b, rg, stream, tm) : 0;
 }
 
 static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
-                        const iefvad_outputs* out, hipStream_t stream, Timer& tm) {
+                        const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr) {
     const void* const img = in.img;
     const void* const ev = in.ev;
     const int32_t in_dtype = in.in_dtype;
@@ -1445,7 +1485,8 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
         const int nb = (B - b0 < mb) ? (B - b0) : mb;
         const size_t row0 = (size_t)b0 * IEF_T;
         const float* const pass_scale[2] = {scale[0] ? scale[0] + row0 : nullptr, scale[1] ? scale[1] + row0 : nullptr};
-        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm)) return rc;
+        const AttnMaps pass_maps = maps ? maps->at((long long)row0) : AttnMaps();
+        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr)) return rc;
     }
     return 0;
 }
@@ -1453,6 +1494,7 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
 // ------------------------------------------------------------------------------------------------
 // whole videos: valid rows in, per-snippet results out (include/iefvad.h, csrc/ragged.h)
 // ------------------------------------------------------------------------------------------------
+static int attn_maps_args(const char* who, const iefvad_handle* h, const iefvad_attn_maps* maps, AttnMaps* am);   // the maps entries' checks, below
 #include "videos.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1600,6 +1642,37 @@ extern "C" int iefvad_forward(iefvad_handle* h, const void* img, const void* ev,
     }
     Timer tm;      // everything else, and every invalid argument (reported by forward_impl), takes the direct path
     return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
+}
+
+// The checks of a maps request that need no device: something is asked for, only at layers the model has, 16-byte aligned, and
+// not in the bf16 arithmetic (whose q | k | v are bf16 planes)
+static int attn_maps_args(const char* who, const iefvad_handle* h, const iefvad_attn_maps* maps, AttnMaps* am) {
+    if (!h) return fail("%s: null handle", who);
+    if (!maps) return fail("%s: null maps", who);
+    memset(am, 0, sizeof(*am));
+    int top = -1;        // the last layer asked for; the pointers are looked at before the handle is
+    for (int l = 0; l < IEFVAD_MAX_LAYERS; ++l) {
+        float* const p[2] = {maps->image[l], maps->event[l]};
+        for (int m = 0; m < 2; ++m) {
+            if (!p[m]) continue;
+            if ((uintptr_t)p[m] & 15) return fail("%s: the attention maps must be 16-byte aligned", who);
+            am->p[m][l] = p[m];
+            top = l;
+        }
+    }
+    if (top < 0) return fail("%s: every map is null (nothing is asked for)", who);
+    if (top >= h->cfg.num_layers) return fail("%s: a map is asked for at layer %d, the model has %d layers", who, top, h->cfg.num_layers);
+    if (h->cfg.compute == IEFVAD_COMPUTE_BF16)
+        return fail("%s: attention maps are not available with compute = BF16 (q | k | v are bf16 planes there); use F32, BF16X6 or FP16X3", who);
+    return 0;
+}
+
+extern "C" int iefvad_forward_attn(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                                   size_t workspace_bytes, const iefvad_outputs* out, const iefvad_attn_maps* maps, void* stream) {
+    AttnMaps am;
+    if (int rc = attn_maps_args("iefvad_forward_attn", h, maps, &am)) return rc;
+    Timer tm;      // direct launches: the map pointers are per call, a cached graph would pin their addresses
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, &am);
 }
 
 extern "C" int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const float* img_row_scale,

@@ -250,6 +250,17 @@ extern "C" int iefvad_forward_videos(iefvad_handle* h, const void* img_rows, con
                                "iefvad_forward_videos");
 }
 
+extern "C" int iefvad_forward_videos_attn(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                          const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                          size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                          const iefvad_attn_maps* maps, void* stream) {
+    static const char* const who = "iefvad_forward_videos_attn";
+    Timer tm;
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    if (int rc = attn_maps_args(who, h, maps, &out.attn)) return rc;
+    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+}
+
 extern "C" int iefvad_forward_videos_scaled(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
                                             const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const float* img_row_scale,
                                             const float* ev_row_scale, void* workspace, size_t workspace_bytes, float* logits,

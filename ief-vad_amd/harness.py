@@ -737,12 +737,14 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
                '(outputs="scores" / "weights" do not return them)')
 
 
-def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=()):
+def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=(),
+                     attn_layers=()):
     """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
     while this thread sends batch k and enqueues its forward; batches complete in order.
     `similarity`: every forward also returns its [4, n] block of series (`forward_videos(similarity=True)`) for the sink.
-    `row_outputs`: every forward also returns those [n, D] tensors (`forward_videos(outputs=...)`); the sink keeps them on the device."""
+    `row_outputs`: every forward also returns those [n, D] tensors (`forward_videos(outputs=...)`); the sink keeps them on the device.
+    `attn_layers`: every forward also returns the attention maps of those layers (`forward_videos(attn_maps=...)`), kept the same way."""
     def stage(pend, k):
         dt, widened = _batch_dtype(pend)
         if widened:               # a narrower video is widened at staging: its own dtype's inf -> max rule applies first (test.py:90-95)
@@ -758,7 +760,8 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
             out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
         sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out)
 
-    sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else {}
+    sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else \
+        dict(attn_maps=attn_layers) if attn_layers else {}
 
     stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
@@ -822,7 +825,7 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
-                 return_device: bool = False, similarity=False, row_outputs=None):
+                 return_device: bool = False, similarity=False, row_outputs=None, attn_maps=None):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -866,10 +869,26 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     [rows, D] tensors of the reference's dict for the VALID snippets only, whatever `outputs=` the model was built with.  The returned
     tuple does not change; `score_loader.last_result` becomes {"row_outputs": {name: ONE [N, D] fp32 device tensor, the videos in
     list order}, "row_offsets": int64 array of len(videos) + 1 offsets into N}.  Nothing D-wide is copied to the host here.  Needs what
-    `similarity="rows"` needs; it does not combine with `similarity` (ValueError)."""
+    `similarity="rows"` needs; it does not combine with `similarity` (ValueError).
+
+    `attn_maps` (True, or an iterable of encoder layer indices; opt-in): the `forward_videos` loop with `attn_maps=` on every call
+    (`iefvad_forward_videos_attn`, csrc/attention_maps.h).  The returned tuple and the scores do not change; `score_loader.last_result`
+    becomes {"attn_maps": {"image", "event": ONE [n, N, T] fp32 device tensor each -- the head-averaged attention weights of the N
+    valid snippets over the T keys of their chunks, layers in the order of "layers"; "layers": the n layer indices, ascending;
+    "row_offsets": int64 array of len(videos) + 1 offsets into N}}.  ValueError with ragged=False, a CPU device, `row_outputs` or
+    `similarity`."""
     on_gpu = torch.device(device).type == 'cuda'
-    from .model import _row_output_keys
+    from .model import _row_output_keys, attn_map_layers
     row_keys = _row_output_keys(row_outputs)
+    attn_layers = ()
+    if attn_maps is not None and attn_maps is not False:
+        if similarity or row_outputs is not None:
+            raise ValueError('attn_maps does not combine with similarity or row_outputs: iefvad_forward_videos_attn returns neither')
+        if not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos')) or ragged is False:
+            raise ValueError('attn_maps takes the forward_videos loop: it needs a HIP device, batch_chunks > 0 and a model with '
+                             'forward_videos (and not ragged=False)')
+        attn_layers = attn_map_layers(attn_maps, model.temporal.num_layers)
+        ragged, host_list = True, False
     if row_outputs is not None:
         if similarity:
             raise ValueError('row_outputs does not combine with similarity: reduce the returned rows with similarity_rows')
@@ -912,6 +931,8 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         sink.dev_sim = []
     if row_outputs is not None:
         sink.dev_rows = {k: [] for k in row_keys}
+    if attn_layers:
+        sink.dev_rows = {"image_attn": [], "event_attn": []}
     with torch.no_grad():
         for s in streams if nl > 1 else ():
             s.wait_stream(torch.cuda.current_stream(device))         # e.g. a `model.to(device)` still in flight
@@ -919,13 +940,19 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
             _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, sim_rows,
                              row_keys)
         elif ragged:
-            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys)
+            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys,
+                             attn_layers)
         else:
             _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
                           bool(similarity))
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
-        if sink.dev_rows is not None:
+        if attn_layers:
+            offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
+            image, event = (v[0] if len(v) == 1 else torch.cat(v, dim=1) if v else torch.zeros(len(attn_layers), 0, maxlen, device=device)
+                            for v in (sink.dev_rows["image_attn"], sink.dev_rows["event_attn"]))
+            score_loader.last_result = {"attn_maps": {"image": image, "event": event, "layers": attn_layers, "row_offsets": offsets}}
+        elif sink.dev_rows is not None:
             D = getattr(getattr(model, 'temporal', None), 'embed_dim', 0)
             score_loader.last_result = {
                 # one library call (the host-list walk's usual case): its tensors as they are, no second copy
@@ -1237,7 +1264,7 @@ def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 
 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
-              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded"):
+              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
@@ -1249,12 +1276,17 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     per video) and "vis_files" (the PNG paths written).
     `vis_route` (read with vis=True only): "padded" = `score_loader(similarity=True)`, whole chunks through an outputs="full" model;
     "rows" = `score_loader(similarity="rows")`, the valid-row routes, any `outputs=`.  A vis evaluation is for plots, so with
-    `batch_chunks` unset "rows" packs 64 chunks in EVERY arithmetic (bf16x6 / fp16x3: the scores move inside the fp32 gates, as below)."""
+    `batch_chunks` unset "rows" packs 64 chunks in EVERY arithmetic (bf16x6 / fp16x3: the scores move inside the fp32 gates, as below).
+    `attn_maps` (True or encoder layer indices): passed on to `score_loader(attn_maps=...)` -- the `forward_videos` loop, 64 chunks per
+    call with `batch_chunks` unset, as for "rows" -- and the result dict gains "attn_maps" (device tensors, see there).  It does not
+    combine with vis=True (ValueError: the vis routes collect the similarity series).  `attn=True` is unrelated: it keeps returning the
+    reference's empty list."""
     if metric_tail not in ("host", "device"):
         raise ValueError('metric_tail must be "host" or "device"')
     if vis_route not in ("padded", "rows"):
         raise ValueError(f'vis_route must be "padded" or "rows" (got {vis_route!r})')
     vis_rows = bool(vis) and vis_route == "rows"
+    want_maps = attn_maps is not None and attn_maps is not False
     model.to(device)
     model.eval()
     if batch_chunks is None:
@@ -1264,10 +1296,11 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
         # the caller asks (batch_chunks=64: scores move at the 1e-7 level, inside the fp32 gates).  Five times the per-video rate on a
         # UCF-sized list.
         packed_same_bits = (getattr(model, "compute", None) in ("f32", "bf16") and torch.device(device).type == "cuda" and lanes == 1)
-        batch_chunks = 64 if (packed_same_bits or vis_rows) else 0
+        batch_chunks = 64 if (packed_same_bits or vis_rows or want_maps) else 0
     # vis=True: the same loop with the four similarity series collected on the device (`score_loader(similarity=True)`, a last result)
     got = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks, lanes=lanes,
-                       return_device=metric_tail == "device", similarity="rows" if vis_rows else bool(vis))
+                       return_device=metric_tail == "device", similarity="rows" if vis_rows else bool(vis),
+                       **(dict(attn_maps=attn_maps) if want_maps else {}))
     scores, classes, wi, we = got[:4]
     if metric_tail == "device":
         res = evaluate_scores_device((got[4], [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
@@ -1276,6 +1309,8 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
         res = evaluate_scores(scores, classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
                               total_samples=total_samples, log=log)
     last = dict(res, scores=scores, classes=classes, w_i_mean=wi, w_e_mean=we)
+    if want_maps:
+        last["attn_maps"] = score_loader.last_result["attn_maps"]
     if vis:
         last["similarity"] = got[-1]
         last["vis_files"] = draw_vis(vis_series(last, gt, vis_flavour), os.path.join('vis', str(args.exp_name)),      # test.py:59-62
@@ -1286,7 +1321,8 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
-         batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded"):
+         batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded",
+         *, attn_maps=None):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
@@ -1294,25 +1330,27 @@ def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, 
     positional orders differ from this one and from each other -- use `ucf_test` / `xd_test` below.
     `metric_tail="device"` (opt-in, here and in `ucf_test` / `xd_test`): the whole metric tail -- global, Ano-AUC and per-class --
     through the library on the device-resident scores (`evaluate_scores_device`) instead of sklearn on the host.
-    `vis_route="rows"` (opt-in, here and in `ucf_test` / `xd_test`): a vis=True evaluation on the valid-row routes (`_run_test`)."""
+    `vis_route="rows"` (opt-in, here and in `ucf_test` / `xd_test`): a vis=True evaluation on the valid-row routes (`_run_test`).
+    `attn_maps=` (keyword-only, here and in `ucf_test` / `xd_test`): the encoder's head-averaged attention maps of every valid snippet
+    in `last_result["attn_maps"]` (`_run_test`, `score_loader`); `attn=True` keeps returning the reference's empty list."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
-                                      False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route)
+                                      False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route, attn_maps=attn_maps)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
-             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded"):
+             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
-                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route)
+                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route, attn_maps)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
-            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded"):
+            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -1320,7 +1358,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
     if label_map is None:
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
-                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route)
+                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps)
     test.last_result = xd_test.last_result
     return ret
 

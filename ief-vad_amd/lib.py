@@ -35,7 +35,7 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows", "iefvad_gemm_split_unit", "iefvad_gemm_split_wide_launches",
            "iefvad_forward_videos_scaled", "iefvad_videos_scaled_workspace_bytes", "iefvad_forward_videos_similarity",
            "iefvad_forward_videos_host_similarity", "iefvad_videos_full_workspace_bytes", "iefvad_forward_videos_full",
-           "iefvad_forward_videos_host_full"]
+           "iefvad_forward_videos_host_full", "iefvad_forward_attn", "iefvad_forward_videos_attn"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -77,6 +77,11 @@ class Outputs(C.Structure):
     _fields_ = [("fused", _fp), ("logits", _fp), ("image_mu", _fp), ("event_mu", _fp),
                 ("image_logvar", _fp), ("event_logvar", _fp), ("w_i", _fp), ("w_e", _fp),
                 ("w_i_mean", _fp), ("w_e_mean", _fp)]
+
+
+class AttnMaps(C.Structure):
+    """iefvad_attn_maps (include/iefvad.h): device fp32 maps per layer, 0 where a layer is not asked for."""
+    _fields_ = [("image", _fp * MAX_LAYERS), ("event", _fp * MAX_LAYERS)]
 
 
 class StageTimes(C.Structure):
@@ -179,6 +184,11 @@ def load_library() -> C.CDLL:
     lib.iefvad_forward_videos_full.restype = C.c_int
     lib.iefvad_forward_videos_host_full.argtypes = lib.iefvad_forward_videos_host.argtypes[:10] + [C.POINTER(Outputs), C.c_void_p]
     lib.iefvad_forward_videos_host_full.restype = C.c_int
+    # the maps entries: `const iefvad_attn_maps*` in front of the stream
+    lib.iefvad_forward_attn.argtypes = lib.iefvad_forward.argtypes[:8] + [C.POINTER(AttnMaps), C.c_void_p]
+    lib.iefvad_forward_attn.restype = C.c_int
+    lib.iefvad_forward_videos_attn.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(AttnMaps), C.c_void_p]
+    lib.iefvad_forward_videos_attn.restype = C.c_int
     lib.iefvad_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
     lib.iefvad_loss_workspace_bytes.restype = C.c_size_t
     lib.iefvad_loss_forward.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,

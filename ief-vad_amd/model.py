@@ -54,7 +54,34 @@ _ROW_ENTRIES = {
     "_similarity": ("", lambda r: (), lambda r: (*r["vectors"], r["stream"], r["similarity"])),
     "_full": ("_full", lambda r: (r["out"],), lambda r: (r["out"], r["stream"])),
     "_scaled": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
+    "_attn": ("", lambda r: (), lambda r: (*r["vectors"], r["maps"], r["stream"])),
 }
+
+
+def attn_map_layers(attn_maps, num_layers: int) -> tuple:
+    """`attn_maps=` -> the encoder layers whose head-averaged attention maps are asked for, ascending: None / False -> none, True -> all
+    `num_layers`, else an int or an iterable of layer indices in 0 .. num_layers - 1 (ValueError otherwise)."""
+    if attn_maps is None or attn_maps is False:
+        return ()
+    if attn_maps is True:
+        return tuple(range(num_layers))
+    try:
+        want = [attn_maps] if isinstance(attn_maps, int) else list(attn_maps)
+    except TypeError:
+        raise ValueError(f"attn_maps takes True or an iterable of layer indices (got {attn_maps!r})") from None
+    bad = [l for l in want if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < num_layers]
+    if bad or not want:
+        raise ValueError(f"attn_maps takes True or layer indices in 0..{num_layers - 1} (got {attn_maps!r})")
+    return tuple(sorted(set(want)))
+
+
+def _attn_maps_struct(image: torch.Tensor, event: torch.Tensor, layers) -> "_lib.AttnMaps":
+    """`iefvad_attn_maps` over the [n, ...] result tensors: slice j is layer layers[j]."""
+    m = _lib.AttnMaps()
+    for j, l in enumerate(layers):
+        m.image[l] = image[j].data_ptr()
+        m.event[l] = event[j].data_ptr()
+    return m
 
 
 def _row_entry_suffix(similarity, outputs, full_entry: str, extras: bool = False):
@@ -423,12 +450,21 @@ class MMFMIL(nn.Module):
         return x.contiguous()
 
     def forward(self, img_visual, ev_visual, padding_mask=None, text=None, lengths=None, return_attn=False,
-                *, timed: bool = False, row_scale=None) -> Dict[str, torch.Tensor]:
+                *, timed: bool = False, row_scale=None, attn_maps=None) -> Dict[str, torch.Tensor]:
         """The reference's call (imf_vad.py:40-44; `padding_mask`, `text`, `lengths`, `return_attn` accepted and ignored as there).
         Keyword-only extras: `timed` (per-stage device times in `last_stage_times`), `row_scale=(s_img, s_ev)`: fp32 DEVICE vectors
         of [B*T] (either may be None) that multiply the input rows inside the library's input load (`iefvad_forward_scaled`: the
-        robustness sweep's `x[:, idx] * 0.01`, test2.py:71-77, without touching the caller's tensors)."""
+        robustness sweep's `x[:, idx] * 0.01`, test2.py:71-77, without touching the caller's tensors).
+        `attn_maps=True` (every encoder layer) or an iterable of layer indices (`iefvad_forward_attn`) adds `image_attn` and `event_attn`,
+        [n, B, T, T] fp32 in ascending layer order -- the head-averaged attention weights the reference's nn.MultiheadAttention calls
+        form and discard (imf_vad.py:115,121) -- and `attn_layers`, the n layer indices.  Every other result keeps its bits.  Not with
+        `timed` or `row_scale` (ValueError), compute="bf16" or model.train() (RuntimeError)."""
         self._noise_code()   # ValueError for an unsupported noise_model, as the reference raises
+        layers = attn_map_layers(attn_maps, self.temporal.num_layers)
+        if layers:
+            if timed or (row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None)):
+                raise ValueError("attn_maps= does not combine with timed=True or row_scale: iefvad_forward_attn takes neither")
+            self._attn_maps_served("model.train()" if self.training else None)
         if self.training:
             return self._forward_train(img_visual, ev_visual)
         if not (img_visual.is_cuda and ev_visual.is_cuda):
@@ -475,7 +511,15 @@ class MMFMIL(nn.Module):
                 o.w_i_mean, o.w_e_mean = res["w_i_mean"].data_ptr(), res["w_e_mean"].data_ptr()
             args = (self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], B,
                     C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), C.byref(o), C.c_void_p(stream))
-            if row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None):
+            if layers:
+                res["image_attn"] = torch.empty(len(layers), B, T, T, **f32)
+                res["event_attn"] = torch.empty(len(layers), B, T, T, **f32)
+                res["attn_layers"] = layers
+                maps = _attn_maps_struct(res["image_attn"], res["event_attn"], layers)
+                rc = lib.iefvad_forward_attn(*args[:8], C.byref(maps), args[8])
+                if rc != 0:
+                    raise RuntimeError("iefvad_forward_attn: " + _lib.last_error())
+            elif row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None):
                 sp = []
                 for sv in row_scale:
                     if sv is not None and (sv.dtype != torch.float32 or sv.device != device or sv.numel() != N or not sv.is_contiguous()):
@@ -491,8 +535,16 @@ class MMFMIL(nn.Module):
             if rc != 0:
                 raise RuntimeError("iefvad_forward: " + _lib.last_error())
         if self.outputs == "full":
-            return {k: res[k] for k in OUTPUT_KEYS}   # the reference's key order
+            return {k: res[k] for k in OUTPUT_KEYS + (("image_attn", "event_attn", "attn_layers") if layers else ())}   # the reference's key order
         return res
+
+    def _attn_maps_served(self, mode):
+        """RuntimeError where a maps request cannot be served: the bf16 arithmetic (its q | k | v are bf16 planes) and training."""
+        if self.compute == "bf16":
+            raise RuntimeError('attn_maps= is not available with compute="bf16" (its q | k | v are bf16 planes in another layout); '
+                               'use "f32", "bf16x6" or "fp16x3"')
+        if mode:
+            raise RuntimeError(f"attn_maps= is an evaluation request; it is not available under {mode} (call model.eval() first)")
 
     def forward_videos_host(self, imgs, evs, lengths, nan_to_num: bool = True, batch_chunks: int = 128, host_threads: int = 0,
                             wire_dtype: Optional[torch.dtype] = None, similarity: bool = False, *, outputs=None) -> Dict[str, torch.Tensor]:
@@ -534,7 +586,7 @@ class MMFMIL(nn.Module):
         front = (pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], (C.c_int32 * n)(*lens), n, 1 if nan_to_num else 0, int(batch_chunks), int(host_threads))
         return self._rows_call("iefvad_forward_videos_host", suffix, device, sum(lens), front, wide=wide)
 
-    def _rows_call(self, base, suffix, device, total, front, *, wide=(), weight_sums=False, workspace_for=None):
+    def _rows_call(self, base, suffix, device, total, front, *, wide=(), weight_sums=False, workspace_for=None, attn_layers=()):
         """One valid-row call, the entry `base + suffix` (`_ROW_ENTRIES`): allocates the results -- the three [total] vectors, a
         [total, D] tensor per key of `wide`, the similarity entries' [4, total] series, `w_colsum` -- and calls the entry with
         (handle, *front, [workspace, bytes,] the suffix's tail).  `workspace_for=(lengths array, nvideos)`: the device entries, whose
@@ -548,8 +600,15 @@ class MMFMIL(nn.Module):
             self._ensure_weights(device, stream)
             f32 = dict(dtype=torch.float32, device=device)
             res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
-            r = {"vectors": tuple(C.c_void_p(t.data_ptr()) for t in res.values()), "stream": C.c_void_p(stream), "out": None,
-                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0}
+            r = {"vectors": tuple(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), "stream": C.c_void_p(stream), "out": None,
+                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0, "maps": None}
+            if suffix == "_attn":
+                T = self.visual_length
+                res["image_attn"] = torch.empty(len(attn_layers), total, T, **f32)
+                res["event_attn"] = torch.empty(len(attn_layers), total, T, **f32)
+                res["attn_layers"] = tuple(attn_layers)
+                maps = _attn_maps_struct(res["image_attn"], res["event_attn"], attn_layers)
+                r["maps"] = C.byref(maps)
             if suffix == "_full":
                 o = _lib.Outputs()
                 for k in res:
@@ -606,7 +665,7 @@ class MMFMIL(nn.Module):
         return dict(zip(OUTPUT_KEYS, outs))
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
-                       weight_sums: bool = False, similarity: bool = False, outputs=None) -> Dict[str, torch.Tensor]:
+                       weight_sums: bool = False, similarity: bool = False, outputs=None, attn_maps=None) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
@@ -623,7 +682,19 @@ class MMFMIL(nn.Module):
         `outputs="full"`, or an iterable of names from OUTPUT_KEYS (`iefvad_forward_videos_full`), adds those keys of the reference's
         dict (imf_vad.py:152-161) as [sum(lengths), D] fp32 device tensors in packed order: the pass keeps them for its row set and
         copies the valid rows out -- whatever `outputs=` the model was built with; no padding is computed or written, and the other
-        three results keep their bits.  An unknown key, `similarity=True` and the sweep's extras are each refused (ValueError)."""
+        three results keep their bits.  An unknown key, `similarity=True` and the sweep's extras are each refused (ValueError).
+        `attn_maps=True` or an iterable of layer indices (`iefvad_forward_videos_attn`) adds `image_attn` and `event_attn`,
+        [n, sum(lengths), T] fp32 in ascending layer order, and `attn_layers`: row r is the head-averaged attention of valid snippet r
+        over the T keys of its chunk (columns >= the chunk's valid rows hold the weight of a pad key, as on the padded route); the other
+        three results keep their bits.  It combines with none of `similarity`, `outputs`, `row_scale`, `weight_sums` and
+        nan_to_num="always" (ValueError); compute="bf16" and model.train() raise RuntimeError."""
+        layers = attn_map_layers(attn_maps, self.temporal.num_layers)
+        if layers:
+            if similarity or outputs is not None or weight_sums or nan_to_num == "always" or \
+                    (row_scale is not None and any(sv is not None for sv in row_scale)):
+                raise ValueError("attn_maps= does not combine with similarity=True, outputs=, row_scale, weight_sums or nan_to_num='always': "
+                                 "iefvad_forward_videos_attn takes none of them")
+            self._attn_maps_served("model.train()" if self.training else None)
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos is an evaluation entry point; call model.eval() first")
         self._noise_code()
@@ -643,6 +714,8 @@ class MMFMIL(nn.Module):
                 raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {nrows} elements (sum of lengths) on {img_rows.device}")
         extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None
         wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_full", extras)
+        if layers:
+            suffix = "_attn"
         if not (img_rows.is_cuda and ev_rows.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         lens = [int(n) for n in lengths]
@@ -663,4 +736,4 @@ class MMFMIL(nn.Module):
         if extras:      # the scaled entry alone takes the two scale vectors, behind nan_to_num
             front += tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in scales)
         return self._rows_call("iefvad_forward_videos", suffix, device, total, front, wide=wide, weight_sums=weight_sums,
-                               workspace_for=(larr, len(lens)))
+                               workspace_for=(larr, len(lens)), attn_layers=layers)

@@ -289,6 +289,35 @@ int iefvad_forward_videos_host_full(iefvad_handle* h, const void* const* img_row
                                     int32_t wire_dtype, const int32_t* lengths, int32_t nvideos, int32_t nan_to_num,
                                     int32_t batch_chunks, int32_t host_threads, const iefvad_outputs* out, void* stream);
 
+/* ---- head-averaged attention maps of the temporal encoder (opt-in) ---------------------------------------------------
+ * What nn.MultiheadAttention(...)(x, x, x) returns second with need_weights=True (imf_vad.py:115,121 form it on every call and
+ * discard it): per encoder layer and modality the mean over the 8 heads of softmax(Q_h K_h^T / sqrt(d_h)), one [256, 256] fp32 map
+ * per 256-snippet chunk; row = query snippet, column = key snippet of the chunk, every row sums to 1.
+ *   iefvad_forward_attn          iefvad_forward plus `maps`; a map is [B*T, T]: query row r of chunk c at row c*256 + r.
+ *   iefvad_forward_videos_attn   iefvad_forward_videos plus `maps`; a map is [sum(lengths), T] in PACKED order: valid query row r
+ *                                of a chunk at the chunk's packed row + r, pad rows are not written.  Key columns >= the chunk's
+ *                                valid rows hold the weight of a pad key, as the padded route gives them (the reference attends
+ *                                to its zero rows).  A video that straddles micro-batch passes lands at each pass's row offset.
+ * A NULL layer is neither computed nor written; image and event are asked for separately.  The maps are formed in fp32 from the
+ * layer's fp32 q | k | v rows by iefvad_attention_maps_kernel (csrc/attention_maps.h) right behind the attention kernel, in a fixed
+ * order without atomics: the same call gives the same bits, and in the f32 arithmetic the valid-row maps equal the `[0:len]` rows of
+ * the dense maps on host-padded chunks bit for bit.  Every other result of the call has the bits of the call without maps.
+ * Workspace: iefvad_workspace_bytes / iefvad_videos_workspace_bytes, unchanged.  Served: compute F32, BF16X6 and FP16X3, D = 768 and
+ * 512, the three input dtypes, IEFVAD_DENSE_ENCODER=1.  These calls launch directly (the hipGraph replay of small batches is not
+ * used: the map pointers are per call).  Refused by name before any HIP call: a NULL handle, NULL maps, maps with every pointer NULL,
+ * a pointer at a layer index >= num_layers, a pointer that is not 16-byte aligned, compute = BF16 (its q | k | v are bf16 planes in
+ * another layout).  NOT covered: the host-list, scaled, similarity and full entries and training take no maps.
+ * Added without a change to any other entry or struct: IEFVAD_ABI_VERSION stays. */
+typedef struct iefvad_attn_maps {        /* DEVICE fp32, each nullable: a NULL layer is not computed */
+    float* image[IEFVAD_MAX_LAYERS];     /* dense: [B*T, T]; videos: [sum(lengths), T] */
+    float* event[IEFVAD_MAX_LAYERS];
+} iefvad_attn_maps;
+int iefvad_forward_attn(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                        size_t workspace_bytes, const iefvad_outputs* out, const iefvad_attn_maps* maps, void* stream);
+int iefvad_forward_videos_attn(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
+                               int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes, float* logits,
+                               float* w_i_mean, float* w_e_mean, const iefvad_attn_maps* maps, void* stream);
+
 /* ---- training-side loss head: forward, and its gradients w.r.t. the model's outputs -----------------
  * The three terms the reference's trainers add up (/root/reference/train/ucf_train.py:68-101, train/xd_train.py:60-75), as
  * device reductions over tensors iefvad_forward already produces:
