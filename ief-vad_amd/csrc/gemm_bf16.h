@@ -259,7 +259,10 @@ __global__ __launch_bounds__(256, 2) void iefvad_gemm_bf16_v1_kernel(GemmBArgs a
 // columns by v[ncol .. ncol + 3] and the 32 lanes of a row are summed by DPP in one fixed order; the sum over the wave tile's 128
 // columns goes to C2[row][column tile] as a plain store (no atomics: the scorer adds the N / 128 partials in ascending order, so a
 // row's logit never depends on which workgroup finished first).  h itself is stored only if C is non-null.
-template <bool MF16, int PASSES, bool DOT = false>
+// NW = 4 (gemm_split_small.h, MF16 and PASSES = 1 only): four waves share ONE image at smem -- wave w parks its 32 rows x 32 columns
+// (accumulator column tiles 0 .. 1 -> image columns 32 w ..), a barrier, and wave w runs the row-wise code over rows rq + 2 u,
+// u = 4 w .. 4 w + 3.  NW = 1 is every other kernel: a private image per wave, all 16 u.
+template <bool MF16, int PASSES, bool DOT = false, int NW = 1>
 __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const GemmBProblem& P, float* smem, int m0, int n0,
                                                    int wrow0, int wcol0, f32x16 (&acc)[PASSES][4],
                                                    f32x4 (&acc16)[2 * PASSES][8], float cscale = 1.0f, float* amax_out = nullptr) {
@@ -273,7 +276,10 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
     const int rq = lane >> 5, cq = lane & 31;
     const int ncol = n0 + wcol0 + 4 * cq;
     const bool has_resid = (epi == EPI_BIAS_RESID || epi == EPI_REFINE || epi == EPI_GATE);
-    float* E = smem + wave * (32 * GB2_EPI_LD);       // 16.9 KB per wave
+    static_assert(NW == 1 || (NW == 4 && MF16 && PASSES == 1), "shared image: four waves, one pass of 16x16 tiles");
+    constexpr int NB = 8 / NW, NU = 16 / NW;          // accumulator column tiles parked, row pairs processed per wave
+    const int B0 = NW == 1 ? 0 : wave * NB, U0 = NW == 1 ? 0 : wave * NU;
+    float* E = smem + (NW == 1 ? wave * (32 * GB2_EPI_LD) : 0);       // 16.9 KB per wave
     const f32x4 bv = *(const f32x4*)(P.bias + ncol);
     float* C32 = P.C;
     bf16_t* C16 = P.Cb;
@@ -284,7 +290,7 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
     float vmax = 0.f;
     // bf16-only results (in_proj q|k|v and the refinement's ReLU output in the bf16 mode): a lane takes EIGHT columns of a row,
     // so that a store is 16 bytes per lane like the fp32 ones (half the store instructions of the 8-byte form)
-    const bool wide16 = C16 && !C32 && !has_resid && !amax_out && (epi == EPI_BIAS || epi == EPI_QKV || epi == EPI_BIAS_RELU);
+    const bool wide16 = NW == 1 && C16 && !C32 && !has_resid && !amax_out && (epi == EPI_BIAS || epi == EPI_QKV || epi == EPI_BIAS_RELU);
     if (wide16) {
         const int rq4 = lane >> 4, c8 = lane & 15;
         const int ncol8 = n0 + wcol0 + 8 * c8;
@@ -339,12 +345,14 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
 #pragma unroll
                 for (int x = 0; x < 2; ++x)
 #pragma unroll
-                    for (int b = 0; b < 8; ++b)
+                    for (int b = 0; b < NB; ++b)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            E[(x * 16 + 4 * q16 + r) * GB2_EPI_LD + b * 16 + r16] = acc16[2 * a + x][b][r];
+                            E[(x * 16 + 4 * q16 + r) * GB2_EPI_LD + (B0 + b) * 16 + r16] = acc16[2 * a + x][b][r];
+                if constexpr (NW > 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); GB2_BARRIER(); }
 #pragma unroll
-                for (int u = 0; u < 16; ++u) {
+                for (int uu = 0; uu < NU; ++uu) {
+                    const int u = U0 + uu;
                     f32x4 v = *(const f32x4*)(E + (rq + 2 * u) * GB2_EPI_LD + 4 * cq);
                     v = v * cscale + bv;
 #pragma unroll
@@ -369,21 +377,22 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
 #pragma unroll
     for (int a = 0; a < PASSES; ++a) {
         const int mrow = m0 + wrow0 + a * 32 + rq;
-        f32x4 res[16];
+        f32x4 res[NU];
         if (has_resid) {
 #pragma unroll
-            for (int u = 0; u < 16; ++u)
-                res[u] = *(const f32x4*)(P.R + (size_t)(mrow + 2 * u) * ldc + ncol);
+            for (int uu = 0; uu < NU; ++uu)
+                res[uu] = *(const f32x4*)(P.R + (size_t)(mrow + 2 * (U0 + uu)) * ldc + ncol);
         }
         if constexpr (MF16) {
             // 16x16 accumulator map: col = lane & 15, row = 4 (lane >> 4) + reg; this pass takes row sub-tiles 2a, 2a+1
 #pragma unroll
             for (int x = 0; x < 2; ++x)
 #pragma unroll
-                for (int b = 0; b < 8; ++b)
+                for (int b = 0; b < NB; ++b)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        E[(x * 16 + 4 * q16 + r) * GB2_EPI_LD + b * 16 + r16] = acc16[2 * a + x][b][r];
+                        E[(x * 16 + 4 * q16 + r) * GB2_EPI_LD + (B0 + b) * 16 + r16] = acc16[2 * a + x][b][r];
+            if constexpr (NW > 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); GB2_BARRIER(); }
         } else {
 #pragma unroll
             for (int b = 0; b < 4; ++b)
@@ -392,18 +401,19 @@ __device__ __forceinline__ void gemm_wave_epilogue(const GemmBArgs& args, const 
                     E[((r & 3) + 8 * (r >> 2) + 4 * h) * GB2_EPI_LD + b * 32 + i] = acc[a][b][r];
         }
 #pragma unroll
-        for (int u = 0; u < 16; ++u) {
+        for (int uu = 0; uu < NU; ++uu) {
+            const int u = U0 + uu;
             f32x4 v = *(const f32x4*)(E + (rq + 2 * u) * GB2_EPI_LD + 4 * cq);
             v = v * cscale + bv;
             if (epi == EPI_QKV) v = v * scale;
             else if (epi == EPI_BIAS_RELU) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = (v[e] < 0.f) ? 0.f : v[e];
-            } else if (epi == EPI_BIAS_RESID) v = v + res[u];
-            else if (epi == EPI_REFINE) v = res[u] - alpha * v;
+            } else if (epi == EPI_BIAS_RESID) v = v + res[uu];
+            else if (epi == EPI_REFINE) v = res[uu] - alpha * v;
             else if (epi == EPI_GATE) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = res[u][e] > 0.f ? alpha * v[e] : 0.f;
+                for (int e = 0; e < 4; ++e) v[e] = res[uu][e] > 0.f ? alpha * v[e] : 0.f;
             }
             const size_t o = (size_t)(mrow + 2 * u) * ldc + nn;
             if (C32) GB2_STORE((f32x4*)(C32 + o), v);

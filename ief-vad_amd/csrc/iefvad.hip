@@ -29,6 +29,7 @@
 #include "gemm_bf16.h"
 #include "gemm_split.h"
 #include "gemm_split_wide.h"
+#include "gemm_split_small.h"
 #include "rowops.h"
 #include "refine_chain_bf16.h"
 #include "outproj_ln_chain_bf16.h"
@@ -704,7 +705,29 @@ static int launch_gemm_b(const GemmBArgs& a, int nz, hipStream_t stream, Timer& 
 }
 
 static std::atomic<unsigned long long> g_split_wide_launches{0};     // iefvad_gemm_split_wide_launches: which tiling ran is otherwise invisible
-static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false, int tile_n = 0) {
+static std::atomic<unsigned long long> g_split_small_launches{0};    // iefvad_gemm_split_small_launches
+// the small tiling of the bf16x6 arithmetic (gemm_split_small.h): the batch-invariant mode below the split kernels' crossover, and its unit entry
+static int launch_gemm_split_small(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage) {
+    const GemmSmallPlan pl = plan_gemm_split_small(a.M, a.N, a.K, nz, a.epi == EPI_BIAS_RELU_DOT, a.p[0].R && a.p[0].C2);
+    if (!pl.ok) {
+        if (pl.why == GEMM_BAD_DOT_EPILOGUE)
+            return fail("gemm(bf16x6, small): the dot-product epilogue takes one problem with its vector (R) and its partial sums (C2)");
+        return fail("gemm(bf16x6, small): shape M=%d N=%d K=%d nz=%d not a multiple of the %dx%dx64 tile", a.M, a.N, a.K, nz, kSplitSmallBM, kSplitBN);
+    }
+    hipEvent_t e = tm.begin(stage);
+    hipLaunchKernelGGL(iefvad_gemm_split_small_kernel, dim3(pl.wgs, 1, nz), dim3(256), GSS_LDS_BYTES, stream, a);
+    g_split_small_launches.fetch_add(1, std::memory_order_relaxed);
+    tm.end(e);
+    tm.gemm_launches += 1;
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// invariant: the handle is in the batch-invariant mode (LaunchPolicy::split_always): what the default mode would have left to the fp32
+// kernels runs on the small tiling (an IEFVAD_SPLIT_TILE preference still forces its tiling; all three give the same bits)
+static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage, bool f16 = false, int tile_n = 0,
+                             bool invariant = false) {
+    if (invariant && !f16 && tile_n == 0 && split_small_preferred(a.M, a.N, a.K, nz)) return launch_gemm_split_small(a, nz, stream, tm, stage);
     const GemmPlan pl = plan_gemm_split(a.M, a.N, a.K, nz, f16, tile_n, a.epi == EPI_BIAS_RELU_DOT, a.p[0].R && a.p[0].C2);
     switch (pl.reject) {
     case GEMM_OK: break;
@@ -760,7 +783,8 @@ struct Proj {
 };
 
 // D: the contraction length (the row width of A), the handle's embed dim
-static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage, int split_tile = 0) {
+static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage, int split_tile = 0,
+                       bool invariant = false) {
     const bool bf16 = (compute == IEFVAD_COMPUTE_BF16);
     if (p.epi == EPI_BIAS_RELU_DOT && !(use_split && compute == IEFVAD_COMPUTE_BF16X6))
         return fail("gemm: the dot-product epilogue exists in the bf16x6 split kernel only");
@@ -779,7 +803,7 @@ static int launch_proj(const Proj& p, int compute, bool use_split, int D, int ro
                 g.p[m].amaxA = p.amaxA[m]; g.p[m].amaxW = p.amaxW[m]; g.p[m].amaxC = p.amaxC[m];
             }
         }
-        return launch_gemm_split(g, p.nz, stream, tm, stage, f16, split_tile_for(split_tile, p.N, f16));
+        return launch_gemm_split(g, p.nz, stream, tm, stage, f16, split_tile_for(split_tile, p.N, f16), invariant);
     }
     if (!bf16) {
         GemmArgs g;
@@ -1156,7 +1180,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             p.amaxC[m] = b.am_qkv(l, m);
             if (bf) p.Cb[m] = b.qkvb[m]; else p.C[m] = b.qkv[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV, h->policy.split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV, h->policy.split_tile, h->policy.split_always)) return rc;
     }
 
     hipEvent_t e = tm.begin(ST_ATT);
@@ -1208,7 +1232,7 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             p.A32[m] = b.att[m]; p.A16[m] = b.attb[m]; p.amaxA[m] = b.am_att(l, m);
             p.C[m] = b.ybuf[m]; p.R[m] = b.cur[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT, h->policy.split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT, h->policy.split_tile, h->policy.split_always)) return rc;
 
         LnArgs la;
         memset(&la, 0, sizeof(la));
@@ -1324,7 +1348,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             p.A32[m] = b.xt[m]; p.A16[m] = b.xtb[m]; p.amaxA[m] = b.am_x(L - 1, m);
         }
         p.C[0] = b.mu_i; p.C2[0] = b.lv_i; p.C[1] = b.mu_e; p.C2[1] = b.lv_e;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD, h->policy.split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD, h->policy.split_tile, h->policy.split_always)) return rc;
 
         // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
         FusionArgs fa;
@@ -1365,7 +1389,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
             if (!keep_fused) p.C[0] = nullptr;
         }
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile, h->policy.split_always)) return rc;
         if (dot) {
             hipEvent_t e = tm.begin(ST_SCORER);
             hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
@@ -1379,7 +1403,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         p.set_w(0, h->ref2[k]);
         p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
         p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
+        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile, h->policy.split_always)) return rc;
     }
 
     // 5. scorer (imf_vad.py:150)
@@ -2302,37 +2326,73 @@ extern "C" int iefvad_gemm_bias(const void* A, const void* W, const float* bias,
 
 extern "C" uint64_t iefvad_gemm_split_wide_launches(void) { return g_split_wide_launches.load(std::memory_order_relaxed); }
 
-extern "C" int iefvad_gemm_split_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
-                                      int32_t qcols, float alpha, int32_t nz, int32_t tile_n, void* stream) {
+// the argument block of the two split unit entries from their common arguments; bm x bn: the tile the shape must fit
+static int gemm_split_unit_args(const char* who, const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
+                                int32_t qcols, float alpha, int32_t nz, int bm, int bn, GemmBArgs& g) {
     static const int epi_of[] = {EPI_BIAS, EPI_QKV, EPI_BIAS_RELU, EPI_BIAS_RESID, EPI_REFINE, EPI_HEADS, EPI_BIAS_RELU_DOT};
-    if (!io) return fail("iefvad_gemm_split_unit: null argument");
     auto aligned = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-    if (epilogue < 0 || epilogue >= (int)(sizeof(epi_of) / sizeof(epi_of[0]))) return fail("iefvad_gemm_split_unit: unknown epilogue %d", epilogue);
-    if (nz < 1 || nz > 2) return fail("iefvad_gemm_split_unit: nz = %d (1 or 2)", nz);
-    if (tile_n != 128 && tile_n != 256) return fail("iefvad_gemm_split_unit: tile_n = %d (128 or 256)", tile_n);
-    if (M <= 0 || N <= 0 || K < 64 || M % GS_BM || N % tile_n || K % 64)
-        return fail("iefvad_gemm_split_unit: shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", M, N, K, GS_BM, tile_n);
+    if (M <= 0 || N <= 0 || K < 64 || M % bm || N % bn || K % 64)
+        return fail("%s: shape M=%d N=%d K=%d not a multiple of the %dx%dx64 tile", who, M, N, K, bm, bn);
     const int epi = epi_of[epilogue];
     const bool heads = epi == EPI_HEADS, dot = epi == EPI_BIAS_RELU_DOT;
     const bool resid = epi == EPI_BIAS_RESID || epi == EPI_REFINE;
-    if (heads ? (N != 2 * ldc || ldc % 128) : (ldc < N || ldc % 4)) return fail("iefvad_gemm_split_unit: ldc = %d does not fit N = %d", ldc, N);
-    if (epi == EPI_QKV && (qcols < 0 || qcols > N || qcols % 8)) return fail("iefvad_gemm_split_unit: qcols = %d", qcols);
-    GemmBArgs g;
+    if (heads ? (N != 2 * ldc || ldc % 128) : (ldc < N || ldc % 4)) return fail("%s: ldc = %d does not fit N = %d", who, ldc, N);
+    if (epi == EPI_QKV && (qcols < 0 || qcols > N || qcols % 8)) return fail("%s: qcols = %d", who, qcols);
     memset(&g, 0, sizeof(g));
     g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = ldc; g.epi = epi; g.alpha = alpha; g.qcols = qcols;
     g.wplane = N * K * 2;
     for (int m = 0; m < nz; ++m) {
         if (!io->A[m] || !io->W[m] || !io->bias[m] || (!io->C[m] && !dot) || ((resid || dot) && !io->R[m]) || ((heads || dot) && !io->C2[m]))
-            return fail("iefvad_gemm_split_unit: problem %d lacks an operand of epilogue %d", m, epilogue);
+            return fail("%s: problem %d lacks an operand of epilogue %d", who, m, epilogue);
         if (!aligned(io->A[m]) || !aligned(io->W[m]) || !aligned(io->bias[m]) || !aligned(io->C[m]) || !aligned(io->R[m]) || !aligned(io->C2[m]))
-            return fail("iefvad_gemm_split_unit: operands must be 16-byte aligned");
+            return fail("%s: operands must be 16-byte aligned", who);
         g.p[m].A = (const bf16_t*)io->A[m]; g.p[m].W = (const bf16_t*)io->W[m]; g.p[m].bias = io->bias[m]; g.p[m].C = io->C[m];
         g.p[m].R = (resid || dot) ? io->R[m] : nullptr;
         g.p[m].C2 = (heads || dot) ? io->C2[m] : nullptr;
     }
+    return 0;
+}
+
+extern "C" int iefvad_gemm_split_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
+                                      int32_t qcols, float alpha, int32_t nz, int32_t tile_n, void* stream) {
+    if (!io) return fail("iefvad_gemm_split_unit: null argument");
+    if (epilogue < 0 || epilogue > IEFVAD_SPLIT_EPI_BIAS_RELU_DOT) return fail("iefvad_gemm_split_unit: unknown epilogue %d", epilogue);
+    if (nz < 1 || nz > 2) return fail("iefvad_gemm_split_unit: nz = %d (1 or 2)", nz);
+    if (tile_n != 128 && tile_n != 256) return fail("iefvad_gemm_split_unit: tile_n = %d (128 or 256)", tile_n);
+    GemmBArgs g;
+    if (int rc = gemm_split_unit_args("iefvad_gemm_split_unit", io, M, N, K, ldc, epilogue, qcols, alpha, nz, GS_BM, tile_n, g)) return rc;
     hipError_t e = raise_lds_limit((const void*)iefvad_gemm_split_n128_kernel);
     if (e == hipSuccess) e = raise_lds_limit((const void*)iefvad_gemm_split_n128x2_kernel);
     if (e != hipSuccess) return fail("iefvad_gemm_split_unit: %s", hipGetErrorString(e));
     Timer tm;
     return launch_gemm_split(g, nz, (hipStream_t)stream, tm, ST_QKV, false, tile_n);
+}
+
+extern "C" uint64_t iefvad_gemm_split_small_launches(void) { return g_split_small_launches.load(std::memory_order_relaxed); }
+
+extern "C" int iefvad_gemm_split_small_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
+                                            int32_t qcols, float alpha, int32_t nz, void* stream) {
+    if (!io) return fail("iefvad_gemm_split_small_unit: null argument");
+    if (epilogue < 0 || epilogue > IEFVAD_SPLIT_EPI_BIAS_RELU_DOT) return fail("iefvad_gemm_split_small_unit: unknown epilogue %d", epilogue);
+    if (nz < 1 || nz > 2) return fail("iefvad_gemm_split_small_unit: nz = %d (1 or 2)", nz);
+    GemmBArgs g;
+    if (int rc = gemm_split_unit_args("iefvad_gemm_split_small_unit", io, M, N, K, ldc, epilogue, qcols, alpha, nz, kSplitSmallBM, kSplitBN, g)) return rc;
+    Timer tm;
+    return launch_gemm_split_small(g, nz, (hipStream_t)stream, tm, ST_QKV);
+}
+
+// Batch-invariant mode (include/iefvad.h): flips LaunchPolicy::split_always.  The cached hipGraphs hold the other mode's launches, so
+// they go (after the device has finished with their staging buffers).  train.h never reads the flag: training keeps its own rule.
+extern "C" int iefvad_set_batch_invariant(iefvad_handle* h, int on) {
+    if (!h) return fail("iefvad_set_batch_invariant: null argument");
+    if (h->cfg.compute == IEFVAD_COMPUTE_FP16X3)
+        return fail("iefvad_set_batch_invariant: compute = FP16X3 has no batch-invariant mode (its operand scales are per chunk and per running maximum)");
+    if (h->cfg.compute != IEFVAD_COMPUTE_BF16X6) return 0;      // f32 and bf16 are batch-invariant as they are
+    const bool want = on != 0;
+    if (h->policy.split_always == want) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    release_graphs(h);
+    h->policy.split_always = want;
+    return 0;
 }

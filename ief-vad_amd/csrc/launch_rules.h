@@ -43,6 +43,10 @@ struct LaunchPolicy {
     bool persist;          // bf16 mode: the persistent out_proj + LayerNorm, heads + fusion and attention kernels from two blocks per CU on (IEFVAD_PERSIST=0: off)
     int split_tile;        // IEFVAD_SPLIT_TILE=128 / 256: the bf16x6 projections on one tiling of the split kernel (unset: plan_gemm_split's rule)
     bool dense_encoder;    // IEFVAD_DENSE_ENCODER=1: whole-video passes run the encoder on whole 256-row chunks (pad rows computed), the tail on the gathered valid rows
+    // iefvad_set_batch_invariant (not an environment switch; launch_policy leaves it false): a bf16x6 handle runs the split
+    // arithmetic at EVERY row count, so its results do not depend on how the caller batches.  Below the split kernels'
+    // crossover the projections run on the small tiling (plan_gemm_split_small, same bits as the 128 x 128 one).
+    bool split_always;
 };
 // from the switches' numeric values (0 = unset): out-of-range values fall back to the defaults
 static inline LaunchPolicy launch_policy(int rowblock_off, int rowblock_min_wgs, int chain_min_blocks, bool persist, int split_tile, bool dense_encoder) {
@@ -53,6 +57,7 @@ static inline LaunchPolicy launch_policy(int rowblock_off, int rowblock_min_wgs,
     p.persist = persist;
     p.split_tile = (split_tile == 128 || split_tile == 256) ? split_tile : 0;
     p.dense_encoder = dense_encoder;
+    p.split_always = false;
     return p;
 }
 
@@ -142,6 +147,34 @@ static inline GemmPlan plan_gemm_split(int M, int N, int K, int nz, bool f16, in
     if (dot_epilogue && (f16 || nz != 1 || !dot_operands)) return gemm_refused(GEMM_BAD_DOT_EPILOGUE);
     return GemmPlan{wide ? GEMM_SPLIT_N128X2 : f16 ? GEMM_SPLIT_F16_N128 : GEMM_SPLIT_N128, (M / GS_BM) * (N / (wide ? 256 : kSplitBN)), GEMM_OK};
 }
+// The small tiling of the bf16x6 arithmetic (gemm_split_small.h): 32 x 128 workgroups of four waves, 24 MFMAs per k-tile and wave
+// against the 128 x 128 tiling's 96, bit-identical to it.  In the batch-invariant mode (LaunchPolicy::split_always) it takes a
+// projection while its own grid fits the chip's 512 workgroup slots (256 CUs x 2 by LDS) in ONE round, i.e. up to kSplitSmallMaxWgs =
+// 128 workgroups of the 128 x 128 tiling, and plan_gemm_split takes the rest.  Measured (tools/batch_invariant_probe.py, K = 768, us per
+// launch, medians of 5 outside each other's min - max; profiles/batch_invariant_probe.log): the small tiling wins at every grid up to
+// 120 workgroups of 128 x 128 -- N = 768: 17.6 against 29.3 at 12, 24.4 against 31.6 at 96; N = 1536: 27.0 against 32.2 at 120;
+// N = 2304: 27.1 against 32.1 at 108 -- and loses from 144 on, its second round (N = 1536: 45.2 against 31.6; N = 2304: 46.7 against
+// 32.0).  That is above kSplitMinWgs = 72, the default mode's crossover between the 128 x 128 tiling and the short-chain fp32 kernels,
+// which stays where it is: the default selection does not change.  Bits do not depend on the choice.  A plan of its own: GemmKernel /
+// GemmReject keep their enumerators.
+static const int kSplitSmallBM = 32;
+static const int kSplitSmallMaxWgs = 128;     // in workgroups of the 128 x 128 tiling: 4 x as many of 32 x 128 = one round of 512 slots
+struct GemmSmallPlan {
+    bool ok;               // false: refused, `why` says which of the shape rules
+    int wgs;               // grid (wgs, 1, nz)
+    GemmReject why;        // GEMM_OK, GEMM_BAD_SHAPE or GEMM_BAD_DOT_EPILOGUE
+};
+static inline GemmSmallPlan plan_gemm_split_small(int M, int N, int K, int nz, bool dot_epilogue = false, bool dot_operands = false) {
+    if (M <= 0 || N <= 0 || M % kSplitSmallBM || N % kSplitBN || K % 64 || K < 64 || nz < 1 || nz > 2) return GemmSmallPlan{false, 0, GEMM_BAD_SHAPE};
+    if (dot_epilogue && (nz != 1 || !dot_operands)) return GemmSmallPlan{false, 0, GEMM_BAD_DOT_EPILOGUE};
+    return GemmSmallPlan{true, (M / kSplitSmallBM) * (N / kSplitBN), GEMM_OK};
+}
+// batch-invariant mode: which split tiling a bf16x6 projection runs on
+static inline bool split_small_preferred(int M, int N, int K, int nz) {
+    if (M % GS_BM || N % kSplitBN || K % 64 || K < 64) return true;      // no 128 x 128 plan: the small plan accepts or refuses the shape
+    return (M / GS_BM) * (N / kSplitBN) * nz <= kSplitSmallMaxWgs;
+}
+
 // IEFVAD_SPLIT_TILE is a preference: a projection the wide tiling cannot take (fp16x3, N % 256 != 0) runs on the narrow one
 static inline int split_tile_for(int preferred, int N, bool f16) {
     return (f16 || (preferred == 256 && N % 256)) ? (f16 ? 0 : 128) : preferred;
@@ -206,6 +239,7 @@ static inline PassFlags plan_pass(const LaunchPolicy& p, int compute, int rows) 
     f.ip_chain = bf && !p.no_inproj_chain && rows % IC_BM == 0 && (rows / IC_BM) * 2 >= p.rowblock_min_wgs;
     f.need_xb0 = bf && !f.ip_chain;
     f.splitmb = (compute == IEFVAD_COMPUTE_BF16X6 || compute == IEFVAD_COMPUTE_FP16X3) && split_eligible(rows, kSplitD, kSplitD, 1);
+    if (p.split_always && compute == IEFVAD_COMPUTE_BF16X6) f.splitmb = true;      // batch-invariant: one arithmetic at every row count
     f.f16mb = f.splitmb && compute == IEFVAD_COMPUTE_FP16X3;
     f.ln_fused = bf && !p.no_ln_fusion && rows % OC_BM == 0 && (rows / OC_BM) * 2 >= p.rowblock_min_wgs;
     return f;
@@ -225,6 +259,7 @@ static inline TailFlags plan_tail(const LaunchPolicy& p, int compute, int rows, 
     const bool bf = compute == IEFVAD_COMPUTE_BF16;
     TailFlags f;
     f.tail_split = splitmb && (!compacted || split_eligible(rows, kSplitD, kSplitD, 1));   // bf16x6: a small compact set runs on the fp32 kernels
+    if (p.split_always && compute == IEFVAD_COMPUTE_BF16X6) f.tail_split = true;           // batch-invariant: compacted or not, hence fold = (K >= 1)
     f.heads_rows = bf && !p.no_heads_fusion && heads_packed && rows % HC_BM == 0 && (rows / HC_BM) * HC_THIRDS >= p.rowblock_min_wgs;
     f.chain = bf && K > 0 && !p.no_chain && chain_packed && rows % RC_BM == 0 && rows / RC_BM >= p.chain_min_blocks;
     f.fold = f.tail_split && compute == IEFVAD_COMPUTE_BF16X6 && K >= 1;

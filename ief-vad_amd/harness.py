@@ -1295,7 +1295,10 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
         # are bit-identical); "bf16x6" / "fp16x3" pick their kernels by batch size, so they keep the reference's per-video pattern unless
         # the caller asks (batch_chunks=64: scores move at the 1e-7 level, inside the fp32 gates).  Five times the per-video rate on a
         # UCF-sized list.
-        packed_same_bits = (getattr(model, "compute", None) in ("f32", "bf16") and torch.device(device).type == "cuda" and lanes == 1)
+        # A "bf16x6" model built with batch_invariant=True runs one arithmetic at every batch size: packed gives its per-video bits too.
+        compute = getattr(model, "compute", None)
+        invariant = compute in ("f32", "bf16") or (compute == "bf16x6" and getattr(model, "batch_invariant", False))
+        packed_same_bits = (invariant and torch.device(device).type == "cuda" and lanes == 1)
         batch_chunks = 64 if (packed_same_bits or vis_rows or want_maps) else 0
     # vis=True: the same loop with the four similarity series collected on the device (`score_loader(similarity=True)`, a last result)
     got = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks, lanes=lanes,

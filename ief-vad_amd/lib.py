@@ -35,7 +35,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_gather_windows", "iefvad_auc_ap_grouped", "iefvad_auc_ap_grouped_workspace_bytes", "iefvad_similarity_rows", "iefvad_gemm_split_unit", "iefvad_gemm_split_wide_launches",
            "iefvad_forward_videos_scaled", "iefvad_videos_scaled_workspace_bytes", "iefvad_forward_videos_similarity",
            "iefvad_forward_videos_host_similarity", "iefvad_videos_full_workspace_bytes", "iefvad_forward_videos_full",
-           "iefvad_forward_videos_host_full", "iefvad_forward_attn", "iefvad_forward_videos_attn"]
+           "iefvad_forward_videos_host_full", "iefvad_forward_attn", "iefvad_forward_videos_attn",
+           "iefvad_gemm_split_small_unit", "iefvad_gemm_split_small_launches", "iefvad_set_batch_invariant"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -258,6 +259,13 @@ def load_library() -> C.CDLL:
     lib.iefvad_gemm_split_unit.restype = C.c_int
     lib.iefvad_gemm_split_wide_launches.argtypes = []
     lib.iefvad_gemm_split_wide_launches.restype = C.c_uint64
+    lib.iefvad_gemm_split_small_unit.argtypes = [C.POINTER(GemmSplitIO), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_float, C.c_int32, C.c_void_p]
+    lib.iefvad_gemm_split_small_unit.restype = C.c_int
+    lib.iefvad_gemm_split_small_launches.argtypes = []
+    lib.iefvad_gemm_split_small_launches.restype = C.c_uint64
+    lib.iefvad_set_batch_invariant.argtypes = [C.c_void_p, C.c_int]
+    lib.iefvad_set_batch_invariant.restype = C.c_int
     lib.iefvad_split_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.iefvad_split_bf16x3.restype = C.c_int
     lib.iefvad_split_bf16x3_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

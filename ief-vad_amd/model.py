@@ -280,15 +280,23 @@ class MMFMIL(nn.Module):
                    "bf16x6": the fp32 path with every dense projection computed as six bf16 MFMA products of the exact
                  three-term bf16 split of both fp32 operands (csrc/gemm_split.h): fp32-accurate -- held to the same
                  tolerances as "f32" -- at the bf16 matrix-core rate.  Batches too small to fill the chip run on the
-                 "f32" kernels, so scores are fp32-accurate but not bit-identical across batch sizes in this mode.
+                 "f32" kernels, so scores are fp32-accurate but not bit-identical across batch sizes in this mode
+                 (unless `batch_invariant=True`, below).
                    "fp16x3" (opt-in, near-fp32): the "bf16x6" flow with two fp16 terms per operand and three products per
                  multiply-add (22-bit products, half the MFMAs); operands are scaled by powers of two from running max |.|
                  words the producing kernels maintain (range-safe).  Per-projection error vs fp64 ~1.8x the fp32 path's.
+      batch_invariant  (default False) with compute="bf16x6": every projection and attention of the evaluation forward runs in the
+                   split arithmetic at EVERY batch size (`iefvad_set_batch_invariant`; small launches on the small tiling of
+                   csrc/gemm_split_small.h), so a video's results are the same bits at B = 1 and B = 8192, padded or on the valid-row
+                   routes, per video, packed or from host lists -- the guarantee "f32" gives.  Still held to the "f32" tolerances; a small
+                   call costs more than in the default mode.  Accepted and inert with "f32" and "bf16" (already invariant); ValueError
+                   with "fp16x3".  Carried by `lanes(n)`; training is not affected.
     """
 
     def __init__(self, num_class: int, embed_dim: int, visual_length: int, visual_width: int, visual_head: int,
                  visual_layers: int, attn_window: int, prompt_prefix: int, prompt_postfix: int, device, args,
-                 *, outputs: str = "full", micro_batch: int = 0, compute: str = "f32", graph_chunks: int = 0):
+                 *, outputs: str = "full", micro_batch: int = 0, compute: str = "f32", graph_chunks: int = 0,
+                 batch_invariant: bool = False):
         super().__init__()
         self.num_class = num_class
         self.visual_length = visual_length
@@ -307,8 +315,12 @@ class MMFMIL(nn.Module):
             raise ValueError("compute must be 'f32', 'bf16', 'bf16x6' or 'fp16x3'")
         self.outputs = outputs
         self.micro_batch = micro_batch
+        if batch_invariant and compute == "fp16x3":
+            raise ValueError('batch_invariant=True is not available with compute="fp16x3" (its operand scales are per chunk and per '
+                             'running maximum); use "bf16x6" ("f32" and "bf16" are batch-invariant as they are)')
         self.compute = compute
         self.graph_chunks = graph_chunks
+        self.batch_invariant = bool(batch_invariant)
         self._handle: Optional[C.c_void_p] = None
         self._handle_key = None
         self._weights_sig = None
@@ -341,7 +353,7 @@ class MMFMIL(nn.Module):
         t = self.temporal
         key = (device.index, t.embed_dim, self.visual_length, t.num_heads, t.num_layers, t.num_refinement_steps,
                self._noise_code(), float(t.lambda_ref), float(t.nu), float(t.epsilon), int(self.micro_batch), self.compute,
-               int(self.graph_chunks))
+               int(self.graph_chunks), bool(self.batch_invariant))
         if self._handle is not None and key == self._handle_key:
             return
         self._release()
@@ -360,6 +372,11 @@ class MMFMIL(nn.Module):
         if rc != 0:
             raise RuntimeError("iefvad_create: " + _lib.last_error())
         self._handle, self._handle_key = h, key
+        if self.batch_invariant:
+            with torch.cuda.device(device):
+                rc = lib.iefvad_set_batch_invariant(h, 1)
+            if rc != 0:
+                raise RuntimeError("iefvad_set_batch_invariant: " + _lib.last_error())
 
     def _ensure_weights(self, device: torch.device, stream: int):
         t = self.temporal

@@ -665,6 +665,28 @@ uint64_t iefvad_gemm_split_wide_launches(void);
 int iefvad_gemm_split_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
                            int32_t qcols, float alpha, int32_t nz, int32_t tile_n, void* stream);
 
+/* The same projection on the SMALL tiling of the bf16x6 arithmetic (32 x 128 block tile, four waves of 32 x 32: a quarter of the
+ * 128 x 128 tiling's MFMAs per wave and k-tile), the kernel the batch-invariant mode launches below the split kernels' crossover.
+ * Same operands and epilogues as iefvad_gemm_split_unit, no tile_n; M % 32 == 0, N % 128 == 0, K % 64 == 0, K >= 64.  Every
+ * output element is summed in the order of the other two tilings: the results agree with theirs bit for bit, and this entry lets a
+ * unit test say so.  iefvad_gemm_split_small_launches counts this kernel's launches the way iefvad_gemm_split_wide_launches
+ * counts the wide tiling's.  Added without a change to any other entry: IEFVAD_ABI_VERSION stays. */
+int iefvad_gemm_split_small_unit(const iefvad_gemm_split_io* io, int32_t M, int32_t N, int32_t K, int32_t ldc, int32_t epilogue,
+                                 int32_t qcols, float alpha, int32_t nz, void* stream);
+uint64_t iefvad_gemm_split_small_launches(void);
+
+/* Batch-invariant mode of an IEFVAD_COMPUTE_BF16X6 handle (on != 0; off is the default).  By default a bf16x6 handle runs a
+ * micro-batch's projections and attention in the split arithmetic only from 6 chunks on and in the f32 arithmetic below, so a
+ * video's results differ at the 1e-7 level with what else is in the launch.  In this mode every projection and every attention of
+ * the evaluation forward runs in the split arithmetic at every row count (the small tiling above takes the small launches): the
+ * results of a chunk or a video are the same bits at B = 1 and B = 8192, on the padded and the valid-row routes, per video,
+ * packed or from host lists.  The arithmetic stays fp32-accurate (the gates of the bf16x6 mode hold); a small call costs more than
+ * in the default mode.  IEFVAD_COMPUTE_F32 and IEFVAD_COMPUTE_BF16 handles are already batch-invariant: the call succeeds and
+ * changes nothing.  IEFVAD_COMPUTE_FP16X3 is refused: its operand scales are per chunk and per running maximum.  The call waits
+ * for the device and releases the handle's cached hipGraphs, so a later small forward captures the new launches.  Training entries
+ * keep their own kernel rule and are not affected.  Not thread-safe against calls on the same handle.  IEFVAD_ABI_VERSION stays. */
+int iefvad_set_batch_invariant(iefvad_handle* h, int on);
+
 /* The exact three-term bf16 split of n fp32 values (n % 4 == 0): planes[0..n) = bf16(x),
  * planes[n..2n) = bf16(x - p0), planes[2n..3n) = bf16(x - p0 - p1), round-to-nearest-even; x == p0 + p1 + p2
  * for finite x.  What iefvad_set_weights applies to every projection matrix in IEFVAD_COMPUTE_BF16X6. */
