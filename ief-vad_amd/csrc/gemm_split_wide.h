@@ -7,7 +7,7 @@
 // wave -- and lets a wave own 32 x 256: the W ring cycles over half-tiles it = 2 kt + hh (columns n0 + 128 hh .. of k-tile kt),
 // while A is staged, read and split ONCE per k-tile for both halves.  Per MFMA: half the split VALU and A staging, 20 % fewer
 // LDS-DMA instructions, 7 % fewer LDS reads; each A panel crosses the fabric for half as many column groups.  32 accumulators,
-// 243 VGPRs, no AGPRs, no scratch, two waves per SIMD.  Each output element sums its k-tiles in ascending order and the six
+// 214-226 VGPRs by epilogue kind (one kernel per kind, at the end of this file), no AGPRs, no scratch, two waves per SIMD.  Each output element sums its k-tiles in ascending order and the six
 // products of a k-tile in gemm_split.h's order, so the results are that kernel's BIT FOR BIT (tests/test_gpu_gemm_split_wide.py),
 // and plan_gemm_split (launch_rules.h) chooses between the two by grid size alone.
 // Measured against the 128 x 128 kernel in one lease: 0.93 of its time from 4,000 workgroups on (235 against 218
@@ -21,12 +21,15 @@
 #pragma once
 #include <type_traits>
 #include "gemm_split.h"
+#include "gemm_split_epilogue.h"
 
 #ifndef GS_WIDE_SPREAD     // 1 = half h splits A half-fragments 2h, 2h+1 of the next k-tile; 0 = the first half splits all four
 #define GS_WIDE_SPREAD 1   // (within noise of each other, profiles/split_wide_gemm_tune.log)
 #endif
 #undef GS_DIAG_STAMP
 
+// EPI, STORE_H: the epilogue kind of the kernel and, for the dot kind, whether h is stored (gemm_split_epilogue.h)
+template <int EPI, bool STORE_H>
 __device__ __forceinline__ void gemm_split_wide_body(const GemmBArgs& args, float* smem) {
     constexpr int NA = 2, NH = 2;                      // 16-row tiles per wave, column halves per block
     constexpr bool F16 = false;                        // (the fp16x3 arithmetic has the narrow tiling only)
@@ -314,11 +317,12 @@ __device__ __forceinline__ void gemm_split_wide_body(const GemmBArgs& args, floa
 #undef GS_FENCE
 #undef GLDS16
     // (the last tile ended with lgkmcnt(0) + barrier: the ring is dead, the epilogue image may overwrite it)
-    f32x16 unused[NA / 2][4];
-    // (NH = 2: once per column half; the park region is private to the wave, whose LDS accesses stay in program order)
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh)
-        gemm_wave_epilogue<true, NA / 2, !F16>(args, P, smem, m0, n0, wrow0, wcol0 + hh * BN, unused, acc16[hh], cscale, F16 ? P.amaxC : nullptr);
+    // The epilogue is specialised per kind (gemm_split_epilogue.h).  Its lane index is laundered here so that hipcc cannot form the
+    // epilogue's lane-dependent addresses above the k-loop, where they would cost the loop its registers.
+    (void)cscale;                                      // (1 here: the specialised epilogue holds it as a constant)
+    int elane = lane;
+    asm volatile("" : "+v"(elane));
+    gemm_split_wide_epilogue<EPI, STORE_H>(args, P, smem, m0, n0, uwave, elane, acc16);
 #ifdef GB2_CLOCK_DIAG
     if (threadIdx.x == 0 && P.C2) {
         unsigned long long* dy = (unsigned long long*)P.C2 + 5 * gridDim.x * gridDim.z + 2 * (blockIdx.x + gridDim.x * blockIdx.z);
@@ -328,8 +332,44 @@ __device__ __forceinline__ void gemm_split_wide_body(const GemmBArgs& args, floa
 #endif
 }
 
-// 128 x 256 as two column halves of 128, two workgroups per CU
-__global__ __launch_bounds__(256, 2) void iefvad_gemm_split_n128x2_kernel(GemmBArgs args) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    gemm_split_wide_body(args, smem);
+// 128 x 256 as two column halves of 128, two workgroups per CU: one kernel per epilogue kind.  The kind is chosen on the host
+// (gemm_split_wide_kernel), so a kernel's code holds one epilogue and hipcc allocates the k-loop's registers as it did for the
+// single kernel (a switch inside one kernel moved the seven kinds' scalar and address work above the loop: 256 VGPRs and scratch).
+// Every name begins with iefvad_gemm_split_n128x2_kernel, which is what the profile summaries select by.
+typedef void (*GemmSplitWideKernel)(GemmBArgs);
+#define GSW_KERNEL(suffix, EPI, STORE_H)                                                                      \
+    __global__ __launch_bounds__(256, 2) void iefvad_gemm_split_n128x2_kernel##suffix(GemmBArgs args) {       \
+        extern __shared__ __attribute__((aligned(16))) float smem[];                                          \
+        gemm_split_wide_body<EPI, STORE_H>(args, smem);                                                       \
+    }
+GSW_KERNEL(, EPI_BIAS, true)
+GSW_KERNEL(_qkv, EPI_QKV, true)
+GSW_KERNEL(_relu, EPI_BIAS_RELU, true)
+GSW_KERNEL(_resid, EPI_BIAS_RESID, true)
+GSW_KERNEL(_refine, EPI_REFINE, true)
+GSW_KERNEL(_heads, EPI_HEADS, true)
+GSW_KERNEL(_gate, EPI_GATE, true)
+GSW_KERNEL(_dot, EPI_BIAS_RELU_DOT, false)
+GSW_KERNEL(_dot_h, EPI_BIAS_RELU_DOT, true)
+#undef GSW_KERNEL
+
+// every kernel above, for the callers that raise the dynamic-LDS limit
+static const GemmSplitWideKernel kGemmSplitWideKernels[] = {
+    iefvad_gemm_split_n128x2_kernel,        iefvad_gemm_split_n128x2_kernel_qkv,   iefvad_gemm_split_n128x2_kernel_relu,
+    iefvad_gemm_split_n128x2_kernel_resid,  iefvad_gemm_split_n128x2_kernel_refine, iefvad_gemm_split_n128x2_kernel_heads,
+    iefvad_gemm_split_n128x2_kernel_gate,   iefvad_gemm_split_n128x2_kernel_dot,   iefvad_gemm_split_n128x2_kernel_dot_h};
+
+// The kernel of an epilogue kind; store_h: the dot kind also stores h (C is given).  nullptr: no such kind.
+static inline GemmSplitWideKernel gemm_split_wide_kernel(int epi, bool store_h) {
+    switch (epi) {
+    case EPI_BIAS: return iefvad_gemm_split_n128x2_kernel;
+    case EPI_QKV: return iefvad_gemm_split_n128x2_kernel_qkv;
+    case EPI_BIAS_RELU: return iefvad_gemm_split_n128x2_kernel_relu;
+    case EPI_BIAS_RESID: return iefvad_gemm_split_n128x2_kernel_resid;
+    case EPI_REFINE: return iefvad_gemm_split_n128x2_kernel_refine;
+    case EPI_HEADS: return iefvad_gemm_split_n128x2_kernel_heads;
+    case EPI_GATE: return iefvad_gemm_split_n128x2_kernel_gate;
+    case EPI_BIAS_RELU_DOT: return store_h ? iefvad_gemm_split_n128x2_kernel_dot_h : iefvad_gemm_split_n128x2_kernel_dot;
+    default: return nullptr;
+    }
 }

@@ -185,7 +185,6 @@ static hipError_t raise_lds_limit(const void* fn = nullptr) {
         {(const void*)iefvad_attention_pbf16_rows_kernel, APB_LDS_BYTES},
         {(const void*)iefvad_gemm_f32_t256_kernel, GB2_LDS_BYTES},
         {(const void*)iefvad_gemm_split_n128_kernel, GS_LDS_BYTES_OF(2)},
-        {(const void*)iefvad_gemm_split_n128x2_kernel, GS_LDS_BYTES_OF(2)},
         {(const void*)iefvad_attention_split_kernel, ATS_LDS_BYTES},
         {(const void*)iefvad_attention_split_rows_kernel, ATS_LDS_BYTES},
         {(const void*)iefvad_attention_split_train_kernel, ATS_LDS_BYTES},
@@ -200,6 +199,10 @@ static hipError_t raise_lds_limit(const void* fn = nullptr) {
     for (const auto& k : table)
         if (!fn || fn == k.fn)
             if (hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes); e != hipSuccess) return e;
+    // the 128 x 256 split tiling is one kernel per epilogue kind: fn = iefvad_gemm_split_n128x2_kernel stands for all of them
+    if (!fn || fn == (const void*)iefvad_gemm_split_n128x2_kernel)
+        for (const GemmSplitWideKernel k : kGemmSplitWideKernels)
+            if (hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2)); e != hipSuccess) return e;
     return hipSuccess;
 }
 
@@ -739,10 +742,22 @@ static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Tim
         return fail("gemm(bf16x6): the dot-product epilogue takes one bf16x6 problem with its vector (R) and its partial sums (C2)");
     }
     const dim3 grid(pl.wgs, 1, nz);
+    // the 128 x 256 tiling has one kernel per epilogue kind, whose stores are unconditional: every problem brings the outputs of its kind
+    GemmSplitWideKernel wide = nullptr;
+    if (pl.kernel == GEMM_SPLIT_N128X2) {
+        const bool dot = a.epi == EPI_BIAS_RELU_DOT;
+        const bool resid = a.epi == EPI_BIAS_RESID || a.epi == EPI_REFINE || a.epi == EPI_GATE;
+        wide = gemm_split_wide_kernel(a.epi, a.p[0].C != nullptr);
+        if (!wide) return fail("gemm(bf16x6): unknown epilogue %d", a.epi);
+        if (a.epi == EPI_HEADS && a.ldc % 128) return fail("gemm(bf16x6): the heads epilogue needs ldc %% 128 == 0 (ldc = %d)", a.ldc);
+        for (int m = 0; m < nz; ++m)
+            if (!a.p[m].bias || (!dot && !a.p[m].C) || ((resid || dot) && !a.p[m].R) || ((dot || a.epi == EPI_HEADS) && !a.p[m].C2))
+                return fail("gemm(bf16x6): problem %d lacks an operand of epilogue %d", m, a.epi);
+    }
     hipEvent_t e = tm.begin(stage);
     switch (pl.kernel) {
     case GEMM_SPLIT_N128X2:
-        hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
+        hipLaunchKernelGGL(wide, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
         g_split_wide_launches.fetch_add(1, std::memory_order_relaxed);
         break;
     case GEMM_SPLIT_F16_N128: hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a); break;
@@ -1149,7 +1164,10 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
         if (rc) return rc;
     }
     if (b.f16mb) {
-        HIP_TRY(hipMemsetAsync(b.am, 0, (size_t)amax_act_tensors(b.L, b.K) * b.mbs * sizeof(float), stream));
+        // every (tensor, chunk) of this micro-batch starts from zero words; a kernel node, not a memset node, when captured (rowops.h)
+        const unsigned words = (unsigned)b.nb * IEF_AMAX_PARTS;
+        hipLaunchKernelGGL(iefvad_amax_zero_kernel, dim3((words / 4 + 255) / 256, amax_act_tensors(b.L, b.K)), dim3(256), 0, stream, b.am,
+                           b.mbs, words);
         hipEvent_t e = tm.begin(ST_CAST);
         hipLaunchKernelGGL(iefvad_amax_chunk_kernel, dim3(b.nb, 2), dim3(256), 0, stream, b.cur[0], b.cur[1], b.am_in(0), b.am_in(1));
         tm.end(e);

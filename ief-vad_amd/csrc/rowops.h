@@ -352,6 +352,15 @@ __global__ __launch_bounds__(256) void iefvad_amax_kernel(const float* in0, cons
 }
 
 // ---- per-chunk max |x| of the raw inputs (fp16x3 mode): one workgroup per (chunk, modality), no atomics
+// Zeroes the per-chunk running-max words of a micro-batch: tensor blockIdx.y's first `words` floats (its chunks x IEF_AMAX_PARTS), the
+// tensors `stride` floats apart.  A kernel, not hipMemsetAsync: in a captured graph the zeroing has to be a kernel node in the chain of
+// the producers and consumers of these words (test_reloaded_model_equals_fresh_model[fp16x3-6] differed from run to run on the replayed
+// graph with a memset node here, TRIED.md).
+__global__ __launch_bounds__(256) void iefvad_amax_zero_kernel(float* am, size_t stride, unsigned words) {
+    const unsigned i = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i < words) *(f32x4*)(am + blockIdx.y * stride + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 __global__ __launch_bounds__(256) void iefvad_amax_chunk_kernel(const float* in0, const float* in1, float* out0, float* out1) {
     __shared__ float part[4];
     const float* in = (blockIdx.y ? in1 : in0) + (size_t)blockIdx.x * IEF_T * IEF_D;

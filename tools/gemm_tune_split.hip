@@ -34,7 +34,7 @@ static float run(const Variant& v, GemmBArgs gs, GemmBArgs gf, int iters) {
         else if (v.kind == 2) hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid2, dim3(256), GS_LDS_BYTES_OF(2), 0, gs);
         else if (v.kind == 3) hipLaunchKernelGGL(iefvad_gemm_split_f16_kernel, grid, dim3(256), GS_LDS_BYTES, 0, gh);
         else if (v.kind == 4) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid2, dim3(256), GS_LDS_BYTES_OF(2), 0, gh);
-        else if (v.kind == 5) hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, gs);   // 128 x 256 as two halves (N % 256 == 0)
+        else if (v.kind == 5) hipLaunchKernelGGL(gemm_split_wide_kernel(v.epi, true), grid, dim3(256), GS_LDS_BYTES_OF(2), 0, gs);   // 128 x 256 as two halves (N % 256 == 0); one kernel per kind, which always stores
         else hipLaunchKernelGGL(iefvad_gemm_f32_t256_kernel, grid, dim3(256), GB2_LDS_BYTES, 0, gf);
     }
     CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
@@ -116,7 +116,8 @@ int main(int argc, char** argv) {
     CK(hipFuncSetAttribute((const void*)iefvad_gemm_split_f16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES));
     CK(hipFuncSetAttribute((const void*)iefvad_gemm_split_f16_n128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2)));
     CK(hipFuncSetAttribute((const void*)iefvad_gemm_f32_t256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GB2_LDS_BYTES));
-    CK(hipFuncSetAttribute((const void*)iefvad_gemm_split_n128x2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2)));
+    for (const GemmSplitWideKernel k : kGemmSplitWideKernels)
+        CK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, GS_LDS_BYTES_OF(2)));
     if (do_sweep) return sweep(A, Wp, bias, C, R, hW, K, M);
     for (int ni = 0; ni < 2; ++ni) {
         const int N = Ns[ni];
@@ -189,7 +190,7 @@ int main(int argc, char** argv) {
         }
         const Variant vs[] = {{"split bias C32", 0, EPI_BIAS, true}, {"split refine C32", 0, EPI_REFINE, true}, {"split none", 0, EPI_BIAS, false},
                               {"n128  bias C32", 2, EPI_BIAS, true}, {"n128  refine C32", 2, EPI_REFINE, true}, {"n128  none", 2, EPI_BIAS, false},
-                              {"n128x2 bias C32", 5, EPI_BIAS, true}, {"n128x2 refine C32", 5, EPI_REFINE, true}, {"n128x2 none", 5, EPI_BIAS, false},
+                              {"n128x2 bias C32", 5, EPI_BIAS, true}, {"n128x2 refine C32", 5, EPI_REFINE, true},
                               {"f16x3 256 bias C32", 3, EPI_BIAS, true}, {"f16x3 256 refine", 3, EPI_REFINE, true}, {"f16x3 256 none", 3, EPI_BIAS, false},
                               {"f16x3 128 bias C32", 4, EPI_BIAS, true}, {"f16x3 128 refine", 4, EPI_REFINE, true}, {"f16x3 128 none", 4, EPI_BIAS, false},
                               {"f32   bias C32", 1, EPI_BIAS, true}, {"f32   refine C32", 1, EPI_REFINE, true}, {"f32   none", 1, EPI_BIAS, false}};
@@ -208,14 +209,18 @@ int main(int argc, char** argv) {
     {   // in-kernel clock and cycles of the split main loop under sustained load
         unsigned long long* dclk; CK(hipMalloc(&dclk, 64 * 8192));
         GemmBArgs g; memset(&g, 0, sizeof(g));
-        g.M = M; g.N = 768; g.K = K; g.lda = K; g.ldc = 768; g.epi = EPI_BIAS; g.wplane = 768 * K * 2;
-        g.p[0].A = (const bf16_t*)A; g.p[0].W = Wp; g.p[0].bias = bias; g.p[0].C = C; g.p[0].C2 = (float*)dclk; g.p[1] = g.p[0];
+        // GS_STAMP_EPI=refine: stamp the refine kind (C = R - alpha (acc + bias), R read from its own buffer) instead of the bias kind
+        const char* se = getenv("GS_STAMP_EPI");
+        const int sepi = se && !strcmp(se, "refine") ? EPI_REFINE : EPI_BIAS;
+        printf("stamps of the %s epilogue\n", sepi == EPI_REFINE ? "refine" : "bias");
+        g.M = M; g.N = 768; g.K = K; g.lda = K; g.ldc = 768; g.epi = sepi; g.alpha = 0.5f; g.wplane = 768 * K * 2;
+        g.p[0].A = (const bf16_t*)A; g.p[0].W = Wp; g.p[0].bias = bias; g.p[0].C = C; g.p[0].R = R; g.p[0].C2 = (float*)dclk; g.p[1] = g.p[0];
       for (int cfgi = 0; cfgi < 4; ++cfgi) {
         dim3 grid((M / GS_BM) * (768 / (cfgi == 1 || cfgi == 2 ? 128 : GS_BN)), 1, 1);
         printf("%s\n", cfgi == 3 ? "128 x 256 as two column halves, two workgroups per CU:" : cfgi == 2 ? "fp16x3, 128 x 128, two workgroups per CU:" : cfgi ? "128 x 128, two workgroups per CU:" : "128 x 256, one workgroup per CU:");
-        GemmBArgs g2 = gh; g2.epi = EPI_BIAS; g2.p[0].C = C; g2.p[0].C2 = (float*)dclk; g2.p[1] = g2.p[0];
+        GemmBArgs g2 = gh; g2.epi = sepi; g2.alpha = 0.5f; g2.p[0].C = C; g2.p[0].R = R; g2.p[0].C2 = (float*)dclk; g2.p[1] = g2.p[0];
         for (int it = 0; it < 4000; ++it) {
-            if (cfgi == 3) hipLaunchKernelGGL(iefvad_gemm_split_n128x2_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g);
+            if (cfgi == 3) hipLaunchKernelGGL(gemm_split_wide_kernel(sepi, true), grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g);
             else if (cfgi == 2) hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g2);
             else if (cfgi) hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), 0, g);
             else hipLaunchKernelGGL(iefvad_gemm_split_kernel, grid, dim3(256), GS_LDS_BYTES, 0, g);
