@@ -11,6 +11,7 @@
 //                            the last LayerNorm output, the whitened rows, mu and logvar of both modalities;
 //                            the refinement states z_0 .. z_K and hidden activations h_0 .. h_{K-1}
 //   iefvad_train_backward  the gradients of every parameter, given the gradients of the eight outputs
+//   iefvad_train_backward_inputs  the same, plus the gradients of the two input feature tensors where asked for
 // Arithmetic: the dense projections of the forward run on the handle's kernels (fp32 MFMA, or the exact bf16x6 split when
 // the batch fills its grid); every product of the backward and the two attention products of the train forward run on
 // iefvad_bgemm_f32_kernel (fp32 MFMA).  Reductions over rows are fixed-order (no atomics): gradients are bit-reproducible.
@@ -552,17 +553,23 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------------
-extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes, const iefvad_output_grads* dout,
-                                     const iefvad_weight_grads* dw, void* stream_) {
-    if (!h) return fail("iefvad_train_backward: null handle");
-    if (h->D != IEF_D) return fail("iefvad_train_backward: training is built for D=768 (this handle has D=%d)", h->D);
-    if (!dout || !dw) return fail("iefvad_train_backward: null argument");
+// One walk serves both entries (`who` names the caller's in the messages).  `dx` (nullable, each member nullable): the gradients of the
+// input features, the layer-0 instance of the d x product every layer above it runs.  A frozen model hands a `dw` of null pointers:
+// launch_dw / launch_db return before any launch for null destinations and ReduceBatch skips them, so what remains is the chain of
+// d x products, the attention backward and the row kernels (whose partial sums for the affine gradients are by-products nobody reduces).
+static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes, const iefvad_output_grads* dout,
+                          const iefvad_weight_grads* dw, const iefvad_input_grads* dxin, void* stream_, const char* who) {
+    if (!h) return fail("%s: null handle", who);
+    float* dx[2] = {dxin ? dxin->img : nullptr, dxin ? dxin->ev : nullptr};      // checked before the handle is looked at
+    if (((uintptr_t)dx[0] | (uintptr_t)dx[1]) & 15) return fail("%s: input-gradient buffers must be 16-byte aligned", who);
+    if (h->D != IEF_D) return fail("%s: training is built for D=768 (this handle has D=%d)", who, h->D);
+    if (!dout || !dw) return fail("%s: null argument", who);
     const TrainRecord* rec = nullptr;
     if (h->train)
         for (int i = 0; i < 8; ++i)
             if (h->train->rec[i].ws == train_ws && h->train->rec[i].stamp) rec = &h->train->rec[i];
-    if (!rec || rec->B != B) return fail("iefvad_train_backward: no iefvad_train_forward with B = %d has filled this training buffer", B);
-    if (int rc = train_check(h, B, train_ws, train_ws_bytes, "iefvad_train_backward")) return rc;
+    if (!rec || rec->B != B) return fail("%s: no iefvad_train_forward with B = %d has filled this training buffer", who, B);
+    if (int rc = train_check(h, B, train_ws, train_ws_bytes, who)) return rc;
     const iefvad_config& c = h->cfg;
     const int L = c.num_layers, K = c.num_steps;
     hipStream_t stream = (hipStream_t)stream_;
@@ -661,6 +668,8 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
             if (int rc = launch_dw(gx, IEF_D, IEF_D, ws + t.att[m][l], dw->out_proj_w[m][l], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->out_proj_b[m][l], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
             if (!db_done)
                 if (int rc = launch_db(gx, IEF_D, IEF_D, dw->out_proj_b[m][l], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
+            // layer 0 of a modality whose in_proj gradients and input gradient are all unasked for: nothing reads its d qkv
+            if (l == 0 && !dx[m] && !dw->in_proj_w[m][0] && !dw->in_proj_b[m][0]) break;
             if (int rc = launch_dx(h, tp ? h->out[m][l].wst : nullptr, gx, IEF_D, h->out[m][l].w, IEF_D, IEF_D, datt, nullptr, nullptr, 1.f, rows, stream)) return rc;
             const long long sQ = (long long)IEF_T * 3 * IEF_D, sP1 = (long long)IEF_H * IEF_T * IEF_T, sP2 = (long long)IEF_T * IEF_T,
                             sA = (long long)IEF_T * IEF_D;
@@ -720,11 +729,24 @@ extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws
             if (int rc = launch_dw(dqkv, 3 * IEF_D, 3 * IEF_D, l == 0 ? rec->x0[m] : ws + t.x[m][l], dw->in_proj_w[m][l], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->in_proj_b[m][l], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
             if (!db_done)
                 if (int rc = launch_db(dqkv, 3 * IEF_D, 3 * IEF_D, dw->in_proj_b[m][l], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
-            // d x_l = d s_l (residual) + d qkv W_in; the input features need no gradient
-            if (l > 0)
-                if (int rc = launch_dx(h, tp ? h->in[m][l].wst : nullptr, dqkv, 3 * IEF_D, h->in[m][l].w, 3 * IEF_D, IEF_D, gx, gx, nullptr, 1.f, rows, stream)) return rc;
+            // d x_l = d s_l (residual) + d qkv W_in: in place for the layers above the first; at layer 0 it is the gradient of the input
+            // features, written to the caller's buffer where one is given (gx is only read there)
+            float* dxl = l > 0 ? gx : dx[m];
+            if (dxl)
+                if (int rc = launch_dx(h, tp ? h->in[m][l].wst : nullptr, dqkv, 3 * IEF_D, h->in[m][l].w, 3 * IEF_D, IEF_D, dxl, gx, nullptr, 1.f, rows, stream)) return rc;
         }
     }
     const_cast<TrainRecord*>(rec)->stamp = 0;      // the scratch tensors have overwritten the saved refinement states
     return 0;
+}
+
+extern "C" int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes, const iefvad_output_grads* dout,
+                                     const iefvad_weight_grads* dw, void* stream) {
+    return train_backward(h, B, train_ws, train_ws_bytes, dout, dw, nullptr, stream, "iefvad_train_backward");
+}
+
+extern "C" int iefvad_train_backward_inputs(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes,
+                                            const iefvad_output_grads* dout, const iefvad_weight_grads* dw,
+                                            const iefvad_input_grads* dx, void* stream) {
+    return train_backward(h, B, train_ws, train_ws_bytes, dout, dw, dx, stream, "iefvad_train_backward_inputs");
 }

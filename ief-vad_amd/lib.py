@@ -36,7 +36,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_forward_videos_scaled", "iefvad_videos_scaled_workspace_bytes", "iefvad_forward_videos_similarity",
            "iefvad_forward_videos_host_similarity", "iefvad_videos_full_workspace_bytes", "iefvad_forward_videos_full",
            "iefvad_forward_videos_host_full", "iefvad_forward_attn", "iefvad_forward_videos_attn",
-           "iefvad_gemm_split_small_unit", "iefvad_gemm_split_small_launches", "iefvad_set_batch_invariant"]
+           "iefvad_gemm_split_small_unit", "iefvad_gemm_split_small_launches", "iefvad_set_batch_invariant",
+           "iefvad_train_backward_inputs"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -72,6 +73,11 @@ class TrainOptions(C.Structure):
 class OutputGrads(C.Structure):
     _fields_ = [("fused", _fp), ("logits", _fp), ("image_mu", _fp), ("event_mu", _fp),
                 ("image_logvar", _fp), ("event_logvar", _fp), ("w_i", _fp), ("w_e", _fp)]
+
+
+class InputGrads(C.Structure):
+    """iefvad_input_grads (include/iefvad.h): where the gradients of the two input feature tensors go, [B*T, D] fp32, 0 = not asked for."""
+    _fields_ = [("img", _fp), ("ev", _fp)]
 
 
 class Outputs(C.Structure):
@@ -205,6 +211,8 @@ def load_library() -> C.CDLL:
     lib.iefvad_train_backward.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.POINTER(OutputGrads), C.POINTER(WeightGrads),
                                           C.c_void_p]
     lib.iefvad_train_backward.restype = C.c_int
+    lib.iefvad_train_backward_inputs.argtypes = lib.iefvad_train_backward.argtypes[:6] + [C.POINTER(InputGrads), C.c_void_p]
+    lib.iefvad_train_backward_inputs.restype = C.c_int
     lib.iefvad_adamw_step.argtypes = [C.c_void_p] * 4 + [C.c_size_t] + [C.c_double] * 5 + [C.c_int32, C.c_void_p]
     lib.iefvad_adamw_step.restype = C.c_int
     lib.iefvad_adamw_step_multi.argtypes = [C.c_void_p, C.c_int32, C.c_uint64] + [C.c_double] * 5 + [C.c_int32, C.c_void_p]

@@ -15,6 +15,7 @@ on a HIP device: there is no CPU path, a CPU tensor raises.
 
 `model.train()` switches `forward` to the train-mode path (attention dropout, activations kept for the backward): the returned
 tensors are differentiable with respect to every parameter, `loss.backward()` runs `iefvad_train_backward`.
+A feature tensor that requires grad receives its gradient too (`iefvad_train_backward_inputs`), in train() and -- dropout off -- in eval().
 """
 from __future__ import annotations
 
@@ -180,14 +181,18 @@ class FusionParams(nn.Module):
 class _TrainForward(torch.autograd.Function):
     """The train-mode forward of the whole model as ONE autograd node: forward = `iefvad_train_forward` (keeps the activations in
     a buffer this node owns), backward = `iefvad_train_backward` (every parameter gradient).  The parameters are inputs of the
-    node, so `loss.backward()` accumulates into their `.grad` exactly as with the reference's modules."""
+    node, so `loss.backward()` accumulates into their `.grad` exactly as with the reference's modules.  So are the two feature
+    tensors: where one requires grad, the backward is `iefvad_train_backward_inputs` and the tensor receives its gradient in its own
+    dtype and shape (the library's fp32 gradient with respect to the widened rows, cast as autograd casts through `.to(torch.float)`).
+    `no_dropout` (the differentiable eval route): every dropout probability 0 and no mask, whatever the layers and the model carry."""
 
     @staticmethod
-    def forward(ctx, model, img, ev, *params):
+    def forward(ctx, model, no_dropout, img, ev, *params):
         lib = _lib.load_library()
         t = model.temporal
         device = img.device
         B, T, D = img.shape
+        ctx.in_meta = ((img.dtype, img.shape), (ev.dtype, ev.shape))
         img = model._prepare_input(img)
         ev = model._prepare_input(ev)
         if ev.dtype != img.dtype:
@@ -195,12 +200,12 @@ class _TrainForward(torch.autograd.Function):
         opt = _lib.TrainOptions()
         for m, name in enumerate(("image", "event")):
             for l, a in enumerate(getattr(t, f"{name}_attn_layers")):
-                opt.dropout_p[m][l] = float(a.dropout)
-        seed = model.__dict__.get("dropout_seed")
+                opt.dropout_p[m][l] = 0.0 if no_dropout else float(a.dropout)
+        seed = 0 if no_dropout else model.__dict__.get("dropout_seed")      # no mask is drawn without dropout: torch's RNG stays where it is
         if seed is None:      # a fresh stream per step, reproducible under torch.manual_seed
             seed = int(torch.empty((), dtype=torch.int64).random_().item())
         opt.seed = seed & 0xFFFFFFFFFFFFFFFF
-        mask = model.__dict__.get("dropout_mask")
+        mask = None if no_dropout else model.__dict__.get("dropout_mask")
         if mask is not None:
             want = (2, t.num_layers, B, t.num_heads, T, T)
             if tuple(mask.shape) != want or mask.dtype != torch.uint8 or mask.device != device or not mask.is_contiguous():
@@ -247,19 +252,29 @@ class _TrainForward(torch.autograd.Function):
                 g = g.contiguous().float()
                 keep.append(g)
                 setattr(dout, k, g.data_ptr())
-        needs = ctx.needs_input_grad[3:]
+        needs = ctx.needs_input_grad[4:]
         grads = [torch.empty_like(p, memory_format=torch.contiguous_format) if n else None for p, n in zip(ctx.params, needs)]
         by_id = {id(p): g for p, g in zip(ctx.params, grads)}
         dw = _lib.WeightGrads()
         model._fill_weight_struct(dw, lambda p: by_id[id(p)].data_ptr() if by_id.get(id(p)) is not None else None)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
-            rc = lib.iefvad_train_backward(model._handle, ctx.B, C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(dout), C.byref(dw),
-                                           C.c_void_p(stream))
+            args = (model._handle, ctx.B, C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(dout), C.byref(dw))
+            # the gradients of the feature tensors: fp32 [B, T, D] for the ones asked for, and the entry that takes them
+            gin = [torch.empty(ctx.B, *shape[1:], dtype=torch.float32, device=device) if n else None
+                   for (_, shape), n in zip(ctx.in_meta, ctx.needs_input_grad[2:4])]
+            if gin[0] is not None or gin[1] is not None:
+                name = "iefvad_train_backward_inputs"
+                dx = _lib.InputGrads(*(g.data_ptr() if g is not None else None for g in gin))
+                rc = lib.iefvad_train_backward_inputs(*args, C.byref(dx), C.c_void_p(stream))
+            else:
+                name = "iefvad_train_backward"
+                rc = lib.iefvad_train_backward(*args, C.c_void_p(stream))
         if rc != 0:
-            raise RuntimeError("iefvad_train_backward: " + _lib.last_error())
+            raise RuntimeError(name + ": " + _lib.last_error())
         ctx.ws = None
-        return (None, None, None, *grads)
+        gin = [g if g is None or g.dtype == dtype else g.to(dtype) for g, (dtype, _) in zip(gin, ctx.in_meta)]
+        return (None, None, *gin, *grads)
 
 
 class MMFMIL(nn.Module):
@@ -291,6 +306,19 @@ class MMFMIL(nn.Module):
                    routes, per video, packed or from host lists -- the guarantee "f32" gives.  Still held to the "f32" tolerances; a small
                    call costs more than in the default mode.  Accepted and inert with "f32" and "bf16" (already invariant); ValueError
                    with "fp16x3".  Carried by `lanes(n)`; training is not affected.
+
+    Without any keyword (the reference's behaviour, imf_vad.py:40-44,109-161 being an ordinary nn.Module):
+      gradients of the features  a feature tensor with `requires_grad=True` receives its `.grad` from `loss.backward()`, in its own dtype
+                   and shape, in train() and in eval() alike -- an adapter or a learned projection upstream of the model trains, and
+                   feature-space saliency works.  In train() the step is the usual one plus the layer-0 product d x = d s + d qkv W_in
+                   per modality asked for (`iefvad_train_backward_inputs`; no parameter gradient changes by a bit).  In eval() with
+                   grad enabled, a feature tensor that requires grad routes the call through the train-mode forward with every
+                   dropout probability forced to 0 and no mask (the reference's eval(): dropout simply off); `attn_maps=`, `timed=True`
+                   and `row_scale=` raise ValueError there.  Every other eval() call -- parameters that require grad included --
+                   keeps the evaluation entry, its graph replay and its bits: the trigger is the inputs, never the parameters.  With
+                   every parameter frozen the backward computes the input gradients alone (no weight-gradient product runs).
+                   compute "f32" / "bf16x6" and D = 768 only, as training; `forward_videos` / `forward_videos_host` stay
+                   evaluation-only and non-differentiable.
     """
 
     def __init__(self, num_class: int, embed_dim: int, visual_length: int, visual_width: int, visual_head: int,
@@ -475,7 +503,9 @@ class MMFMIL(nn.Module):
         `attn_maps=True` (every encoder layer) or an iterable of layer indices (`iefvad_forward_attn`) adds `image_attn` and `event_attn`,
         [n, B, T, T] fp32 in ascending layer order -- the head-averaged attention weights the reference's nn.MultiheadAttention calls
         form and discard (imf_vad.py:115,121) -- and `attn_layers`, the n layer indices.  Every other result keeps its bits.  Not with
-        `timed` or `row_scale` (ValueError), compute="bf16" or model.train() (RuntimeError)."""
+        `timed` or `row_scale` (ValueError), compute="bf16" or model.train() (RuntimeError).
+        In eval() with grad enabled, a feature tensor that requires grad makes the call differentiable (the train-mode forward with every
+        dropout probability forced to 0, the class docstring's keyword-free section); the three extras raise ValueError there."""
         self._noise_code()   # ValueError for an unsupported noise_model, as the reference raises
         layers = attn_map_layers(attn_maps, self.temporal.num_layers)
         if layers:
@@ -484,6 +514,15 @@ class MMFMIL(nn.Module):
             self._attn_maps_served("model.train()" if self.training else None)
         if self.training:
             return self._forward_train(img_visual, ev_visual)
+        if torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad):
+            # eval() with a feature tensor that requires grad: the reference differentiates here too, dropout simply off
+            scaled = row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None)
+            asked = [n for n, on in (("attn_maps=", bool(layers)), ("timed=True", timed), ("row_scale=", scaled)) if on]
+            if asked:
+                raise ValueError(f"{' / '.join(asked)} with a feature tensor that requires grad in eval(): the differentiable eval route "
+                                 "runs the train-mode forward without dropout, which takes none of attn_maps, timed and row_scale "
+                                 "(detach the features, or call under torch.no_grad())")
+            return self._forward_train(img_visual, ev_visual, no_dropout=True)
         if not (img_visual.is_cuda and ev_visual.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback "
                                "(move the inputs with .to('cuda'))")
@@ -574,7 +613,8 @@ class MMFMIL(nn.Module):
         half the bytes cross PCIe; same results as `forward_videos` on `rows.to(torch.bfloat16)` (include/iefvad.h).
         `similarity=True` (`iefvad_forward_videos_host_similarity`) adds "similarity" as `forward_videos` does.
         `outputs="full"` or an iterable of OUTPUT_KEYS names (`iefvad_forward_videos_host_full`) adds those keys as [sum(lengths), D]
-        fp32 device tensors in list order, as `forward_videos` does; it does not combine with `similarity=True` (ValueError)."""
+        fp32 device tensors in list order, as `forward_videos` does; it does not combine with `similarity=True` (ValueError).
+        An evaluation entry: nothing it returns is differentiable (features that require grad get no gradient here; use `forward`)."""
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos_host is an evaluation entry point; call model.eval() first")
         self._noise_code()
@@ -653,10 +693,11 @@ class MMFMIL(nn.Module):
         return res
 
     # ------------------------------------------------------------------ train mode
-    def _forward_train(self, img_visual, ev_visual) -> Dict[str, torch.Tensor]:
+    def _forward_train(self, img_visual, ev_visual, no_dropout: bool = False) -> Dict[str, torch.Tensor]:
         """`model.train()` forward (/root/reference/train/ucf_train.py:43,60-66): the same dict, differentiable with respect to
-        every parameter -- `iefvad_train_forward` keeps the activations, `loss.backward()` reaches `iefvad_train_backward`
-        through `_TrainForward`.  Attention dropout (imf_vad.py:70) uses each layer's `.dropout` (as nn.MultiheadAttention
+        every parameter and to the feature tensors that require grad -- `iefvad_train_forward` keeps the activations,
+        `loss.backward()` reaches `iefvad_train_backward` / `iefvad_train_backward_inputs` through `_TrainForward`.
+        `no_dropout=True`: the eval() route for features that require grad (dropout off whatever the layers say).  Attention dropout (imf_vad.py:70) uses each layer's `.dropout` (as nn.MultiheadAttention
         keeps it); the mask comes from the library's counter-based generator seeded from torch's RNG (`self.dropout_seed` pins
         it), or from `self.dropout_mask` (uint8 [2, L, B, 8, T, T], 1 = keep) when a test injects one."""
         if self.compute not in ("f32", "bf16x6"):
@@ -678,7 +719,11 @@ class MMFMIL(nn.Module):
             slots = [(m._parameters, n) for m in self.temporal.modules() for n in m._parameters if m._parameters[n] is not None]
             self.__dict__["_param_slots"] = slots
         params = [d[n] for d, n in slots]
-        outs = _TrainForward.apply(self, img_visual.detach(), ev_visual.detach(), *params)
+        # a feature tensor that requires grad is an input of the node as it is (its dtype, its strides: the widening and the
+        # contiguous copy happen inside the node, so the gradient lands on the caller's tensor); the others are detached
+        img_in = img_visual if img_visual.requires_grad else img_visual.detach()
+        ev_in = ev_visual if ev_visual.requires_grad else ev_visual.detach()
+        outs = _TrainForward.apply(self, bool(no_dropout), img_in, ev_in, *params)
         return dict(zip(OUTPUT_KEYS, outs))
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
@@ -704,7 +749,8 @@ class MMFMIL(nn.Module):
         [n, sum(lengths), T] fp32 in ascending layer order, and `attn_layers`: row r is the head-averaged attention of valid snippet r
         over the T keys of its chunk (columns >= the chunk's valid rows hold the weight of a pad key, as on the padded route); the other
         three results keep their bits.  It combines with none of `similarity`, `outputs`, `row_scale`, `weight_sums` and
-        nan_to_num="always" (ValueError); compute="bf16" and model.train() raise RuntimeError."""
+        nan_to_num="always" (ValueError); compute="bf16" and model.train() raise RuntimeError.
+        An evaluation entry: nothing it returns is differentiable (rows that require grad get no gradient here; use `forward`)."""
         layers = attn_map_layers(attn_maps, self.temporal.num_layers)
         if layers:
             if similarity or outputs is not None or weight_sums or nan_to_num == "always" or \

@@ -371,7 +371,20 @@ int iefvad_loss_backward(const float* logits, const float* image_mu, const float
  *   keep_mask        device, nullable: uint8 [2][L][B][8][T][T], 1 = keep -- an injected mask replaces the generator (tests, replay)
  * iefvad_train_backward: `dout` holds the gradients handed to the eight outputs (each nullable = zero; [B*T, D], logits [B*T]);
  * every non-null pointer of `dw` ([same shape as the parameter], fp32) receives that parameter's gradient (overwritten, not
- * accumulated).  Reductions over rows are fixed-order: the same inputs give the same bits on every run. */
+ * accumulated).  Reductions over rows are fixed-order: the same inputs give the same bits on every run.
+ *
+ * iefvad_train_backward_inputs is the same backward with one more request: `dx` names where the gradients of the two INPUT feature
+ * tensors go (each [B*T, D] fp32, device, 16-byte aligned, nullable; overwritten, not accumulated).  For a non-null member, layer 0 of
+ * that modality runs the product the layers above it already run, d x = d s (residual) + d qkv W_in (K = 2304), into the caller's
+ * buffer: on the exact split kernel where the batch fills its grid (IEFVAD_COMPUTE_BF16X6), on the fp32 MFMA kernel otherwise.  The
+ * gradient is with respect to the fp32 values the forward computed on: for in_dtype f16 / bf16 that is the WIDENED rows, so the caller
+ * rounds it to the narrow type if it wants `.grad` in the feature dtype.  Nothing else changes: the residual gradient is only read, no
+ * parameter gradient moves by a bit because an input gradient was asked for, and dx = NULL (or both members null) launches exactly what
+ * iefvad_train_backward launches -- that entry IS this one with dx = NULL.  The rule of ONE backward per forward is unchanged.
+ * A frozen model: every pointer of `dw` may be null.  Then the backward skips every weight-gradient product (the split-K d W launches
+ * and their reductions), every bias column sum, and the reductions of the classifier / LayerNorm-affine partial sums (the partial sums
+ * themselves are by-products of the kernels that form d x and stay); and where neither the in_proj gradients of a modality's layer 0
+ * nor its input gradient are asked for, layer 0's attention backward (nothing reads its d qkv) is skipped too. */
 typedef struct iefvad_train_options {
     float dropout_p[2][IEFVAD_MAX_LAYERS];
     uint64_t seed;
@@ -412,6 +425,10 @@ int iefvad_train_forward(iefvad_handle* h, const void* img, const void* ev, int3
                          void* stream);
 int iefvad_train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes, const iefvad_output_grads* dout,
                           const iefvad_weight_grads* dw, void* stream);
+typedef struct iefvad_input_grads { float* img; float* ev; } iefvad_input_grads;   /* device, [B*T, D] fp32, each nullable */
+int iefvad_train_backward_inputs(iefvad_handle* h, int32_t B, void* train_ws, size_t train_ws_bytes,
+                                 const iefvad_output_grads* dout, const iefvad_weight_grads* dw,
+                                 const iefvad_input_grads* dx, void* stream);
 
 /* The trainers' input rule (/root/reference/train/ucf_train.py:50-53, xd_train.py:40-43: `if torch.isnan(x).any(): x =
  * torch.nan_to_num(x, nan=0.0)`, per tensor) for the two fp32 input tensors of a step, without the host read of the flag: one scan,
