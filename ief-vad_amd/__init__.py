@@ -5,6 +5,6 @@ include/iefvad.h).  Importing the package does not load the library; the first f
 fails loudly if the library is missing -- there is no CPU fallback.
 """
 from . import harness, layers, lib, losses, module, synth, trainer  # noqa: F401
-from .model import MMFMIL, OUTPUT_KEYS  # noqa: F401
+from .model import MMFMIL, OUTPUT_KEYS, perturb_rows  # noqa: F401
 
-__all__ = ["MMFMIL", "OUTPUT_KEYS", "harness", "layers", "lib", "losses", "module", "synth", "trainer"]
+__all__ = ["MMFMIL", "OUTPUT_KEYS", "harness", "layers", "lib", "losses", "module", "synth", "trainer", "perturb_rows"]

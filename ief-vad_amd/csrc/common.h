@@ -146,3 +146,57 @@ __device__ __forceinline__ unsigned dropout_bits(unsigned long long seed, unsign
     const unsigned a = fmix32(lo ^ (unsigned)seed);
     return fmix32(a + (unsigned)(seed >> 32) + hi * 0x9E3779B1u) >> 8;      // 24 uniform bits
 }
+
+// Additive Gaussian noise on input rows (iefvad_forward_perturbed, iefvad_forward_videos_perturbed, iefvad_perturb_rows; include/iefvad.h).
+// The reference declares the noise study's flags and implements none of them (test2.py:35-37,214-220), so these semantics are this
+// library's own: "parity unpinned", as for the dropout mask above.  eps is a standard normal in fp32 and a pure function of
+// (seed, modality m, noise id, column): columns come in pairs (2q, 2q + 1) by Box-Muller from two 24-bit draws of the generator above,
+// u1 = (b1 + 1) 2^-24 in (0, 1], u2 = b2 2^-24 in [0, 1) (both exact in fp32; 2 u2 is exact too, so sincospif takes the angle without
+// a rounded 2 pi); |eps| <= sqrt(48 ln 2) = 5.77.  harness.gaussian_rows is the host model (fp64, rounded once).
+struct RowNoise {
+    const float* amp[2];        // DEVICE [rows] fp32 amplitudes (image, event), nullable each; 0 leaves the row's bits alone
+    const int* id;              // DEVICE [rows] noise ids >= 0, nullable: row0 + the row's index in the view
+    unsigned long long seed;
+    long long row0;             // row of the CALL that the view's first row is
+    bool any() const { return amp[0] || amp[1]; }
+    RowNoise at(long long rows) const {
+        RowNoise o = *this;
+        for (int m = 0; m < 2; ++m)
+            if (amp[m]) o.amp[m] += rows;
+        if (id) o.id += rows;
+        o.row0 += rows;
+        return o;
+    }
+};
+// The noise mode of a load kernel is a trailing parameter PACK, empty or one RowNoise: the instantiations without noise keep the
+// signature, the kernel-argument layout, the name and the code they had before the mode existed.
+__device__ __forceinline__ RowNoise row_noise_of() { return RowNoise{{nullptr, nullptr}, nullptr, 0ull, 0ll}; }
+__device__ __forceinline__ RowNoise row_noise_of(const RowNoise& nz) { return nz; }
+__device__ __forceinline__ void gauss_pair(unsigned long long seed, unsigned id, int m, int q, float& e0, float& e1) {
+    const unsigned long long idx = (((unsigned long long)id * 2 + (unsigned)m) << 11) | ((unsigned)q << 1);
+    const float u1 = (float)(dropout_bits(seed, idx) + 1u) * 0x1p-24f;
+    const float u2 = (float)dropout_bits(seed, idx | 1) * 0x1p-24f;
+    const float rho = sqrtf(-2.0f * logf(u1));
+    float s, c;
+    sincospif(2.0f * u2, &s, &c);
+    e0 = rho * c;
+    e1 = rho * s;
+}
+// w (four consecutive columns from `col`, a multiple of 4, of a row of source type T, widened) += amp * eps, as torch forms
+// `x + amp * eps` for a T tensor and an fp32 eps: the product rounded to fp32 on its own, the fp32 sum rounded to T.  The two barriers
+// keep hipcc from contracting product and sum into an FMA and from folding the narrowing into a mixed-precision instruction (rowops.h,
+// iefvad_cast_scaled_kernel).
+template <typename T>
+__device__ __forceinline__ void add_row_noise4(f32x4& w, float amp, unsigned long long seed, unsigned id, int m, int col) {
+    float eps[4];
+    gauss_pair(seed, id, m, col >> 1, eps[0], eps[1]);
+    gauss_pair(seed, id, m, (col >> 1) + 1, eps[2], eps[3]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float p = amp * eps[e];
+        asm volatile("" : "+v"(p));
+        float s = w[e] + p;
+        asm volatile("" : "+v"(s));
+        w[e] = (float)(T)s;
+    }
+}

@@ -338,11 +338,28 @@ static int launch_cast(const void* in0, const void* in1, float* o0, float* o1, b
 
 template <typename T, int W>
 static int launch_cast_scaled(const void* in0, const void* in1, float* o0, float* o1, bf16_t* b0, bf16_t* b1, size_t n, const float* s0,
-                              const float* s1, hipStream_t stream) {
+                              const float* s1, const RowNoise& nz, hipStream_t stream) {
     size_t blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL((iefvad_cast_scaled_kernel<T, W>), dim3((unsigned)blocks, 2), dim3(256), 0, stream, (const T*)in0, (const T*)in1, o0, o1, b0, b1,
-                       n, s0, s1);
+    // an amplitude vector selects the noise instantiation; without one the kernel of iefvad_forward_scaled runs, as it always has
+    if (nz.any())
+        hipLaunchKernelGGL((iefvad_cast_scaled_kernel<T, W, RowNoise>), dim3((unsigned)blocks, 2), dim3(256), 0, stream, (const T*)in0, (const T*)in1,
+                           o0, o1, b0, b1, n, s0, s1, nz);
+    else
+        hipLaunchKernelGGL((iefvad_cast_scaled_kernel<T, W>), dim3((unsigned)blocks, 2), dim3(256), 0, stream, (const T*)in0, (const T*)in1, o0, o1,
+                           b0, b1, n, s0, s1);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// iefvad_perturb_rows: both modalities in one launch (a null source / destination pair is skipped by the kernel)
+template <typename T, int W>
+static int launch_perturb_rows(const void* in0, const void* in1, void* o0, void* o1, size_t n, const float* s0, const float* s1, int fix_all,
+                               const RowNoise& nz, float big, hipStream_t stream) {
+    size_t blocks = (n / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL((iefvad_perturb_rows_kernel<T, W>), dim3((unsigned)blocks, 2), dim3(256), 0, stream, (const T*)in0, (const T*)in1, (T*)o0,
+                       (T*)o1, n, s0, s1, fix_all, nz, big);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -982,6 +999,7 @@ struct VideosOut {
     float* w_i_mean;
     float* w_e_mean;
     const float* scale[2];           // iefvad_forward_videos_scaled: per-row input scales (image, event), [rows] each
+    RowNoise noise;                  // iefvad_forward_videos_perturbed: per-row noise amplitudes, ids and seed (common.h); all null otherwise
     double* w_colsum;                // iefvad_forward_videos_scaled: [2, D], the call's column sums of w_i / w_e over its valid rows
     // the similarity entries: the [4, sim_stride] series; packed row r of this view is column row0 + r.  With it the tail keeps fused
     // (= z_K) and both mu of its row set (tail_keep).
@@ -1004,6 +1022,7 @@ struct VideosOut {
         if (w_e_mean) o.w_e_mean += rows;
         for (int m = 0; m < 2; ++m)
             if (scale[m]) o.scale[m] += rows;
+        o.noise = noise.at(rows);
         for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
             if (wide[t]) o.wide[t] += rows * D;
         o.attn = attn.at(rows);
@@ -1104,8 +1123,8 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
 }
 
 // 0. inputs: `.to(torch.float)` (imf_vad.py:41-42) into b.cur; bf16 mode also gets the bf16 operand copy (b.need_xb0)
-static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, const float* const scale[2], const RaggedPass* rg,
-                            hipStream_t stream, Timer& tm) {
+static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, const float* const scale[2], const RowNoise& nz,
+                            const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     const size_t D = h->D, n = b.R * D;
     const void* const pi = in.img;
     const void* const pe = in.ev;
@@ -1129,21 +1148,28 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
         const VideosOut& o = rg->out;
         const int nan_all = o.nan_mode == 2;
         const bool scaled = o.scale[0] || o.scale[1] || nan_all;
+        const bool noisy = o.noise.any();       // an amplitude vector selects the noise instantiation; every other call launches what it always has
         dispatch_in(in_dtype, d512, [&](auto t, auto w) {
             using T = typename decltype(t)::type;
             constexpr int W = decltype(w)::value;
-            hipLaunchKernelGGL((scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>),
-                               dim3(b.nb, 2, IEF_RAGGED_SLICES), dim3(256), 0, stream, (const T*)pi, (const T*)pe, rg->d_chunks,
-                               rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, b.enc_rows_mode ? 0 : IEF_T, o.scale[0], o.scale[1], nan_all);
+            const dim3 grid(b.nb, 2, IEF_RAGGED_SLICES);
+            const int nrows = b.enc_rows_mode ? 0 : IEF_T;
+            if (noisy)
+                hipLaunchKernelGGL((iefvad_scatter_rows_kernel<T, W, true, RowNoise>), grid, dim3(256), 0, stream, (const T*)pi, (const T*)pe,
+                                   rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0], o.scale[1], nan_all, o.noise);
+            else
+                hipLaunchKernelGGL((scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>), grid, dim3(256), 0,
+                                   stream, (const T*)pi, (const T*)pe, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0],
+                                   o.scale[1], nan_all);
             return 0;
         });
         tm.end(e);
         HIP_TRY(hipGetLastError());
-    } else if (scale[0] || scale[1]) {
-        // iefvad_forward_scaled: the rows pass through the cast kernel whatever their type, scaled on the way (rowops.h)
+    } else if (scale[0] || scale[1] || nz.any()) {
+        // iefvad_forward_scaled / _perturbed: the rows pass through the cast kernel whatever their type, scaled and perturbed on the way (rowops.h)
         hipEvent_t e = tm.begin(ST_CAST);
         const int rc = dispatch_in(in_dtype, d512, [&](auto t, auto w) {
-            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, scale[0], scale[1], stream);
+            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, scale[0], scale[1], nz, stream);
         });
         tm.end(e);
         if (rc) return rc;
@@ -1497,10 +1523,11 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
 // chunks are built from them on the device, everything behind the encoder runs on the valid rows only, results go to rg->out (`out`
 // must be all-null, `scale` kNoScale: rg->out carries the packed scales).
 static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
-                        const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr) {
+                        const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr,
+                        const RowNoise* nz = nullptr) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
     if (rg) maps = &rg->out.attn;                 // a whole-video pass: the maps at the pass's first packed row
-    if (int rc = pass_load_inputs(h, b, in, scale, rg, stream, tm)) return rc;
+    if (int rc = pass_load_inputs(h, b, in, scale, nz ? *nz : RowNoise{}, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
         if (int rc = pass_encoder_layer(h, b, l, rg, maps, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
@@ -1509,7 +1536,7 @@ static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const s
 }
 
 static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
-                        const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr) {
+                        const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr, const RowNoise* nz = nullptr) {
     const void* const img = in.img;
     const void* const ev = in.ev;
     const int32_t in_dtype = in.in_dtype;
@@ -1528,7 +1555,9 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
         const size_t row0 = (size_t)b0 * IEF_T;
         const float* const pass_scale[2] = {scale[0] ? scale[0] + row0 : nullptr, scale[1] ? scale[1] + row0 : nullptr};
         const AttnMaps pass_maps = maps ? maps->at((long long)row0) : AttnMaps();
-        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr)) return rc;
+        const RowNoise pass_nz = nz ? nz->at((long long)row0) : RowNoise{};       // ids default to the row of the CALL: b T + t
+        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr, &pass_nz))
+            return rc;
     }
     return 0;
 }
@@ -1717,13 +1746,58 @@ extern "C" int iefvad_forward_attn(iefvad_handle* h, const void* img, const void
     return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, &am);
 }
 
+// The row perturbation of a call as the kernels take it (common.h): the caller's amplitudes, ids and seed at row 0 of the call
+static RowNoise row_noise(const iefvad_perturb& p) {
+    RowNoise nz = {};
+    nz.amp[0] = p.noise_amp[0]; nz.amp[1] = p.noise_amp[1];
+    nz.id = p.noise_row;
+    nz.seed = p.seed;
+    return nz;
+}
+static int perturb_aligned(const char* who, const iefvad_perturb& p) {
+    if (((uintptr_t)p.noise_amp[0] | (uintptr_t)p.noise_amp[1] | (uintptr_t)p.noise_row) & 3)
+        return fail("%s: noise amplitude and noise row vectors must be 4-byte aligned", who);
+    return 0;
+}
+
+extern "C" int iefvad_forward_perturbed(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const iefvad_perturb* p,
+                                        void* workspace, size_t workspace_bytes, const iefvad_outputs* out, void* stream) {
+    if (!h) return fail("iefvad_forward_perturbed: null argument");
+    if (!p) return fail("iefvad_forward_perturbed: null perturbation");
+    if (int rc = perturb_aligned("iefvad_forward_perturbed", *p)) return rc;
+    const RowNoise nz = row_noise(*p);
+    if (!p->scale[0] && !p->scale[1] && !nz.any()) return iefvad_forward(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream);
+    Timer tm;      // direct launches: vectors and seed are per call, a cached graph would pin them
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, p->scale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, &nz);
+}
+
 extern "C" int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const float* img_row_scale,
                                      const float* ev_row_scale, void* workspace, size_t workspace_bytes, const iefvad_outputs* out, void* stream) {
     if (!h) return fail("iefvad_forward_scaled: null argument");
-    if (!img_row_scale && !ev_row_scale) return iefvad_forward(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream);
-    Timer tm;      // direct launches: the scale vectors are per call, a cached graph would pin their addresses
-    const float* const scale[2] = {img_row_scale, ev_row_scale};
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, scale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
+    iefvad_perturb p = {};
+    p.scale[0] = img_row_scale; p.scale[1] = ev_row_scale;
+    return iefvad_forward_perturbed(h, img, ev, in_dtype, B, &p, workspace, workspace_bytes, out, stream);
+}
+
+extern "C" int iefvad_perturb_rows(const void* img_rows, const void* ev_rows, int32_t in_dtype, int32_t D, int64_t rows, int32_t nan_to_num_all,
+                                   const iefvad_perturb* p, void* out_img, void* out_ev, void* stream) {
+    static const char* const who = "iefvad_perturb_rows";
+    if (!p) return fail("%s: null perturbation", who);
+    if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
+    if (D != IEF_D && D != IEF_D512) return fail("%s: D must be %d or %d (got %d)", who, IEF_D, IEF_D512, D);
+    if (rows <= 0 || rows > 0x7fffffffLL) return fail("%s: rows must be in 1 .. 2^31 - 1 (got %lld)", who, (long long)rows);
+    if ((!img_rows && out_img) || (!ev_rows && out_ev)) return fail("%s: an output without its source rows", who);
+    if (!out_img && !out_ev) return fail("%s: null outputs (nothing is asked for)", who);
+    if (((uintptr_t)img_rows | (uintptr_t)ev_rows | (uintptr_t)out_img | (uintptr_t)out_ev) & 15) return fail("%s: buffers must be 16-byte aligned", who);
+    if (((uintptr_t)p->scale[0] | (uintptr_t)p->scale[1]) & 3) return fail("%s: row scale vectors must be 4-byte aligned", who);
+    if (int rc = perturb_aligned(who, *p)) return rc;
+    const RowNoise nz = row_noise(*p);
+    const float big = in_dtype == IEFVAD_IN_F32 ? 3.40282347e38f : in_dtype == IEFVAD_IN_F16 ? 65504.f : 3.38953139e38f;     // RaggedLimits (ragged.h)
+    return dispatch_in(in_dtype, D == IEF_D512, [&](auto t, auto w) {
+        return launch_perturb_rows<typename decltype(t)::type, decltype(w)::value>(out_img ? img_rows : nullptr, out_ev ? ev_rows : nullptr, out_img, out_ev,
+                                                                                  (size_t)rows * D, p->scale[0], p->scale[1], nan_to_num_all != 0, nz,
+                                                                                  big, (hipStream_t)stream);
+    });
 }
 
 extern "C" int iefvad_forward_timed(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B,

@@ -63,10 +63,17 @@ __global__ __launch_bounds__(256) void iefvad_nanflag_kernel(const T* img, const
 // is multiplied by sc0[r] / sc1[r] (nullable) AFTER the replacement (test2.py:70-77) with the semantics of
 // iefvad_cast_scaled_kernel (rowops.h): fp32 product, rounded to T before the widening, a scale of exactly 1 leaves the bits
 // alone.  Pad rows are the zeros written here, never scaled.  SC = false is the kernel of iefvad_forward_videos, unchanged.
-template <typename T, int D, bool SC = false>
+// NOISE = RowNoise (iefvad_forward_videos_perturbed with an amplitude vector; a mode of SC): behind the scale, packed row r gets
+// nz.amp[m][r] * eps added (add_row_noise4, common.h); an amplitude of exactly 0 leaves the bits alone.  The row's noise id is nz.id[r],
+// or -- nz.id NULL -- its packed row in the CALL, nz.row0 + src_row + r: src_row is pass-relative.  The mode is a parameter pack
+// (row_noise_of, common.h): without it the kernels are, name and code, the ones they were.
+template <typename T, int D, bool SC = false, typename... NOISE>
 __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, const T* ev, const RaggedChunk* chunks, const int* flags,
                                                                   float* out0, float* out1, __bf16* ob0, __bf16* ob1, int nrows,
-                                                                  const float* sc0, const float* sc1, int fix_all) {
+                                                                  const float* sc0, const float* sc1, int fix_all, NOISE... noise) {
+    constexpr bool NZ = sizeof...(NOISE) == 1;
+    static_assert(sizeof...(NOISE) <= 1 && (SC || !NZ), "the noise mode is one RowNoise, on the scaled chunker");
+    const RowNoise nz = row_noise_of(noise...);
     constexpr int NJ = D / 256;
     const RaggedChunk c = chunks[blockIdx.x];
     const int m = blockIdx.y;
@@ -77,6 +84,8 @@ __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, 
     const bool fix = (SC && fix_all) || (flags && flags[2 * c.video + m] != 0);
     const float* sc = SC ? (m ? sc1 : sc0) : nullptr;
     if (sc) sc += c.src_row;
+    const float* na = NZ ? nz.amp[m] : nullptr;
+    if (na) na += c.src_row;
     const float big = RaggedLimits<T>::max();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nr = nrows ? nrows : ragged_rows(c.valid);
@@ -121,6 +130,11 @@ __global__ __launch_bounds__(256) void iefvad_scatter_rows_kernel(const T* img, 
                             w[e] = (float)(T)prod;
                         }
                     }
+                }
+                if (NZ && na && r < c.valid) {
+                    const float a = na[r];
+                    if (a != 0.0f)
+                        add_row_noise4<T>(w, a, nz.seed, nz.id ? (unsigned)nz.id[c.src_row + r] : (unsigned)(nz.row0 + c.src_row + r), m, col);
                 }
                 *(f32x4*)(out + (size_t)r * D + col) = w;
                 if (ob) *(bf16x4_t*)(ob + (size_t)r * D + col) = to_bf16x4(w);

@@ -310,13 +310,20 @@ __global__ __launch_bounds__(256) void iefvad_cast_kernel(const T* in0, const T*
 // /root/reference/test2.py:71-77 `x[:, idx] = x[:, idx] * 0.01`): the product is formed in fp32 and, for fp16 / bf16 sources, rounded
 // to the source type before the widening -- torch multiplies a half tensor in fp32 and stores a half tensor, and the model then
 // widens it (imf_vad.py:41-42).  A NULL scale vector, or a scale of exactly 1, leaves the row's bits alone.
-template <typename T, int D>
+// NOISE = RowNoise (iefvad_forward_perturbed with an amplitude vector): behind the scale, row r gets nz.amp[m][r] * eps added
+// (add_row_noise4, common.h; amplitude 0: bits alone); its noise id is nz.id[r], or nz.row0 + r.  The mode is a parameter pack
+// (row_noise_of, common.h): without it the kernel is, name and code, the one it was.
+template <typename T, int D, typename... NOISE>
 __global__ __launch_bounds__(256) void iefvad_cast_scaled_kernel(const T* in0, const T* in1, float* out0, float* out1, __bf16* ob0, __bf16* ob1,
-                                                                 size_t n, const float* s0, const float* s1) {
+                                                                 size_t n, const float* s0, const float* s1, NOISE... noise) {
+    constexpr bool NZ = sizeof...(NOISE) == 1;
+    static_assert(sizeof...(NOISE) <= 1, "the noise mode is one RowNoise");
+    const RowNoise nz = row_noise_of(noise...);
     const T* in = blockIdx.y ? in1 : in0;
     float* out = blockIdx.y ? out1 : out0;
     __bf16* ob = blockIdx.y ? ob1 : ob0;
     const float* sc = blockIdx.y ? s1 : s0;
+    const float* na = NZ ? nz.amp[blockIdx.y] : nullptr;
     for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx * 4 < n; idx += (size_t)gridDim.x * blockDim.x) {
         const size_t o = idx * 4;   // n is a multiple of 4, and so is the row length: the four elements share a row
         const float f = sc ? sc[o / D] : 1.0f;
@@ -333,8 +340,53 @@ __global__ __launch_bounds__(256) void iefvad_cast_scaled_kernel(const T* in0, c
                 v[e] = (float)(T)prod;
             }
         }
+        if (NZ && na) {
+            const size_t r = o / D;
+            const float a = na[r];
+            if (a != 0.0f) add_row_noise4<T>(v, a, nz.seed, nz.id ? (unsigned)nz.id[r] : (unsigned)(nz.row0 + (long long)r), blockIdx.y, (int)(o - r * D));
+        }
         if (out) *(f32x4*)(out + o) = v;
         if (ob) *(bf16x4_t*)(ob + o) = to_bf16x4(v);
+    }
+}
+
+// The perturbation of one input row on its own (iefvad_perturb_rows: the unit entry the fused loads above are tested against): the
+// NaN rule if `fix_all`, the row scale, the row noise -- the steps and roundings of the two kernels above and of the chunker's
+// (ragged.h) -- with the result written in the source type.  A row that no step touches keeps its bits, NaN payloads included.
+// blockIdx.y = modality; a modality without a source or a destination is skipped.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void iefvad_perturb_rows_kernel(const T* in0, const T* in1, T* out0, T* out1, size_t n, const float* s0,
+                                                                  const float* s1, int fix_all, RowNoise nz, float big) {
+    const int m = blockIdx.y;
+    const T* in = m ? in1 : in0;
+    T* out = m ? out1 : out0;
+    if (!in || !out) return;
+    const float* sc = m ? s1 : s0;
+    const float* na = nz.amp[m];
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx * 4 < n; idx += (size_t)gridDim.x * blockDim.x) {
+        const size_t o = idx * 4, r = o / D;
+        const float f = sc ? sc[r] : 1.0f;
+        const float a = na ? na[r] : 0.0f;
+        T raw[4];
+        f32x4 w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            raw[e] = in[o + e];
+            w[e] = (float)raw[e];
+            if (fix_all) {
+                const float x = w[e];
+                w[e] = (x != x) ? 0.f : (x > big ? big : (x < -big ? -big : x));     // torch.nan_to_num(nan=0.0)
+            }
+            if (f != 1.0f) {
+                float prod = w[e] * f;
+                asm volatile("" : "+v"(prod));
+                w[e] = (float)(T)prod;
+            }
+        }
+        if (a != 0.0f) add_row_noise4<T>(w, a, nz.seed, nz.id ? (unsigned)nz.id[r] : (unsigned)(nz.row0 + (long long)r), m, (int)(o - r * D));
+        const bool touched = fix_all || f != 1.0f || a != 0.0f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[o + e] = touched ? (T)w[e] : raw[e];
     }
 }
 

@@ -109,6 +109,8 @@ static int videos_args(const char* who, const VideosOut& out, int32_t in_dtype, 
     if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
     if ((uintptr_t)out.w_colsum & 7) return fail("%s: w_colsum must be 8-byte aligned", who);
     if (((uintptr_t)out.scale[0] | (uintptr_t)out.scale[1]) & 3) return fail("%s: row scale vectors must be 4-byte aligned", who);
+    if (((uintptr_t)out.noise.amp[0] | (uintptr_t)out.noise.amp[1] | (uintptr_t)out.noise.id) & 3)
+        return fail("%s: noise amplitude and noise row vectors must be 4-byte aligned", who);
     return 0;
 }
 
@@ -261,17 +263,38 @@ extern "C" int iefvad_forward_videos_attn(iefvad_handle* h, const void* img_rows
     return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
 }
 
+// The two sweep entries: the record carries the scales and, for _perturbed, the noise amplitudes, ids and seed to the chunker
+static int forward_videos_perturbed(const char* who, iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                    const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const iefvad_perturb& p, void* workspace,
+                                    size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream) {
+    Timer tm;
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    out.scale[0] = p.scale[0]; out.scale[1] = p.scale[1];
+    out.noise.amp[0] = p.noise_amp[0]; out.noise.amp[1] = p.noise_amp[1];
+    out.noise.id = p.noise_row;
+    out.noise.seed = p.seed;
+    out.w_colsum = w_colsum;
+    out.sweep_codes = true;
+    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+}
+
+extern "C" int iefvad_forward_videos_perturbed(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                               const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const iefvad_perturb* perturb,
+                                               void* workspace, size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                               double* w_colsum, void* stream) {
+    if (!perturb) return fail("iefvad_forward_videos_perturbed: null perturbation");
+    return forward_videos_perturbed("iefvad_forward_videos_perturbed", h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, *perturb,
+                                    workspace, workspace_bytes, logits, w_i_mean, w_e_mean, w_colsum, stream);
+}
+
 extern "C" int iefvad_forward_videos_scaled(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
                                             const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const float* img_row_scale,
                                             const float* ev_row_scale, void* workspace, size_t workspace_bytes, float* logits,
                                             float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream) {
-    Timer tm;
-    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
-    out.scale[0] = img_row_scale; out.scale[1] = ev_row_scale;
-    out.w_colsum = w_colsum;
-    out.sweep_codes = true;
-    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm,
-                               "iefvad_forward_videos_scaled");
+    iefvad_perturb p = {};
+    p.scale[0] = img_row_scale; p.scale[1] = ev_row_scale;
+    return forward_videos_perturbed("iefvad_forward_videos_scaled", h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, p, workspace,
+                                    workspace_bytes, logits, w_i_mean, w_e_mean, w_colsum, stream);
 }
 
 extern "C" int iefvad_forward_videos_similarity(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,

@@ -1383,6 +1383,108 @@ def sweep_plan():
     return ([("IMG_NOISE", s, 0) for s in SWEEP_LEVELS] + [("EV_NOISE", 0, s) for s in SWEEP_LEVELS])
 
 
+def noise_plan():
+    """(name, keyword arguments of `PerturbationSweep.level`) for the noise study the reference's flags promise and never run
+    (test2.py:214-220; semantics defined by this package, "parity unpinned"): the six SWEEP_LEVELS as Gaussian sigma per modality, as
+    outlier ratio per modality, and as modality-drop probability."""
+    plan = []
+    for key, name in (("noise_sigma_img", "IMG_GAUSS"), ("noise_sigma_ev", "EV_GAUSS"), ("outlier_img", "IMG_OUTLIER"),
+                      ("outlier_ev", "EV_OUTLIER"), ("dropout_prob", "MODALITY_DROP")):
+        plan += [(name, {key: s}) for s in SWEEP_LEVELS]
+    return plan
+
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _fmix32(x):
+    """murmur3's 32-bit finaliser on uint64 arrays holding 32-bit values (csrc/common.h, fmix32)."""
+    x = x ^ (x >> np.uint64(16))
+    x = (x * np.uint64(0x85EBCA6B)) & _M32
+    x = x ^ (x >> np.uint64(13))
+    x = (x * np.uint64(0xC2B2AE35)) & _M32
+    return x ^ (x >> np.uint64(16))
+
+
+def dropout_bits(seed: int, idx):
+    """Host model of the library's counter-based 24-bit generator (csrc/common.h, dropout_bits): `idx` a uint64 array."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    idx = np.asarray(idx, dtype=np.uint64)
+    lo, hi = idx & _M32, idx >> np.uint64(32)
+    a = _fmix32(lo ^ np.uint64(seed & 0xFFFFFFFF))
+    return _fmix32((a + np.uint64(seed >> 32) + hi * np.uint64(0x9E3779B1)) & _M32) >> np.uint64(8)
+
+
+def gaussian_rows(seed: int, modality: int, row_ids, D: int) -> np.ndarray:
+    """Host model of the library's row noise (include/iefvad.h, `iefvad_perturb`; csrc/common.h, gauss_pair): eps[len(row_ids), D] fp32,
+    a standard normal that is a pure function of (seed, modality, noise id, column).  Columns come in pairs (2q, 2q + 1) by Box-Muller
+    from two draws of `dropout_bits` at idx = ((id * 2 + modality) << 11) | (q << 1) and idx | 1; fp64 throughout, rounded once to fp32
+    (the device computes in fp32: tests/test_gpu_perturb.py measures the difference)."""
+    ids = np.asarray(row_ids, dtype=np.uint64).reshape(-1, 1)
+    q = np.arange(D // 2, dtype=np.uint64).reshape(1, -1)
+    idx = ((ids * np.uint64(2) + np.uint64(modality)) << np.uint64(11)) | (q << np.uint64(1))
+    b1 = dropout_bits(seed, idx).astype(np.float64)
+    b2 = dropout_bits(seed, idx | np.uint64(1)).astype(np.float64)
+    u1, u2 = (b1 + 1.0) * 2.0 ** -24, b2 * 2.0 ** -24
+    rho = np.sqrt(-2.0 * np.log(u1))
+    eps = np.empty((ids.shape[0], D), dtype=np.float64)
+    eps[:, 0::2] = rho * np.cos(2.0 * np.pi * u2)
+    eps[:, 1::2] = rho * np.sin(2.0 * np.pi * u2)
+    return eps.astype(np.float32)
+
+
+def sweep_row_perturbation(lengths: Sequence[int], plans, T: int, noise_sigma=(0.0, 0.0), outlier_sigma: float = 1.0,
+                           nchunks: Optional[Sequence[int]] = None, first_ids: Optional[Sequence[int]] = None):
+    """The row vectors of one level of the noise study over the listed videos -> ((scale_img, scale_ev), (amp_img, amp_ev), ids), fp32
+    host tensors (ids: int32), None where a modality has nothing of the kind.  `plans[v]` = (att, out, drop): `att` / `out` the pairs
+    (image, event) of time steps drawn for attenuation (scale 0.01, test2.py:70-77) and for outliers (amplitude `outlier_sigma` instead of
+    `noise_sigma[m]`), None where not drawn; `drop` the dropped modality (0 image, 1 event: scale 0 on all its valid rows) or None.
+    `nchunks` None: the packed valid rows (sum(lengths) elements, ids None: the valid-row call numbers its rows itself).  `nchunks[v]`
+    given: the padded layout, nchunks[v] * T rows per video -- pad rows get amplitude 0 and, for a dropped modality, keep scale 1 -- and
+    ids = first_ids[v] + the snippet's index in its video (0 on pad rows, which carry no noise)."""
+    padded = nchunks is not None
+    want_scale = [any(p[0][m] is not None and p[0][m].numel() for p in plans) or any(p[2] == m for p in plans) for m in (0, 1)]
+    want_amp = [noise_sigma[m] != 0 or any(p[1][m] is not None and p[1][m].numel() for p in plans) for m in (0, 1)]
+    scale, amp, ids = ([], []), ([], []), []
+    for v, (n, (att, out, drop)) in enumerate(zip(lengths, plans)):
+        n = int(n)
+        rows = int(nchunks[v]) * T if padded else n
+        reps = -(-rows // T)
+        for m in (0, 1):
+            if want_scale[m]:
+                step = torch.ones(T)
+                if att[m] is not None and att[m].numel():
+                    step[att[m]] = 0.01
+                sc = step.repeat(reps)[:rows].clone()
+                if drop == m:
+                    sc[:n] = 0.0
+                scale[m].append(sc)
+            if want_amp[m]:
+                step = torch.full((T,), float(noise_sigma[m]))
+                if out[m] is not None and out[m].numel():
+                    step[out[m]] = float(outlier_sigma)
+                a = step.repeat(reps)[:rows].clone()
+                a[n:] = 0.0
+                amp[m].append(a)
+        if padded:
+            i = torch.zeros(rows, dtype=torch.int32)
+            i[:n] = torch.arange(int(first_ids[v]), int(first_ids[v]) + n, dtype=torch.int32)
+            ids.append(i)
+    cat = lambda parts: torch.cat(parts).contiguous() if parts else None
+    return ((cat(scale[0]), cat(scale[1])), (cat(amp[0]), cat(amp[1])), cat(ids) if padded and any(want_amp) else None)
+
+
+def perturb_rows_host(x: torch.Tensor, scale, amp, seed, modality: int, ids) -> torch.Tensor:
+    """The CPU plumbing path's perturbed copy of [rows, D] features, with torch ops: `x * scale` where the scale is not 1, then
+    `x + amp * eps` (fp32 sum, rounded to x's dtype) where the amplitude is not 0, eps = `gaussian_rows(seed, modality, ids, D)`."""
+    if scale is not None:
+        x = torch.where((scale != 1)[:, None], x * scale[:, None].to(x.dtype), x)
+    if amp is not None:
+        eps = torch.from_numpy(gaussian_rows(seed, modality, ids.numpy(), x.shape[-1]))
+        x = torch.where((amp != 0)[:, None], (x.float() + amp[:, None] * eps).to(x.dtype), x)
+    return x
+
+
 class SweepResult(tuple):
     """The 12 numbers `run_test` returns (test2.py:119-123), in its order, with names."""
     FIELDS = ("brier", "kl", "w_img_mean", "w_ev_mean", "auc", "ap", "w_img_anomalous", "w_ev_anomalous",
@@ -1505,16 +1607,26 @@ class PerturbationSweep:
         self.rows = tuple(torch.cat([t.to(dt) for t in parts]).contiguous().to(self.device) for parts in (imgs, evs))
         self._init_gt(gt)
 
-    def _pass_rows(self, draws=None):
+    def _pass_rows(self, draws=None, noise=None, rows=None):
         """One `forward_videos` call over the whole list: mode "always" of the NaN rule, the level's packed scale vectors, the
-        column sums of the fusion weights from the device."""
-        scale = None
-        if draws is not None:
+        column sums of the fusion weights from the device.  `noise` = (plans, sigmas, outlier_sigma, seed): a level of the noise study,
+        its packed scale and amplitude vectors (`sweep_row_perturbation`); the call numbers its packed rows itself, which is the
+        snippet's index in the list.  `rows`: other device rows than the resident clean ones (tools/perturb_probe.py: a copy perturbed
+        on the host)."""
+        rows = self.rows if rows is None else rows
+        scale, kw = None, {}
+        dev = lambda t: t.to(self.device) if t is not None else None
+        if noise is not None:
+            plans, sigmas, outlier_sigma, seed = noise
+            sc, amp, _ = sweep_row_perturbation(self.lengths, plans, self.T, sigmas, outlier_sigma)
+            scale = (dev(sc[0]), dev(sc[1]))
+            if amp[0] is not None or amp[1] is not None:
+                kw = dict(row_noise=(dev(amp[0]), dev(amp[1])), noise_seed=seed)
+        elif draws is not None:
             si, se = sweep_row_scales(self.lengths, draws, self.T)
             scale = (si.to(self.device) if si is not None else None, se.to(self.device) if se is not None else None)
         with torch.no_grad():
-            out = self.model.forward_videos(self.rows[0], self.rows[1], self.lengths, nan_to_num="always", row_scale=scale,
-                                            weight_sums=True)
+            out = self.model.forward_videos(rows[0], rows[1], self.lengths, nan_to_num="always", row_scale=scale, weight_sums=True, **kw)
         return {"p": torch.sigmoid(out["logits"]).float(), "wi_row": out["w_i_mean"], "we_row": out["w_e_mean"],
                 "wi_dim": out["w_colsum"][0] / self.total, "we_dim": out["w_colsum"][1] / self.total}
 
@@ -1537,15 +1649,31 @@ class PerturbationSweep:
         return out
 
     # one packed pass over the list; `draws[v]` = (image time steps, event time steps) to attenuate in video v, or None
-    def _pass(self, draws=None):
+    def _pass(self, draws=None, noise=None):
         if self.ragged:
-            return self._pass_rows(draws)
+            return self._pass_rows(draws, noise)
         probs, wi_rows, we_rows = [], [], []
         wi_dim = we_dim = None
         on_gpu = self.device.type == 'cuda'
+        first = np.concatenate([[0], np.cumsum(self.lengths)])       # a video's first snippet in the list: the noise ids
         with torch.no_grad():
             for batch, (img, ev, valid) in zip(self.batches, self.packed):
-                if draws is None:
+                if noise is not None:
+                    plans, sigmas, outlier_sigma, seed = noise
+                    sc, amp, ids = sweep_row_perturbation([self.lengths[v] for v in batch], [plans[v] for v in batch], self.T, sigmas,
+                                                          outlier_sigma, [self.nchunks[v] for v in batch], [first[v] for v in batch])
+                    if on_gpu:
+                        dev = lambda t: t.to(self.device) if t is not None else None
+                        kw = {}
+                        if ids is not None:
+                            kw = dict(row_noise=(dev(amp[0]), dev(amp[1])), noise_seed=seed, noise_rows=dev(ids))
+                        out = self.model(img, ev, None, None, None, row_scale=(dev(sc[0]), dev(sc[1])), **kw)
+                    else:       # CPU plumbing: the perturbed copy with torch ops and the host model of the generator
+                        D = img.shape[-1]
+                        xi = perturb_rows_host(img.reshape(-1, D), sc[0], amp[0], seed, 0, ids).reshape(img.shape)
+                        xe = perturb_rows_host(ev.reshape(-1, D), sc[1], amp[1], seed, 1, ids).reshape(ev.shape)
+                        out = self.model(xi, xe, None, None, None)
+                elif draws is None:
                     out = self.model(img, ev, None, None, None)
                 else:
                     si, se = self._scales(batch, draws)
@@ -1581,15 +1709,41 @@ class PerturbationSweep:
         g = self.gt.reshape(-1).cpu().numpy()
         return roc_auc_score(g, y), average_precision_score(g, y)
 
-    def level(self, sigma_img=0, sigma_ev=0) -> SweepResult:
+    def level(self, sigma_img=0, sigma_ev=0, *, noise_sigma_img=0, noise_sigma_ev=0, outlier_img=0, outlier_ev=0, outlier_sigma=1.0,
+              dropout_prob=0, noise_seed=None) -> SweepResult:
+        """One level.  `sigma_img`, `sigma_ev`: the reference's attenuation (test2.py:70-77).  The keyword-only levels are the noise study
+        whose flags the reference declares and never reads (test2.py:35-37,214-220); their semantics are defined here ("parity
+        unpinned"), all on valid snippets only: `noise_sigma_*` -- every valid snippet of the modality gets x + sigma * eps, eps the
+        library's standard normal (`gaussian_rows`); `outlier_*` = rho -- per video `torch.randperm(T)[:int(T * rho)]` time steps of
+        every chunk get amplitude `outlier_sigma` instead; `dropout_prob` = p -- per video one `torch.rand(2)` draw u: if u[0] < p, the
+        image modality (u[1] < 0.5) or the event modality gets row scale 0 on all its rows.  Draw order per video: the two attenuation
+        draws, image outliers, event outliers, the drop draw, each only when its level is non-zero -- `level(sigma_img, sigma_ev)`
+        consumes torch's RNG exactly as it always has.  With noise or outliers and `noise_seed=None`, one 63-bit seed is drawn from
+        torch's RNG before the per-video draws.  Noise ids are the snippet's index in the list, on both routes."""
         c = self.clean()
         k_img, k_ev = int(self.T * sigma_img), int(self.T * sigma_ev)
-        draws = []
+        study = bool(noise_sigma_img or noise_sigma_ev or outlier_img or outlier_ev or dropout_prob)
+        if (noise_sigma_img or noise_sigma_ev or outlier_img or outlier_ev) and noise_seed is None:
+            noise_seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+        draws, plans = [], []
         for _ in self.lengths:       # the reference's draw order: per video, image then event; no draw for a zero sigma
             di = torch.randperm(self.T)[:k_img] if sigma_img else None
             de = torch.randperm(self.T)[:k_ev] if sigma_ev else None
             draws.append((di, de))
-        n = self._pass(draws)
+            if study:
+                oi = torch.randperm(self.T)[:int(self.T * outlier_img)] if outlier_img else None
+                oe = torch.randperm(self.T)[:int(self.T * outlier_ev)] if outlier_ev else None
+                drop = None
+                if dropout_prob:
+                    u = torch.rand(2)
+                    if float(u[0]) < dropout_prob:
+                        drop = 0 if float(u[1]) < 0.5 else 1
+                plans.append(((di, de), (oi, oe), drop))
+        n = self._pass(draws, (plans, (noise_sigma_img, noise_sigma_ev), outlier_sigma, noise_seed)) if study else self._pass(draws)
+        return self._result(c, n)
+
+    def _result(self, c, n) -> SweepResult:
+        """run_test's 12 numbers (test2.py:89-123) from the clean pass `c` and a perturbed pass `n`"""
         rep = self.repeat
         yc, yn = c["p"].double(), n["p"].double()
         brier = ((yn[:, None] - self.gt) ** 2).mean()
@@ -1606,18 +1760,21 @@ class PerturbationSweep:
 
 
 def run_perturbation_test(args, model, loader, gt, device, sigma_img=0, sigma_ev=0, clean_cache: Optional[dict] = None,
-                          batch_chunks: int = 64, ragged: bool = False) -> SweepResult:
+                          batch_chunks: int = 64, ragged: bool = False, *, noise_sigma_img=0, noise_sigma_ev=0, outlier_img=0, outlier_ev=0,
+                          outlier_sigma=1.0, dropout_prob=0, noise_seed=None) -> SweepResult:
     """One level of the sweep with the call shape of the reference's `run_test(args, model, loader, gt, device,
     sigma_img, sigma_ev)` (test2.py:35) and its 12-tuple.  `clean_cache` (a dict the caller keeps across levels) holds
     the `PerturbationSweep`, so the unpacked list and the clean pass are shared by all levels.  `ragged=True`: the sweep's
-    valid-row route (HIP only; `PerturbationSweep`)."""
+    valid-row route (HIP only; `PerturbationSweep`).  The keyword-only levels are those of `PerturbationSweep.level`: the noise study of
+    test2.py:214-220, which the reference declares and does not implement ("parity unpinned")."""
     model.eval()
     sweep = clean_cache.get("sweep") if clean_cache is not None else None
     if sweep is None:
         sweep = PerturbationSweep(args, model, loader, gt, device, batch_chunks, ragged=ragged)
         if clean_cache is not None:
             clean_cache["sweep"] = sweep
-    return sweep.level(sigma_img, sigma_ev)
+    return sweep.level(sigma_img, sigma_ev, noise_sigma_img=noise_sigma_img, noise_sigma_ev=noise_sigma_ev, outlier_img=outlier_img,
+                       outlier_ev=outlier_ev, outlier_sigma=outlier_sigma, dropout_prob=dropout_prob, noise_seed=noise_seed)
 
 
 # ------------------------------------------------------------------------------------------------

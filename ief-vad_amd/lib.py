@@ -37,7 +37,7 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_forward_videos_host_similarity", "iefvad_videos_full_workspace_bytes", "iefvad_forward_videos_full",
            "iefvad_forward_videos_host_full", "iefvad_forward_attn", "iefvad_forward_videos_attn",
            "iefvad_gemm_split_small_unit", "iefvad_gemm_split_small_launches", "iefvad_set_batch_invariant",
-           "iefvad_train_backward_inputs"]
+           "iefvad_train_backward_inputs", "iefvad_forward_perturbed", "iefvad_forward_videos_perturbed", "iefvad_perturb_rows"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -89,6 +89,12 @@ class Outputs(C.Structure):
 class AttnMaps(C.Structure):
     """iefvad_attn_maps (include/iefvad.h): device fp32 maps per layer, 0 where a layer is not asked for."""
     _fields_ = [("image", _fp * MAX_LAYERS), ("event", _fp * MAX_LAYERS)]
+
+
+class Perturb(C.Structure):
+    """iefvad_perturb (include/iefvad.h): device row scales, noise amplitudes (image, event; 0 = none), noise ids (0 = the call's row index)
+    and the generator's seed."""
+    _fields_ = [("scale", _fp * 2), ("noise_amp", _fp * 2), ("noise_row", _fp), ("seed", C.c_uint64)]
 
 
 class StageTimes(C.Structure):
@@ -164,6 +170,12 @@ def load_library() -> C.CDLL:
     lib.iefvad_forward_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.POINTER(Outputs), C.c_void_p]
     lib.iefvad_forward_scaled.restype = C.c_int
+    # the perturbed entries: the two scale pointers replaced by one `const iefvad_perturb*`
+    lib.iefvad_forward_perturbed.argtypes = lib.iefvad_forward_scaled.argtypes[:5] + [C.POINTER(Perturb)] + lib.iefvad_forward_scaled.argtypes[7:]
+    lib.iefvad_forward_perturbed.restype = C.c_int
+    lib.iefvad_perturb_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(Perturb), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+    lib.iefvad_perturb_rows.restype = C.c_int
     lib.iefvad_forward_timed.argtypes = lib.iefvad_forward.argtypes + [C.POINTER(StageTimes)]
     lib.iefvad_forward_timed.restype = C.c_int
     lib.iefvad_videos_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
@@ -177,6 +189,9 @@ def load_library() -> C.CDLL:
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.c_void_p]
     lib.iefvad_forward_videos_scaled.restype = C.c_int
+    lib.iefvad_forward_videos_perturbed.argtypes = (lib.iefvad_forward_videos_scaled.argtypes[:7] + [C.POINTER(Perturb)] +
+                                                    lib.iefvad_forward_videos_scaled.argtypes[9:])
+    lib.iefvad_forward_videos_perturbed.restype = C.c_int
     lib.iefvad_forward_videos_host.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.iefvad_forward_videos_host.restype = C.c_int

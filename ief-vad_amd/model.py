@@ -55,6 +55,7 @@ _ROW_ENTRIES = {
     "_similarity": ("", lambda r: (), lambda r: (*r["vectors"], r["stream"], r["similarity"])),
     "_full": ("_full", lambda r: (r["out"],), lambda r: (r["out"], r["stream"])),
     "_scaled": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
+    "_perturbed": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
     "_attn": ("", lambda r: (), lambda r: (*r["vectors"], r["maps"], r["stream"])),
 }
 
@@ -99,6 +100,70 @@ def _row_entry_suffix(similarity, outputs, full_entry: str, extras: bool = False
         raise ValueError("outputs= does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
                          "iefvad_forward_videos_scaled returns no [rows, D] tensor")
     return wide, "_scaled" if extras else "_full" if wide else "_similarity" if similarity else ""
+
+
+def _perturb_struct(nrows: int, device, row_scale, row_noise, noise_seed, noise_rows, what: str):
+    """The `iefvad_perturb` of a call over `nrows` rows on `device`, and whether it carries noise.  `row_scale` / `row_noise`: None or a pair
+    of contiguous fp32 device vectors of `nrows` elements (either may be None); `noise_rows`: None or a contiguous int32 device vector of
+    noise ids; `noise_seed`: the generator's seed, required with `row_noise` (ValueError).  `what` names the row count in the messages."""
+    pairs = {}
+    for name, pair in (("row_scale", row_scale), ("row_noise", row_noise)):
+        pair = (None, None) if pair is None else tuple(pair)
+        if len(pair) != 2:
+            raise ValueError(f"{name} must be a pair (image vector, event vector), either may be None")
+        for v in pair:
+            if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != device or v.numel() != nrows
+                                  or not v.is_contiguous()):
+                raise ValueError(f"{name} vectors must be contiguous fp32 tensors of {nrows} elements ({what}) on {device}")
+        pairs[name] = pair
+    noisy = any(v is not None for v in pairs["row_noise"])
+    if noisy and noise_seed is None:
+        raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
+    if noise_rows is not None:
+        if not noisy:
+            raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
+        if (not isinstance(noise_rows, torch.Tensor) or noise_rows.dtype != torch.int32 or noise_rows.device != device
+                or noise_rows.numel() != nrows or not noise_rows.is_contiguous()):
+            raise ValueError(f"noise_rows must be a contiguous int32 tensor of {nrows} elements ({what}) on {device}")
+    p = _lib.Perturb()
+    for m in (0, 1):
+        p.scale[m] = pairs["row_scale"][m].data_ptr() if pairs["row_scale"][m] is not None else None
+        p.noise_amp[m] = pairs["row_noise"][m].data_ptr() if pairs["row_noise"][m] is not None else None
+    p.noise_row = noise_rows.data_ptr() if noise_rows is not None else None
+    p.seed = (int(noise_seed) & 0xFFFFFFFFFFFFFFFF) if noise_seed is not None else 0
+    return p, noisy
+
+
+def perturb_rows(img_rows: Optional[torch.Tensor], ev_rows: Optional[torch.Tensor], *, row_scale=None, row_noise=None, noise_seed=None,
+                 noise_rows=None, nan_to_num: bool = False):
+    """The perturbation of input rows on its own (`iefvad_perturb_rows`, include/iefvad.h): [rows, D] device tensors (fp32, fp16 or bf16,
+    D = 768 or 512; either may be None) -> (image rows, event rows) of the same dtype after, in this order, `nan_to_num` (torch.nan_to_num
+    on every row), the row scale and the row noise, exactly as the input loads of `MMFMIL.forward(row_scale=, row_noise=)` and
+    `MMFMIL.forward_videos(...)` form them.  The noise study's semantics are this package's own (the reference implements none:
+    "parity unpinned"); this entry is what the fused loads are tested against."""
+    src = [t for t in (img_rows, ev_rows) if t is not None]
+    if not src:
+        raise ValueError("perturb_rows needs at least one of img_rows, ev_rows")
+    x0 = src[0]
+    if any(t.dim() != 2 or t.shape != x0.shape or t.dtype != x0.dtype or t.device != x0.device for t in src):
+        raise ValueError("perturb_rows takes [rows, D] tensors of one shape, dtype and device")
+    if x0.dtype not in _IN_DTYPES:
+        raise ValueError(f"feature dtype {x0.dtype} is not supported (fp32, fp16 or bf16)")
+    if not x0.is_cuda:
+        raise RuntimeError("iefvad_amd.perturb_rows runs on a HIP device only; there is no CPU fallback (harness.gaussian_rows is the host model)")
+    rows, D = x0.shape
+    p, _ = _perturb_struct(rows, x0.device, row_scale, row_noise, noise_seed, noise_rows, "the rows")
+    lib = _lib.load_library()
+    ins = [t.contiguous() if t is not None else None for t in (img_rows, ev_rows)]
+    outs = [torch.empty_like(t) if t is not None else None for t in ins]
+    with torch.cuda.device(x0.device):
+        stream = torch.cuda.current_stream(x0.device).cuda_stream
+        ptr = [C.c_void_p(t.data_ptr()) if t is not None else None for t in ins + outs]
+        rc = lib.iefvad_perturb_rows(ptr[0], ptr[1], _IN_DTYPES[x0.dtype], D, rows, 1 if nan_to_num else 0, C.byref(p), ptr[2], ptr[3],
+                                     C.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError("iefvad_perturb_rows: " + _lib.last_error())
+    return outs[0], outs[1]
 
 
 class _LinearParams(nn.Module):
@@ -495,7 +560,7 @@ class MMFMIL(nn.Module):
         return x.contiguous()
 
     def forward(self, img_visual, ev_visual, padding_mask=None, text=None, lengths=None, return_attn=False,
-                *, timed: bool = False, row_scale=None, attn_maps=None) -> Dict[str, torch.Tensor]:
+                *, timed: bool = False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None, noise_rows=None) -> Dict[str, torch.Tensor]:
         """The reference's call (imf_vad.py:40-44; `padding_mask`, `text`, `lengths`, `return_attn` accepted and ignored as there).
         Keyword-only extras: `timed` (per-stage device times in `last_stage_times`), `row_scale=(s_img, s_ev)`: fp32 DEVICE vectors
         of [B*T] (either may be None) that multiply the input rows inside the library's input load (`iefvad_forward_scaled`: the
@@ -504,10 +569,27 @@ class MMFMIL(nn.Module):
         [n, B, T, T] fp32 in ascending layer order -- the head-averaged attention weights the reference's nn.MultiheadAttention calls
         form and discard (imf_vad.py:115,121) -- and `attn_layers`, the n layer indices.  Every other result keeps its bits.  Not with
         `timed` or `row_scale` (ValueError), compute="bf16" or model.train() (RuntimeError).
+        `row_noise=(a_img, a_ev)` with `noise_seed=` (`iefvad_forward_perturbed`): fp32 DEVICE vectors of [B*T] (either may be None); behind
+        the scale, row r of modality m gets a_m[r] * eps added in the input load, eps the library's counter-based standard normal of
+        (noise_seed, m, noise id, column) (include/iefvad.h; host model `harness.gaussian_rows`); the noise id is `noise_rows[r]` (int32
+        DEVICE vector) or the row index b*T + t.  Give pad rows amplitude 0.  The reference implements no such noise: these semantics are
+        this package's own ("parity unpinned").  `row_noise` without `noise_seed`, with `timed`, `attn_maps`, model.train() or features
+        that require grad raises ValueError.
         In eval() with grad enabled, a feature tensor that requires grad makes the call differentiable (the train-mode forward with every
         dropout probability forced to 0, the class docstring's keyword-free section); the three extras raise ValueError there."""
         self._noise_code()   # ValueError for an unsupported noise_model, as the reference raises
         layers = attn_map_layers(attn_maps, self.temporal.num_layers)
+        noisy = row_noise is not None and any(v is not None for v in row_noise)
+        if noisy:
+            if noise_seed is None:
+                raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
+            grad = torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad)
+            asked = [n for n, on in (("attn_maps=", bool(layers)), ("timed=True", timed), ("model.train()", self.training),
+                                     ("features that require grad", grad)) if on]
+            if asked:
+                raise ValueError(f"row_noise= does not combine with {' / '.join(asked)}: iefvad_forward_perturbed is a plain evaluation forward")
+        elif noise_rows is not None:
+            raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
         if layers:
             if timed or (row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None)):
                 raise ValueError("attn_maps= does not combine with timed=True or row_scale: iefvad_forward_attn takes neither")
@@ -575,6 +657,11 @@ class MMFMIL(nn.Module):
                 rc = lib.iefvad_forward_attn(*args[:8], C.byref(maps), args[8])
                 if rc != 0:
                     raise RuntimeError("iefvad_forward_attn: " + _lib.last_error())
+            elif noisy:
+                pert, _ = _perturb_struct(N, device, row_scale, row_noise, noise_seed, noise_rows, "B*T")
+                rc = lib.iefvad_forward_perturbed(*args[:5], C.byref(pert), *args[5:])
+                if rc != 0:
+                    raise RuntimeError("iefvad_forward_perturbed: " + _lib.last_error())
             elif row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None):
                 sp = []
                 for sv in row_scale:
@@ -727,7 +814,8 @@ class MMFMIL(nn.Module):
         return dict(zip(OUTPUT_KEYS, outs))
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
-                       weight_sums: bool = False, similarity: bool = False, outputs=None, attn_maps=None) -> Dict[str, torch.Tensor]:
+                       weight_sums: bool = False, similarity: bool = False, outputs=None, attn_maps=None, row_noise=None, noise_seed=None,
+                       noise_rows=None) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
@@ -737,6 +825,10 @@ class MMFMIL(nn.Module):
         DEVICE vectors of sum(lengths) elements (either may be None), multiply the packed rows inside the library's input load,
         after the NaN rule (test2.py:70-77 on valid rows); `weight_sums=True` adds `w_colsum`, a [2, D] float64 device tensor: the
         sums over all valid rows of w_i / w_e (test2.py:86-87), reduced on the device.
+        `row_noise=(a_img, a_ev)` with `noise_seed=` (`iefvad_forward_videos_perturbed`), fp32 DEVICE vectors of sum(lengths) elements
+        (either may be None), is a further extra of the sweep: behind the scale, packed row r gets a_m[r] * eps added, as in `forward`;
+        the noise id is `noise_rows[r]` (int32 DEVICE vector) or the packed row r of the call, in whatever micro-batch pass it falls.  The
+        semantics are this package's own ("parity unpinned": the reference implements no noise); without a seed it is a ValueError.
         `similarity=True` (`iefvad_forward_videos_similarity`) adds "similarity", a [4, sum(lengths)] fp32 device tensor: the series of
         `harness.SIMILARITY_KEYS` (test.py:235-238) of every valid snippet, reduced inside the library from the pass's own fused / mu
         rows -- whatever `outputs=` the model was built with; the other three results keep their bits.  The sweep's extras do not
@@ -754,8 +846,9 @@ class MMFMIL(nn.Module):
         layers = attn_map_layers(attn_maps, self.temporal.num_layers)
         if layers:
             if similarity or outputs is not None or weight_sums or nan_to_num == "always" or \
-                    (row_scale is not None and any(sv is not None for sv in row_scale)):
-                raise ValueError("attn_maps= does not combine with similarity=True, outputs=, row_scale, weight_sums or nan_to_num='always': "
+                    (row_scale is not None and any(sv is not None for sv in row_scale)) or \
+                    (row_noise is not None and any(sv is not None for sv in row_noise)):
+                raise ValueError("attn_maps= does not combine with similarity=True, outputs=, row_scale, row_noise, weight_sums or nan_to_num='always': "
                                  "iefvad_forward_videos_attn takes none of them")
             self._attn_maps_served("model.train()" if self.training else None)
         if self.training:
@@ -775,10 +868,19 @@ class MMFMIL(nn.Module):
             if sv is not None and (not isinstance(sv, torch.Tensor) or sv.dtype != torch.float32 or sv.device != img_rows.device
                                    or sv.numel() != nrows or not sv.is_contiguous()):
                 raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {nrows} elements (sum of lengths) on {img_rows.device}")
-        extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None
+        noisy = row_noise is not None and any(v is not None for v in row_noise)
+        if noisy and noise_seed is None:
+            raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
+        if noise_rows is not None and not noisy:
+            raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
+        extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None or noisy
         wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_full", extras)
         if layers:
             suffix = "_attn"
+        pert = None
+        if noisy:
+            pert, _ = _perturb_struct(nrows, img_rows.device, row_scale, row_noise, noise_seed, noise_rows, "sum of lengths")
+            suffix = "_perturbed"
         if not (img_rows.is_cuda and ev_rows.is_cuda):
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         lens = [int(n) for n in lengths]
@@ -796,7 +898,9 @@ class MMFMIL(nn.Module):
             img, ev = img.to(torch.float), ev.to(torch.float)
         larr = (C.c_int32 * len(lens))(*lens)
         front = (C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), nan_mode)
-        if extras:      # the scaled entry alone takes the two scale vectors, behind nan_to_num
+        if pert is not None:      # the perturbed entry: one struct in the place of the two scale vectors
+            front += (C.byref(pert),)
+        elif extras:    # the scaled entry alone takes the two scale vectors, behind nan_to_num
             front += tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in scales)
         return self._rows_call("iefvad_forward_videos", suffix, device, total, front, wide=wide, weight_sums=weight_sums,
                                workspace_for=(larr, len(lens)), attn_layers=layers)

@@ -477,6 +477,49 @@ int iefvad_host_gather_bf16(void* dst, const void* const* srcs, const size_t* nb
 int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const float* img_row_scale,
                           const float* ev_row_scale, void* workspace, size_t workspace_bytes, const iefvad_outputs* out, void* stream);
 
+/* ---- row perturbations for the noise study: additive Gaussian noise next to the row scale ---------------------------------------
+ * test2.py declares the study's arguments (run_test's outlier_img / outlier_ev :35-37, --noise_sigma_img / _ev :214-217,
+ * --outlier_ratio :218, --dropout_prob :220) and reads none of them: the reference implements no Gaussian noise, no outliers and no
+ * modality drop.  The semantics below are therefore this library's own -- PARITY UNPINNED -- and what is pinned is internal
+ * consistency: the fused load equals perturbed rows materialised first (iefvad_perturb_rows), the generator equals its host model
+ * (harness.gaussian_rows), the padded and the valid-row route agree.
+ * Row r of modality m (m = 0 image, 1 event) of a call enters the model as follows, in this order:
+ *   1. the NaN rule of the entry, as without a perturbation;
+ *   2. y = x if scale[m] is NULL or scale[m][r] == 1, else y = T(fp32(x) * scale[m][r])                 (iefvad_forward_scaled, T = in_dtype);
+ *   3. z = y, bits untouched, if noise_amp[m] is NULL or noise_amp[m][r] == 0, else z = T(fp32(y) + p), p = noise_amp[m][r] * eps
+ *      rounded to fp32 on its own (no fused multiply-add): what `y + amp * eps` gives in torch for a tensor of dtype T and an fp32 eps.
+ * Pad rows of the valid-row entry are the zeros the library writes and are never perturbed; on the padded entry they are rows of the
+ * caller's tensor: give them amplitude 0 and scale 1.
+ * eps is a standard normal in fp32, a pure function of (seed, m, id, column d): columns are generated in pairs (2q, 2q + 1) by Box-Muller
+ * from the library's 24-bit counter-based generator g(seed, index) (the one behind the train-mode dropout mask):
+ *     idx = ((uint64(id) * 2 + m) << 11) | (q << 1);   b1 = g(seed, idx);   b2 = g(seed, idx | 1)
+ *     u1 = (b1 + 1) 2^-24 in (0, 1];   u2 = b2 2^-24 in [0, 1);   rho = sqrt(-2 ln u1)
+ *     eps[2q] = rho cos(2 pi u2);   eps[2q + 1] = rho sin(2 pi u2)                        |eps| <= sqrt(48 ln 2) = 5.77
+ * id is noise_row[r], or -- noise_row NULL -- the row's index in the CALL: b T + t on the padded entry, the packed row on the valid-row
+ * entry (whatever micro-batch pass it falls into).  With ids that name the snippet in the list the same snippet gets the same noise on
+ * either route, in any batch composition.
+ * With both noise_amp NULL the two forward entries launch, and return the bits of, iefvad_forward_scaled / iefvad_forward_videos_scaled
+ * (which are thin wrappers over them).  A call with an amplitude vector launches directly (no graph replay: seed and pointers are per
+ * call).  iefvad_forward_videos_perturbed takes the arguments of iefvad_forward_videos_scaled with the two scale pointers replaced by the
+ * struct; its workspace is iefvad_videos_scaled_workspace_bytes.  iefvad_perturb_rows writes rows 1.-3. of `rows` rows of width D (768 or
+ * 512) in `in_dtype`, nan_to_num_all != 0 applying torch.nan_to_num to every row first; either source may be NULL when its output is.
+ * Refused by name before any launch: a NULL struct, an unknown in_dtype, D other than 768 / 512 (the unit entry), vectors that are not
+ * 4-byte aligned.  NOT covered: the host-list entries, the similarity / full / maps entries, and training take no perturbation.
+ * Added without a change to any other entry or struct: IEFVAD_ABI_VERSION stays. */
+typedef struct {
+    const float*   scale[2];      /* DEVICE [rows] fp32, nullable each: the row scales (image, event) */
+    const float*   noise_amp[2];  /* DEVICE [rows] fp32, nullable each */
+    const int32_t* noise_row;     /* DEVICE [rows] int32 >= 0, nullable: noise ids; NULL = the call's row index */
+    uint64_t       seed;
+} iefvad_perturb;
+int iefvad_forward_perturbed(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const iefvad_perturb* perturb,
+                             void* workspace, size_t workspace_bytes, const iefvad_outputs* out, void* stream);          /* rows = B*T */
+int iefvad_forward_videos_perturbed(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
+                                    int32_t nvideos, int32_t nan_to_num, const iefvad_perturb* perturb, void* workspace,
+                                    size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream);
+int iefvad_perturb_rows(const void* img_rows, const void* ev_rows, int32_t in_dtype, int32_t D, int64_t rows, int32_t nan_to_num_all,
+                        const iefvad_perturb* perturb, void* out_img, void* out_ev, void* stream);                      /* outputs in in_dtype */
+
 /* ---- metric tail of the evaluation loop --------------------------------------------------------------
  * What /root/reference/test.py:158-159 (train/ucf_test.py:153-154, train/xd_test.py:146-147) computes with sklearn on the host,
  *     ROC1 = roc_auc_score(gt, np.repeat(ap1, 16));   AP1 = average_precision_score(gt, np.repeat(ap1, 16))
