@@ -15,6 +15,7 @@
 #include <exception>
 #include <new>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "attention_f32.h"
@@ -312,17 +313,15 @@ extern "C" void iefvad_destroy(iefvad_handle* h) {
 template <typename T> struct InType { using type = T; };
 template <int W> struct RowWidth { static constexpr int value = W; };
 template <typename F>
-static void dispatch_d(bool d512, F&& f) {
-    if (d512) f(RowWidth<IEF_D512>{});
-    else f(RowWidth<IEF_D>{});
+static int dispatch_d(bool d512, F&& f) {      // f returns its launch's return code
+    if (d512) return f(RowWidth<IEF_D512>{});
+    return f(RowWidth<IEF_D>{});
 }
 template <typename F>
 static int dispatch_in(int in_dtype, bool d512, F&& f) {
-    int rc = 0;
-    dispatch_d(d512, [&](auto w) {
-        rc = in_dtype == IEFVAD_IN_F32 ? f(InType<float>{}, w) : in_dtype == IEFVAD_IN_F16 ? f(InType<__half>{}, w) : f(InType<__hip_bfloat16>{}, w);
+    return dispatch_d(d512, [&](auto w) {
+        return in_dtype == IEFVAD_IN_F32 ? f(InType<float>{}, w) : in_dtype == IEFVAD_IN_F16 ? f(InType<__half>{}, w) : f(InType<__hip_bfloat16>{}, w);
     });
-    return rc;
 }
 
 template <typename T>
@@ -666,6 +665,22 @@ struct Timer {
     }
 };
 
+// One checked launch: the launch, then hipGetLastError through `fail`.  With a timer and a stage, the launch sits in a span of that stage.
+template <typename... P, typename... A>
+static int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A&&... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, std::forward<A>(args)...);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+template <typename... P, typename... A>
+static int launch(Timer& tm, int stage, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, A&&... args) {
+    hipEvent_t e = tm.begin(stage);
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, std::forward<A>(args)...);
+    tm.end(e);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 static void release_events(iefvad_handle* h) {
     if (h->events) {
         h->events->release_all();
@@ -681,11 +696,11 @@ static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm,
         return fail("gemm: shape M=%d N=%d K=%d not a multiple of the %dx%dx%d tile", a.M, a.N, a.K, GEMM_BM, GEMM_BN,
                     GEMM_BK);
     const dim3 grid(pl.wgs, 1, nz);
-    hipEvent_t e = tm.begin(stage);
+    tm.gemm_launches += 1;
     switch (pl.kernel) {
-    case GEMM_F32_TINY: hipLaunchKernelGGL(iefvad_gemm_f32_tiny_kernel, grid, dim3(256), 0, stream, a); break;
-    case GEMM_F32_SMALL: hipLaunchKernelGGL(iefvad_gemm_f32_small_kernel, grid, dim3(256), 0, stream, a); break;
-    case GEMM_F32_128: hipLaunchKernelGGL(iefvad_gemm_f32_kernel, grid, dim3(256), 0, stream, a); break;
+    case GEMM_F32_TINY: return launch(tm, stage, iefvad_gemm_f32_tiny_kernel, grid, dim3(256), 0, stream, a);
+    case GEMM_F32_SMALL: return launch(tm, stage, iefvad_gemm_f32_small_kernel, grid, dim3(256), 0, stream, a);
+    case GEMM_F32_128: return launch(tm, stage, iefvad_gemm_f32_kernel, grid, dim3(256), 0, stream, a);
     case GEMM_F32_T256: {
         GemmBArgs b;
         memset(&b, 0, sizeof(b));
@@ -694,15 +709,10 @@ static int launch_gemm(const GemmArgs& a, int nz, hipStream_t stream, Timer& tm,
             b.p[m].A = (const bf16_t*)a.p[m].A; b.p[m].W = (const bf16_t*)a.p[m].W;     // fp32 data behind the typed pointer
             b.p[m].bias = a.p[m].bias; b.p[m].C = a.p[m].C; b.p[m].R = a.p[m].R; b.p[m].C2 = a.p[m].C2;
         }
-        hipLaunchKernelGGL(iefvad_gemm_f32_t256_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, b);
-        break;
+        return launch(tm, stage, iefvad_gemm_f32_t256_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, b);
     }
-    default: break;
+    default: return fail("gemm: the plan names no fp32 kernel");
     }
-    tm.end(e);
-    tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
 static int launch_gemm_b(const GemmBArgs& a, int nz, hipStream_t stream, Timer& tm, int stage) {
@@ -711,17 +721,13 @@ static int launch_gemm_b(const GemmBArgs& a, int nz, hipStream_t stream, Timer& 
         return fail("gemm(bf16): shape M=%d N=%d K=%d not a multiple of the %dx%dx%d tile", a.M, a.N, a.K, GEMM_BM,
                     GEMM_BN, GEMMB_BK);
     const dim3 grid(pl.wgs, 1, nz);
-    hipEvent_t e = tm.begin(stage);
-    switch (pl.kernel) {
-    case GEMM_BF16_W256: hipLaunchKernelGGL(iefvad_gemm_bf16_w256_kernel, grid, dim3(512), GB3_LDS_BYTES, stream, a); break;
-    case GEMM_BF16_PIPE: hipLaunchKernelGGL(iefvad_gemm_bf16_pipe_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, a); break;
-    case GEMM_BF16_V1: hipLaunchKernelGGL(iefvad_gemm_bf16_v1_kernel, grid, dim3(256), 0, stream, a); break;
-    default: break;
-    }
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    switch (pl.kernel) {
+    case GEMM_BF16_W256: return launch(tm, stage, iefvad_gemm_bf16_w256_kernel, grid, dim3(512), GB3_LDS_BYTES, stream, a);
+    case GEMM_BF16_PIPE: return launch(tm, stage, iefvad_gemm_bf16_pipe_kernel, grid, dim3(256), GB2_LDS_BYTES, stream, a);
+    case GEMM_BF16_V1: return launch(tm, stage, iefvad_gemm_bf16_v1_kernel, grid, dim3(256), 0, stream, a);
+    default: return fail("gemm(bf16): the plan names no bf16 kernel");
+    }
 }
 
 static std::atomic<unsigned long long> g_split_wide_launches{0};     // iefvad_gemm_split_wide_launches: which tiling ran is otherwise invisible
@@ -734,13 +740,9 @@ static int launch_gemm_split_small(const GemmBArgs& a, int nz, hipStream_t strea
             return fail("gemm(bf16x6, small): the dot-product epilogue takes one problem with its vector (R) and its partial sums (C2)");
         return fail("gemm(bf16x6, small): shape M=%d N=%d K=%d nz=%d not a multiple of the %dx%dx64 tile", a.M, a.N, a.K, nz, kSplitSmallBM, kSplitBN);
     }
-    hipEvent_t e = tm.begin(stage);
-    hipLaunchKernelGGL(iefvad_gemm_split_small_kernel, dim3(pl.wgs, 1, nz), dim3(256), GSS_LDS_BYTES, stream, a);
     g_split_small_launches.fetch_add(1, std::memory_order_relaxed);
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(tm, stage, iefvad_gemm_split_small_kernel, dim3(pl.wgs, 1, nz), dim3(256), GSS_LDS_BYTES, stream, a);
 }
 
 // invariant: the handle is in the batch-invariant mode (LaunchPolicy::split_always): what the default mode would have left to the fp32
@@ -771,20 +773,18 @@ static int launch_gemm_split(const GemmBArgs& a, int nz, hipStream_t stream, Tim
             if (!a.p[m].bias || (!dot && !a.p[m].C) || ((resid || dot) && !a.p[m].R) || ((dot || a.epi == EPI_HEADS) && !a.p[m].C2))
                 return fail("gemm(bf16x6): problem %d lacks an operand of epilogue %d", m, a.epi);
     }
-    hipEvent_t e = tm.begin(stage);
+    void (*kernel)(GemmBArgs) = nullptr;
     switch (pl.kernel) {
     case GEMM_SPLIT_N128X2:
-        hipLaunchKernelGGL(wide, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
+        kernel = wide;
         g_split_wide_launches.fetch_add(1, std::memory_order_relaxed);
         break;
-    case GEMM_SPLIT_F16_N128: hipLaunchKernelGGL(iefvad_gemm_split_f16_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a); break;
-    case GEMM_SPLIT_N128: hipLaunchKernelGGL(iefvad_gemm_split_n128_kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a); break;
-    default: break;
+    case GEMM_SPLIT_F16_N128: kernel = iefvad_gemm_split_f16_n128_kernel; break;
+    case GEMM_SPLIT_N128: kernel = iefvad_gemm_split_n128_kernel; break;
+    default: return fail("gemm(bf16x6): the plan names no split kernel");
     }
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(tm, stage, kernel, grid, dim3(256), GS_LDS_BYTES_OF(2), stream, a);
 }
 
 static size_t in_elem_bytes(int in_dtype) { return in_dtype == IEFVAD_IN_F32 ? 4 : 2; }
@@ -812,19 +812,42 @@ struct Proj {
     void set_w(int m, const ProjW& r) {
         W32[m] = r.w; W16[m] = r.wb; Ws[m] = r.ws; Wh[m] = r.wh; amaxW[m] = r.wa; bias[m] = r.b;
     }
+    // the shape half: one problem (w0) or one per modality (w0, w1); operands, alpha, qcols and the amax words are the caller's
+    static Proj of(int epi, int N, int ldc, const ProjW& w0, const ProjW* w1 = nullptr) {
+        Proj p;
+        memset(&p, 0, sizeof(p));
+        p.N = N; p.ldc = ldc; p.epi = epi; p.nz = w1 ? 2 : 1;
+        p.set_w(0, w0);
+        if (w1) p.set_w(1, *w1);
+        return p;
+    }
 };
 
-// D: the contraction length (the row width of A), the handle's embed dim
-static int launch_proj(const Proj& p, int compute, bool use_split, int D, int rows, hipStream_t stream, Timer& tm, int stage, int split_tile = 0,
-                       bool invariant = false) {
-    const bool bf16 = (compute == IEFVAD_COMPUTE_BF16);
-    if (p.epi == EPI_BIAS_RELU_DOT && !(use_split && compute == IEFVAD_COMPUTE_BF16X6))
+// What every projection of one forward shares.  D: the contraction length (the row width of A), the handle's embed dim;
+// invariant: the batch-invariant mode (launch_gemm_split)
+struct ProjCtx {
+    int compute;
+    bool use_split;
+    int D, rows;
+    hipStream_t stream;
+    Timer* tm;
+    int split_tile;
+    bool invariant;
+};
+
+static float precision_factor(const iefvad_config& c) {      // the Student-t factor of the precision weights (imf_vad.py:134)
+    return (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;
+}
+
+static int launch_proj(const ProjCtx& x, const Proj& p, int stage) {
+    const bool bf16 = (x.compute == IEFVAD_COMPUTE_BF16);
+    if (p.epi == EPI_BIAS_RELU_DOT && !(x.use_split && x.compute == IEFVAD_COMPUTE_BF16X6))
         return fail("gemm: the dot-product epilogue exists in the bf16x6 split kernel only");
-    if (use_split) {   // one rule for every projection of a micro-batch: the 768-wide, single-problem grid fills the chip
-        const bool f16 = (compute == IEFVAD_COMPUTE_FP16X3);
+    if (x.use_split) {   // one rule for every projection of a micro-batch: the 768-wide, single-problem grid fills the chip
+        const bool f16 = (x.compute == IEFVAD_COMPUTE_FP16X3);
         GemmBArgs g;
         memset(&g, 0, sizeof(g));
-        g.M = rows; g.N = p.N; g.K = IEF_D; g.lda = IEF_D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
+        g.M = x.rows; g.N = p.N; g.K = IEF_D; g.lda = IEF_D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
         g.wplane = p.N * IEF_D * 2;
         for (int m = 0; m < p.nz; ++m) {
             g.p[m].A = (const bf16_t*)p.A32[m];          // fp32 data behind the typed pointer
@@ -835,26 +858,26 @@ static int launch_proj(const Proj& p, int compute, bool use_split, int D, int ro
                 g.p[m].amaxA = p.amaxA[m]; g.p[m].amaxW = p.amaxW[m]; g.p[m].amaxC = p.amaxC[m];
             }
         }
-        return launch_gemm_split(g, p.nz, stream, tm, stage, f16, split_tile_for(split_tile, p.N, f16), invariant);
+        return launch_gemm_split(g, p.nz, x.stream, *x.tm, stage, f16, split_tile_for(x.split_tile, p.N, f16), x.invariant);
     }
     if (!bf16) {
         GemmArgs g;
         memset(&g, 0, sizeof(g));
-        g.M = rows; g.N = p.N; g.K = D; g.lda = D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
+        g.M = x.rows; g.N = p.N; g.K = x.D; g.lda = x.D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
         for (int m = 0; m < p.nz; ++m) {
             g.p[m].A = p.A32[m]; g.p[m].W = p.W32[m]; g.p[m].bias = p.bias[m]; g.p[m].C = p.C[m]; g.p[m].R = p.R[m];
             g.p[m].C2 = p.C2[m];
         }
-        return launch_gemm(g, p.nz, stream, tm, stage);
+        return launch_gemm(g, p.nz, x.stream, *x.tm, stage);
     }
     GemmBArgs g;
     memset(&g, 0, sizeof(g));
-    g.M = rows; g.N = p.N; g.K = IEF_D; g.lda = IEF_D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
+    g.M = x.rows; g.N = p.N; g.K = IEF_D; g.lda = IEF_D; g.ldc = p.ldc; g.epi = p.epi; g.alpha = p.alpha; g.qcols = p.qcols;
     for (int m = 0; m < p.nz; ++m) {
         g.p[m].A = p.A16[m]; g.p[m].W = p.W16[m]; g.p[m].bias = p.bias[m]; g.p[m].C = p.C[m]; g.p[m].Cb = p.Cb[m];
         g.p[m].R = p.R[m]; g.p[m].C2 = p.C2[m];
     }
-    return launch_gemm_b(g, p.nz, stream, tm, stage);
+    return launch_gemm_b(g, p.nz, x.stream, *x.tm, stage);
 }
 
 // ---- the four row-block launches of the bf16 mode: shared by forward_pass and by the unit entry iefvad_rowblock_unit, so a unit test
@@ -868,13 +891,9 @@ static int launch_inproj_chain(iefvad_handle* h, int l, const void* const A[2], 
     }
     // q is pre-scaled for the softmax by log2(e)/sqrt(96): both attention kernels use exp2
     ia.M = rows; ia.alpha = (1.0f / sqrtf((float)IEF_DH)) * 1.4426950408889634f; ia.wave_stride = (unsigned)wstream_wave_stride_bytes(IC_NPASS);
-    hipEvent_t e = tm.begin(ST_QKV);
-    if (a_fp32) hipLaunchKernelGGL(iefvad_inproj_chain_f32in_kernel, dim3(rows / IC_BM, 2), dim3(512), IC_LDS_BYTES, stream, ia);
-    else hipLaunchKernelGGL(iefvad_inproj_chain_bf16_kernel, dim3(rows / IC_BM, 2), dim3(512), IC_LDS_BYTES, stream, ia);
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(tm, ST_QKV, a_fp32 ? iefvad_inproj_chain_f32in_kernel : iefvad_inproj_chain_bf16_kernel, dim3(rows / IC_BM, 2), dim3(512), IC_LDS_BYTES,
+                  stream, ia);
 }
 
 static int launch_outproj_ln_chain(iefvad_handle* h, int l, bool whiten, const bf16_t* const A[2], const float* const R[2], float* const y[2],
@@ -893,22 +912,18 @@ static int launch_outproj_ln_chain(iefvad_handle* h, int l, bool whiten, const b
     const bool uniform = (y[0] != nullptr) == (y[1] != nullptr) && (yb[0] != nullptr) == (yb[1] != nullptr) && (y[0] || yb[0]);
     const StagePlan pl = plan_outproj_ln(h->policy, h->num_cus, rows, uniform);
     const dim3 grid(pl.gx, pl.gy);
-    hipEvent_t e = tm.begin(ST_OUT);
-    if (pl.kernel == STAGE_OUTLN_PCHAIN) {    // the persistent kernel is compiled per set of stored results
-        if (y[0] && yb[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, true>), grid, dim3(512), OP_LDS_BYTES, stream, oa);
-        else if (y[0]) hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<true, false>), grid, dim3(512), OP_LDS_BYTES, stream, oa);
-        else hipLaunchKernelGGL((iefvad_outproj_ln_pchain_bf16_kernel<false, true>), grid, dim3(512), OP_LDS_BYTES, stream, oa);
-    } else
-        hipLaunchKernelGGL(iefvad_outproj_ln_chain_bf16_kernel, grid, dim3(512), OC_LDS_BYTES, stream, oa);
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (pl.kernel != STAGE_OUTLN_PCHAIN) return launch(tm, ST_OUT, iefvad_outproj_ln_chain_bf16_kernel, grid, dim3(512), OC_LDS_BYTES, stream, oa);
+    // the persistent kernel is compiled per set of stored results
+    void (*const kernel)(OutLnChainArgs) = (y[0] && yb[0]) ? iefvad_outproj_ln_pchain_bf16_kernel<true, true>
+                                           : y[0]          ? iefvad_outproj_ln_pchain_bf16_kernel<true, false>
+                                                           : iefvad_outproj_ln_pchain_bf16_kernel<false, true>;
+    return launch(tm, ST_OUT, kernel, grid, dim3(512), OP_LDS_BYTES, stream, oa);
 }
 
 // bf16-mode attention over `nb` chunks per modality; `chunks` != nullptr: the row-compressed chunks of a whole-video pass (`_rows` kernels)
-static void launch_attention_bf16(iefvad_handle* h, const bf16_t* const qkv[2], bf16_t* const out[2], int nb, const RaggedChunk* chunks,
-                                  bool head_major, int rows, hipStream_t stream) {
+static int launch_attention_bf16(iefvad_handle* h, const bf16_t* const qkv[2], bf16_t* const out[2], int nb, const RaggedChunk* chunks,
+                                 bool head_major, int rows, hipStream_t stream, Timer& tm) {
     AttnBArgs ab;
     for (int m = 0; m < 2; ++m) { ab.qkv[m] = qkv[m]; ab.out[m] = out[m]; }
     ab.nchunks = nb;
@@ -918,11 +933,11 @@ static void launch_attention_bf16(iefvad_handle* h, const bf16_t* const qkv[2], 
     const StagePlan pl = plan_attention_bf16(h->policy, h->num_cus, nb, chunks != nullptr);
     const dim3 grid(pl.gx, pl.gy, pl.gz);
     switch (pl.kernel) {
-    case STAGE_ATTN_PBF16_ROWS: hipLaunchKernelGGL(iefvad_attention_pbf16_rows_kernel, grid, dim3(512), APB_LDS_BYTES, stream, ab); break;
-    case STAGE_ATTN_PBF16: hipLaunchKernelGGL(iefvad_attention_pbf16_kernel, grid, dim3(512), APB_LDS_BYTES, stream, ab); break;
-    case STAGE_ATTN_BF16_ROWS: hipLaunchKernelGGL(iefvad_attention_bf16_rows_kernel, grid, dim3(256), 0, stream, ab); break;
-    case STAGE_ATTN_BF16: hipLaunchKernelGGL(iefvad_attention_bf16_kernel, grid, dim3(256), 0, stream, ab); break;
-    default: break;
+    case STAGE_ATTN_PBF16_ROWS: return launch(tm, ST_ATT, iefvad_attention_pbf16_rows_kernel, grid, dim3(512), APB_LDS_BYTES, stream, ab);
+    case STAGE_ATTN_PBF16: return launch(tm, ST_ATT, iefvad_attention_pbf16_kernel, grid, dim3(512), APB_LDS_BYTES, stream, ab);
+    case STAGE_ATTN_BF16_ROWS: return launch(tm, ST_ATT, iefvad_attention_bf16_rows_kernel, grid, dim3(256), 0, stream, ab);
+    case STAGE_ATTN_BF16: return launch(tm, ST_ATT, iefvad_attention_bf16_kernel, grid, dim3(256), 0, stream, ab);
+    default: return fail("attention(bf16): the plan names no kernel");
     }
 }
 
@@ -933,13 +948,9 @@ static int launch_heads_chain(iefvad_handle* h, HeadsChainArgs& ha, int rows, fl
     ha.M = rows; ha.factor = factor; ha.eps = h->cfg.epsilon; ha.wave_stride = (unsigned)heads_stream_wave_stride_bytes();
     const StagePlan pl = plan_heads(h->policy, h->num_cus, rows);
     const dim3 grid(pl.gx, pl.gy);
-    hipEvent_t e = tm.begin(ST_HEAD);
-    if (pl.kernel == STAGE_HEADS_PCHAIN) hipLaunchKernelGGL(iefvad_heads_pchain_bf16_kernel, grid, dim3(512), HP_LDS_BYTES, stream, ha);
-    else hipLaunchKernelGGL(iefvad_heads_chain_bf16_kernel, grid, dim3(512), HC_LDS_BYTES, stream, ha);
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (pl.kernel == STAGE_HEADS_PCHAIN) return launch(tm, ST_HEAD, iefvad_heads_pchain_bf16_kernel, grid, dim3(512), HP_LDS_BYTES, stream, ha);
+    return launch(tm, ST_HEAD, iefvad_heads_chain_bf16_kernel, grid, dim3(512), HC_LDS_BYTES, stream, ha);
 }
 
 static int launch_refine_chain(iefvad_handle* h, const float* z_in, float* z_out, float* logits, int rows, hipStream_t stream, Timer& tm) {
@@ -950,12 +961,8 @@ static int launch_refine_chain(iefvad_handle* h, const float* z_in, float* z_out
     ca.z_out = z_out;           // may be z_in (in place): a workgroup reads its 64 rows before it writes them
     ca.logits = logits;
     ca.M = rows; ca.K = K; ca.lambda = h->cfg.lambda_ref; ca.wave_stride = (unsigned)chain_wave_stride_bytes(K);
-    hipEvent_t e = tm.begin(ST_REFINE);
-    hipLaunchKernelGGL(iefvad_refine_chain_bf16_kernel, dim3(rows / RC_BM), dim3(64 * RC_NW), RC_LDS_BYTES, stream, ca);
-    tm.end(e);
     tm.gemm_launches += 1;
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(tm, ST_REFINE, iefvad_refine_chain_bf16_kernel, dim3(rows / RC_BM), dim3(64 * RC_NW), RC_LDS_BYTES, stream, ca);
 }
 
 // The feature rows a call or a pass reads, both modalities in one element type: [B, 256, D] blocks (dense) or packed valid rows
@@ -1122,6 +1129,11 @@ static PassBuffers pass_buffers(const iefvad_handle* h, int nb, size_t row0, voi
     return b;
 }
 
+// the projections of a pass on its current row set (pass_tail: with use_split = b.tail_split)
+static ProjCtx proj_ctx(const iefvad_handle* h, const PassBuffers& b, hipStream_t stream, Timer& tm) {
+    return ProjCtx{h->cfg.compute, b.splitmb, h->D, b.rows, stream, &tm, h->policy.split_tile, h->policy.split_always};
+}
+
 // 0. inputs: `.to(torch.float)` (imf_vad.py:41-42) into b.cur; bf16 mode also gets the bf16 operand copy (b.need_xb0)
 static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, const float* const scale[2], const RowNoise& nz,
                             const RaggedPass* rg, hipStream_t stream, Timer& tm) {
@@ -1142,29 +1154,24 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
                 if (b.need_xb0) HIP_TRY(hipMemsetAsync(b.xb[m] + o, 0, nz * sizeof(bf16_t), stream));
             }
         }
-        hipEvent_t e = tm.begin(ST_CAST);
         // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
         // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
         const VideosOut& o = rg->out;
         const int nan_all = o.nan_mode == 2;
         const bool scaled = o.scale[0] || o.scale[1] || nan_all;
         const bool noisy = o.noise.any();       // an amplitude vector selects the noise instantiation; every other call launches what it always has
-        dispatch_in(in_dtype, d512, [&](auto t, auto w) {
-            using T = typename decltype(t)::type;
-            constexpr int W = decltype(w)::value;
-            const dim3 grid(b.nb, 2, IEF_RAGGED_SLICES);
-            const int nrows = b.enc_rows_mode ? 0 : IEF_T;
-            if (noisy)
-                hipLaunchKernelGGL((iefvad_scatter_rows_kernel<T, W, true, RowNoise>), grid, dim3(256), 0, stream, (const T*)pi, (const T*)pe,
-                                   rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0], o.scale[1], nan_all, o.noise);
-            else
-                hipLaunchKernelGGL((scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>), grid, dim3(256), 0,
-                                   stream, (const T*)pi, (const T*)pe, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0],
-                                   o.scale[1], nan_all);
-            return 0;
-        });
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
+        if (int rc = dispatch_in(in_dtype, d512, [&](auto t, auto w) {
+                using T = typename decltype(t)::type;
+                constexpr int W = decltype(w)::value;
+                const dim3 grid(b.nb, 2, IEF_RAGGED_SLICES);
+                const int nrows = b.enc_rows_mode ? 0 : IEF_T;
+                if (noisy)
+                    return launch(tm, ST_CAST, iefvad_scatter_rows_kernel<T, W, true, RowNoise>, grid, dim3(256), 0, stream, (const T*)pi, (const T*)pe,
+                                  rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0], o.scale[1], nan_all, o.noise);
+                return launch(tm, ST_CAST, scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>, grid, dim3(256), 0,
+                              stream, (const T*)pi, (const T*)pe, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0], o.scale[1],
+                              nan_all);
+            })) return rc;
     } else if (scale[0] || scale[1] || nz.any()) {
         // iefvad_forward_scaled / _perturbed: the rows pass through the cast kernel whatever their type, scaled and perturbed on the way (rowops.h)
         hipEvent_t e = tm.begin(ST_CAST);
@@ -1192,12 +1199,9 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
     if (b.f16mb) {
         // every (tensor, chunk) of this micro-batch starts from zero words; a kernel node, not a memset node, when captured (rowops.h)
         const unsigned words = (unsigned)b.nb * IEF_AMAX_PARTS;
-        hipLaunchKernelGGL(iefvad_amax_zero_kernel, dim3((words / 4 + 255) / 256, amax_act_tensors(b.L, b.K)), dim3(256), 0, stream, b.am,
-                           b.mbs, words);
-        hipEvent_t e = tm.begin(ST_CAST);
-        hipLaunchKernelGGL(iefvad_amax_chunk_kernel, dim3(b.nb, 2), dim3(256), 0, stream, b.cur[0], b.cur[1], b.am_in(0), b.am_in(1));
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
+        const dim3 zero_grid((words / 4 + 255) / 256, amax_act_tensors(b.L, b.K));
+        if (int rc = launch(iefvad_amax_zero_kernel, zero_grid, dim3(256), 0, stream, b.am, b.mbs, words)) return rc;
+        if (int rc = launch(tm, ST_CAST, iefvad_amax_chunk_kernel, dim3(b.nb, 2), dim3(256), 0, stream, b.cur[0], b.cur[1], b.am_in(0), b.am_in(1))) return rc;
     }
     return 0;
 }
@@ -1209,27 +1213,25 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
     const int D = h->D, L = c.num_layers, rows = b.rows, nb = b.nb;
     const bool d512 = h->D == IEF_D512;      // iefvad_create_ex: f32 arithmetic only, so every bf16 / split branch below is 768-wide
     const RaggedChunk* enc_chunks = b.enc_rows_mode ? rg->d_chunks : nullptr;
-    Proj p;
+    const ProjCtx px = proj_ctx(h, b, stream, tm);
     if (b.ip_chain) {
         const void* ipA[2] = {(l == 0) ? (const void*)b.cur[0] : (const void*)b.xb[0], (l == 0) ? (const void*)b.cur[1] : (const void*)b.xb[1]};
         if (int rc = launch_inproj_chain(h, l, ipA, l == 0, b.qkvb, rows, stream, tm)) return rc;
     } else {
-        memset(&p, 0, sizeof(p));
-        p.N = 3 * D; p.ldc = 3 * D; p.epi = EPI_QKV; p.qcols = D; p.nz = 2;
+        Proj p = Proj::of(EPI_QKV, 3 * D, 3 * D, h->in[0][l], &h->in[1][l]);
+        p.qcols = D;
         // q is pre-scaled for the softmax by log2(e)/sqrt(d_h): both attention kernels use exp2
         p.alpha = 1.0f / sqrtf((float)h->DH) * 1.4426950408889634f;
         for (int m = 0; m < 2; ++m) {
-            p.set_w(m, h->in[m][l]);
             p.A32[m] = b.cur[m]; p.A16[m] = b.xb[m]; p.amaxA[m] = l == 0 ? b.am_in(m) : b.am_x(l - 1, m);
             p.amaxC[m] = b.am_qkv(l, m);
             if (bf) p.Cb[m] = b.qkvb[m]; else p.C[m] = b.qkv[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_QKV, h->policy.split_tile, h->policy.split_always)) return rc;
+        if (int rc = launch_proj(px, p, ST_QKV)) return rc;
     }
 
-    hipEvent_t e = tm.begin(ST_ATT);
     if (bf) {
-        launch_attention_bf16(h, b.qkvb, b.attb, nb, enc_chunks, b.ip_chain, rows, stream);
+        if (int rc = launch_attention_bf16(h, b.qkvb, b.attb, nb, enc_chunks, b.ip_chain, rows, stream, tm)) return rc;
     } else {
         AttnArgs aa;
         memset(&aa, 0, sizeof(aa));
@@ -1243,10 +1245,8 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
                                          : b.splitmb ? (enc_chunks ? iefvad_attention_split_rows_kernel : iefvad_attention_split_kernel)
                                          : d512      ? (enc_chunks ? iefvad_attention_f32_rows_d64_kernel : iefvad_attention_f32_d64_kernel)
                                                      : (enc_chunks ? iefvad_attention_f32_rows_kernel : iefvad_attention_f32_kernel);
-        hipLaunchKernelGGL(kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), b.splitmb ? ATS_LDS_BYTES : 0, stream, aa);
+        if (int rc = launch(tm, ST_ATT, kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), b.splitmb ? ATS_LDS_BYTES : 0, stream, aa)) return rc;
     }
-    tm.end(e);
-    HIP_TRY(hipGetLastError());
 
     if (maps && (maps->p[0][l] || maps->p[1][l])) {
         // the layer's head-averaged attention weights, from q | k | v while they are alive (attention_maps.h).  The entries refuse
@@ -1259,24 +1259,19 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
         ma.chunks = rg ? rg->d_chunks : nullptr;
         void (*const kernel)(AttnMapArgs) = d512 ? (enc_chunks ? iefvad_attention_maps_kernel<true, 64> : iefvad_attention_maps_kernel<false, 64>)
                                                  : (enc_chunks ? iefvad_attention_maps_kernel<true, IEF_DH> : iefvad_attention_maps_kernel<false, IEF_DH>);
-        e = tm.begin(ST_ATT);
-        hipLaunchKernelGGL(kernel, dim3(2, 2 * nb), dim3(256), 0, stream, ma);
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
+        if (int rc = launch(tm, ST_ATT, kernel, dim3(2, 2 * nb), dim3(256), 0, stream, ma)) return rc;
     }
 
     if (b.ln_fused) {      // out_proj + residual + LayerNorm(s) in one row-owning kernel
         float* oy[2] = {(l < L - 1) ? b.xbuf[0] : nullptr, (l < L - 1) ? b.xbuf[1] : nullptr};      // fp32 rows are only the next layer's residual
         if (int rc = launch_outproj_ln_chain(h, l, l == L - 1, b.attb, b.cur, oy, b.xb, rows, stream, tm)) return rc;
     } else {
-        memset(&p, 0, sizeof(p));
-        p.N = D; p.ldc = D; p.epi = EPI_BIAS_RESID; p.nz = 2;
+        Proj p = Proj::of(EPI_BIAS_RESID, D, D, h->out[0][l], &h->out[1][l]);
         for (int m = 0; m < 2; ++m) {
-            p.set_w(m, h->out[m][l]);
             p.A32[m] = b.att[m]; p.A16[m] = b.attb[m]; p.amaxA[m] = b.am_att(l, m);
             p.C[m] = b.ybuf[m]; p.R[m] = b.cur[m];
         }
-        if (int rc = launch_proj(p, c.compute, b.splitmb, D, rows, stream, tm, ST_OUT, h->policy.split_tile, h->policy.split_always)) return rc;
+        if (int rc = launch_proj(px, p, ST_OUT)) return rc;
 
         LnArgs la;
         memset(&la, 0, sizeof(la));
@@ -1290,12 +1285,9 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
             la.yb[m] = bf ? b.xb[m] : nullptr;
             la.amax[m] = b.am_x(l, m);
         }
-        e = tm.begin(ST_LN);
-        dispatch_d(d512, [&](auto w) {
-            hipLaunchKernelGGL(iefvad_layernorm_kernel<decltype(w)::value>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
-        });
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
+        const dim3 grid((rows + ROW_WAVES - 1) / ROW_WAVES, 2);
+        if (int rc = dispatch_d(d512, [&](auto w) { return launch(tm, ST_LN, iefvad_layernorm_kernel<decltype(w)::value>, grid, dim3(256), 0, stream, la); }))
+            return rc;
     }
     b.cur[0] = b.xbuf[0]; b.cur[1] = b.xbuf[1];
     return 0;
@@ -1324,12 +1316,9 @@ static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass*
                 for (int m = 0; m < 2; ++m)
                     HIP_TRY(bf ? hipMemsetAsync(b.attb[m] + tail0, 0, tailn * sizeof(bf16_t), stream)
                                : hipMemsetAsync(b.att[m] + tail0, 0, tailn * sizeof(float), stream));
-            hipEvent_t e = tm.begin(ST_CAST);
-            dispatch_d(h->D == IEF_D512, [&](auto w) {
-                hipLaunchKernelGGL(iefvad_compact_rows_kernel<decltype(w)::value>, dim3(b.nb, 2), dim3(256), 0, stream, ca);
-            });
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
+            if (int rc = dispatch_d(h->D == IEF_D512, [&](auto w) {
+                    return launch(tm, ST_CAST, iefvad_compact_rows_kernel<decltype(w)::value>, dim3(b.nb, 2), dim3(256), 0, stream, ca);
+                })) return rc;
             b.rows = mc;
             b.compacted = true;
         }
@@ -1355,9 +1344,11 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const int D = h->D, L = c.num_layers, K = c.num_steps, rows = b.rows;
     const bool d512 = h->D == IEF_D512;
-    const float factor = (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;   // imf_vad.py:134
+    const float factor = precision_factor(c);
     const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
     float* const z = b.z;
+    ProjCtx px = proj_ctx(h, b, stream, tm);
+    px.use_split = b.tail_split;
 
     const bool chain = b.chain, fold = b.fold;
     const TailKeep keep = tail_keep(out, rg);
@@ -1375,24 +1366,17 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         const bool means = b.wim_out || b.wem_out;
         ha.nsum_part = means ? b.ybuf[0] : nullptr;        // y is dead after the last LayerNorm: 48 of its 768 floats per row
         if (int rc = launch_heads_chain(h, ha, rows, factor, stream, tm)) return rc;
-        if (means) {
-            hipEvent_t e = tm.begin(ST_FUSION);
-            hipLaunchKernelGGL(iefvad_rowmean_finish_kernel, dim3((2 * rows + 255) / 256), dim3(256), 0, stream, ha.nsum_part,
-                               b.wim_out, b.wem_out, rows, HC_NPART);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
-        }
+        if (means)
+            if (int rc = launch(tm, ST_FUSION, iefvad_rowmean_finish_kernel, dim3((2 * rows + 255) / 256), dim3(256), 0, stream, ha.nsum_part, b.wim_out,
+                                b.wem_out, rows, HC_NPART)) return rc;
     } else {
         // 2. mu / logvar heads (imf_vad.py:125-128): one [768 -> 1536] projection per modality
-        Proj p;
-        memset(&p, 0, sizeof(p));
-        p.N = 2 * D; p.ldc = D; p.epi = EPI_HEADS; p.nz = 2;
+        Proj p = Proj::of(EPI_HEADS, 2 * D, D, h->head[0], &h->head[1]);
         for (int m = 0; m < 2; ++m) {
-            p.set_w(m, h->head[m]);
             p.A32[m] = b.xt[m]; p.A16[m] = b.xtb[m]; p.amaxA[m] = b.am_x(L - 1, m);
         }
         p.C[0] = b.mu_i; p.C2[0] = b.lv_i; p.C[1] = b.mu_e; p.C2[1] = b.lv_e;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_HEAD, h->policy.split_tile, h->policy.split_always)) return rc;
+        if (int rc = launch_proj(px, p, ST_HEAD)) return rc;
 
         // 3. precision weights + fusion (imf_vad.py:130-144), fp32 in both modes
         FusionArgs fa;
@@ -1403,10 +1387,8 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         fa.zb = (bf && !chain) ? b.zb : nullptr;
         fa.nrows = rows; fa.factor = factor; fa.eps = c.epsilon;
         fa.z_amax = b.am_z(0);
-        hipEvent_t e = tm.begin(ST_FUSION);
-        dispatch_d(d512, [&](auto w) { hipLaunchKernelGGL(iefvad_fusion_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, fa); });
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
+        if (int rc = dispatch_d(d512, [&](auto w) { return launch(tm, ST_FUSION, iefvad_fusion_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, fa); }))
+            return rc;
     }
 
     if (chain)
@@ -1423,43 +1405,31 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
     for (int k = 0; k < K && !chain; ++k) {
         const bool dot = fold && k == K - 1;
-        Proj p;
-        memset(&p, 0, sizeof(p));
-        p.N = D; p.ldc = D; p.epi = EPI_BIAS_RELU; p.nz = 1;
-        p.set_w(0, h->ref1[k]);
+        Proj p = Proj::of(EPI_BIAS_RELU, D, D, h->ref1[k]);
         p.A32[0] = z; p.A16[0] = b.zb; p.amaxA[0] = b.am_z(k); p.amaxC[0] = b.am_h(k);
         p.C[0] = bf ? nullptr : b.hbuf; p.Cb[0] = bf ? b.hb : nullptr;
         if (dot) {
             p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
             if (!keep_fused) p.C[0] = nullptr;
         }
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile, h->policy.split_always)) return rc;
+        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
         if (dot) {
-            hipEvent_t e = tm.begin(ST_SCORER);
-            hipLaunchKernelGGL((iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>), row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
-                               h->score_fold, b.logits, rows);
-            tm.end(e);
-            HIP_TRY(hipGetLastError());
+            if (int rc = launch(tm, ST_SCORER, iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>, row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
+                                h->score_fold, b.logits, rows)) return rc;
             if (!keep_fused) break;
         }
-        memset(&p, 0, sizeof(p));
-        p.N = D; p.ldc = D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
-        p.set_w(0, h->ref2[k]);
+        p = Proj::of(EPI_REFINE, D, D, h->ref2[k]);
+        p.alpha = c.lambda_ref;
         p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
         p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
-        if (int rc = launch_proj(p, c.compute, b.tail_split, D, rows, stream, tm, ST_REFINE, h->policy.split_tile, h->policy.split_always)) return rc;
+        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
     }
 
     // 5. scorer (imf_vad.py:150)
-    if (!chain && !fold) {
-        hipEvent_t e = tm.begin(ST_SCORER);
-        dispatch_d(d512, [&](auto w) {
-            hipLaunchKernelGGL(iefvad_scorer_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, z, h->cls_w, h->cls_b, b.logits, rows);
+    if (!chain && !fold)
+        return dispatch_d(d512, [&](auto w) {
+            return launch(tm, ST_SCORER, iefvad_scorer_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, z, h->cls_w, h->cls_b, b.logits, rows);
         });
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
-    }
-
     return 0;
 }
 
@@ -1471,21 +1441,13 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
     const bool d512 = h->D == IEF_D512;
     const RaggedChunk* const chunks = b.compacted ? nullptr : rg->d_chunks;
     const int valid_rows = rg->valid_rows, nslabs = b.compacted ? (valid_rows + 255) / 256 : b.nb;
-    hipEvent_t e = tm.begin(ST_SCORER);
-    hipLaunchKernelGGL(iefvad_rows_out_kernel, dim3(nslabs), dim3(256), 0, stream, b.logits, b.wim_out, b.wem_out, o.logits, o.w_i_mean,
-                       o.w_e_mean, chunks, valid_rows);
-    tm.end(e);
-    HIP_TRY(hipGetLastError());
-    if (o.similarity) {
-        // the four series of the pass's valid rows from z_K / mu_i / mu_e (similarity.h)
-        e = tm.begin(ST_SCORER);
-        dispatch_d(d512, [&](auto w) {
-            hipLaunchKernelGGL(iefvad_similarity_rowset_kernel<decltype(w)::value>, dim3(nslabs, SIM_SLICES), dim3(256), 0, stream, b.z, b.mu_i,
-                               b.mu_e, chunks, valid_rows, o.similarity, o.sim_stride, o.row0);
-        });
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
-    }
+    if (int rc = launch(tm, ST_SCORER, iefvad_rows_out_kernel, dim3(nslabs), dim3(256), 0, stream, b.logits, b.wim_out, b.wem_out, o.logits, o.w_i_mean,
+                        o.w_e_mean, chunks, valid_rows)) return rc;
+    if (o.similarity)      // the four series of the pass's valid rows from z_K / mu_i / mu_e (similarity.h)
+        if (int rc = dispatch_d(d512, [&](auto w) {
+                return launch(tm, ST_SCORER, iefvad_similarity_rowset_kernel<decltype(w)::value>, dim3(nslabs, SIM_SLICES), dim3(256), 0, stream, b.z, b.mu_i,
+                              b.mu_e, chunks, valid_rows, o.similarity, o.sim_stride, o.row0);
+            })) return rc;
     // the full entries: the valid rows of the kept tensors -> the caller's packed tensors
     RowsOutWideArgs wa;
     memset(&wa, 0, sizeof(wa));
@@ -1496,24 +1458,19 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
     if (nt) {
         wa.chunks = chunks;
         wa.valid_rows = valid_rows;
-        e = tm.begin(ST_SCORER);
-        dispatch_d(d512, [&](auto w) {
-            hipLaunchKernelGGL(iefvad_rows_out_wide_kernel<decltype(w)::value>, dim3(nslabs, nt, IEF_RAGGED_SLICES), dim3(256), 0, stream, wa);
-        });
-        tm.end(e);
-        HIP_TRY(hipGetLastError());
+        if (int rc = dispatch_d(d512, [&](auto w) {
+                return launch(tm, ST_SCORER, iefvad_rows_out_wide_kernel<decltype(w)::value>, dim3(nslabs, nt, IEF_RAGGED_SLICES), dim3(256), 0, stream, wa);
+            })) return rc;
     }
     if (o.w_colsum) {
         // column sums of the stored weights over the valid rows (ragged.h)
-        e = tm.begin(ST_FUSION);
-        dispatch_d(d512, [&](auto w) {
-            hipLaunchKernelGGL(iefvad_colsum_rows_kernel<decltype(w)::value>, dim3(nslabs, 2), dim3(256), 0, stream, b.n_i, b.n_e, chunks,
-                               valid_rows, rg->colsum_part);
+        hipEvent_t e = tm.begin(ST_FUSION);      // one span over both launches
+        int rc = dispatch_d(d512, [&](auto w) {
+            return launch(iefvad_colsum_rows_kernel<decltype(w)::value>, dim3(nslabs, 2), dim3(256), 0, stream, b.n_i, b.n_e, chunks, valid_rows, rg->colsum_part);
         });
-        hipLaunchKernelGGL(iefvad_colsum_finish_kernel, dim3(2 * h->D / 16), dim3(256), 0, stream, rg->colsum_part, nslabs, 2 * h->D,
-                           rg->first_pass, o.w_colsum);
+        if (!rc) rc = launch(iefvad_colsum_finish_kernel, dim3(2 * h->D / 16), dim3(256), 0, stream, rg->colsum_part, nslabs, 2 * h->D, rg->first_pass, o.w_colsum);
         tm.end(e);
-        HIP_TRY(hipGetLastError());
+        if (rc) return rc;
     }
     return 0;
 }
@@ -2363,8 +2320,7 @@ extern "C" int iefvad_rowblock_unit(iefvad_handle* h, int32_t stage, int32_t lay
             ha.mu[m] = io->mu[m]; ha.lv[m] = io->logvar[m]; ha.n[m] = io->w[m];
         }
         ha.z = io->z;
-        const float factor = (h->cfg.noise_model == IEFVAD_NOISE_STUDENT_T) ? (h->cfg.nu + 1.0f) / h->cfg.nu : 1.0f;
-        return launch_heads_chain(h, ha, rows, factor, stream, tm);
+        return launch_heads_chain(h, ha, rows, precision_factor(h->cfg), stream, tm);
     }
     case IEFVAD_UNIT_REFINE: {
         if (K < 1 || !h->chain_stream) return fail("iefvad_rowblock_unit: the refinement chain needs K >= 1 (K = %d)", K);
@@ -2376,9 +2332,7 @@ extern "C" int iefvad_rowblock_unit(iefvad_handle* h, int32_t stage, int32_t lay
         bf16_t* out[2] = {(bf16_t*)io->yb[0], (bf16_t*)io->yb[1]};
         for (int m = 0; m < 2; ++m)
             if (!qkv[m] || !out[m] || !aligned(qkv[m]) || !aligned(out[m])) return fail("iefvad_rowblock_unit: ATTENTION needs x[m] and yb[m], 16-byte aligned");
-        launch_attention_bf16(h, qkv, out, rows / IEF_T, nullptr, true, rows, stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch_attention_bf16(h, qkv, out, rows / IEF_T, nullptr, true, rows, stream, tm);
     }
     default:
         return fail("iefvad_rowblock_unit: unknown stage %d", stage);

@@ -1,5 +1,7 @@
 // Orchestration of the train-mode forward and of the model's backward pass (include/iefvad.h: iefvad_train_forward /
-// iefvad_train_backward; kernels in backward.h).  Included by iefvad.hip behind the handle, launch_proj and the error helpers.
+// iefvad_train_backward; kernels in backward.h).  Included by iefvad.hip behind the handle, launch, launch_proj(ProjCtx, Proj, stage)
+// and the error helpers.  The backward is written per Linear -- linear_param_grads(BwdCtx, LinearGrads) for dW and db (launch_dw, then
+// launch_db unless the bias sums rode along), launch_dx(BwdCtx, ProjW, ...) for dX -- and per head product (head_product over HeadViews).
 //
 // What the reference does per training step (/root/reference/train/ucf_train.py:43-106, train/xd_train.py:35-78): model.train(),
 // outputs = model(img, ev, None, prompt_text, lengths), the three loss terms, loss.backward(), optimizer.step().  Here:
@@ -120,7 +122,7 @@ static int launch_bgemm(const BgemmArgs& a, bool akc, bool bkc, int nz, hipStrea
         return fail("bgemm: shape M=%d N=%d K=%d is not a multiple of the 128 x %d x 16 tile", a.M, a.N, a.K, bn);
     if ((a.lda | a.ldb) & 3) return fail("bgemm: leading dimensions must be multiples of 4 floats");
     dim3 grid((unsigned)((a.M / BG_BM) * (a.N / bn) * nz));
-#define BG_LAUNCH(AK, BK_, BN_) hipLaunchKernelGGL((iefvad_bgemm_f32_kernel<AK, BK_, BN_>), grid, dim3(256), 0, stream, a)
+#define BG_LAUNCH(AK, BK_, BN_) return launch(iefvad_bgemm_f32_kernel<AK, BK_, BN_>, grid, dim3(256), 0, stream, a)
     if (bn == 128) {
         if (akc && bkc) BG_LAUNCH(true, true, 128);
         else if (akc) BG_LAUNCH(true, false, 128);
@@ -133,8 +135,36 @@ static int launch_bgemm(const BgemmArgs& a, bool akc, bool bkc, int nz, hipStrea
         else BG_LAUNCH(false, false, 96);
     }
 #undef BG_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return 0;
+}
+
+// The five tensors the per-(chunk, head) products of attention index: the q, k and v column blocks of qkv [rows, 2304], the
+// probabilities P [B, 8, 256, 256], and a [rows, 768] tensor read 96 columns per head.  Strides in floats.
+struct HeadView { float* p; int ld; long long chunk_stride, head_stride; };
+static HeadView q_of(float* qkv) { return HeadView{qkv, 3 * IEF_D, (long long)IEF_T * 3 * IEF_D, IEF_DH}; }
+static HeadView k_of(float* qkv) { return q_of(qkv + IEF_D); }
+static HeadView v_of(float* qkv) { return q_of(qkv + 2 * IEF_D); }
+static HeadView probs(float* P) { return HeadView{P, IEF_T, (long long)IEF_H * IEF_T * IEF_T, (long long)IEF_T * IEF_T}; }
+static HeadView head_rows(float* att) { return HeadView{att, IEF_D, (long long)IEF_T * IEF_D, IEF_DH}; }
+
+// C[M, N] = alpha * A B over K for every (chunk, head) of `nchunks` chunks; akc / bkc: K runs along the columns of A / of B as stored
+// (launch_bgemm).  a_drop != 0: A is the sign-carrying P and dropout(P) is formed from it (BgemmArgs.a_drop).
+static int head_product(HeadView C, HeadView A, bool akc, HeadView B, bool bkc, int M, int N, int K, float alpha, float a_drop, int nchunks,
+                        hipStream_t stream) {
+    BgemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = A.p; a.B = B.p; a.C = C.p;
+    a.M = M; a.N = N; a.K = K; a.lda = A.ld; a.ldb = B.ld; a.ldc = C.ld;
+    a.a1 = A.chunk_stride; a.a2 = A.head_stride; a.b1 = B.chunk_stride; a.b2 = B.head_stride; a.c1 = C.chunk_stride; a.c2 = C.head_stride;
+    a.nz2 = IEF_H; a.alpha = alpha; a.a_drop = a_drop;
+    return launch_bgemm(a, akc, bkc, nchunks * IEF_H, stream);
+}
+
+// The dropout stream of (modality, layer) of the library's generator, and the slice of an injected mask that replaces it
+static unsigned long long dropout_seed(unsigned long long opt_seed, int m, int l) {
+    return opt_seed * 0x100000001B3ull + (unsigned long long)(m * IEFVAD_MAX_LAYERS + l + 1) * 0x9E3779B97F4A7C15ull;
+}
+static const uint8_t* keep_mask_of(const iefvad_train_options* opt, int m, int l, int L, size_t PU) {
+    return opt->keep_mask ? opt->keep_mask + ((size_t)m * L + l) * PU : nullptr;
 }
 
 // bf16x6 handles: the three-plane splits of every TRANSPOSED projection matrix, so that dX = dY W runs as the NT product
@@ -159,27 +189,42 @@ static int ensure_train_planes(iefvad_handle* h, hipStream_t stream) {
     return 0;
 }
 
-// dX[rows, n_in] = alpha * dY[rows, n_out] * W[n_out, n_in] (+ R) (gated by G): the input gradient of a Linear whose weight is stored
-// [out, in] as torch stores it.  `planes_t` (bf16x6 handles, full grids): the same product on the split kernel.
-static int launch_dx(iefvad_handle* h, const bf16_t* planes_t, const float* dY, int ldy, const float* W, int n_out, int n_in, float* dX,
-                     const float* R, const float* G, float alpha, int rows, hipStream_t stream) {
-    if (planes_t && n_in == IEF_D && ldy == n_out && split_eligible(rows, IEF_D, n_out, 1) && (!R || !G) && (G || alpha == 1.f)) {
+// What the whole backward shares: the split-K scratch `part` and the column-sum scratch `cpart` of the training buffer, and which
+// products of a bf16x6 handle run on the split kernels
+struct BwdCtx {
+    iefvad_handle* h;
+    int rows;
+    hipStream_t stream;
+    float* part; size_t part_floats;
+    float* cpart; size_t cpart_floats;
+    bool split_tn;      // dW on the split TN kernel (gemm_split_tn.h)
+    bool split_dx;      // dX on the split kernel over ProjW::wst, where the grid fills it
+};
+
+// dX[rows, 768] = alpha * dY[rows, w.N] * W[w.N, 768] (+ R) (gated by G): the input gradient of a Linear whose weight is stored
+// [out, in] as torch stores it.
+static int launch_dx(const BwdCtx& x, const ProjW& w, const float* dY, float* dX, const float* R, const float* G, float alpha) {
+    if (x.split_dx && w.wst && split_eligible(x.rows, IEF_D, w.N, 1) && (!R || !G) && (G || alpha == 1.f)) {
         GemmBArgs g;
         memset(&g, 0, sizeof(g));
-        g.M = rows; g.N = IEF_D; g.K = n_out; g.lda = n_out; g.ldc = IEF_D; g.alpha = alpha;
+        g.M = x.rows; g.N = IEF_D; g.K = w.N; g.lda = w.N; g.ldc = IEF_D; g.alpha = alpha;
         g.epi = G ? EPI_GATE : (R ? EPI_BIAS_RESID : EPI_BIAS);
-        g.wplane = IEF_D * n_out * 2;
+        g.wplane = IEF_D * w.N * 2;
         g.p[0].A = (const bf16_t*)dY;            // fp32 data behind the typed pointer
-        g.p[0].W = planes_t; g.p[0].bias = h->zero_bias; g.p[0].C = dX; g.p[0].R = G ? G : R;
+        g.p[0].W = w.wst; g.p[0].bias = x.h->zero_bias; g.p[0].C = dX; g.p[0].R = G ? G : R;
         Timer tm;
-        return launch_gemm_split(g, 1, stream, tm, ST_REFINE, false, h->policy.split_tile);      // N = 768: either tiling takes it
+        return launch_gemm_split(g, 1, x.stream, tm, ST_REFINE, false, x.h->policy.split_tile);      // N = 768: either tiling takes it
     }
     BgemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.A = dY; a.B = W; a.C = dX; a.R = R; a.G = G;
-    a.M = rows; a.N = n_in; a.K = n_out; a.lda = ldy; a.ldb = n_in; a.ldc = n_in; a.nz2 = 1; a.alpha = alpha;
-    (void)h;
-    return launch_bgemm(a, true, false, 1, stream);
+    a.A = dY; a.B = w.w; a.C = dX; a.R = R; a.G = G;
+    a.M = x.rows; a.N = IEF_D; a.K = w.N; a.lda = w.N; a.ldb = IEF_D; a.ldc = IEF_D; a.nz2 = 1; a.alpha = alpha;
+    return launch_bgemm(a, true, false, 1, x.stream);
+}
+
+static int reduce_parts(const float* part, size_t stride, int nparts, size_t n, float* out, float alpha, hipStream_t stream) {
+    if (!out) return 0;
+    return launch(iefvad_reduce_parts_kernel, dim3((unsigned)((n + RED_STRIP - 1) / RED_STRIP)), dim3(256), 0, stream, part, stride, nparts, n, out, alpha);
 }
 
 // a batch of fixed-order reductions for one launch of iefvad_reduce_parts_multi_kernel (null destinations are skipped)
@@ -192,92 +237,85 @@ struct ReduceBatch {
         j.part[c] = part; j.stride[c] = stride; j.nparts[c] = nparts; j.n[c] = n; j.out[c] = out; j.alpha[c] = alpha;
         j.first[c + 1] = j.first[c] + (unsigned)((n + RED_STRIP - 1) / RED_STRIP);
     }
-    void launch(hipStream_t stream) {
-        if (j.count == 0) return;
-        hipLaunchKernelGGL(iefvad_reduce_parts_multi_kernel, dim3(j.first[j.count]), dim3(256), 0, stream, j);
+    int launch(hipStream_t stream) {
+        if (j.count == 0) return 0;
+        return ::launch(iefvad_reduce_parts_multi_kernel, dim3(j.first[j.count]), dim3(256), 0, stream, j);
     }
 };
 
-// dW[n_out, 768] = alpha * dY^T X over the rows, split-K with fixed-order reduction; dW may be null (frozen parameter).
-// `dW2` (nullable) receives rows [n_split, n_out) as a tensor of its own (the stacked mu | logvar heads).
-static int launch_dw(const float* dY, int ldy, int n_out, const float* X, float* dW, float* dW2, int n_split, float alpha, int rows,
-                     float* part, size_t part_floats, hipStream_t stream, bool split_tn = false, float* db = nullptr, float* db2 = nullptr,
-                     float* cpart = nullptr, size_t cpart_floats = 0, bool* db_done = nullptr) {
-    if (db_done) *db_done = false;
-    if (!dW && !dW2) return 0;
+// The parameter gradients of one Linear y = x W^T + b with W = w->w [w->N, 768]: dW = alpha * dY^T X and db = alpha * column sums of dY
+// over the rows; null destinations are frozen parameters.  dW2 / db2 (nullable) receive rows / columns [n_split, w->N) as tensors of
+// their own (the stacked mu | logvar heads).
+struct LinearGrads {
+    const float* dY; const ProjW* w; const float* X; float alpha;
+    float *dW, *db; float *dW2 = nullptr, *db2 = nullptr; int n_split = 0;
+    int n_first() const { return n_split > 0 ? n_split : w->N; }      // outputs of dW / db; the rest, if any, are dW2's / db2's
+};
+
+// dW by split-K with fixed-order reduction.  `db_done`: the bias sums rode along (the split TN kernel, room in cpart) and are reduced too.
+static int launch_dw(const BwdCtx& x, const LinearGrads& g, bool& db_done) {
+    db_done = false;
+    if (!g.dW && !g.dW2) return 0;
+    const int rows = x.rows, n_out = g.w->N, n1 = g.n_first();
     const int splits = splitk_splits(rows, n_out);
     const size_t per = (size_t)n_out * IEF_D;
-    if ((size_t)splits * per > part_floats) return fail("train_backward: split-K scratch too small");
+    if ((size_t)splits * per > x.part_floats) return fail("train_backward: split-K scratch too small");
     const int ms = rows / splits;
-    if (split_tn && ms % TN_BK == 0 && n_out % 128 == 0 && (ldy & 3) == 0) {
+    if (x.split_tn && ms % TN_BK == 0 && n_out % 128 == 0) {
         // bf16x6 handles: the same partial products on the bf16 matrix pipe (gemm_split_tn.h), the same fixed-order reduction behind them:
         // the 128 x 256 block (64 x 128 per wave, two workgroups per CU) over as many RAGGED row slices as fill the chip's workgroup slots
         // once (at most the slices the scratch was sized for)
-        TnArgs g;
-        memset(&g, 0, sizeof(g));
-        g.A = dY; g.B = X; g.C = part; g.M = n_out; g.N = IEF_D; g.lda = ldy; g.ldb = IEF_D; g.ldc = IEF_D;
-        g.nk_total = rows / TN_BK;
+        TnArgs t;
+        memset(&t, 0, sizeof(t));
+        t.A = g.dY; t.B = g.X; t.C = x.part; t.M = n_out; t.N = IEF_D; t.lda = n_out; t.ldb = IEF_D; t.ldc = IEF_D;
+        t.nk_total = rows / TN_BK;
         const int tiles = (n_out / 128) * (IEF_D / 256);
         int slices = (2 * g_num_cus) / tiles;
-        if (slices > g.nk_total / 8) slices = g.nk_total / 8;
+        if (slices > t.nk_total / 8) slices = t.nk_total / 8;
         if (slices > splits) slices = splits;          // the scratch (part, cpart) holds `splits` partial results
         if (slices < 1) slices = 1;
-        g.slices = slices;
-        g.tiles_n = IEF_D / 256;
+        t.slices = slices;
+        t.tiles_n = IEF_D / 256;
         // the bias gradient of the same Linear (column sums of dY) rides along in the first column block's workgroups
-        const bool with_db = (db || db2) && cpart && db_done && (size_t)slices * n_out <= cpart_floats;
-        g.colsum = with_db ? cpart : nullptr;
-        hipLaunchKernelGGL(iefvad_gemm_split_tn256_kernel, dim3((unsigned)((n_out / 128) * g.tiles_n * slices)), dim3(256), TN_LDS_BYTES_OF(4), stream, g);
-        HIP_TRY(hipGetLastError());
+        db_done = (g.db || g.db2) && (size_t)slices * n_out <= x.cpart_floats;
+        t.colsum = db_done ? x.cpart : nullptr;
+        if (int rc = launch(iefvad_gemm_split_tn256_kernel, dim3((unsigned)((n_out / 128) * t.tiles_n * slices)), dim3(256), TN_LDS_BYTES_OF(4), x.stream, t))
+            return rc;
         // one launch reduces the weight partials (both halves of a stacked product) and the bias partials that rode along
         ReduceBatch rb;
-        rb.add(part, per, slices, (size_t)(n_split > 0 ? n_split : n_out) * IEF_D, dW, alpha);
-        if (dW2) rb.add(part + (size_t)n_split * IEF_D, per, slices, (size_t)(n_out - n_split) * IEF_D, dW2, alpha);
-        if (with_db) {
-            rb.add(cpart, (size_t)n_out, slices, (size_t)(n_split > 0 ? n_split : n_out), db, alpha);
-            if (db2) rb.add(cpart + n_split, (size_t)n_out, slices, (size_t)(n_out - n_split), db2, alpha);
-            *db_done = true;
+        rb.add(x.part, per, slices, (size_t)n1 * IEF_D, g.dW, g.alpha);
+        if (g.dW2) rb.add(x.part + (size_t)n1 * IEF_D, per, slices, (size_t)(n_out - n1) * IEF_D, g.dW2, g.alpha);
+        if (db_done) {
+            rb.add(x.cpart, (size_t)n_out, slices, (size_t)n1, g.db, g.alpha);
+            if (g.db2) rb.add(x.cpart + n1, (size_t)n_out, slices, (size_t)(n_out - n1), g.db2, g.alpha);
         }
-        rb.launch(stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return rb.launch(x.stream);
     }
     BgemmArgs a;
     memset(&a, 0, sizeof(a));
-    a.A = dY; a.B = X; a.C = part;
-    a.M = n_out; a.N = IEF_D; a.K = ms; a.lda = ldy; a.ldb = IEF_D; a.ldc = IEF_D;
-    a.a1 = (long long)ms * ldy; a.b1 = (long long)ms * IEF_D; a.c1 = (long long)per; a.nz2 = 1; a.alpha = 1.f;
-    if (int rc = launch_bgemm(a, false, false, splits, stream)) return rc;
-    if (dW) {
-        const size_t n = (size_t)(n_split > 0 ? n_split : n_out) * IEF_D;
-        hipLaunchKernelGGL(iefvad_reduce_parts_kernel, dim3((unsigned)((n + RED_STRIP - 1) / RED_STRIP)), dim3(256), 0, stream, part, per, splits, n, dW, alpha);
-    }
-    if (dW2) {
-        const size_t n = (size_t)(n_out - n_split) * IEF_D;
-        hipLaunchKernelGGL(iefvad_reduce_parts_kernel, dim3((unsigned)((n + RED_STRIP - 1) / RED_STRIP)), dim3(256), 0, stream, part + (size_t)n_split * IEF_D,
-                           per, splits, n, dW2, alpha);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    a.A = g.dY; a.B = g.X; a.C = x.part;
+    a.M = n_out; a.N = IEF_D; a.K = ms; a.lda = n_out; a.ldb = IEF_D; a.ldc = IEF_D;
+    a.a1 = (long long)ms * n_out; a.b1 = (long long)ms * IEF_D; a.c1 = (long long)per; a.nz2 = 1; a.alpha = 1.f;
+    if (int rc = launch_bgemm(a, false, false, splits, x.stream)) return rc;
+    if (int rc = reduce_parts(x.part, per, splits, (size_t)n1 * IEF_D, g.dW, g.alpha, x.stream)) return rc;
+    return reduce_parts(x.part + (size_t)n1 * IEF_D, per, splits, (size_t)(n_out - n1) * IEF_D, g.dW2, g.alpha, x.stream);
 }
 
-// db[ncols] = alpha * column sums of Y[rows, ld]; db2 (nullable) takes columns [n_split, ncols)
-static int launch_db(const float* Y, int ld, int ncols, float* db, float* db2, int n_split, float alpha, int rows, float* cpart,
-                     hipStream_t stream) {
-    if (!db && !db2) return 0;
-    const int nblk = (rows + kColsumRows - 1) / kColsumRows;
-    hipLaunchKernelGGL(iefvad_colsum_kernel, dim3((ncols + 255) / 256, nblk), dim3(256), 0, stream, Y, ld, rows, ncols, kColsumRows, cpart);
-    if (db) {
-        const size_t n = n_split > 0 ? n_split : ncols;
-        hipLaunchKernelGGL(iefvad_reduce_parts_kernel, dim3((unsigned)((n + RED_STRIP - 1) / RED_STRIP)), dim3(256), 0, stream, cpart, (size_t)ncols, nblk, n, db, alpha);
-    }
-    if (db2) {
-        const size_t n = ncols - n_split;
-        hipLaunchKernelGGL(iefvad_reduce_parts_kernel, dim3((unsigned)((n + RED_STRIP - 1) / RED_STRIP)), dim3(256), 0, stream, cpart + n_split, (size_t)ncols, nblk,
-                           n, db2, alpha);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+// db (and db2) from a colsum launch of their own
+static int launch_db(const BwdCtx& x, const LinearGrads& g) {
+    if (!g.db && !g.db2) return 0;
+    const int ncols = g.w->N, n1 = g.n_first();
+    const int nblk = (x.rows + kColsumRows - 1) / kColsumRows;
+    const dim3 grid((ncols + 255) / 256, nblk);
+    if (int rc = launch(iefvad_colsum_kernel, grid, dim3(256), 0, x.stream, g.dY, ncols, x.rows, ncols, kColsumRows, x.cpart)) return rc;
+    if (int rc = reduce_parts(x.cpart, (size_t)ncols, nblk, (size_t)n1, g.db, g.alpha, x.stream)) return rc;
+    return reduce_parts(x.cpart + n1, (size_t)ncols, nblk, (size_t)(ncols - n1), g.db2, g.alpha, x.stream);
+}
+
+static int linear_param_grads(const BwdCtx& x, const LinearGrads& g) {
+    bool db_done = false;
+    if (int rc = launch_dw(x, g, db_done)) return rc;
+    return db_done ? 0 : launch_db(x, g);
 }
 
 // What a train-mode forward leaves on the handle for its backward: which buffer it filled, at which batch size, and whether the
@@ -310,7 +348,7 @@ static int train_check(const iefvad_handle* h, int32_t B, const void* ws, size_t
 }
 
 // ---- the trainers' NaN rule on the device ----------------------------------------------------------------------------------------------
-// /root/reference/train/ucf_train.py:50-53 (xd_train.py:40-43): `if torch.isnan(x).any(): x = torch.nan_to_num(x, nan=0.0)` per input
+// /root/reference/train/ucf_train.py:50-53 (xd_train.py has no such rule): `if torch.isnan(x).any(): x = torch.nan_to_num(x, nan=0.0)` per input
 // tensor -- in torch an isnan pass that writes a bool tensor, a reduction, a HOST read of the flag (the step's launches cannot run
 // ahead of the device) and, when it fires, a rewriting pass.  Here: one scan of both tensors (a flag word each, set by any thread
 // that sees a NaN) and a repair launch whose workgroups return at once when their tensor's flag is clear; nothing comes back to the
@@ -342,10 +380,8 @@ extern "C" int iefvad_nan_rule(float* a, float* b, size_t n, void* flags_ws, voi
     if (n % 4 || (((uintptr_t)a | (uintptr_t)b) & 15) || ((uintptr_t)flags_ws & 7)) return fail("iefvad_nan_rule: n %% 4 == 0 and 16-byte aligned tensors, please");
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(hipMemsetAsync(flags_ws, 0, 8, stream));
-    hipLaunchKernelGGL(iefvad_nan_scan_kernel, dim3(2048, 2), dim3(256), 0, stream, a, b, n / 4, (unsigned*)flags_ws);
-    hipLaunchKernelGGL(iefvad_nan_fix_kernel, dim3(2048, 2), dim3(256), 0, stream, a, b, n / 4, (const unsigned*)flags_ws);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (int rc = launch(iefvad_nan_scan_kernel, dim3(2048, 2), dim3(256), 0, stream, a, b, n / 4, (unsigned*)flags_ws)) return rc;
+    return launch(iefvad_nan_fix_kernel, dim3(2048, 2), dim3(256), 0, stream, a, b, n / 4, (const unsigned*)flags_ws);
 }
 
 // ---- train-mode forward -------------------------------------------------------------------------------------------------------------
@@ -404,122 +440,84 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             }
     }
     const bool splitmb = c.compute == IEFVAD_COMPUTE_BF16X6 && split_eligible(rows, IEF_D, IEF_D, 1);
-    const float qscale = 1.0f / sqrtf((float)IEF_DH);
-    const float factor = (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;
+    // invariant = false on purpose: the batch-invariant mode is the evaluation forward's, training keeps its own rule
+    const ProjCtx px{c.compute, splitmb, IEF_D, rows, stream, &tm, h->policy.split_tile, false};
+    const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
 
-    // `.to(torch.float)` (imf_vad.py:41-42) into the saved layer-0 inputs; fp32 inputs are read where they are
     auto xin = [&](int m, int l) -> const float* { return l == 0 ? rec->x0[m] : ws + t.x[m][l]; };
     auto zst = [&](int k) -> float* { return k == K ? rec->zK : ws + t.z[k]; };
+    // `.to(torch.float)` (imf_vad.py:41-42) into the saved layer-0 inputs; fp32 inputs are read where they are
     if (in_dtype != IEFVAD_IN_F32) {
         if (int rc = dispatch_in(in_dtype, false, [&](auto ty, auto) {
                 return launch_cast<typename decltype(ty)::type>(img, ev, ws + t.x[0][0], ws + t.x[1][0], nullptr, nullptr, t.U, 2, stream);
             })) return rc;
     }
+    // a plain LayerNorm of both modalities: of(m) names modality m's rows, gain, bias and result
+    struct LnOne { const float* x; const float* g; const float* b; float* y; };
+    auto layernorm = [&](auto of) -> int {
+        LnArgs la;
+        memset(&la, 0, sizeof(la));
+        la.nrows = rows; la.eps = 1e-5f;
+        for (int m = 0; m < 2; ++m) {
+            const LnOne o = of(m);
+            la.x[m] = o.x; la.g1[m] = o.g; la.b1[m] = o.b; la.y[m] = o.y;
+        }
+        return launch(iefvad_layernorm_kernel<IEF_D>, dim3(row_grid.x, 2), dim3(256), 0, stream, la);
+    };
 
     for (int l = 0; l < L; ++l) {
-        Proj p;
-        memset(&p, 0, sizeof(p));
-        p.N = 3 * IEF_D; p.ldc = 3 * IEF_D; p.epi = EPI_QKV; p.qcols = IEF_D; p.nz = 2;
-        p.alpha = qscale;                               // q * 1/sqrt(dh) before the bmm, as F.multi_head_attention_forward does
-        for (int m = 0; m < 2; ++m) {
-            p.set_w(m, h->in[m][l]);
-            p.A32[m] = xin(m, l); p.C[m] = ws + t.qkv[m][l];
-        }
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_QKV, h->policy.split_tile)) return rc;
+        Proj p = Proj::of(EPI_QKV, 3 * IEF_D, 3 * IEF_D, h->in[0][l], &h->in[1][l]);
+        p.qcols = IEF_D;
+        p.alpha = 1.0f / sqrtf((float)IEF_DH);          // q * 1/sqrt(dh) before the bmm, as F.multi_head_attention_forward does
+        for (int m = 0; m < 2; ++m) { p.A32[m] = xin(m, l); p.C[m] = ws + t.qkv[m][l]; }
+        if (int rc = launch_proj(px, p, ST_QKV)) return rc;
 
         // bf16x6: S = q k^T -> softmax -> dropout -> Pd v in ONE launch for both modalities (attention_split.h, TRAIN: the eval kernel
         // with the sign-carrying P stored for the backward); IEFVAD_TRAIN_ATTN=unfused keeps the three launches below (A/B: the test
         // runs one model of each).  The fp32 arithmetic keeps them: its products stay on the fp32 MFMA instruction.
-        if (fused) {
-            AttnArgs aa;
-            AttnTrainArgs tx;
-            memset(&aa, 0, sizeof(aa));
-            memset(&tx, 0, sizeof(tx));
-            aa.nchunks = B;
-            for (int m = 0; m < 2; ++m) {
-                const float pdrop = opt->dropout_p[m][l];
-                const bool drop = pdrop > 0.f || opt->keep_mask;
-                aa.qkv[m] = ws + t.qkv[m][l];
-                aa.out[m] = ws + t.att[m][l];
-                tx.P[m] = ws + t.P[m][l];
-                tx.drop[m] = drop ? 1 : 0;
-                tx.keep[m] = opt->keep_mask ? opt->keep_mask + ((size_t)m * L + l) * t.PU : nullptr;
-                tx.seed[m] = opt->seed * 0x100000001B3ull + (unsigned long long)(m * IEFVAD_MAX_LAYERS + l + 1) * 0x9E3779B97F4A7C15ull;
-                tx.drop_p[m] = pdrop;
-            }
-            if (opt->keep_mask)
-                hipLaunchKernelGGL(iefvad_attention_split_train_mask_kernel, dim3(IEF_H, 2, 2 * B), dim3(256), ATS_LDS_BYTES, stream, aa, tx);
-            else
-                hipLaunchKernelGGL(iefvad_attention_split_train_kernel, dim3(IEF_H, 2, 2 * B), dim3(256), ATS_LDS_BYTES, stream, aa, tx);
-            HIP_TRY(hipGetLastError());
-        } else
+        AttnArgs aa;
+        AttnTrainArgs tx;
+        memset(&aa, 0, sizeof(aa));
+        memset(&tx, 0, sizeof(tx));
+        aa.nchunks = B;
         for (int m = 0; m < 2; ++m) {
-            float* qkv = ws + t.qkv[m][l];
+            float* const qkv = ws + t.qkv[m][l];
+            float* const P = ws + t.P[m][l];
+            float* const att = ws + t.att[m][l];
             const float pdrop = opt->dropout_p[m][l];
             const bool drop = pdrop > 0.f || opt->keep_mask;
+            const uint8_t* const keep = keep_mask_of(opt, m, l, L, t.PU);
+            const unsigned long long seed = dropout_seed(opt->seed, m, l);
+            if (fused) {
+                aa.qkv[m] = qkv; aa.out[m] = att;
+                tx.P[m] = P; tx.drop[m] = drop ? 1 : 0; tx.keep[m] = keep; tx.seed[m] = seed; tx.drop_p[m] = pdrop;
+                continue;
+            }
             // S = q k^T per (chunk, head)
-            BgemmArgs a;
-            memset(&a, 0, sizeof(a));
-            a.A = qkv; a.B = qkv + IEF_D; a.C = ws + t.P[m][l];
-            a.M = IEF_T; a.N = IEF_T; a.K = IEF_DH; a.lda = a.ldb = 3 * IEF_D; a.ldc = IEF_T;
-            a.a1 = a.b1 = (long long)IEF_T * 3 * IEF_D; a.a2 = a.b2 = IEF_DH;
-            a.c1 = (long long)IEF_H * IEF_T * IEF_T; a.c2 = (long long)IEF_T * IEF_T; a.nz2 = IEF_H; a.alpha = 1.f;
-            if (int rc = launch_bgemm(a, true, true, B * IEF_H, stream)) return rc;
+            if (int rc = head_product(probs(P), q_of(qkv), true, k_of(qkv), true, IEF_T, IEF_T, IEF_DH, 1.f, 0.f, B, stream)) return rc;
             SoftmaxDropArgs sa;
-            sa.S = ws + t.P[m][l];
-            sa.drop = drop ? 1 : 0;
-            sa.keep = opt->keep_mask ? opt->keep_mask + ((size_t)m * L + l) * t.PU : nullptr;
-            sa.seed = opt->seed * 0x100000001B3ull + (unsigned long long)(m * IEFVAD_MAX_LAYERS + l + 1) * 0x9E3779B97F4A7C15ull;
-            sa.p = pdrop;
+            sa.S = P; sa.drop = drop ? 1 : 0; sa.keep = keep; sa.seed = seed; sa.p = pdrop;
             sa.rows = (long long)B * IEF_H * IEF_T;
-            hipLaunchKernelGGL(iefvad_softmax_dropout_kernel, dim3((unsigned)((sa.rows + 3) / 4)), dim3(256), 0, stream, sa);
-            HIP_TRY(hipGetLastError());
-            // attention output = dropout(P) v
-            memset(&a, 0, sizeof(a));
-            a.A = ws + t.P[m][l]; a.B = qkv + 2 * IEF_D; a.C = ws + t.att[m][l];
-            if (drop) a.a_drop = (float)(1.0 / (1.0 - (double)pdrop));      // dropout(P) from the sign-carrying tensor, in the A tile's staging
-            a.M = IEF_T; a.N = IEF_DH; a.K = IEF_T; a.lda = IEF_T; a.ldb = 3 * IEF_D; a.ldc = IEF_D;
-            a.a1 = (long long)IEF_H * IEF_T * IEF_T; a.a2 = (long long)IEF_T * IEF_T;
-            a.b1 = (long long)IEF_T * 3 * IEF_D; a.b2 = IEF_DH; a.c1 = (long long)IEF_T * IEF_D; a.c2 = IEF_DH; a.nz2 = IEF_H; a.alpha = 1.f;
-            if (int rc = launch_bgemm(a, true, false, B * IEF_H, stream)) return rc;
+            if (int rc = launch(iefvad_softmax_dropout_kernel, dim3((unsigned)((sa.rows + 3) / 4)), dim3(256), 0, stream, sa)) return rc;
+            // attention output = dropout(P) v: dropout(P) from the sign-carrying tensor, in the A tile's staging
+            const float a_drop = drop ? (float)(1.0 / (1.0 - (double)pdrop)) : 0.f;
+            if (int rc = head_product(head_rows(att), probs(P), true, v_of(qkv), false, IEF_T, IEF_DH, IEF_T, 1.f, a_drop, B, stream)) return rc;
         }
+        if (fused)
+            if (int rc = launch(opt->keep_mask ? iefvad_attention_split_train_mask_kernel : iefvad_attention_split_train_kernel, dim3(IEF_H, 2, 2 * B),
+                                dim3(256), ATS_LDS_BYTES, stream, aa, tx)) return rc;
 
-        memset(&p, 0, sizeof(p));
-        p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RESID; p.nz = 2;
-        for (int m = 0; m < 2; ++m) {
-            p.set_w(m, h->out[m][l]);
-            p.A32[m] = ws + t.att[m][l]; p.C[m] = ws + t.s[m][l]; p.R[m] = xin(m, l);
-        }
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_OUT, h->policy.split_tile)) return rc;
-
-        LnArgs la;
-        memset(&la, 0, sizeof(la));
-        la.nrows = rows; la.eps = 1e-5f;
-        for (int m = 0; m < 2; ++m) {
-            la.x[m] = ws + t.s[m][l]; la.g1[m] = h->norm_w[m][l]; la.b1[m] = h->norm_b[m][l]; la.y[m] = ws + t.x[m][l + 1];
-        }
-        hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
-        HIP_TRY(hipGetLastError());
+        p = Proj::of(EPI_BIAS_RESID, IEF_D, IEF_D, h->out[0][l], &h->out[1][l]);
+        for (int m = 0; m < 2; ++m) { p.A32[m] = ws + t.att[m][l]; p.C[m] = ws + t.s[m][l]; p.R[m] = xin(m, l); }
+        if (int rc = launch_proj(px, p, ST_OUT)) return rc;
+        if (int rc = layernorm([&](int m) { return LnOne{ws + t.s[m][l], h->norm_w[m][l], h->norm_b[m][l], ws + t.x[m][l + 1]}; })) return rc;
     }
-    {   // whitening LayerNorm (imf_vad.py:117,123) as a launch of its own: the backward needs its input, the last norm's output
-        LnArgs la;
-        memset(&la, 0, sizeof(la));
-        la.nrows = rows; la.eps = 1e-5f;
-        for (int m = 0; m < 2; ++m) {
-            la.x[m] = ws + t.x[m][L]; la.g1[m] = h->whiten_w[m]; la.b1[m] = h->whiten_b[m]; la.y[m] = ws + t.E[m];
-        }
-        hipLaunchKernelGGL(iefvad_layernorm_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES, 2), dim3(256), 0, stream, la);
-        HIP_TRY(hipGetLastError());
-    }
+    // whitening LayerNorm (imf_vad.py:117,123) as a launch of its own: the backward needs its input, the last norm's output
+    if (int rc = layernorm([&](int m) { return LnOne{ws + t.x[m][L], h->whiten_w[m], h->whiten_b[m], ws + t.E[m]}; })) return rc;
     {
-        Proj p;
-        memset(&p, 0, sizeof(p));
-        p.N = 2 * IEF_D; p.ldc = IEF_D; p.epi = EPI_HEADS; p.nz = 2;
-        for (int m = 0; m < 2; ++m) {
-            p.set_w(m, h->head[m]);
-            p.A32[m] = ws + t.E[m]; p.C[m] = rec->mu[m]; p.C2[m] = rec->lv[m];
-        }
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_HEAD, h->policy.split_tile)) return rc;
+        Proj p = Proj::of(EPI_HEADS, 2 * IEF_D, IEF_D, h->head[0], &h->head[1]);
+        for (int m = 0; m < 2; ++m) { p.A32[m] = ws + t.E[m]; p.C[m] = rec->mu[m]; p.C2[m] = rec->lv[m]; }
+        if (int rc = launch_proj(px, p, ST_HEAD)) return rc;
     }
     {
         FusionArgs fa;
@@ -527,29 +525,21 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
         fa.mu_i = rec->mu[0]; fa.lv_i = rec->lv[0]; fa.mu_e = rec->mu[1]; fa.lv_e = rec->lv[1];
         fa.n_i = out->w_i; fa.n_e = out->w_e; fa.z = zst(0);
         fa.n_i_mean = out->w_i_mean; fa.n_e_mean = out->w_e_mean;
-        fa.nrows = rows; fa.factor = factor; fa.eps = c.epsilon;
-        hipLaunchKernelGGL(iefvad_fusion_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
-        HIP_TRY(hipGetLastError());
+        fa.nrows = rows; fa.factor = precision_factor(c); fa.eps = c.epsilon;
+        if (int rc = launch(iefvad_fusion_kernel<IEF_D>, row_grid, dim3(256), 0, stream, fa)) return rc;
     }
     for (int k = 0; k < K; ++k) {
-        Proj p;
-        memset(&p, 0, sizeof(p));
-        p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_BIAS_RELU; p.nz = 1;
-        p.set_w(0, h->ref1[k]);
+        Proj p = Proj::of(EPI_BIAS_RELU, IEF_D, IEF_D, h->ref1[k]);
         p.A32[0] = zst(k); p.C[0] = ws + t.hid[k];
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
-        memset(&p, 0, sizeof(p));
-        p.N = IEF_D; p.ldc = IEF_D; p.epi = EPI_REFINE; p.alpha = c.lambda_ref; p.nz = 1;
-        p.set_w(0, h->ref2[k]);
+        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
+        p = Proj::of(EPI_REFINE, IEF_D, IEF_D, h->ref2[k]);
+        p.alpha = c.lambda_ref;
         p.A32[0] = ws + t.hid[k]; p.C[0] = zst(k + 1); p.R[0] = zst(k);
-        if (int rc = launch_proj(p, c.compute, splitmb, IEF_D, rows, stream, tm, ST_REFINE, h->policy.split_tile)) return rc;
+        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
     }
     float* logits = out->logits ? out->logits : ws + t.logits;
-    hipLaunchKernelGGL(iefvad_scorer_kernel<IEF_D>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, rec->zK, h->cls_w, h->cls_b,
-                       logits, rows);
-    HIP_TRY(hipGetLastError());
     // (the dict entries of imf_vad.py:152-161 that are also saved tensors were written in place: TrainRecord)
-    return 0;
+    return launch(iefvad_scorer_kernel<IEF_D>, row_grid, dim3(256), 0, stream, rec->zK, h->cls_w, h->cls_b, logits, rows);
 }
 
 // ---- backward -------------------------------------------------------------------------------------------------------------------------
@@ -564,12 +554,17 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
     if (((uintptr_t)dx[0] | (uintptr_t)dx[1]) & 15) return fail("%s: input-gradient buffers must be 16-byte aligned", who);
     if (h->D != IEF_D) return fail("%s: training is built for D=768 (this handle has D=%d)", who, h->D);
     if (!dout || !dw) return fail("%s: null argument", who);
-    const TrainRecord* rec = nullptr;
+    TrainRecord* live = nullptr;
     if (h->train)
         for (int i = 0; i < 8; ++i)
-            if (h->train->rec[i].ws == train_ws && h->train->rec[i].stamp) rec = &h->train->rec[i];
-    if (!rec || rec->B != B) return fail("%s: no iefvad_train_forward with B = %d has filled this training buffer", who, B);
+            if (h->train->rec[i].ws == train_ws && h->train->rec[i].stamp) live = &h->train->rec[i];
+    if (!live || live->B != B) return fail("%s: no iefvad_train_forward with B = %d has filled this training buffer", who, B);
     if (int rc = train_check(h, B, train_ws, train_ws_bytes, who)) return rc;
+    // The scratch tensors overwrite the saved refinement states (train_layout): the forward's record is retired HERE, before the first
+    // launch, so that a backward that fails midway leaves no live record over clobbered data.  `rec` is this call's copy.
+    const TrainRecord taken = *live;
+    const TrainRecord* rec = &taken;
+    live->stamp = 0;
     const iefvad_config& c = h->cfg;
     const int L = c.num_layers, K = c.num_steps;
     hipStream_t stream = (hipStream_t)stream_;
@@ -577,44 +572,35 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
     float* ws = (float*)train_ws;
     const int rows = B * IEF_T;
     const int nblk = (rows + BWD_ROWS_PER_BLOCK - 1) / BWD_ROWS_PER_BLOCK;
-    const float factor = (c.noise_model == IEFVAD_NOISE_STUDENT_T) ? (c.nu + 1.0f) / c.nu : 1.0f;
     const float qscale = 1.0f / sqrtf((float)IEF_DH);
-    float* part = ws + t.part;
-    float* cpart = ws + t.cpart;
     float* rpart = ws + t.rpart;
     float* g = ws + t.g;
     float* da = ws + t.da;
     if (int rc = ensure_train_planes(h, stream)) return rc;
-    const bool tp = h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && h->tplanes_valid;      // dX on the split kernel where the grid fills it
-    const bool tn = h->cfg.compute == IEFVAD_COMPUTE_BF16X6;              // dW on the split TN kernel (gemm_split_tn.h)
+    const bool x6 = c.compute == IEFVAD_COMPUTE_BF16X6;
+    const BwdCtx bx{h, rows, stream, ws + t.part, t.part_floats, ws + t.cpart, t.cpart_floats, x6, x6 && h->tplanes_valid};
 
     // classifier (imf_vad.py:150)
     {
         ScorerBwdArgs sa;
         sa.dlogit = dout->logits; sa.dfused = dout->fused; sa.z = rec->zK; sa.w = h->cls_w; sa.g = g;
         sa.part_w = rpart; sa.part_b = rpart + (size_t)nblk * IEF_D; sa.rows = rows;
-        hipLaunchKernelGGL(iefvad_scorer_bwd_kernel, dim3(nblk), dim3(256), 0, stream, sa);
+        if (int rc = launch(iefvad_scorer_bwd_kernel, dim3(nblk), dim3(256), 0, stream, sa)) return rc;
         ReduceBatch rb;
         rb.add(rpart, (size_t)IEF_D, nblk, (size_t)IEF_D, dw->cls_w, 1.f);
         rb.add(rpart + (size_t)nblk * IEF_D, (size_t)1, nblk, (size_t)1, dw->cls_b, 1.f);
-        rb.launch(stream);
-        HIP_TRY(hipGetLastError());
+        if (int rc = rb.launch(stream)) return rc;
     }
     // refinement steps, last to first (imf_vad.py:146-149): z_{k+1} = z_k - lambda (W2 relu(W1 z_k + b1) + b2); g = d z_{k+1}
     for (int k = K - 1; k >= 0; --k) {
         const float nl = -c.lambda_ref;
-        { bool db_done = false;
-            if (int rc = launch_dw(g, IEF_D, IEF_D, ws + t.hid[k], dw->ref_w2[k], nullptr, 0, nl, rows, part, t.part_floats, stream, tn, dw->ref_b2[k], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
-            if (!db_done)
-                if (int rc = launch_db(g, IEF_D, IEF_D, dw->ref_b2[k], nullptr, 0, nl, rows, cpart, stream)) return rc; }
+        float* const hid = ws + t.hid[k];
+        if (int rc = linear_param_grads(bx, LinearGrads{g, &h->ref2[k], hid, nl, dw->ref_w2[k], dw->ref_b2[k]})) return rc;
         // d a = (-lambda g W2) gated by h > 0  (ReLU backward on the saved activation)
-        if (int rc = launch_dx(h, tp ? h->ref2[k].wst : nullptr, g, IEF_D, h->ref2[k].w, IEF_D, IEF_D, da, nullptr, ws + t.hid[k], nl, rows, stream)) return rc;
-        { bool db_done = false;
-            if (int rc = launch_dw(da, IEF_D, IEF_D, k == K ? rec->zK : ws + t.z[k], dw->ref_w1[k], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->ref_b1[k], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
-            if (!db_done)
-                if (int rc = launch_db(da, IEF_D, IEF_D, dw->ref_b1[k], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
+        if (int rc = launch_dx(bx, h->ref2[k], g, da, nullptr, hid, nl)) return rc;
+        if (int rc = linear_param_grads(bx, LinearGrads{da, &h->ref1[k], ws + t.z[k], 1.f, dw->ref_w1[k], dw->ref_b1[k]})) return rc;
         // d z_k = g + d a W1   (in place: every element of g is read by the thread that overwrites it)
-        if (int rc = launch_dx(h, tp ? h->ref1[k].wst : nullptr, da, IEF_D, h->ref1[k].w, IEF_D, IEF_D, g, g, nullptr, 1.f, rows, stream)) return rc;
+        if (int rc = launch_dx(bx, h->ref1[k], da, g, g, nullptr, 1.f)) return rc;
     }
     // fusion (imf_vad.py:130-144) -> d mu | d logvar of both modalities, stacked
     {
@@ -625,30 +611,25 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
         fa.d_mu_i = dout->image_mu; fa.d_lv_i = dout->image_logvar; fa.d_mu_e = dout->event_mu; fa.d_lv_e = dout->event_logvar;
         fa.d_n_i = dout->w_i; fa.d_n_e = dout->w_e;
         fa.dh_i = ws + t.dh[0]; fa.dh_e = ws + t.dh[1];
-        fa.rows = rows; fa.factor = factor; fa.eps = c.epsilon;
-        hipLaunchKernelGGL(iefvad_fusion_bwd_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa);
-        HIP_TRY(hipGetLastError());
+        fa.rows = rows; fa.factor = precision_factor(c); fa.eps = c.epsilon;
+        if (int rc = launch(iefvad_fusion_bwd_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa)) return rc;
     }
     for (int m = 0; m < 2; ++m) {
         const float* dhm = ws + t.dh[m];
         float* gx = ws + t.gx;
         // heads (imf_vad.py:125-128): mu.weight | logvar.weight are stacked [1536, 768] in the handle
-        { bool db_done = false;
-            if (int rc = launch_dw(dhm, 2 * IEF_D, 2 * IEF_D, ws + t.E[m], dw->mu_w[m], dw->logvar_w[m], IEF_D, 1.f, rows, part, t.part_floats, stream, tn, dw->mu_b[m], dw->logvar_b[m], cpart, t.cpart_floats, &db_done)) return rc;
-            if (!db_done)
-                if (int rc = launch_db(dhm, 2 * IEF_D, 2 * IEF_D, dw->mu_b[m], dw->logvar_b[m], IEF_D, 1.f, rows, cpart, stream)) return rc; }
-        if (int rc = launch_dx(h, tp ? h->head[m].wst : nullptr, dhm, 2 * IEF_D, h->head[m].w, 2 * IEF_D, IEF_D, gx, nullptr, nullptr, 1.f, rows, stream)) return rc;
+        if (int rc = linear_param_grads(bx, LinearGrads{dhm, &h->head[m], ws + t.E[m], 1.f, dw->mu_w[m], dw->mu_b[m], dw->logvar_w[m], dw->logvar_b[m], IEF_D}))
+            return rc;
+        if (int rc = launch_dx(bx, h->head[m], dhm, gx, nullptr, nullptr, 1.f)) return rc;
         // whitening LayerNorm (imf_vad.py:117,123), then the layers last to first
         auto ln_bwd = [&](const float* x, const float* gamma, float* dgamma, float* dbeta) -> int {
             LnBwdArgs la;
             la.x = x; la.dy = gx; la.g = gamma; la.dx = gx; la.part_g = rpart; la.part_b = rpart + (size_t)nblk * IEF_D; la.rows = rows; la.eps = 1e-5f;
-            hipLaunchKernelGGL(iefvad_layernorm_bwd_kernel, dim3(nblk), dim3(256), 0, stream, la);
+            if (int rc = launch(iefvad_layernorm_bwd_kernel, dim3(nblk), dim3(256), 0, stream, la)) return rc;
             ReduceBatch rb;
             rb.add(rpart, (size_t)IEF_D, nblk, (size_t)IEF_D, dgamma, 1.f);
             rb.add(rpart + (size_t)nblk * IEF_D, (size_t)IEF_D, nblk, (size_t)IEF_D, dbeta, 1.f);
-            rb.launch(stream);
-            HIP_TRY(hipGetLastError());
-            return 0;
+            return rb.launch(stream);
         };
         if (int rc = ln_bwd(ws + t.x[m][L], h->whiten_w[m], dw->whiten_w[m], dw->whiten_b[m])) return rc;
         for (int l = L - 1; l >= 0; --l) {
@@ -658,22 +639,16 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
             float* datt = ws + t.datt;
             float* dqkv = ws + t.dqkv;
             float* dP = ws + t.dP;
-            const float* qkv = ws + t.qkv[m][l];
-            const float* P = ws + t.P[m][l];
+            float* qkv = ws + t.qkv[m][l];
+            float* P = ws + t.P[m][l];
             // P carries the dropout mask in its sign bits (when a probability or a mask was in force in the forward): dropout(P) is formed
             // from it where it is read (the d S launch / the softmax backward, the A operand of d v)
             const bool signed_p = rec->drop[m][l];
             const float drop_scale = signed_p ? (float)(1.0 / (1.0 - (double)rec->drop_p[m][l])) : 1.0f;
-            { bool db_done = false;
-            if (int rc = launch_dw(gx, IEF_D, IEF_D, ws + t.att[m][l], dw->out_proj_w[m][l], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->out_proj_b[m][l], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
-            if (!db_done)
-                if (int rc = launch_db(gx, IEF_D, IEF_D, dw->out_proj_b[m][l], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
+            if (int rc = linear_param_grads(bx, LinearGrads{gx, &h->out[m][l], ws + t.att[m][l], 1.f, dw->out_proj_w[m][l], dw->out_proj_b[m][l]})) return rc;
             // layer 0 of a modality whose in_proj gradients and input gradient are all unasked for: nothing reads its d qkv
             if (l == 0 && !dx[m] && !dw->in_proj_w[m][0] && !dw->in_proj_b[m][0]) break;
-            if (int rc = launch_dx(h, tp ? h->out[m][l].wst : nullptr, gx, IEF_D, h->out[m][l].w, IEF_D, IEF_D, datt, nullptr, nullptr, 1.f, rows, stream)) return rc;
-            const long long sQ = (long long)IEF_T * 3 * IEF_D, sP1 = (long long)IEF_H * IEF_T * IEF_T, sP2 = (long long)IEF_T * IEF_T,
-                            sA = (long long)IEF_T * IEF_D;
-            BgemmArgs a;
+            if (int rc = launch_dx(bx, h->out[m][l], gx, datt, nullptr, nullptr, 1.f)) return rc;
             // bf16x6: d S = Pd .* d Pd - P rowsum(Pd .* d Pd) with d Pd = d att v^T in ONE launch (attention_split.h, BWD: the product on the
             // split arithmetic, the softmax backward on its accumulators); after an IEFVAD_TRAIN_ATTN=unfused forward the product stays on
             // the fp32 MFMA kernel with the stand-alone softmax backward (A/B)
@@ -685,58 +660,35 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
                 memset(&tx, 0, sizeof(tx));
                 aa.nchunks = B;
                 aa.qkv[0] = qkv;
-                tx.dO[0] = datt; tx.P[0] = const_cast<float*>(P); tx.drop[0] = signed_p ? 1 : 0; tx.drop_p[0] = rec->drop_p[m][l]; tx.dS[0] = dP;
+                tx.dO[0] = datt; tx.P[0] = P; tx.drop[0] = signed_p ? 1 : 0; tx.drop_p[0] = rec->drop_p[m][l]; tx.dS[0] = dP;
                 tx.dQ[0] = dqkv; tx.q_scale = qscale;
-                hipLaunchKernelGGL(iefvad_attention_split_ds_kernel, dim3(IEF_H, 2, B), dim3(256), ATS_LDS_BYTES, stream, aa, tx);
-                HIP_TRY(hipGetLastError());
+                if (int rc = launch(iefvad_attention_split_ds_kernel, dim3(IEF_H, 2, B), dim3(256), ATS_LDS_BYTES, stream, aa, tx)) return rc;
             } else {
-            // d Pd = d att v^T
-            memset(&a, 0, sizeof(a));
-            a.A = datt; a.B = qkv + 2 * IEF_D; a.C = dP;
-            a.M = IEF_T; a.N = IEF_T; a.K = IEF_DH; a.lda = IEF_D; a.ldb = 3 * IEF_D; a.ldc = IEF_T;
-            a.a1 = sA; a.a2 = IEF_DH; a.b1 = sQ; a.b2 = IEF_DH; a.c1 = sP1; a.c2 = sP2; a.nz2 = IEF_H; a.alpha = 1.f;
-            if (int rc = launch_bgemm(a, true, true, B * IEF_H, stream)) return rc;
+                // d Pd = d att v^T
+                if (int rc = head_product(probs(dP), head_rows(datt), true, v_of(qkv), true, IEF_T, IEF_T, IEF_DH, 1.f, 0.f, B, stream)) return rc;
             }
             // d v = Pd^T d att
-            memset(&a, 0, sizeof(a));
-            a.A = P; a.B = datt; a.C = dqkv + 2 * IEF_D;
-            a.M = IEF_T; a.N = IEF_DH; a.K = IEF_T; a.lda = IEF_T; a.ldb = IEF_D; a.ldc = 3 * IEF_D;
-            a.a1 = sP1; a.a2 = sP2; a.b1 = sA; a.b2 = IEF_DH; a.c1 = sQ; a.c2 = IEF_DH; a.nz2 = IEF_H; a.alpha = 1.f;
-            if (signed_p) a.a_drop = drop_scale;
-            if (int rc = launch_bgemm(a, false, false, B * IEF_H, stream)) return rc;
-            // d S = Pd .* d Pd - P rowsum(Pd .* d Pd)
+            if (int rc = head_product(v_of(dqkv), probs(P), false, head_rows(datt), false, IEF_T, IEF_DH, IEF_T, 1.f, signed_p ? drop_scale : 0.f, B, stream))
+                return rc;
             if (!ds_fused) {
+                // d S = Pd .* d Pd - P rowsum(Pd .* d Pd)
                 const long long srows = (long long)B * IEF_H * IEF_T;
-                hipLaunchKernelGGL(iefvad_softmax_bwd_kernel, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, stream, P, drop_scale, dP, srows);
-                HIP_TRY(hipGetLastError());
-            }
-            // d q (before the 1/sqrt(96) scale) = qscale * d S k  (ds_fused: done by the same launch, on the d S in its registers)
-            if (!ds_fused) {
-            memset(&a, 0, sizeof(a));
-            a.A = dP; a.B = qkv + IEF_D; a.C = dqkv;
-            a.M = IEF_T; a.N = IEF_DH; a.K = IEF_T; a.lda = IEF_T; a.ldb = 3 * IEF_D; a.ldc = 3 * IEF_D;
-            a.a1 = sP1; a.a2 = sP2; a.b1 = sQ; a.b2 = IEF_DH; a.c1 = sQ; a.c2 = IEF_DH; a.nz2 = IEF_H; a.alpha = qscale;
-            if (int rc = launch_bgemm(a, true, false, B * IEF_H, stream)) return rc;
+                if (int rc = launch(iefvad_softmax_bwd_kernel, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, stream, P, drop_scale, dP, srows)) return rc;
+                // d q (before the 1/sqrt(96) scale) = qscale * d S k  (ds_fused: done by the same launch, on the d S in its registers)
+                if (int rc = head_product(q_of(dqkv), probs(dP), true, k_of(qkv), false, IEF_T, IEF_DH, IEF_T, qscale, 0.f, B, stream)) return rc;
             }
             // d k = d S^T q_scaled
-            memset(&a, 0, sizeof(a));
-            a.A = dP; a.B = qkv; a.C = dqkv + IEF_D;
-            a.M = IEF_T; a.N = IEF_DH; a.K = IEF_T; a.lda = IEF_T; a.ldb = 3 * IEF_D; a.ldc = 3 * IEF_D;
-            a.a1 = sP1; a.a2 = sP2; a.b1 = sQ; a.b2 = IEF_DH; a.c1 = sQ; a.c2 = IEF_DH; a.nz2 = IEF_H; a.alpha = 1.f;
-            if (int rc = launch_bgemm(a, false, false, B * IEF_H, stream)) return rc;
+            if (int rc = head_product(k_of(dqkv), probs(dP), false, q_of(qkv), false, IEF_T, IEF_DH, IEF_T, 1.f, 0.f, B, stream)) return rc;
             // in_proj (packed q | k | v, imf_vad.py:69-72)
-            { bool db_done = false;
-            if (int rc = launch_dw(dqkv, 3 * IEF_D, 3 * IEF_D, l == 0 ? rec->x0[m] : ws + t.x[m][l], dw->in_proj_w[m][l], nullptr, 0, 1.f, rows, part, t.part_floats, stream, tn, dw->in_proj_b[m][l], nullptr, cpart, t.cpart_floats, &db_done)) return rc;
-            if (!db_done)
-                if (int rc = launch_db(dqkv, 3 * IEF_D, 3 * IEF_D, dw->in_proj_b[m][l], nullptr, 0, 1.f, rows, cpart, stream)) return rc; }
+            const float* xl = l == 0 ? rec->x0[m] : ws + t.x[m][l];
+            if (int rc = linear_param_grads(bx, LinearGrads{dqkv, &h->in[m][l], xl, 1.f, dw->in_proj_w[m][l], dw->in_proj_b[m][l]})) return rc;
             // d x_l = d s_l (residual) + d qkv W_in: in place for the layers above the first; at layer 0 it is the gradient of the input
             // features, written to the caller's buffer where one is given (gx is only read there)
             float* dxl = l > 0 ? gx : dx[m];
             if (dxl)
-                if (int rc = launch_dx(h, tp ? h->in[m][l].wst : nullptr, dqkv, 3 * IEF_D, h->in[m][l].w, 3 * IEF_D, IEF_D, dxl, gx, nullptr, 1.f, rows, stream)) return rc;
+                if (int rc = launch_dx(bx, h->in[m][l], dqkv, dxl, gx, nullptr, 1.f)) return rc;
         }
     }
-    const_cast<TrainRecord*>(rec)->stamp = 0;      // the scratch tensors have overwritten the saved refinement states
     return 0;
 }
 

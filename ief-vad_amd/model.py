@@ -335,9 +335,9 @@ class _TrainForward(torch.autograd.Function):
             else:
                 name = "iefvad_train_backward"
                 rc = lib.iefvad_train_backward(*args, C.c_void_p(stream))
+        ctx.ws = None                       # the library retired the forward's record, on failure too: its scratch overwrites saved states
         if rc != 0:
             raise RuntimeError(name + ": " + _lib.last_error())
-        ctx.ws = None
         gin = [g if g is None or g.dtype == dtype else g.to(dtype) for g, (dtype, _) in zip(gin, ctx.in_meta)]
         return (None, None, *gin, *grads)
 

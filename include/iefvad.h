@@ -430,7 +430,7 @@ int iefvad_train_backward_inputs(iefvad_handle* h, int32_t B, void* train_ws, si
                                  const iefvad_output_grads* dout, const iefvad_weight_grads* dw,
                                  const iefvad_input_grads* dx, void* stream);
 
-/* The trainers' input rule (/root/reference/train/ucf_train.py:50-53, xd_train.py:40-43: `if torch.isnan(x).any(): x =
+/* The trainers' input rule (/root/reference/train/ucf_train.py:50-53; xd_train.py has none: `if torch.isnan(x).any(): x =
  * torch.nan_to_num(x, nan=0.0)`, per tensor) for the two fp32 input tensors of a step, without the host read of the flag: one scan,
  * one repair launch that returns at once for a tensor without NaN; a tensor WITH a NaN is rewritten IN PLACE as torch.nan_to_num
  * does (NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX).  a, b: device, n floats each (n % 4 == 0, 16-byte aligned); flags_ws: 8 device
