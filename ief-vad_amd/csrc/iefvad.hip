@@ -45,6 +45,7 @@
 #include "backward.h"
 #include "metrics.h"
 #include "similarity.h"
+#include "trajectory.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -104,7 +105,10 @@ struct iefvad_handle {
     float* whiten_b[2];
     float* cls_w;
     float* cls_b;
-    float* score_fold;     // bf16x6, K >= 1: v = -lambda W2_K^T c [D] and s0 = b_c - lambda (c . b2_K) [1] of the folded scorer (rowops.h)
+    int steps;             // refinement steps the evaluation entries run: cfg.num_steps unless iefvad_set_steps chose a prefix
+    // bf16x6, K >= 1: per block k, v = -lambda W2_k^T c [D] and s0 = b_c - lambda (c . b2_k) [1] of the folded scorer (rowops.h), D + 4
+    // floats apart; a forward of `steps` steps reads block steps - 1 (score_fold_of)
+    float* score_fold;
     // the arenas of the ProjW forms: bf16 copies (BF16), three-plane splits (BF16X6), fp16 planes (FP16X3); amax_dev holds the
     // running-max words of the matrices (filled at set_weights) and, behind them, of the activations of the current micro-batch
     bf16_t* arena_b;
@@ -131,6 +135,10 @@ static size_t amax_words(int L, int K, int mb_chunks) {
 // the split modes (bf16x6 / fp16x3) gain 2.4 % from 4x longer launches as well (fewer kernel-boundary tails)
 static const int kDefaultMicroBatchF32 = 256;
 static const int kDefaultMicroBatchBF16 = 1024;
+
+static const float* score_fold_of(const iefvad_handle* h, int steps) {
+    return h->score_fold && steps >= 1 ? h->score_fold + (size_t)(steps - 1) * (h->D + 4) : nullptr;
+}
 
 static int micro_batch(const iefvad_handle* h) {
     if (h->cfg.micro_batch > 0) return h->cfg.micro_batch < 16384 ? h->cfg.micro_batch : 16384;   // attention grid.z = 2 x chunks
@@ -245,6 +253,7 @@ static int create_impl(const char* who, bool allow_512, const iefvad_config* cfg
     if (!h) return fail("%s: out of host memory", who);
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
+    h->steps = cfg->num_steps;
     h->D = d512 ? IEF_D512 : IEF_D;
     h->DH = h->D / IEF_H;
     // The library's only environment switches: alternative paths that tests compare the default against, and a trace
@@ -454,7 +463,7 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     if (!w->cls_w || !w->cls_b) return fail("iefvad_set_weights: null classifier weight");
 
     const size_t total = 2 * L * (3 * DD + 3 * D + DD + D + 2 * D) + 2 * (2 * D) + 2 * (2 * DD + 2 * D) +
-                         (size_t)K * (2 * DD + 2 * D) + D + 4 + (D + 4);
+                         (size_t)K * (2 * DD + 2 * D) + D + 4 + (size_t)(K > 1 ? K : 1) * (D + 4);
     if (!h->arena) {
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipMalloc((void**)&h->arena, total * sizeof(float)));
@@ -513,11 +522,13 @@ extern "C" int iefvad_set_weights(iefvad_handle* h, const iefvad_weights* w, voi
     p += 3;                                      // back to a 16-byte boundary: the folded scorer's vector is read 16 bytes per lane
     h->score_fold = nullptr;
     if (h->cfg.compute == IEFVAD_COMPUTE_BF16X6 && K >= 1) {
-        // the scores-only forward drops the last refinement projection: logits = c . z_{K-1} + v . h + s0 (forward_pass, step 4)
+        // the scores-only forward drops the last refinement projection: logits = c . z_{K-1} + v . h + s0 (forward_pass, step 4).  One
+        // vector per block (one launch: grid.y = block; the blocks' W2 / b2 are 2 DD + 2 D floats apart in the arena, above), so that a
+        // forward of any prefix of the steps (iefvad_set_steps) finds the one of its last block.
         h->score_fold = p;
-        p += D + 4;
-        hipLaunchKernelGGL(iefvad_scorer_fold_weights_kernel, dim3((unsigned)(D / 16 + 1)), dim3(256), 0, stream, h->ref2[K - 1].w,
-                           h->ref2[K - 1].b, h->cls_w, h->cls_b, h->cfg.lambda_ref, h->score_fold, (int)D);
+        p += (size_t)K * (D + 4);
+        hipLaunchKernelGGL(iefvad_scorer_fold_weights_kernel, dim3((unsigned)(D / 16 + 1), K), dim3(256), 0, stream, h->ref2[0].w, h->ref2[0].b,
+                           h->cls_w, h->cls_b, h->cfg.lambda_ref, h->score_fold, (int)D, 2 * DD + 2 * D, (int)(D + 4));
         HIP_TRY(hipGetLastError());
     }
     if ((size_t)(p - h->arena) > h->arena_floats) return fail("iefvad_set_weights: arena overflow");
@@ -954,13 +965,13 @@ static int launch_heads_chain(iefvad_handle* h, HeadsChainArgs& ha, int rows, fl
 }
 
 static int launch_refine_chain(iefvad_handle* h, const float* z_in, float* z_out, float* logits, int rows, hipStream_t stream, Timer& tm) {
-    const int K = h->cfg.num_steps;
+    const int K = h->steps;                // a prefix of the packed stream, which is in step order; the waves' streams stay cfg.num_steps long
     ChainArgs ca;
     memset(&ca, 0, sizeof(ca));
     ca.z_in = z_in; ca.stream = h->chain_stream; ca.cls_w = h->cls_w; ca.cls_b = h->cls_b;
     ca.z_out = z_out;           // may be z_in (in place): a workgroup reads its 64 rows before it writes them
     ca.logits = logits;
-    ca.M = rows; ca.K = K; ca.lambda = h->cfg.lambda_ref; ca.wave_stride = (unsigned)chain_wave_stride_bytes(K);
+    ca.M = rows; ca.K = K; ca.lambda = h->cfg.lambda_ref; ca.wave_stride = (unsigned)chain_wave_stride_bytes(h->cfg.num_steps);
     tm.gemm_launches += 1;
     return launch(tm, ST_REFINE, iefvad_refine_chain_bf16_kernel, dim3(rows / RC_BM), dim3(64 * RC_NW), RC_LDS_BYTES, stream, ca);
 }
@@ -1000,6 +1011,17 @@ struct AttnMaps {
     }
 };
 
+// The refinement trajectory a call asked for (include/iefvad.h, csrc/trajectory.h): the [steps + 1, stride] logits and the
+// [steps, stride] update norms of the whole CALL, either nullable; a pass writes columns row0 + packed row of the pass.  z_prev: the
+// pass's second state buffer ([R, D] floats behind the base workspace), set by the entry.
+struct TrajOut {
+    float* logits_steps;
+    float* delta_norm;
+    long long stride, row0;
+    float* z_prev;
+    bool any() const { return logits_steps || delta_norm; }
+};
+
 enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 struct VideosOut {
     float* logits;                   // [rows] each
@@ -1017,6 +1039,7 @@ struct VideosOut {
     // iefvad_rows_out_wide_kernel copies the valid rows out (pass_rows_out).
     float* wide[ROWS_OUT_WIDE_MAX];
     AttnMaps attn;                   // iefvad_forward_videos_attn: the packed [rows, 256] maps, written inside the encoder (pass_encoder_layer)
+    TrajOut traj;                    // iefvad_forward_videos_trajectory: the per-step series; like the similarity series it keeps its base and takes its column from row0
     long long row0;                  // packed row of the call's list (the host entries: of the whole list) that this view's first row is
     int nan_mode;                    // 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 = every video and modality (test2.py:59-60)
     bool sweep_codes;                // the scaled entry: nan_mode outside 0..2 is refused (the other entries read any non-zero value as 1)
@@ -1033,6 +1056,7 @@ struct VideosOut {
         for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
             if (wide[t]) o.wide[t] += rows * D;
         o.attn = attn.at(rows);
+        o.traj.row0 += rows;
         o.row0 += rows;
         return o;
     }
@@ -1323,7 +1347,7 @@ static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass*
             b.compacted = true;
         }
     }
-    static_cast<TailFlags&>(b) = plan_tail(h->policy, h->cfg.compute, b.rows, h->cfg.num_steps, b.splitmb, b.compacted, h->heads_stream != nullptr,
+    static_cast<TailFlags&>(b) = plan_tail(h->policy, h->cfg.compute, b.rows, h->steps, b.splitmb, b.compacted, h->heads_stream != nullptr,
                                            h->chain_stream != nullptr);
     return 0;
 }
@@ -1338,11 +1362,32 @@ static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg) {
                     out->image_logvar || rows(kWideLvI, false), out->event_logvar || rows(kWideLvE, false)};
 }
 
-// 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer
-static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+// The probe of state z_k of a trajectory pass (trajectory.h): k = 0 behind the fusion, k = j + 1 behind step j.  `copy_logits`: entry k
+// is the pass's logits, already in b.logits (the folded scorer).
+static int pass_step_probe(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const TrajOut& tj, int k, int steps, bool copy_logits,
+                           hipStream_t stream, Timer& tm) {
+    float* const lo = tj.logits_steps ? tj.logits_steps + (long long)k * tj.stride : nullptr;
+    float* const dn = (tj.delta_norm && k > 0) ? tj.delta_norm + (long long)(k - 1) * tj.stride : nullptr;
+    const int store_prev = tj.delta_norm && k < steps;
+    if (!lo && !dn && !store_prev) return 0;
+    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
+    const int valid_rows = rg ? rg->valid_rows : b.rows;
+    const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
+    return dispatch_d(h->D == IEF_D512, [&](auto w) {
+        return launch(tm, ST_SCORER, iefvad_step_probe_kernel<decltype(w)::value>, dim3(nslabs, TRAJ_SLICES), dim3(256), 0, stream, (const float*)b.z, tj.z_prev,
+                      (const float*)h->cls_w, (const float*)h->cls_b, copy_logits ? (const float*)b.logits : (const float*)nullptr, chunks, valid_rows, lo, dn,
+                      tj.row0, k == 0 ? 1 : 0, store_prev);
+    });
+}
+
+// 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer.  K is the handle's current step count
+// (iefvad_set_steps): blocks 0 .. K - 1 run.  `tj` (nullable): the pass records its trajectory -- a probe launch behind the fusion and
+// behind every step; the state must then pass through HBM between steps, so the bf16 arithmetic takes its launch-per-projection
+// route (bit-identical to the chain kernel) and the folded bf16x6 tail forms z_K as a pass that keeps `fused` does.
+static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, const TrajOut* tj, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
-    const int D = h->D, L = c.num_layers, K = c.num_steps, rows = b.rows;
+    const int D = h->D, L = c.num_layers, K = h->steps, rows = b.rows;
     const bool d512 = h->D == IEF_D512;
     const float factor = precision_factor(c);
     const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
@@ -1350,9 +1395,10 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     ProjCtx px = proj_ctx(h, b, stream, tm);
     px.use_split = b.tail_split;
 
-    const bool chain = b.chain, fold = b.fold;
+    const bool chain = b.chain && !tj, fold = b.fold;
     const TailKeep keep = tail_keep(out, rg);
-    const bool keep_fused = keep.fused;
+    const bool keep_fused = keep.fused || tj;
+    const float* const score_fold = score_fold_of(h, K);
     // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
     if (b.heads_rows) {
         HeadsChainArgs ha;
@@ -1391,6 +1437,9 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
             return rc;
     }
 
+    if (tj)
+        if (int rc = pass_step_probe(h, b, rg, *tj, 0, K, false, stream, tm)) return rc;
+
     if (chain)
         if (int rc = launch_refine_chain(h, z, keep_fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
 
@@ -1409,13 +1458,13 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         p.A32[0] = z; p.A16[0] = b.zb; p.amaxA[0] = b.am_z(k); p.amaxC[0] = b.am_h(k);
         p.C[0] = bf ? nullptr : b.hbuf; p.Cb[0] = bf ? b.hb : nullptr;
         if (dot) {
-            p.epi = EPI_BIAS_RELU_DOT; p.R[0] = h->score_fold; p.C2[0] = fold_part;
+            p.epi = EPI_BIAS_RELU_DOT; p.R[0] = score_fold; p.C2[0] = fold_part;
             if (!keep_fused) p.C[0] = nullptr;
         }
         if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
         if (dot) {
             if (int rc = launch(tm, ST_SCORER, iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>, row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
-                                h->score_fold, b.logits, rows)) return rc;
+                                score_fold, b.logits, rows)) return rc;
             if (!keep_fused) break;
         }
         p = Proj::of(EPI_REFINE, D, D, h->ref2[k]);
@@ -1423,6 +1472,8 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
         p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
         p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
         if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
+        if (tj)
+            if (int rc = pass_step_probe(h, b, rg, *tj, k + 1, K, dot, stream, tm)) return rc;
     }
 
     // 5. scorer (imf_vad.py:150)
@@ -1481,19 +1532,21 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
 // must be all-null, `scale` kNoScale: rg->out carries the packed scales).
 static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
                         const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr,
-                        const RowNoise* nz = nullptr) {
+                        const RowNoise* nz = nullptr, const TrajOut* tj = nullptr) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
     if (rg) maps = &rg->out.attn;                 // a whole-video pass: the maps at the pass's first packed row
+    if (rg) tj = rg->out.traj.any() ? &rg->out.traj : nullptr;
     if (int rc = pass_load_inputs(h, b, in, scale, nz ? *nz : RowNoise{}, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
         if (int rc = pass_encoder_layer(h, b, l, rg, maps, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
-    if (int rc = pass_tail(h, b, out, rg, stream, tm)) return rc;
+    if (int rc = pass_tail(h, b, out, rg, tj, stream, tm)) return rc;
     return rg ? pass_rows_out(h, b, rg, stream, tm) : 0;
 }
 
 static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
-                        const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr, const RowNoise* nz = nullptr) {
+                        const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr, const RowNoise* nz = nullptr,
+                        const TrajOut* tj = nullptr) {
     const void* const img = in.img;
     const void* const ev = in.ev;
     const int32_t in_dtype = in.in_dtype;
@@ -1513,7 +1566,10 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
         const float* const pass_scale[2] = {scale[0] ? scale[0] + row0 : nullptr, scale[1] ? scale[1] + row0 : nullptr};
         const AttnMaps pass_maps = maps ? maps->at((long long)row0) : AttnMaps();
         const RowNoise pass_nz = nz ? nz->at((long long)row0) : RowNoise{};       // ids default to the row of the CALL: b T + t
-        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr, &pass_nz))
+        TrajOut pass_tj = tj ? *tj : TrajOut{};
+        pass_tj.row0 = (long long)row0;
+        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr, &pass_nz,
+                                  tj ? &pass_tj : nullptr))
             return rc;
     }
     return 0;
@@ -1542,6 +1598,7 @@ struct GraphEntry {
     size_t workspace_bytes;
     hipGraphExec_t exec;
     unsigned long long last_use;
+    int steps;                   // the handle's step count at capture (iefvad_set_steps): a graph of K steps never replays for k
 };
 
 struct GraphCache {
@@ -1609,7 +1666,7 @@ static int forward_graphed(iefvad_handle* h, const void* img, const void* ev, in
     }
     GraphEntry* hit = nullptr;
     for (auto& e : gc.entries)
-        if (e.B == B && e.in_dtype == in_dtype && e.outmask == outmask && e.workspace == workspace && e.workspace_bytes == workspace_bytes) hit = &e;
+        if (e.B == B && e.in_dtype == in_dtype && e.outmask == outmask && e.workspace == workspace && e.workspace_bytes == workspace_bytes && e.steps == h->steps) hit = &e;
     if (!hit) {
         iefvad_outputs so;
         float** sf = (float**)&so;
@@ -1644,7 +1701,7 @@ static int forward_graphed(iefvad_handle* h, const void* img, const void* ev, in
             (void)hipGraphExecDestroy(gc.entries[lru].exec);
             gc.entries.erase(gc.entries.begin() + (long)lru);
         }
-        gc.entries.push_back(GraphEntry{B, in_dtype, outmask, workspace, workspace_bytes, exec, 0});
+        gc.entries.push_back(GraphEntry{B, in_dtype, outmask, workspace, workspace_bytes, exec, 0, h->steps});
         hit = &gc.entries.back();
     }
     hit->last_use = ++gc.clock;
@@ -2441,4 +2498,65 @@ extern "C" int iefvad_set_batch_invariant(iefvad_handle* h, int on) {
     release_graphs(h);
     h->policy.split_always = want;
     return 0;
+}
+
+// Call-time step count (include/iefvad.h): the evaluation entries run refinement blocks 0 .. steps - 1.  Nothing resident depends on
+// the count (every block's folded-scorer vector is there since iefvad_set_weights, the chain's stream is in step order), and the
+// graph cache is keyed by it, so this only records the number.
+extern "C" int iefvad_set_steps(iefvad_handle* h, int32_t steps) {
+    if (!h) return fail("iefvad_set_steps: null argument");
+    if (steps < 0 || steps > h->cfg.num_steps) return fail("iefvad_set_steps: steps %d outside 0..%d (the handle's num_steps)", steps, h->cfg.num_steps);
+    h->steps = steps;
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the refinement trajectory (include/iefvad.h, csrc/trajectory.h)
+// ------------------------------------------------------------------------------------------------
+// The checks of a trajectory request that need no device: something is asked for, 4-byte aligned, a stride that holds the call's rows
+static int trajectory_args(const char* who, const iefvad_trajectory* t, long long rows, TrajOut* tj) {
+    if (!t) return fail("%s: null trajectory", who);
+    if (!t->logits_steps && !t->delta_norm) return fail("%s: logits_steps and delta_norm are both null (nothing is asked for)", who);
+    if (((uintptr_t)t->logits_steps | (uintptr_t)t->delta_norm) & 3) return fail("%s: logits_steps and delta_norm must be 4-byte aligned", who);
+    if ((long long)t->stride < rows) return fail("%s: stride %zu is less than the call's %lld rows", who, t->stride, rows);
+    *tj = TrajOut{t->logits_steps, t->delta_norm, (long long)t->stride, 0, nullptr};
+    return 0;
+}
+
+extern "C" size_t iefvad_trajectory_workspace_bytes(const iefvad_handle* h, int32_t B) {
+    const size_t base = iefvad_workspace_bytes(h, B);
+    if (!base) return 0;
+    const int mb = micro_batch(h);
+    return base + (size_t)(B < mb ? B : mb) * IEF_T * h->D * sizeof(float);
+}
+
+extern "C" int iefvad_forward_trajectory(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                                         size_t workspace_bytes, const iefvad_outputs* out, const iefvad_trajectory* trajectory, void* stream) {
+    static const char* const who = "iefvad_forward_trajectory";
+    if (!h) return fail("%s: null handle", who);
+    if (!img || !ev || !out) return fail("%s: null argument", who);
+    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
+    TrajOut tj;
+    if (int rc = trajectory_args(who, trajectory, (long long)B * IEF_T, &tj)) return rc;
+    const size_t need = iefvad_trajectory_workspace_bytes(h, B);
+    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    tj.z_prev = (float*)((char*)workspace + iefvad_workspace_bytes(h, B));
+    Timer tm;      // direct launches: the series' pointers are per call, a cached graph would pin their addresses
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, nullptr, &tj);
+}
+
+extern "C" int iefvad_forward_videos_trajectory(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                                const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                                size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                                const iefvad_trajectory* trajectory, void* stream) {
+    static const char* const who = "iefvad_forward_videos_trajectory";
+    if (!h) return fail("%s: null handle", who);
+    if (!lengths) return fail("%s: null argument", who);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    long long rows, chunks;
+    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    if (int rc = trajectory_args(who, trajectory, rows, &out.traj)) return rc;
+    Timer tm;
+    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
 }

@@ -263,10 +263,16 @@ __global__ __launch_bounds__(256) void iefvad_scorer_fold_kernel(const float* z,
 // microseconds, not a 768-long dependent chain per thread): fp64 throughout, rounded once to fp32.  A workgroup takes 16 elements;
 // thread (seg = t >> 4, jj = t & 15) sums n = 48 seg .. 48 seg + 47 in ascending order, thread (0, jj) then adds the 16 segment sums
 // in ascending order -- a fixed order that no launch parameter changes.  Block b < D / 16: v[16 b + jj]; block D / 16: s0.  D = 768.
+// blockIdx.y = refinement block: its W2 / b2 lie step_stride floats behind the previous block's (the arena order of iefvad_set_weights),
+// its vector fold_stride floats behind the previous one -- every block's vector in one launch, each computed as a launch of its own would.
 #define FOLD_SEGS 16
 __global__ __launch_bounds__(256) void iefvad_scorer_fold_weights_kernel(const float* __restrict__ w2, const float* __restrict__ b2,
                                                                          const float* __restrict__ c, const float* __restrict__ bc,
-                                                                         float lambda, float* __restrict__ fold, int D) {
+                                                                         float lambda, float* __restrict__ fold, int D, size_t step_stride,
+                                                                         int fold_stride) {
+    w2 += blockIdx.y * step_stride;
+    b2 += blockIdx.y * step_stride;
+    fold += (size_t)blockIdx.y * fold_stride;
     __shared__ double part[FOLD_SEGS][16];
     const int seg = threadIdx.x >> 4, jj = threadIdx.x & 15;
     const int len = D / FOLD_SEGS, n0 = seg * len;

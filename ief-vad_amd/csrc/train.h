@@ -390,6 +390,9 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
                                     void* stream_) {
     if (!h) return fail("iefvad_train_forward: null handle");
     if (h->D != IEF_D) return fail("iefvad_train_forward: training is built for D=768 (this handle has D=%d)", h->D);
+    if (h->steps != h->cfg.num_steps)
+        return fail("iefvad_train_forward: the handle runs %d of its %d refinement steps (iefvad_set_steps); training takes all of them", h->steps,
+                    h->cfg.num_steps);
     const bool fused = train_attn_fused(h);
     if (int rc = train_check(h, B, train_ws, train_ws_bytes, "iefvad_train_forward")) return rc;
     if (!img || !ev || !out || !opt) return fail("iefvad_train_forward: null argument");

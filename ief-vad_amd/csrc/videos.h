@@ -80,13 +80,19 @@ static size_t videos_extra_bytes(const iefvad_handle* h, long long chunks, bool 
     return (w_rows || colsum ? 2 * nb * IEF_T * (size_t)h->D * sizeof(float) : 0) + (colsum ? nb * 2 * (size_t)h->D * sizeof(double) : 0);
 }
 
-// the three public workspace queries: 0 for arguments no call would accept
-static size_t videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, bool w_rows, bool colsum) {
+// the second state buffer of a trajectory pass (trajectory.h): [R, D] floats behind everything else
+static size_t videos_traj_bytes(const iefvad_handle* h, long long chunks) { return videos_pass_chunks(h, chunks) * IEF_T * (size_t)h->D * sizeof(float); }
+
+// the public workspace queries: 0 for arguments no call would accept
+static size_t videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, bool w_rows, bool colsum, bool traj = false) {
     if (!h || !lengths || nvideos <= 0) return 0;
     long long rows, chunks;
     if (videos_layout(lengths, nvideos, &rows, &chunks) || chunks > 0x7fffffffLL) return 0;
     const size_t base = iefvad_workspace_bytes(h, (int32_t)chunks);
-    return base ? base + videos_extra_bytes(h, chunks, w_rows, colsum) : 0;
+    return base ? base + videos_extra_bytes(h, chunks, w_rows, colsum) + (traj ? videos_traj_bytes(h, chunks) : 0) : 0;
+}
+extern "C" size_t iefvad_videos_trajectory_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
+    return videos_workspace_bytes(h, lengths, nvideos, false, false, true);
 }
 extern "C" size_t iefvad_videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
     return videos_workspace_bytes(h, lengths, nvideos, false, false);
@@ -150,7 +156,8 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
     if (int rc = videos_layout(lengths, nvideos, &total_rows, &total_chunks, who)) return rc;
     if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
     const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
-    const size_t need = base + videos_extra_bytes(h, total_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
+    const size_t extra = videos_extra_bytes(h, total_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
+    const size_t need = base + extra + (out.traj.any() ? videos_traj_bytes(h, total_chunks) : 0);
     if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     if (((uintptr_t)workspace & 15) || ((uintptr_t)in.img & 15) || ((uintptr_t)in.ev & 15)) return fail("%s: buffers must be 16-byte aligned", who);
 
@@ -236,6 +243,7 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
         rg.first_pass = c0 == 0;
         rg.out = out.at(row0, h->D);          // pass-relative, like src_row
         rg.out.nan_mode = nan_mode;
+        if (out.traj.any()) rg.out.traj.z_prev = (float*)((char*)workspace + base + extra);
         rc = forward_pass(h, in.at((size_t)row0, h->D), kNoScale, nb, 0, workspace, &none, &rg, stream, tm);
         row0 += vrows;
     }

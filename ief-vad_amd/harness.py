@@ -624,14 +624,17 @@ class _ScoreSink:
         self.total = 0
         self.dev_sim: Optional[List[torch.Tensor]] = None     # score_loader(similarity=True): per forward [4, valid snippets of its videos]
         self.dev_rows: Optional[Dict[str, List[torch.Tensor]]] = None   # score_loader(row_outputs=...): per key, per forward [valid snippets, D]
+        self.dev_traj: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None   # score_loader(trajectory=True): per forward ([steps + 1, slots], [steps, slots])
 
-    def add(self, logits, wi, we, lens, stride=None, sim=None, rows=None):
+    def add(self, logits, wi, we, lens, stride=None, sim=None, rows=None, traj=None):
         """One forward's flat fp32 vectors over videos of `lens` snippets: back to back (the valid-row routes), or video i in
         stride[i] slots of which the first lens[i] count (the padded route: its chunks * maxlen).  `sim`: the forward's
         `similarity_rows` over the valid snippets of its videos, back to back.  `rows`: the forward's dict, from which the
         [valid snippets, D] tensors of `dev_rows` are kept (on the device, as they are)."""
         if sim is not None:
             self.dev_sim.append(sim)
+        if self.dev_traj is not None and traj is not None:      # laid out like `logits`: the same slots, one row per step
+            self.dev_traj.append(traj)
         if self.dev_rows is not None and rows is not None:
             for k, v in self.dev_rows.items():
                 v.append(rows[k])
@@ -687,7 +690,7 @@ def _lane_stream(stream):
 
 
 def _score_padded(models, stagers, streams, loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                  similarity=False):
+                  similarity=False, trajectory=False):
     """Padded route (the only one on the CPU): `model(img, ev, ...)` on zero-padded chunks, one forward per video
     (batch_chunks <= 0) or per batch, which closes as soon as it holds `batch_chunks` chunks; forwards round-robin over the lanes.
     `_unpack_item` has applied the NaN rule in each tensor's own dtype; a mixed batch is widened while it is staged.
@@ -701,8 +704,12 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
             else:
                 img = torch.cat([p[0].to(dt) for p in pend], dim=0).to(device)
                 ev = torch.cat([p[1].to(dt) for p in pend], dim=0).to(device)
-            out = models[k](img, ev, None, None, None)
+            out = models[k](img, ev, None, None, None, **(dict(trajectory=True) if trajectory else {}))
             logits = out['logits'].reshape(-1)
+            traj = None
+            if trajectory:
+                ls = out['logits_steps']
+                traj = (ls.reshape(ls.shape[0], -1), out['delta_norm'].reshape(ls.shape[0] - 1, -1))
             if 'w_i_mean' in out:
                 wi, we = out['w_i_mean'].reshape(-1), out['w_e_mean'].reshape(-1)
             else:
@@ -716,7 +723,7 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
                 starts = np.concatenate([[0], np.cumsum(stride)[:-1]])
                 index = np.concatenate([np.arange(o, o + n, dtype=np.int32) for o, n in zip(starts, lens)])
                 sim = similarity_rows(out['fused'], out['image_mu'], out['event_mu'], torch.from_numpy(index))
-            sink.add(logits.float(), wi.float(), we.float(), lens, stride, sim)
+            sink.add(logits.float(), wi.float(), we.float(), lens, stride, sim, traj=traj)
 
     pend, pend_chunks, nsent = [], 0, 0
     for item in loader:
@@ -738,7 +745,7 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
 
 
 def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=(),
-                     attn_layers=()):
+                     attn_layers=(), trajectory=False):
     """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
     while this thread sends batch k and enqueues its forward; batches complete in order.
@@ -758,10 +765,11 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
         with _lane_stream(streams[k]):
             img, ev = stagers[k].send(staged)
             out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
-        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out)
+        sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out,
+                 traj=(out['logits_steps'], out['delta_norm']) if trajectory else None)
 
     sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else \
-        dict(attn_maps=attn_layers) if attn_layers else {}
+        dict(attn_maps=attn_layers) if attn_layers else dict(trajectory=True) if trajectory else {}
 
     stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
@@ -825,7 +833,8 @@ def _score_rows_list(model, loader, sink, maxlen, dataset, label_map, batch_chun
 def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, dataset: str = 'ucfcrime',
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
-                 return_device: bool = False, similarity=False, row_outputs=None, attn_maps=None):
+                 return_device: bool = False, similarity=False, row_outputs=None, attn_maps=None, steps: Optional[int] = None,
+                 trajectory: bool = False):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -876,8 +885,25 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     becomes {"attn_maps": {"image", "event": ONE [n, N, T] fp32 device tensor each -- the head-averaged attention weights of the N
     valid snippets over the T keys of their chunks, layers in the order of "layers"; "layers": the n layer indices, ascending;
     "row_offsets": int64 array of len(videos) + 1 offsets into N}}.  ValueError with ragged=False, a CPU device, `row_outputs` or
-    `similarity`."""
+    `similarity`.
+
+    `steps` (an integer in 0 .. K; a model with `set_steps`, i.e. `iefvad_amd.MMFMIL`): the walk runs with only the first `steps`
+    refinement blocks (`MMFMIL.set_steps`); the model's own count is restored afterwards, also when a forward raises.
+    `trajectory=True` (the per-video / padded route and the `forward_videos` loop; HIP device): every forward also returns its
+    refinement trajectory (`forward(..., trajectory=True)` / `forward_videos(..., trajectory=True)`).  The returned tuple does not
+    change; `score_loader.last_result` becomes {"trajectory": {"scores_steps": [steps + 1, N] float32 array, the sigmoid of the logits
+    after 0 .. steps steps for the N valid snippets, the videos in list order; "delta_norm": [steps, N] array of ||z_{k+1} - z_k||;
+    "scores_steps_device": the first one as a device tensor; "row_offsets": int64 array of len(videos) + 1 offsets into N}}.  The
+    host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError otherwise); it does not combine with
+    `similarity`, `row_outputs` or `attn_maps`."""
     on_gpu = torch.device(device).type == 'cuda'
+    if (steps is not None or trajectory) and not hasattr(model, 'set_steps'):
+        raise ValueError('steps= and trajectory=True need a model with set_steps (iefvad_amd.MMFMIL)')
+    if trajectory:
+        if similarity or row_outputs is not None or (attn_maps is not None and attn_maps is not False):
+            raise ValueError('trajectory=True does not combine with similarity, row_outputs or attn_maps')
+        if not on_gpu:
+            raise ValueError('trajectory=True needs a HIP device')
     from .model import _row_output_keys, attn_map_layers
     row_keys = _row_output_keys(row_outputs)
     attn_layers = ()
@@ -917,6 +943,9 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     elif ragged and not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos')):
         raise ValueError("ragged=True needs a HIP device, batch_chunks > 0 and a model with forward_videos")
     use_list = bool(ragged and host_list and hasattr(model, 'forward_videos_host'))
+    if trajectory and use_list:
+        raise ValueError('trajectory=True is not served by the host-list walk (iefvad_forward_videos_host has no trajectory entry): '
+                         'pass host_list=False for the forward_videos loop')
     # staging buffers are pinned allocations: they live with the lane (model object) across calls, not with the call
     stagers = [None] * nl
     for k, m in enumerate(models if on_gpu else ()):
@@ -933,21 +962,45 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         sink.dev_rows = {k: [] for k in row_keys}
     if attn_layers:
         sink.dev_rows = {"image_attn": [], "event_attn": []}
+    if trajectory:
+        sink.dev_traj = []
     with torch.no_grad():
         for s in streams if nl > 1 else ():
             s.wait_stream(torch.cuda.current_stream(device))         # e.g. a `model.to(device)` still in flight
-        if use_list:
-            _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, sim_rows,
-                             row_keys)
-        elif ragged:
-            _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys,
-                             attn_layers)
-        else:
-            _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                          bool(similarity))
+        prev_steps = getattr(model, '_steps', None)
+        if steps is not None:
+            model.set_steps(steps)
+        try:
+            if use_list:
+                _score_rows_list(model, test_loader, sink, maxlen, dataset, label_map, batch_chunks, host_list_bytes, wire_bf16, sim_rows,
+                                 row_keys)
+            elif ragged:
+                _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys,
+                                 attn_layers, trajectory)
+            else:
+                _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
+                              bool(similarity), trajectory)
+            nsteps = getattr(model, 'steps', 0)
+        finally:
+            if steps is not None:
+                model.set_steps(prev_steps)
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
-        if attn_layers:
+        if trajectory:
+            # the slots of every forward side by side, then the valid ones in video order (the padded route leaves gaps)
+            valid = sum(n for _, n in sink.spans)
+            if sink.dev_traj:
+                ls, dn = (torch.cat([t[i] for t in sink.dev_traj], dim=1) for i in (0, 1))
+                if valid != sink.total:
+                    idx = torch.from_numpy(np.concatenate([np.arange(o, o + n, dtype=np.int64) for o, n in sink.spans])).to(ls.device)
+                    ls, dn = ls[:, idx], dn[:, idx]
+            else:
+                ls, dn = torch.zeros(nsteps + 1, 0, device=device), torch.zeros(nsteps, 0, device=device)
+            sc = torch.sigmoid(ls).contiguous()
+            score_loader.last_result = {"trajectory": {
+                "scores_steps": sc.cpu().numpy(), "delta_norm": dn.cpu().numpy(), "scores_steps_device": sc,
+                "row_offsets": np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)}}
+        elif attn_layers:
             offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
             image, event = (v[0] if len(v) == 1 else torch.cat(v, dim=1) if v else torch.zeros(len(attn_layers), 0, maxlen, device=device)
                             for v in (sink.dev_rows["image_attn"], sink.dev_rows["event_attn"]))
@@ -1264,7 +1317,7 @@ def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 
 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
-              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None):
+              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None, steps=None, trajectory=False):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
@@ -1280,7 +1333,14 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     `attn_maps` (True or encoder layer indices): passed on to `score_loader(attn_maps=...)` -- the `forward_videos` loop, 64 chunks per
     call with `batch_chunks` unset, as for "rows" -- and the result dict gains "attn_maps" (device tensors, see there).  It does not
     combine with vis=True (ValueError: the vis routes collect the similarity series).  `attn=True` is unrelated: it keeps returning the
-    reference's empty list."""
+    reference's empty list.
+    `steps`: the evaluation runs only the first `steps` refinement blocks (`score_loader(steps=...)`).  `trajectory=True`: one walk
+    gives the whole ablation -- `score_loader(trajectory=True)` on the per-video route or the `forward_videos` loop -- and the result
+    dict gains "trajectory" (see there), "auc_steps" and "ap_steps": the global AUC / AP of the scores after k = 0 .. steps steps, by
+    the metric tail in use (sklearn, or `iefvad_auc_ap`).  Entry k is what a `steps=k` evaluation returns; nothing more is printed.  It
+    does not combine with vis=True or `attn_maps`."""
+    if trajectory and (vis or (attn_maps is not None and attn_maps is not False)):
+        raise ValueError("trajectory=True does not combine with vis=True or attn_maps")
     if metric_tail not in ("host", "device"):
         raise ValueError('metric_tail must be "host" or "device"')
     if vis_route not in ("padded", "rows"):
@@ -1303,7 +1363,8 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     # vis=True: the same loop with the four similarity series collected on the device (`score_loader(similarity=True)`, a last result)
     got = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks, lanes=lanes,
                        return_device=metric_tail == "device", similarity="rows" if vis_rows else bool(vis),
-                       **(dict(attn_maps=attn_maps) if want_maps else {}))
+                       **(dict(attn_maps=attn_maps) if want_maps else {}), **(dict(steps=steps) if steps is not None else {}),
+                       **(dict(trajectory=True, host_list=False) if trajectory else {}))
     scores, classes, wi, we = got[:4]
     if metric_tail == "device":
         res = evaluate_scores_device((got[4], [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
@@ -1314,6 +1375,15 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     last = dict(res, scores=scores, classes=classes, w_i_mean=wi, w_e_mean=we)
     if want_maps:
         last["attn_maps"] = score_loader.last_result["attn_maps"]
+    if trajectory:
+        tr = last["trajectory"] = score_loader.last_result["trajectory"]
+        if metric_tail == "device":
+            pairs = [device_auc_ap(row, gt) for row in tr["scores_steps_device"]]
+        else:       # the calls of evaluate_scores (test.py:158-159) on each step's scores
+            from sklearn.metrics import average_precision_score, roc_auc_score
+            pairs = [(roc_auc_score(gt, np.repeat(row.tolist(), 16)), average_precision_score(gt, np.repeat(row.tolist(), 16)))
+                     for row in tr["scores_steps"]]
+        last["auc_steps"], last["ap_steps"] = [p[0] for p in pairs], [p[1] for p in pairs]
     if vis:
         last["similarity"] = got[-1]
         last["vis_files"] = draw_vis(vis_series(last, gt, vis_flavour), os.path.join('vis', str(args.exp_name)),      # test.py:59-62
@@ -1325,7 +1395,7 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
          batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded",
-         *, attn_maps=None):
+         *, attn_maps=None, steps=None, trajectory=False):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
@@ -1335,25 +1405,31 @@ def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, 
     through the library on the device-resident scores (`evaluate_scores_device`) instead of sklearn on the host.
     `vis_route="rows"` (opt-in, here and in `ucf_test` / `xd_test`): a vis=True evaluation on the valid-row routes (`_run_test`).
     `attn_maps=` (keyword-only, here and in `ucf_test` / `xd_test`): the encoder's head-averaged attention maps of every valid snippet
-    in `last_result["attn_maps"]` (`_run_test`, `score_loader`); `attn=True` keeps returning the reference's empty list."""
+    in `last_result["attn_maps"]` (`_run_test`, `score_loader`); `attn=True` keeps returning the reference's empty list.
+    `steps=` / `trajectory=True` (keyword-only, here and in `ucf_test` / `xd_test`): evaluate with the first `steps` refinement blocks
+    only / add the per-step scores, update norms and "auc_steps", "ap_steps" to `last_result` from the one walk (`_run_test`)."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
-                                      False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route, attn_maps=attn_maps)
+                                      False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route, attn_maps=attn_maps, steps=steps,
+                                      trajectory=trajectory)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
-             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None):
+             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
+             steps=None, trajectory=False):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
-                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route, attn_maps)
+                                          ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route, attn_maps, steps,
+                                          trajectory)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
-            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None):
+            batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
+            steps=None, trajectory=False):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -1361,7 +1437,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
     if label_map is None:
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
-                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps)
+                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps, steps, trajectory)
     test.last_result = xd_test.last_result
     return ret
 

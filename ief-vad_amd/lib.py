@@ -37,7 +37,9 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_forward_videos_host_similarity", "iefvad_videos_full_workspace_bytes", "iefvad_forward_videos_full",
            "iefvad_forward_videos_host_full", "iefvad_forward_attn", "iefvad_forward_videos_attn",
            "iefvad_gemm_split_small_unit", "iefvad_gemm_split_small_launches", "iefvad_set_batch_invariant",
-           "iefvad_train_backward_inputs", "iefvad_forward_perturbed", "iefvad_forward_videos_perturbed", "iefvad_perturb_rows"]
+           "iefvad_train_backward_inputs", "iefvad_forward_perturbed", "iefvad_forward_videos_perturbed", "iefvad_perturb_rows",
+           "iefvad_set_steps", "iefvad_trajectory_workspace_bytes", "iefvad_forward_trajectory", "iefvad_videos_trajectory_workspace_bytes",
+           "iefvad_forward_videos_trajectory"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -89,6 +91,11 @@ class Outputs(C.Structure):
 class AttnMaps(C.Structure):
     """iefvad_attn_maps (include/iefvad.h): device fp32 maps per layer, 0 where a layer is not asked for."""
     _fields_ = [("image", _fp * MAX_LAYERS), ("event", _fp * MAX_LAYERS)]
+
+
+class Trajectory(C.Structure):
+    """iefvad_trajectory (include/iefvad.h): device fp32 [steps + 1, stride] logits and [steps, stride] update norms (0 = not asked for)."""
+    _fields_ = [("logits_steps", _fp), ("delta_norm", _fp), ("stride", C.c_size_t)]
 
 
 class Perturb(C.Structure):
@@ -289,6 +296,17 @@ def load_library() -> C.CDLL:
     lib.iefvad_gemm_split_small_launches.restype = C.c_uint64
     lib.iefvad_set_batch_invariant.argtypes = [C.c_void_p, C.c_int]
     lib.iefvad_set_batch_invariant.restype = C.c_int
+    lib.iefvad_set_steps.argtypes = [C.c_void_p, C.c_int32]
+    lib.iefvad_set_steps.restype = C.c_int
+    # the trajectory entries: `const iefvad_trajectory*` in front of the stream
+    lib.iefvad_trajectory_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]
+    lib.iefvad_trajectory_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_trajectory.argtypes = lib.iefvad_forward.argtypes[:8] + [C.POINTER(Trajectory), C.c_void_p]
+    lib.iefvad_forward_trajectory.restype = C.c_int
+    lib.iefvad_videos_trajectory_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    lib.iefvad_videos_trajectory_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_videos_trajectory.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(Trajectory), C.c_void_p]
+    lib.iefvad_forward_videos_trajectory.restype = C.c_int
     lib.iefvad_split_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.iefvad_split_bf16x3.restype = C.c_int
     lib.iefvad_split_bf16x3_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

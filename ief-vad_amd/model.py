@@ -57,6 +57,7 @@ _ROW_ENTRIES = {
     "_scaled": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
     "_perturbed": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
     "_attn": ("", lambda r: (), lambda r: (*r["vectors"], r["maps"], r["stream"])),
+    "_trajectory": ("_trajectory", lambda r: (), lambda r: (*r["vectors"], r["traj"], r["stream"])),
 }
 
 
@@ -372,6 +373,12 @@ class MMFMIL(nn.Module):
                    call costs more than in the default mode.  Accepted and inert with "f32" and "bf16" (already invariant); ValueError
                    with "fp16x3".  Carried by `lanes(n)`; training is not affected.
 
+    The K-step refinement at call time (not in the reference, whose K is fixed at construction):
+      set_steps(k)  every evaluation call runs only the first k of the K refinement blocks, then the classifier (`iefvad_set_steps`) --
+                   bit for bit what a model built with num_refinement_steps = k and given the first k blocks returns.  `None` restores K.
+      trajectory=True  (`forward`, `forward_videos`) adds `logits_steps` (the logits after 0 .. steps steps) and `delta_norm`
+                   (||z_{k+1} - z_k|| per step) from the one forward; every other result keeps its bits.
+
     Without any keyword (the reference's behaviour, imf_vad.py:40-44,109-161 being an ordinary nn.Module):
       gradients of the features  a feature tensor with `requires_grad=True` receives its `.grad` from `loss.backward()`, in its own dtype
                    and shape, in train() and in eval() alike -- an adapter or a learned projection upstream of the model trains, and
@@ -414,6 +421,7 @@ class MMFMIL(nn.Module):
         self.compute = compute
         self.graph_chunks = graph_chunks
         self.batch_invariant = bool(batch_invariant)
+        self._steps: Optional[int] = None      # set_steps: None = all K refinement steps
         self._handle: Optional[C.c_void_p] = None
         self._handle_key = None
         self._weights_sig = None
@@ -470,6 +478,26 @@ class MMFMIL(nn.Module):
                 rc = lib.iefvad_set_batch_invariant(h, 1)
             if rc != 0:
                 raise RuntimeError("iefvad_set_batch_invariant: " + _lib.last_error())
+        if self._steps is not None and lib.iefvad_set_steps(h, int(self._steps)) != 0:
+            raise RuntimeError("iefvad_set_steps: " + _lib.last_error())
+
+    @property
+    def steps(self) -> int:
+        """Refinement steps an evaluation call runs: K, or what `set_steps` chose."""
+        return self.temporal.num_refinement_steps if self._steps is None else self._steps
+
+    def set_steps(self, k: Optional[int]):
+        """Run only the first `k` of the K refinement blocks in every evaluation call (`iefvad_set_steps`): 0 <= k <= K, `None` restores K.
+        The results are bit for bit those of a model built with num_refinement_steps = k that was given the first k blocks.  Carried to
+        the lanes of `lanes(n)`.  model.train() forwards refuse a model whose count is not K (RuntimeError from the library)."""
+        K = self.temporal.num_refinement_steps
+        if k is not None:
+            if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= K:
+                raise ValueError(f"set_steps takes None or an integer in 0..{K} (the model's num_refinement_steps), got {k!r}")
+        for m in [self] + list(self.__dict__.get("_lane_copies", [])):
+            m._steps = k
+            if m._handle is not None and _lib.load_library().iefvad_set_steps(m._handle, K if k is None else int(k)) != 0:
+                raise RuntimeError("iefvad_set_steps: " + _lib.last_error())
 
     def _ensure_weights(self, device: torch.device, stream: int):
         t = self.temporal
@@ -560,7 +588,8 @@ class MMFMIL(nn.Module):
         return x.contiguous()
 
     def forward(self, img_visual, ev_visual, padding_mask=None, text=None, lengths=None, return_attn=False,
-                *, timed: bool = False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None, noise_rows=None) -> Dict[str, torch.Tensor]:
+                *, timed: bool = False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None, noise_rows=None,
+                trajectory: bool = False) -> Dict[str, torch.Tensor]:
         """The reference's call (imf_vad.py:40-44; `padding_mask`, `text`, `lengths`, `return_attn` accepted and ignored as there).
         Keyword-only extras: `timed` (per-stage device times in `last_stage_times`), `row_scale=(s_img, s_ev)`: fp32 DEVICE vectors
         of [B*T] (either may be None) that multiply the input rows inside the library's input load (`iefvad_forward_scaled`: the
@@ -576,8 +605,24 @@ class MMFMIL(nn.Module):
         this package's own ("parity unpinned").  `row_noise` without `noise_seed`, with `timed`, `attn_maps`, model.train() or features
         that require grad raises ValueError.
         In eval() with grad enabled, a feature tensor that requires grad makes the call differentiable (the train-mode forward with every
-        dropout probability forced to 0, the class docstring's keyword-free section); the three extras raise ValueError there."""
+        dropout probability forced to 0, the class docstring's keyword-free section); the three extras raise ValueError there.
+        `trajectory=True` (`iefvad_forward_trajectory`) adds `logits_steps`, [steps + 1, B, T, 1]: c . z_k + b_c for the states z_0 ..
+        z_steps of the refinement (logits; apply the sigmoid), and `delta_norm`, [steps, B, T]: ||z_{k+1} - z_k||_2 = lambda ||r_k||, with
+        steps = `self.steps`.  Row k of `logits_steps` is what `set_steps(k)` returns as `logits`; every other result keeps its bits.
+        compute="bf16" runs such a call with two GEMM launches per step in place of its one chain kernel (same bits, slower).  It combines
+        with none of `timed`, `attn_maps`, `row_scale`, `row_noise` and features that require grad (ValueError), and not with model.train()
+        (RuntimeError)."""
         self._noise_code()   # ValueError for an unsupported noise_model, as the reference raises
+        if trajectory:
+            grad = torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad)
+            asked = [n for n, on in (("timed=True", timed), ("attn_maps=", attn_maps is not None and attn_maps is not False),
+                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
+                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise)),
+                                     ("features that require grad", grad)) if on]
+            if asked:
+                raise ValueError(f"trajectory=True does not combine with {' / '.join(asked)}: iefvad_forward_trajectory is a plain evaluation forward")
+            if self.training:
+                raise RuntimeError("trajectory=True is an evaluation request; it is not available under model.train() (call model.eval() first)")
         layers = attn_map_layers(attn_maps, self.temporal.num_layers)
         noisy = row_noise is not None and any(v is not None for v in row_noise)
         if noisy:
@@ -624,7 +669,7 @@ class MMFMIL(nn.Module):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._ensure_handle(device)
             self._ensure_weights(device, stream)
-            need = lib.iefvad_workspace_bytes(self._handle, B)
+            need = lib.iefvad_trajectory_workspace_bytes(self._handle, B) if trajectory else lib.iefvad_workspace_bytes(self._handle, B)
             if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
                 self._workspace = None
                 self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
@@ -649,7 +694,16 @@ class MMFMIL(nn.Module):
                 o.w_i_mean, o.w_e_mean = res["w_i_mean"].data_ptr(), res["w_e_mean"].data_ptr()
             args = (self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], B,
                     C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), C.byref(o), C.c_void_p(stream))
-            if layers:
+            if trajectory:
+                steps = self.steps
+                ls = torch.empty(steps + 1, B, T, 1, **f32)
+                dn = torch.empty(steps, B, T, **f32)
+                traj = _lib.Trajectory(ls.data_ptr(), dn.data_ptr() if steps else None, N)
+                rc = lib.iefvad_forward_trajectory(*args[:8], C.byref(traj), args[8])
+                if rc != 0:
+                    raise RuntimeError("iefvad_forward_trajectory: " + _lib.last_error())
+                res["logits_steps"], res["delta_norm"] = ls, dn
+            elif layers:
                 res["image_attn"] = torch.empty(len(layers), B, T, T, **f32)
                 res["event_attn"] = torch.empty(len(layers), B, T, T, **f32)
                 res["attn_layers"] = layers
@@ -678,7 +732,8 @@ class MMFMIL(nn.Module):
             if rc != 0:
                 raise RuntimeError("iefvad_forward: " + _lib.last_error())
         if self.outputs == "full":
-            return {k: res[k] for k in OUTPUT_KEYS + (("image_attn", "event_attn", "attn_layers") if layers else ())}   # the reference's key order
+            extra = ("image_attn", "event_attn", "attn_layers") if layers else ("logits_steps", "delta_norm") if trajectory else ()
+            return {k: res[k] for k in OUTPUT_KEYS + extra}   # the reference's key order
         return res
 
     def _attn_maps_served(self, mode):
@@ -745,7 +800,13 @@ class MMFMIL(nn.Module):
             f32 = dict(dtype=torch.float32, device=device)
             res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
             r = {"vectors": tuple(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), "stream": C.c_void_p(stream), "out": None,
-                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0, "maps": None}
+                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0, "maps": None, "traj": None}
+            if suffix == "_trajectory":
+                steps = self.steps
+                res["logits_steps"] = torch.empty(steps + 1, total, **f32)
+                res["delta_norm"] = torch.empty(steps, total, **f32)
+                traj = _lib.Trajectory(res["logits_steps"].data_ptr(), res["delta_norm"].data_ptr() if steps else None, total)
+                r["traj"] = C.byref(traj)
             if suffix == "_attn":
                 T = self.visual_length
                 res["image_attn"] = torch.empty(len(attn_layers), total, T, **f32)
@@ -815,7 +876,7 @@ class MMFMIL(nn.Module):
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
                        weight_sums: bool = False, similarity: bool = False, outputs=None, attn_maps=None, row_noise=None, noise_seed=None,
-                       noise_rows=None) -> Dict[str, torch.Tensor]:
+                       noise_rows=None, trajectory: bool = False) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
@@ -842,7 +903,21 @@ class MMFMIL(nn.Module):
         over the T keys of its chunk (columns >= the chunk's valid rows hold the weight of a pad key, as on the padded route); the other
         three results keep their bits.  It combines with none of `similarity`, `outputs`, `row_scale`, `weight_sums` and
         nan_to_num="always" (ValueError); compute="bf16" and model.train() raise RuntimeError.
+        `trajectory=True` (`iefvad_forward_videos_trajectory`) adds `logits_steps`, [steps + 1, sum(lengths)], and `delta_norm`,
+        [steps, sum(lengths)], as `forward` does, in packed order, valid rows only; the other three results keep their bits.  It combines
+        with none of `attn_maps`, `row_scale`, `row_noise`, `similarity`, `outputs`, `weight_sums` and nan_to_num="always" (ValueError);
+        model.train() raises RuntimeError.
         An evaluation entry: nothing it returns is differentiable (rows that require grad get no gradient here; use `forward`)."""
+        if trajectory:
+            asked = [n for n, on in (("attn_maps=", attn_maps is not None and attn_maps is not False),
+                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
+                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise)),
+                                     ("similarity=True", similarity), ("outputs=", outputs is not None), ("weight_sums=True", weight_sums),
+                                     ("nan_to_num='always'", isinstance(nan_to_num, str) and nan_to_num == "always")) if on]
+            if asked:
+                raise ValueError(f"trajectory=True does not combine with {' / '.join(asked)}: iefvad_forward_videos_trajectory takes none of them")
+            if self.training:
+                raise RuntimeError("trajectory=True is an evaluation request; it is not available under model.train() (call model.eval() first)")
         layers = attn_map_layers(attn_maps, self.temporal.num_layers)
         if layers:
             if similarity or outputs is not None or weight_sums or nan_to_num == "always" or \
@@ -877,6 +952,8 @@ class MMFMIL(nn.Module):
         wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_full", extras)
         if layers:
             suffix = "_attn"
+        if trajectory:
+            suffix = "_trajectory"
         pert = None
         if noisy:
             pert, _ = _perturb_struct(nrows, img_rows.device, row_scale, row_noise, noise_seed, noise_rows, "sum of lengths")

@@ -747,6 +747,40 @@ uint64_t iefvad_gemm_split_small_launches(void);
  * keep their own kernel rule and are not affected.  Not thread-safe against calls on the same handle.  IEFVAD_ABI_VERSION stays. */
 int iefvad_set_batch_invariant(iefvad_handle* h, int on);
 
+/* Call-time step count: every EVALUATION entry of the handle (dense, scaled, perturbed, attn, the whole-video entries, the host
+ * lists) runs refinement blocks 0 .. steps - 1 of the handle's cfg.num_steps, then the classifier.  0 <= steps <= cfg.num_steps;
+ * the default is cfg.num_steps; a value outside the range is refused by name and changes nothing.  The results are, bit for bit,
+ * those of a handle created with num_steps = steps that was given the first `steps` blocks -- both launch the same kernels on the
+ * same data (IEFVAD_COMPUTE_BF16: the chain kernel reads a prefix of its packed stream; IEFVAD_COMPUTE_BF16X6: the folded scorer's
+ * vector exists for every block).  Cached hipGraphs are keyed by the count.  iefvad_train_forward refuses a handle whose count is
+ * not cfg.num_steps.  Makes no HIP call.  Not thread-safe against calls on the same handle.  IEFVAD_ABI_VERSION stays. */
+int iefvad_set_steps(iefvad_handle* h, int32_t steps);
+
+/* ---- the refinement trajectory -------------------------------------------------------------------------------------
+ * One forward, and per snippet the whole K-step iteration z_{k+1} = z_k - lambda (W2_k relu(W1_k z_k + b1_k) + b2_k):
+ *   logits_steps[k * stride + r] = c . z_k + b_c          k = 0 .. steps      (logits: the caller applies the sigmoid)
+ *   delta_norm[k * stride + r]   = ||z_{k+1} - z_k||_2    k = 0 .. steps - 1  (= lambda ||r_k||, the convergence diagnostic)
+ * with steps the handle's current count (iefvad_set_steps) and r the row of the call: b T + t (dense) or the packed row (whole
+ * videos; valid rows only, no padding is computed or written).  `stride` is the number of ELEMENTS between two steps, at least the
+ * call's rows.  Either pointer may be null, not both; device pointers, 4-byte aligned.  Row k of logits_steps is what a
+ * steps = k call returns as `logits` (the same bits wherever that call uses the plain scorer; row `steps` is this call's logits).
+ * Every other output of the call has the bits of the same call without a trajectory.  Cost: one HBM-bound row kernel per state
+ * (iefvad_step_probe_kernel, csrc/trajectory.h) and a second [rows, D] fp32 state buffer behind the base workspace -- use the
+ * _trajectory_workspace_bytes queries.  IEFVAD_COMPUTE_BF16 runs a trajectory pass on its launch-per-projection route (2 K GEMM
+ * launches in place of the one chain kernel; the same bits, slower); IEFVAD_COMPUTE_BF16X6 stores h of the last step and forms
+ * z_steps as a call that returns `fused` does.  Direct launches (no hipGraph).  Null-argument and range checks come before the
+ * first launch.  Added without a change to any other entry: IEFVAD_ABI_VERSION stays. */
+typedef struct iefvad_trajectory { float* logits_steps; float* delta_norm; size_t stride; } iefvad_trajectory;
+size_t iefvad_trajectory_workspace_bytes(const iefvad_handle* h, int32_t B);
+int iefvad_forward_trajectory(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                              size_t workspace_bytes, const iefvad_outputs* out, const iefvad_trajectory* trajectory, void* stream);
+/* Mirrors iefvad_forward_videos: [steps + 1, stride] and [steps, stride] in packed order. */
+size_t iefvad_videos_trajectory_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos);
+int iefvad_forward_videos_trajectory(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                     const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                     size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                     const iefvad_trajectory* trajectory, void* stream);
+
 /* The exact three-term bf16 split of n fp32 values (n % 4 == 0): planes[0..n) = bf16(x),
  * planes[n..2n) = bf16(x - p0), planes[2n..3n) = bf16(x - p0 - p1), round-to-nearest-even; x == p0 + p1 + p2
  * for finite x.  What iefvad_set_weights applies to every projection matrix in IEFVAD_COMPUTE_BF16X6. */
