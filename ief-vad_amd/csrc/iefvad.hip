@@ -46,6 +46,7 @@
 #include "metrics.h"
 #include "similarity.h"
 #include "trajectory.h"
+#include "variants.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -1022,6 +1023,19 @@ struct TrajOut {
     bool any() const { return logits_steps || delta_norm; }
 };
 
+// The fusion ablations a call asked for (include/iefvad.h, csrc/variants.h): the [count, stride] logits of the whole CALL; a pass writes
+// columns row0 + packed row of the pass.  ws: the stacked state [count, R, D], its h scratch of the same size and the [count, R]
+// logits of a pass (variants_bytes), behind everything else of the workspace; set by the entry.
+struct VarOut {
+    int count;
+    int kind[IEF_MAX_VARIANTS];
+    float* logits;
+    long long stride, row0;
+    float* ws;
+    bool any() const { return logits != nullptr; }
+};
+static size_t variants_bytes(size_t pass_chunks, int D, int count) { return (size_t)count * pass_chunks * IEF_T * (2 * (size_t)D + 1) * sizeof(float); }
+
 enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 struct VideosOut {
     float* logits;                   // [rows] each
@@ -1039,6 +1053,7 @@ struct VideosOut {
     // iefvad_rows_out_wide_kernel copies the valid rows out (pass_rows_out).
     float* wide[ROWS_OUT_WIDE_MAX];
     AttnMaps attn;                   // iefvad_forward_videos_attn: the packed [rows, 256] maps, written inside the encoder (pass_encoder_layer)
+    VarOut var;                      // iefvad_forward_videos_variants: the ablations' logits; keeps its base and takes its column from row0
     TrajOut traj;                    // iefvad_forward_videos_trajectory: the per-step series; like the similarity series it keeps its base and takes its column from row0
     long long row0;                  // packed row of the call's list (the host entries: of the whole list) that this view's first row is
     int nan_mode;                    // 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 = every video and modality (test2.py:59-60)
@@ -1057,6 +1072,7 @@ struct VideosOut {
             if (wide[t]) o.wide[t] += rows * D;
         o.attn = attn.at(rows);
         o.traj.row0 += rows;
+        o.var.row0 += rows;
         o.row0 += rows;
         return o;
     }
@@ -1356,10 +1372,11 @@ static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass*
 // entries) or reduces it to the similarity series (fused and both mu) before it ends -- then it stays in the workspace alias of
 // pass_buffers.  Kernel selection does not look at these.
 struct TailKeep { bool fused, mu_i, mu_e, lv_i, lv_e; };
-static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg) {
+static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg, const VarOut* vo) {
     auto rows = [&](int t, bool in_series) { return rg && (rg->out.wide[t] || (in_series && rg->out.similarity)); };
-    return TailKeep{out->fused || rows(kWideFused, true), out->image_mu || rows(kWideMuI, true), out->event_mu || rows(kWideMuE, true),
-                    out->image_logvar || rows(kWideLvI, false), out->event_logvar || rows(kWideLvE, false)};
+    const bool heads = vo != nullptr;         // the ablations re-form z0 from all four head tensors (pass_variants)
+    return TailKeep{out->fused || rows(kWideFused, true), out->image_mu || rows(kWideMuI, true) || heads, out->event_mu || rows(kWideMuE, true) || heads,
+                    out->image_logvar || rows(kWideLvI, false) || heads, out->event_logvar || rows(kWideLvE, false) || heads};
 }
 
 // The probe of state z_k of a trajectory pass (trajectory.h): k = 0 behind the fusion, k = j + 1 behind step j.  `copy_logits`: entry k
@@ -1380,11 +1397,15 @@ static int pass_step_probe(iefvad_handle* h, const PassBuffers& b, const RaggedP
     });
 }
 
+static int pass_refine_score(iefvad_handle* h, PassBuffers& b, const RaggedPass* rg, const TrajOut* tj, bool chain, bool keep_fused, hipStream_t stream,
+                             Timer& tm);
+
 // 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer.  K is the handle's current step count
 // (iefvad_set_steps): blocks 0 .. K - 1 run.  `tj` (nullable): the pass records its trajectory -- a probe launch behind the fusion and
 // behind every step; the state must then pass through HBM between steps, so the bf16 arithmetic takes its launch-per-projection
 // route (bit-identical to the chain kernel) and the folded bf16x6 tail forms z_K as a pass that keeps `fused` does.
-static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, const TrajOut* tj, hipStream_t stream, Timer& tm) {
+static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, const TrajOut* tj, const VarOut* vo,
+                     hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const int D = h->D, L = c.num_layers, K = h->steps, rows = b.rows;
@@ -1395,10 +1416,9 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     ProjCtx px = proj_ctx(h, b, stream, tm);
     px.use_split = b.tail_split;
 
-    const bool chain = b.chain && !tj, fold = b.fold;
-    const TailKeep keep = tail_keep(out, rg);
+    const bool chain = b.chain && !tj;
+    const TailKeep keep = tail_keep(out, rg, vo);
     const bool keep_fused = keep.fused || tj;
-    const float* const score_fold = score_fold_of(h, K);
     // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
     if (b.heads_rows) {
         HeadsChainArgs ha;
@@ -1439,6 +1459,24 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
 
     if (tj)
         if (int rc = pass_step_probe(h, b, rg, *tj, 0, K, false, stream, tm)) return rc;
+    return pass_refine_score(h, b, rg, tj, chain, keep_fused, stream, tm);
+}
+
+// 4 - 5 of the tail on the state b.z of b.rows rows (scratch b.hbuf / b.hb / b.zb, partial sums in the y region, logits to b.logits),
+// with the kernels b's TailFlags name: the call's own tail (pass_tail), and once more the stacked states of its fusion ablations
+// (pass_variants).  chain: the bf16 chain kernel takes steps and scorer; keep_fused: z_K is wanted, not the logits alone.
+static int pass_refine_score(iefvad_handle* h, PassBuffers& b, const RaggedPass* rg, const TrajOut* tj, bool chain, bool keep_fused, hipStream_t stream,
+                             Timer& tm) {
+    const iefvad_config& c = h->cfg;
+    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
+    const int D = h->D, K = h->steps, rows = b.rows;
+    const bool d512 = h->D == IEF_D512;
+    const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
+    float* const z = b.z;
+    ProjCtx px = proj_ctx(h, b, stream, tm);
+    px.use_split = b.tail_split;
+    const bool fold = b.fold;
+    const float* const score_fold = score_fold_of(h, K);
 
     if (chain)
         if (int rc = launch_refine_chain(h, z, keep_fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
@@ -1526,27 +1564,67 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
     return 0;
 }
 
+// 7. the fusion ablations of a pass (variants.h), behind its own results: the variants' z0 from the kept mu / logvar of the row set,
+// stacked as ONE row set of count x rows rows behind the workspace, then steps 4 - 5 on it with the kernels plan_tail names for that
+// row count (bf16: one chain launch where the rule says chain; bf16x6 on the split kernels: a scores-only tail with the folded
+// scorer; f32: the fp32 tilings, bit-identical to each other), then the valid rows' logits to the call's [count, stride] result.
+static int pass_variants(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const VarOut& vo, hipStream_t stream, Timer& tm) {
+    const iefvad_config& c = h->cfg;
+    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
+    const bool d512 = h->D == IEF_D512;
+    const int V = vo.count, rows = b.rows;
+    const size_t n = (size_t)V * b.R * h->D;
+    PassBuffers s = b;
+    s.rows = V * rows;
+    s.z = vo.ws;
+    s.hbuf = vo.ws + n;
+    s.hb = (bf16_t*)s.hbuf; s.zb = s.hb + (size_t)V * rows * h->D;
+    s.logits = vo.ws + 2 * n;
+    static_cast<TailFlags&>(s) = plan_tail(h->policy, c.compute, s.rows, h->steps, b.splitmb, b.compacted, h->heads_stream != nullptr,
+                                           h->chain_stream != nullptr);
+    VariantArgs va;
+    memset(&va, 0, sizeof(va));
+    va.mu_i = b.mu_i; va.lv_i = b.lv_i; va.mu_e = b.mu_e; va.lv_e = b.lv_e;
+    va.z = s.z;
+    va.zb = (bf && !s.chain) ? s.zb : nullptr;
+    va.nrows = rows; va.count = V;
+    for (int v = 0; v < V; ++v) va.kind[v] = vo.kind[v];
+    va.factor = precision_factor(c); va.eps = c.epsilon;
+    if (int rc = dispatch_d(d512, [&](auto w) {
+            return launch(tm, ST_FUSION, iefvad_fusion_variants_kernel<decltype(w)::value>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, va);
+        })) return rc;
+    if (int rc = pass_refine_score(h, s, rg, nullptr, s.chain, false, stream, tm)) return rc;
+    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
+    const int valid_rows = rg ? rg->valid_rows : rows;
+    const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
+    return launch(tm, ST_SCORER, iefvad_variants_out_kernel, dim3(nslabs, V), dim3(256), 0, stream, (const float*)s.logits, rows, chunks, valid_rows, vo.logits,
+                  vo.stride, vo.row0);
+}
+
 // One micro-batch of `nb` chunks.  Dense (rg == nullptr): `in` holds the pass's [nb, 256, 768] blocks, `scale` their per-row scales
 // (kNoScale but for iefvad_forward_scaled), results go to `out` at row offset row0.  Ragged: `in` holds the pass's packed rows, the
 // chunks are built from them on the device, everything behind the encoder runs on the valid rows only, results go to rg->out (`out`
 // must be all-null, `scale` kNoScale: rg->out carries the packed scales).
 static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
                         const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr,
-                        const RowNoise* nz = nullptr, const TrajOut* tj = nullptr) {
+                        const RowNoise* nz = nullptr, const TrajOut* tj = nullptr, const VarOut* vo = nullptr) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
     if (rg) maps = &rg->out.attn;                 // a whole-video pass: the maps at the pass's first packed row
     if (rg) tj = rg->out.traj.any() ? &rg->out.traj : nullptr;
+    if (rg) vo = rg->out.var.any() ? &rg->out.var : nullptr;
     if (int rc = pass_load_inputs(h, b, in, scale, nz ? *nz : RowNoise{}, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
         if (int rc = pass_encoder_layer(h, b, l, rg, maps, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
-    if (int rc = pass_tail(h, b, out, rg, tj, stream, tm)) return rc;
-    return rg ? pass_rows_out(h, b, rg, stream, tm) : 0;
+    if (int rc = pass_tail(h, b, out, rg, tj, vo, stream, tm)) return rc;
+    if (rg)
+        if (int rc = pass_rows_out(h, b, rg, stream, tm)) return rc;
+    return vo ? pass_variants(h, b, rg, *vo, stream, tm) : 0;
 }
 
 static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
                         const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr, const RowNoise* nz = nullptr,
-                        const TrajOut* tj = nullptr) {
+                        const TrajOut* tj = nullptr, const VarOut* vo = nullptr) {
     const void* const img = in.img;
     const void* const ev = in.ev;
     const int32_t in_dtype = in.in_dtype;
@@ -1568,8 +1646,10 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
         const RowNoise pass_nz = nz ? nz->at((long long)row0) : RowNoise{};       // ids default to the row of the CALL: b T + t
         TrajOut pass_tj = tj ? *tj : TrajOut{};
         pass_tj.row0 = (long long)row0;
+        VarOut pass_vo = vo ? *vo : VarOut{};
+        pass_vo.row0 = (long long)row0;
         if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr, &pass_nz,
-                                  tj ? &pass_tj : nullptr))
+                                  tj ? &pass_tj : nullptr, vo ? &pass_vo : nullptr))
             return rc;
     }
     return 0;
@@ -2557,6 +2637,71 @@ extern "C" int iefvad_forward_videos_trajectory(iefvad_handle* h, const void* im
     if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
     VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
     if (int rc = trajectory_args(who, trajectory, rows, &out.traj)) return rc;
+    Timer tm;
+    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the fusion ablations (include/iefvad.h, csrc/variants.h)
+// ------------------------------------------------------------------------------------------------
+// The checks of a variants request that need no device
+static int variants_args(const char* who, const iefvad_handle* h, const iefvad_variants* v, long long rows, VarOut* vo) {
+    if (h->cfg.compute == IEFVAD_COMPUTE_FP16X3) return fail("%s: compute = FP16X3 is not supported (IEFVAD_COMPUTE_FP16X3 has no fusion variants)", who);
+    if (!v) return fail("%s: null variants", who);
+    if (!v->logits) return fail("%s: null variants logits", who);
+    if ((uintptr_t)v->logits & 3) return fail("%s: variants logits must be 4-byte aligned", who);
+    if (v->count < 1 || v->count > IEF_MAX_VARIANTS) return fail("%s: count %d outside 1..%d", who, v->count, IEF_MAX_VARIANTS);
+    *vo = VarOut{};
+    for (int i = 0; i < v->count; ++i) {
+        if (v->kind[i] < IEFVAD_VARIANT_FUSED || v->kind[i] > IEFVAD_VARIANT_EQUAL) return fail("%s: unknown variant kind %d at %d", who, v->kind[i], i);
+        for (int j = 0; j < i; ++j)
+            if (v->kind[j] == v->kind[i]) return fail("%s: variant kind %d is repeated (at %d and %d)", who, v->kind[i], j, i);
+        vo->kind[i] = v->kind[i];
+    }
+    if ((long long)v->stride < rows) return fail("%s: stride %zu is less than the call's %lld rows", who, v->stride, rows);
+    vo->count = v->count; vo->logits = v->logits; vo->stride = (long long)v->stride;
+    return 0;
+}
+
+extern "C" size_t iefvad_variants_workspace_bytes(const iefvad_handle* h, int32_t B, int32_t count) {
+    const size_t base = iefvad_workspace_bytes(h, B);
+    if (!base || count < 1 || count > IEF_MAX_VARIANTS) return 0;
+    const int mb = micro_batch(h);
+    return base + variants_bytes((size_t)(B < mb ? B : mb), h->D, count);
+}
+
+extern "C" int iefvad_forward_variants(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                                       size_t workspace_bytes, const iefvad_outputs* out, const iefvad_variants* variants, void* stream) {
+    static const char* const who = "iefvad_forward_variants";
+    if (!h) return fail("%s: null handle", who);
+    if (!img || !ev || !out) return fail("%s: null argument", who);
+    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
+    VarOut vo;
+    if (int rc = variants_args(who, h, variants, (long long)B * IEF_T, &vo)) return rc;
+    const size_t need = iefvad_variants_workspace_bytes(h, B, vo.count);
+    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    vo.ws = (float*)((char*)workspace + iefvad_workspace_bytes(h, B));
+    Timer tm;      // direct launches: the result's pointer is per call, a cached graph would pin its address
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, nullptr, nullptr, &vo);
+}
+
+extern "C" size_t iefvad_videos_variants_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t count) {
+    if (count < 1 || count > IEF_MAX_VARIANTS) return 0;
+    return videos_workspace_bytes(h, lengths, nvideos, false, false, false, count);
+}
+
+extern "C" int iefvad_forward_videos_variants(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                              const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                              size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                              const iefvad_variants* variants, void* stream) {
+    static const char* const who = "iefvad_forward_videos_variants";
+    if (!h) return fail("%s: null handle", who);
+    if (!lengths) return fail("%s: null argument", who);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    long long rows, chunks;
+    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    if (int rc = variants_args(who, h, variants, rows, &out.var)) return rc;
     Timer tm;
     return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
 }

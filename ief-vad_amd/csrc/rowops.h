@@ -151,14 +151,18 @@ __global__ __launch_bounds__(256) void iefvad_layernorm_kernel(LnArgs a) {
 //   w_m = factor * exp(-logvar_m) ; den = w_i + w_e + eps ; n_m = w_m / den ; z = n_i*mu_i + n_e*mu_e
 // The literal formula is kept (including its inf/inf = NaN behaviour for logvar < -88.7).
 // one element of the fusion; the literal operation order of the reference (shared with the heads row-block kernels)
-__device__ __forceinline__ void fuse_elem(float mi, float li, float me, float le, float factor, float eps,
-                                          float& ni, float& ne, float& z) {
-    const float wi = __fmul_rn(factor, expf(-li));
-    const float we = __fmul_rn(factor, expf(-le));
+// the weight-combination half: from the two precisions on (shared with the ablation kernel of variants.h, which substitutes into wi / we)
+__device__ __forceinline__ void fuse_weights(float wi, float we, float mi, float me, float eps, float& ni, float& ne, float& z) {
     const float den = __fadd_rn(__fadd_rn(wi, we), eps);
     ni = wi / den;
     ne = we / den;
     z = __fadd_rn(__fmul_rn(ni, mi), __fmul_rn(ne, me));
+}
+__device__ __forceinline__ void fuse_elem(float mi, float li, float me, float le, float factor, float eps,
+                                          float& ni, float& ne, float& z) {
+    const float wi = __fmul_rn(factor, expf(-li));
+    const float we = __fmul_rn(factor, expf(-le));
+    fuse_weights(wi, we, mi, me, eps, ni, ne, z);
 }
 
 struct FusionArgs {

@@ -84,12 +84,15 @@ static size_t videos_extra_bytes(const iefvad_handle* h, long long chunks, bool 
 static size_t videos_traj_bytes(const iefvad_handle* h, long long chunks) { return videos_pass_chunks(h, chunks) * IEF_T * (size_t)h->D * sizeof(float); }
 
 // the public workspace queries: 0 for arguments no call would accept
-static size_t videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, bool w_rows, bool colsum, bool traj = false) {
+static size_t videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, bool w_rows, bool colsum, bool traj = false,
+                                     int variants = 0) {
     if (!h || !lengths || nvideos <= 0) return 0;
     long long rows, chunks;
     if (videos_layout(lengths, nvideos, &rows, &chunks) || chunks > 0x7fffffffLL) return 0;
     const size_t base = iefvad_workspace_bytes(h, (int32_t)chunks);
-    return base ? base + videos_extra_bytes(h, chunks, w_rows, colsum) + (traj ? videos_traj_bytes(h, chunks) : 0) : 0;
+    return base ? base + videos_extra_bytes(h, chunks, w_rows, colsum) + (traj ? videos_traj_bytes(h, chunks) : 0) +
+                      (variants ? variants_bytes(videos_pass_chunks(h, chunks), h->D, variants) : 0)
+                : 0;
 }
 extern "C" size_t iefvad_videos_trajectory_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
     return videos_workspace_bytes(h, lengths, nvideos, false, false, true);
@@ -157,7 +160,8 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
     if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
     const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
     const size_t extra = videos_extra_bytes(h, total_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
-    const size_t need = base + extra + (out.traj.any() ? videos_traj_bytes(h, total_chunks) : 0);
+    const size_t traj_bytes = out.traj.any() ? videos_traj_bytes(h, total_chunks) : 0;
+    const size_t need = base + extra + traj_bytes + (out.var.any() ? variants_bytes(videos_pass_chunks(h, total_chunks), h->D, out.var.count) : 0);
     if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     if (((uintptr_t)workspace & 15) || ((uintptr_t)in.img & 15) || ((uintptr_t)in.ev & 15)) return fail("%s: buffers must be 16-byte aligned", who);
 
@@ -244,6 +248,7 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
         rg.out = out.at(row0, h->D);          // pass-relative, like src_row
         rg.out.nan_mode = nan_mode;
         if (out.traj.any()) rg.out.traj.z_prev = (float*)((char*)workspace + base + extra);
+        if (out.var.any()) rg.out.var.ws = (float*)((char*)workspace + base + extra + traj_bytes);      // the stacked states of the ablations, behind everything else
         rc = forward_pass(h, in.at((size_t)row0, h->D), kNoScale, nb, 0, workspace, &none, &rg, stream, tm);
         row0 += vrows;
     }

@@ -624,7 +624,8 @@ class _ScoreSink:
         self.total = 0
         self.dev_sim: Optional[List[torch.Tensor]] = None     # score_loader(similarity=True): per forward [4, valid snippets of its videos]
         self.dev_rows: Optional[Dict[str, List[torch.Tensor]]] = None   # score_loader(row_outputs=...): per key, per forward [valid snippets, D]
-        self.dev_traj: Optional[List[Tuple[torch.Tensor, torch.Tensor]]] = None   # score_loader(trajectory=True): per forward ([steps + 1, slots], [steps, slots])
+        # score_loader(trajectory=True): per forward ([steps + 1, slots], [steps, slots]); score_loader(fusion_variants=): per forward ([V, slots],)
+        self.dev_traj: Optional[List[Tuple[torch.Tensor, ...]]] = None
 
     def add(self, logits, wi, we, lens, stride=None, sim=None, rows=None, traj=None):
         """One forward's flat fp32 vectors over videos of `lens` snippets: back to back (the valid-row routes), or video i in
@@ -690,7 +691,7 @@ def _lane_stream(stream):
 
 
 def _score_padded(models, stagers, streams, loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                  similarity=False, trajectory=False):
+                  similarity=False, trajectory=False, variants=()):
     """Padded route (the only one on the CPU): `model(img, ev, ...)` on zero-padded chunks, one forward per video
     (batch_chunks <= 0) or per batch, which closes as soon as it holds `batch_chunks` chunks; forwards round-robin over the lanes.
     `_unpack_item` has applied the NaN rule in each tensor's own dtype; a mixed batch is widened while it is staged.
@@ -704,12 +705,14 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
             else:
                 img = torch.cat([p[0].to(dt) for p in pend], dim=0).to(device)
                 ev = torch.cat([p[1].to(dt) for p in pend], dim=0).to(device)
-            out = models[k](img, ev, None, None, None, **(dict(trajectory=True) if trajectory else {}))
+            out = models[k](img, ev, None, None, None, **(dict(trajectory=True) if trajectory else dict(fusion_variants=variants) if variants else {}))
             logits = out['logits'].reshape(-1)
             traj = None
             if trajectory:
                 ls = out['logits_steps']
                 traj = (ls.reshape(ls.shape[0], -1), out['delta_norm'].reshape(ls.shape[0] - 1, -1))
+            if variants:
+                traj = (out['logits_variants'].reshape(len(variants), -1),)
             if 'w_i_mean' in out:
                 wi, we = out['w_i_mean'].reshape(-1), out['w_e_mean'].reshape(-1)
             else:
@@ -745,7 +748,7 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
 
 
 def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=(),
-                     attn_layers=(), trajectory=False):
+                     attn_layers=(), trajectory=False, variants=()):
     """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
     while this thread sends batch k and enqueues its forward; batches complete in order.
@@ -766,10 +769,11 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
             img, ev = stagers[k].send(staged)
             out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
         sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out,
-                 traj=(out['logits_steps'], out['delta_norm']) if trajectory else None)
+                 traj=(out['logits_steps'], out['delta_norm']) if trajectory else (out['logits_variants'],) if variants else None)
 
     sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else \
-        dict(attn_maps=attn_layers) if attn_layers else dict(trajectory=True) if trajectory else {}
+        dict(attn_maps=attn_layers) if attn_layers else dict(trajectory=True) if trajectory else \
+        dict(fusion_variants=variants) if variants else {}
 
     stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
@@ -834,7 +838,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
                  return_device: bool = False, similarity=False, row_outputs=None, attn_maps=None, steps: Optional[int] = None,
-                 trajectory: bool = False):
+                 trajectory: bool = False, fusion_variants=None):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -895,8 +899,24 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     after 0 .. steps steps for the N valid snippets, the videos in list order; "delta_norm": [steps, N] array of ||z_{k+1} - z_k||;
     "scores_steps_device": the first one as a device tensor; "row_offsets": int64 array of len(videos) + 1 offsets into N}}.  The
     host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError otherwise); it does not combine with
-    `similarity`, `row_outputs` or `attn_maps`."""
+    `similarity`, `row_outputs` or `attn_maps`.
+    `fusion_variants` (True: all four, or names from "fused", "image", "event", "equal"; the per-video / padded route and the
+    `forward_videos` loop; HIP device): every forward also returns its fusion ablations (`forward(..., fusion_variants=...)` /
+    `forward_videos(..., fusion_variants=...)`).  The returned tuple does not change; `score_loader.last_result` becomes {"variants":
+    {"names": the names in the order asked for; "scores": per video a [V, snippets] float32 array, the sigmoid of the variants' logits;
+    "scores_device": ONE [V, N] device tensor of the N valid snippets, the videos in list order; "row_offsets": int64 array of
+    len(videos) + 1 offsets into N}}.  The host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError
+    otherwise); it does not combine with `trajectory`, `similarity`, `row_outputs` or `attn_maps`."""
     on_gpu = torch.device(device).type == 'cuda'
+    from .model import fusion_variant_names
+    variants = fusion_variant_names(fusion_variants)
+    if variants:
+        if trajectory or similarity or row_outputs is not None or (attn_maps is not None and attn_maps is not False):
+            raise ValueError('fusion_variants does not combine with trajectory, similarity, row_outputs or attn_maps')
+        if not hasattr(model, '_variants_served'):
+            raise ValueError('fusion_variants needs a model with the fusion_variants keyword (iefvad_amd.MMFMIL)')
+        if not on_gpu:
+            raise ValueError('fusion_variants needs a HIP device')
     if (steps is not None or trajectory) and not hasattr(model, 'set_steps'):
         raise ValueError('steps= and trajectory=True need a model with set_steps (iefvad_amd.MMFMIL)')
     if trajectory:
@@ -946,6 +966,9 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     if trajectory and use_list:
         raise ValueError('trajectory=True is not served by the host-list walk (iefvad_forward_videos_host has no trajectory entry): '
                          'pass host_list=False for the forward_videos loop')
+    if variants and use_list:
+        raise ValueError('fusion_variants is not served by the host-list walk (iefvad_forward_videos_host has no variants entry): '
+                         'pass host_list=False for the forward_videos loop')
     # staging buffers are pinned allocations: they live with the lane (model object) across calls, not with the call
     stagers = [None] * nl
     for k, m in enumerate(models if on_gpu else ()):
@@ -962,7 +985,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         sink.dev_rows = {k: [] for k in row_keys}
     if attn_layers:
         sink.dev_rows = {"image_attn": [], "event_attn": []}
-    if trajectory:
+    if trajectory or variants:
         sink.dev_traj = []
     with torch.no_grad():
         for s in streams if nl > 1 else ():
@@ -976,10 +999,10 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                                  row_keys)
             elif ragged:
                 _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys,
-                                 attn_layers, trajectory)
+                                 attn_layers, trajectory, variants)
             else:
                 _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                              bool(similarity), trajectory)
+                              bool(similarity), trajectory, variants)
             nsteps = getattr(model, 'steps', 0)
         finally:
             if steps is not None:
@@ -1000,6 +1023,21 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
             score_loader.last_result = {"trajectory": {
                 "scores_steps": sc.cpu().numpy(), "delta_norm": dn.cpu().numpy(), "scores_steps_device": sc,
                 "row_offsets": np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)}}
+        elif variants:
+            valid = sum(n for _, n in sink.spans)
+            if sink.dev_traj:
+                lv = torch.cat([t[0] for t in sink.dev_traj], dim=1)
+                if valid != sink.total:      # the padded route leaves gaps between the videos' slots
+                    idx = torch.from_numpy(np.concatenate([np.arange(o, o + n, dtype=np.int64) for o, n in sink.spans])).to(lv.device)
+                    lv = lv[:, idx]
+            else:
+                lv = torch.zeros(len(variants), 0, device=device)
+            sc = torch.sigmoid(lv).contiguous()
+            offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
+            host = sc.cpu().numpy()
+            score_loader.last_result = {"variants": {
+                "names": tuple(variants), "scores": [host[:, a:b] for a, b in zip(offsets[:-1], offsets[1:])], "scores_device": sc,
+                "row_offsets": offsets}}
         elif attn_layers:
             offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
             image, event = (v[0] if len(v) == 1 else torch.cat(v, dim=1) if v else torch.zeros(len(attn_layers), 0, maxlen, device=device)
@@ -1317,7 +1355,8 @@ def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 
 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
-              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None, steps=None, trajectory=False):
+              batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None, steps=None, trajectory=False,
+              fusion_variants=None):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
@@ -1338,7 +1377,15 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     gives the whole ablation -- `score_loader(trajectory=True)` on the per-video route or the `forward_videos` loop -- and the result
     dict gains "trajectory" (see there), "auc_steps" and "ap_steps": the global AUC / AP of the scores after k = 0 .. steps steps, by
     the metric tail in use (sklearn, or `iefvad_auc_ap`).  Entry k is what a `steps=k` evaluation returns; nothing more is printed.  It
-    does not combine with vis=True or `attn_maps`."""
+    does not combine with vis=True or `attn_maps`.
+    `fusion_variants` (True or names): one walk gives the fusion ablation table -- `score_loader(fusion_variants=...)` on the per-video
+    route or the `forward_videos` loop -- and the result dict gains "variants" (see there), "auc_variants" and "ap_variants": name ->
+    the global AUC / AP of that variant's scores, by the metric tail in use (sklearn, or `iefvad_auc_ap`).  "fused" is what the call
+    itself returns; nothing more is printed.  It does not combine with vis=True, `attn_maps` or `trajectory`."""
+    if fusion_variants is not None and fusion_variants is not False and \
+            (vis or trajectory or (attn_maps is not None and attn_maps is not False)):
+        raise ValueError("fusion_variants does not combine with vis=True, attn_maps or trajectory")
+    want_variants = fusion_variants is not None and fusion_variants is not False
     if trajectory and (vis or (attn_maps is not None and attn_maps is not False)):
         raise ValueError("trajectory=True does not combine with vis=True or attn_maps")
     if metric_tail not in ("host", "device"):
@@ -1364,7 +1411,8 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     got = score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks, lanes=lanes,
                        return_device=metric_tail == "device", similarity="rows" if vis_rows else bool(vis),
                        **(dict(attn_maps=attn_maps) if want_maps else {}), **(dict(steps=steps) if steps is not None else {}),
-                       **(dict(trajectory=True, host_list=False) if trajectory else {}))
+                       **(dict(trajectory=True, host_list=False) if trajectory else {}),
+                       **(dict(fusion_variants=fusion_variants, host_list=False) if want_variants else {}))
     scores, classes, wi, we = got[:4]
     if metric_tail == "device":
         res = evaluate_scores_device((got[4], [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
@@ -1384,6 +1432,16 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
             pairs = [(roc_auc_score(gt, np.repeat(row.tolist(), 16)), average_precision_score(gt, np.repeat(row.tolist(), 16)))
                      for row in tr["scores_steps"]]
         last["auc_steps"], last["ap_steps"] = [p[0] for p in pairs], [p[1] for p in pairs]
+    if want_variants:
+        va = last["variants"] = score_loader.last_result["variants"]
+        if metric_tail == "device":
+            pairs = [device_auc_ap(row, gt) for row in va["scores_device"]]
+        else:       # the calls of evaluate_scores (test.py:158-159) on each variant's scores
+            from sklearn.metrics import average_precision_score, roc_auc_score
+            rows = np.concatenate(va["scores"], axis=1) if va["scores"] else np.zeros((len(va["names"]), 0), np.float32)
+            pairs = [(roc_auc_score(gt, np.repeat(row.tolist(), 16)), average_precision_score(gt, np.repeat(row.tolist(), 16))) for row in rows]
+        last["auc_variants"] = {n: p[0] for n, p in zip(va["names"], pairs)}
+        last["ap_variants"] = {n: p[1] for n, p in zip(va["names"], pairs)}
     if vis:
         last["similarity"] = got[-1]
         last["vis_files"] = draw_vis(vis_series(last, gt, vis_flavour), os.path.join('vis', str(args.exp_name)),      # test.py:59-62
@@ -1395,7 +1453,7 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
          batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded",
-         *, attn_maps=None, steps=None, trajectory=False):
+         *, attn_maps=None, steps=None, trajectory=False, fusion_variants=None):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
@@ -1407,29 +1465,31 @@ def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, 
     `attn_maps=` (keyword-only, here and in `ucf_test` / `xd_test`): the encoder's head-averaged attention maps of every valid snippet
     in `last_result["attn_maps"]` (`_run_test`, `score_loader`); `attn=True` keeps returning the reference's empty list.
     `steps=` / `trajectory=True` (keyword-only, here and in `ucf_test` / `xd_test`): evaluate with the first `steps` refinement blocks
-    only / add the per-step scores, update norms and "auc_steps", "ap_steps" to `last_result` from the one walk (`_run_test`)."""
+    only / add the per-step scores, update norms and "auc_steps", "ap_steps" to `last_result` from the one walk (`_run_test`).
+    `fusion_variants=` (keyword-only, here and in `ucf_test` / `xd_test`): True or names; adds the fusion ablations' scores ("variants")
+    and "auc_variants", "ap_variants" (name -> float) to `last_result` from the one walk (`_run_test`)."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
                                       False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route, attn_maps=attn_maps, steps=steps,
-                                      trajectory=trajectory)
+                                      trajectory=trajectory, fusion_variants=fusion_variants)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
              batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
-             steps=None, trajectory=False):
+             steps=None, trajectory=False, fusion_variants=None):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
                                           ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route, attn_maps, steps,
-                                          trajectory)
+                                          trajectory, fusion_variants)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
-            steps=None, trajectory=False):
+            steps=None, trajectory=False, fusion_variants=None):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -1437,7 +1497,8 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
     if label_map is None:
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
-                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps, steps, trajectory)
+                                         ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps, steps, trajectory,
+                                         fusion_variants)
     test.last_result = xd_test.last_result
     return ret
 

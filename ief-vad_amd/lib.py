@@ -39,7 +39,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_gemm_split_small_unit", "iefvad_gemm_split_small_launches", "iefvad_set_batch_invariant",
            "iefvad_train_backward_inputs", "iefvad_forward_perturbed", "iefvad_forward_videos_perturbed", "iefvad_perturb_rows",
            "iefvad_set_steps", "iefvad_trajectory_workspace_bytes", "iefvad_forward_trajectory", "iefvad_videos_trajectory_workspace_bytes",
-           "iefvad_forward_videos_trajectory"]
+           "iefvad_forward_videos_trajectory", "iefvad_variants_workspace_bytes", "iefvad_forward_variants",
+           "iefvad_videos_variants_workspace_bytes", "iefvad_forward_videos_variants"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -96,6 +97,14 @@ class AttnMaps(C.Structure):
 class Trajectory(C.Structure):
     """iefvad_trajectory (include/iefvad.h): device fp32 [steps + 1, stride] logits and [steps, stride] update norms (0 = not asked for)."""
     _fields_ = [("logits_steps", _fp), ("delta_norm", _fp), ("stride", C.c_size_t)]
+
+
+VARIANT_NAMES = ("fused", "image", "event", "equal")      # IEFVAD_VARIANT_FUSED .. IEFVAD_VARIANT_EQUAL, in the enum's order
+
+
+class Variants(C.Structure):
+    """iefvad_variants (include/iefvad.h): `count` kinds (indices into VARIANT_NAMES) and the device fp32 [count, stride] logits."""
+    _fields_ = [("count", C.c_int32), ("kind", C.c_int32 * 4), ("logits", _fp), ("stride", C.c_size_t)]
 
 
 class Perturb(C.Structure):
@@ -307,6 +316,15 @@ def load_library() -> C.CDLL:
     lib.iefvad_videos_trajectory_workspace_bytes.restype = C.c_size_t
     lib.iefvad_forward_videos_trajectory.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(Trajectory), C.c_void_p]
     lib.iefvad_forward_videos_trajectory.restype = C.c_int
+    # the fusion-ablation entries: `const iefvad_variants*` in front of the stream, the variant count behind the queries' arguments
+    lib.iefvad_variants_workspace_bytes.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    lib.iefvad_variants_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_variants.argtypes = lib.iefvad_forward.argtypes[:8] + [C.POINTER(Variants), C.c_void_p]
+    lib.iefvad_forward_variants.restype = C.c_int
+    lib.iefvad_videos_variants_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_int32]
+    lib.iefvad_videos_variants_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_videos_variants.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(Variants), C.c_void_p]
+    lib.iefvad_forward_videos_variants.restype = C.c_int
     lib.iefvad_split_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.iefvad_split_bf16x3.restype = C.c_int
     lib.iefvad_split_bf16x3_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -58,7 +58,38 @@ _ROW_ENTRIES = {
     "_perturbed": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
     "_attn": ("", lambda r: (), lambda r: (*r["vectors"], r["maps"], r["stream"])),
     "_trajectory": ("_trajectory", lambda r: (), lambda r: (*r["vectors"], r["traj"], r["stream"])),
+    "_variants": ("_variants", lambda r: (r["nvariants"],), lambda r: (*r["vectors"], r["variants"], r["stream"])),
 }
+
+
+def fusion_variant_names(fusion_variants) -> tuple:
+    """`fusion_variants=` -> the names asked for, in the caller's order: None / False -> none, True -> all four in the order of
+    `lib.VARIANT_NAMES` ("fused", "image", "event", "equal"), else a name or an iterable of names, each at most once (ValueError
+    otherwise)."""
+    if fusion_variants is None or fusion_variants is False:
+        return ()
+    if fusion_variants is True:
+        return tuple(_lib.VARIANT_NAMES)
+    try:
+        names = [fusion_variants] if isinstance(fusion_variants, str) else list(fusion_variants)
+    except TypeError:
+        raise ValueError(f"fusion_variants takes True or an iterable of names from {_lib.VARIANT_NAMES} (got {fusion_variants!r})") from None
+    bad = [n for n in names if n not in _lib.VARIANT_NAMES]
+    if bad or not names:
+        raise ValueError(f"unknown fusion variant(s) {bad}: fusion_variants takes True or names from {_lib.VARIANT_NAMES} (got {fusion_variants!r})")
+    if len(set(names)) != len(names):
+        raise ValueError(f"fusion_variants names a variant more than once: {names}")
+    return tuple(names)
+
+
+def _variants_struct(names, logits: torch.Tensor, stride: int) -> "_lib.Variants":
+    """`iefvad_variants` over the [V, ...] result tensor: row v is variant names[v]."""
+    v = _lib.Variants()
+    v.count = len(names)
+    for j, n in enumerate(names):
+        v.kind[j] = _lib.VARIANT_NAMES.index(n)
+    v.logits, v.stride = logits.data_ptr(), stride
+    return v
 
 
 def attn_map_layers(attn_maps, num_layers: int) -> tuple:
@@ -379,6 +410,12 @@ class MMFMIL(nn.Module):
       trajectory=True  (`forward`, `forward_videos`) adds `logits_steps` (the logits after 0 .. steps steps) and `delta_norm`
                    (||z_{k+1} - z_k|| per step) from the one forward; every other result keeps its bits.
 
+    The fusion ablations of a trained model (not in the reference, which forms `fused` inline, imf_vad.py:130-150):
+      fusion_variants=True or names  (`forward`, `forward_videos`) adds `logits_variants`: the logits the model gives with the event
+                   branch ("image") or the image branch ("event") removed at the fusion, with both precisions forced equal ("equal"),
+                   and unchanged ("fused" = `logits`) -- encoder and heads run once, the refinement and classifier once more on the
+                   stacked variants.  Every other result keeps its bits.
+
     Without any keyword (the reference's behaviour, imf_vad.py:40-44,109-161 being an ordinary nn.Module):
       gradients of the features  a feature tensor with `requires_grad=True` receives its `.grad` from `loss.backward()`, in its own dtype
                    and shape, in train() and in eval() alike -- an adapter or a learned projection upstream of the model trains, and
@@ -589,7 +626,7 @@ class MMFMIL(nn.Module):
 
     def forward(self, img_visual, ev_visual, padding_mask=None, text=None, lengths=None, return_attn=False,
                 *, timed: bool = False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None, noise_rows=None,
-                trajectory: bool = False) -> Dict[str, torch.Tensor]:
+                trajectory: bool = False, fusion_variants=None) -> Dict[str, torch.Tensor]:
         """The reference's call (imf_vad.py:40-44; `padding_mask`, `text`, `lengths`, `return_attn` accepted and ignored as there).
         Keyword-only extras: `timed` (per-stage device times in `last_stage_times`), `row_scale=(s_img, s_ev)`: fp32 DEVICE vectors
         of [B*T] (either may be None) that multiply the input rows inside the library's input load (`iefvad_forward_scaled`: the
@@ -611,8 +648,24 @@ class MMFMIL(nn.Module):
         steps = `self.steps`.  Row k of `logits_steps` is what `set_steps(k)` returns as `logits`; every other result keeps its bits.
         compute="bf16" runs such a call with two GEMM launches per step in place of its one chain kernel (same bits, slower).  It combines
         with none of `timed`, `attn_maps`, `row_scale`, `row_noise` and features that require grad (ValueError), and not with model.train()
-        (RuntimeError)."""
+        (RuntimeError).
+        `fusion_variants=True` (all four, in the order "fused", "image", "event", "equal") or an iterable of those names
+        (`iefvad_forward_variants`) adds `logits_variants`, [V, B, T] fp32 in the order named, and `fusion_variants`, the names: the logits
+        (apply the sigmoid) of the model with one substitution in the fusion w_m = f exp(-lv_m), z0 = (w_i mu_i + w_e mu_e) / (w_i + w_e + eps)
+        -- "image": w_e := 0, "event": w_i := 0, "equal": lv_i := lv_e := 0, "fused": none (equal to `logits`; bit for bit with "f32" and
+        "bf16") -- followed by the `self.steps` refinement steps and the classifier.  Every other result keeps its bits.  An unknown or
+        repeated name, and a combination with `timed`, `trajectory`, `attn_maps`, `row_scale` or `row_noise`, is a ValueError;
+        compute="fp16x3", model.train() and a feature tensor that requires grad are RuntimeErrors."""
         self._noise_code()   # ValueError for an unsupported noise_model, as the reference raises
+        variants = fusion_variant_names(fusion_variants)
+        if variants:
+            asked = [n for n, on in (("timed=True", timed), ("trajectory=True", trajectory),
+                                     ("attn_maps=", attn_maps is not None and attn_maps is not False),
+                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
+                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise))) if on]
+            if asked:
+                raise ValueError(f"fusion_variants= does not combine with {' / '.join(asked)}: iefvad_forward_variants is a plain evaluation forward")
+            self._variants_served(torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad))
         if trajectory:
             grad = torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad)
             asked = [n for n, on in (("timed=True", timed), ("attn_maps=", attn_maps is not None and attn_maps is not False),
@@ -669,7 +722,8 @@ class MMFMIL(nn.Module):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._ensure_handle(device)
             self._ensure_weights(device, stream)
-            need = lib.iefvad_trajectory_workspace_bytes(self._handle, B) if trajectory else lib.iefvad_workspace_bytes(self._handle, B)
+            need = lib.iefvad_trajectory_workspace_bytes(self._handle, B) if trajectory else \
+                lib.iefvad_variants_workspace_bytes(self._handle, B, len(variants)) if variants else lib.iefvad_workspace_bytes(self._handle, B)
             if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
                 self._workspace = None
                 self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
@@ -703,6 +757,13 @@ class MMFMIL(nn.Module):
                 if rc != 0:
                     raise RuntimeError("iefvad_forward_trajectory: " + _lib.last_error())
                 res["logits_steps"], res["delta_norm"] = ls, dn
+            elif variants:
+                res["logits_variants"] = torch.empty(len(variants), B, T, **f32)
+                res["fusion_variants"] = variants
+                vs = _variants_struct(variants, res["logits_variants"], N)
+                rc = lib.iefvad_forward_variants(*args[:8], C.byref(vs), args[8])
+                if rc != 0:
+                    raise RuntimeError("iefvad_forward_variants: " + _lib.last_error())
             elif layers:
                 res["image_attn"] = torch.empty(len(layers), B, T, T, **f32)
                 res["event_attn"] = torch.empty(len(layers), B, T, T, **f32)
@@ -732,9 +793,21 @@ class MMFMIL(nn.Module):
             if rc != 0:
                 raise RuntimeError("iefvad_forward: " + _lib.last_error())
         if self.outputs == "full":
-            extra = ("image_attn", "event_attn", "attn_layers") if layers else ("logits_steps", "delta_norm") if trajectory else ()
+            extra = ("image_attn", "event_attn", "attn_layers") if layers else ("logits_steps", "delta_norm") if trajectory else \
+                ("logits_variants", "fusion_variants") if variants else ()
             return {k: res[k] for k in OUTPUT_KEYS + extra}   # the reference's key order
         return res
+
+    def _variants_served(self, grad: bool):
+        """RuntimeError where a fusion-variants request cannot be served: the fp16x3 arithmetic, training, differentiable features."""
+        if self.compute == "fp16x3":
+            raise RuntimeError('fusion_variants= is not available with compute="fp16x3" (its per-chunk running-max words have no home for '
+                               'the stacked states); use "f32", "bf16x6" or "bf16"')
+        if self.training:
+            raise RuntimeError("fusion_variants= is an evaluation request; it is not available under model.train() (call model.eval() first)")
+        if grad:
+            raise RuntimeError("fusion_variants= is an evaluation request: nothing it returns is differentiable, and a feature tensor "
+                               "requires grad (detach the features, or call under torch.no_grad())")
 
     def _attn_maps_served(self, mode):
         """RuntimeError where a maps request cannot be served: the bf16 arithmetic (its q | k | v are bf16 planes) and training."""
@@ -785,7 +858,7 @@ class MMFMIL(nn.Module):
         front = (pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], (C.c_int32 * n)(*lens), n, 1 if nan_to_num else 0, int(batch_chunks), int(host_threads))
         return self._rows_call("iefvad_forward_videos_host", suffix, device, sum(lens), front, wide=wide)
 
-    def _rows_call(self, base, suffix, device, total, front, *, wide=(), weight_sums=False, workspace_for=None, attn_layers=()):
+    def _rows_call(self, base, suffix, device, total, front, *, wide=(), weight_sums=False, workspace_for=None, attn_layers=(), variants=()):
         """One valid-row call, the entry `base + suffix` (`_ROW_ENTRIES`): allocates the results -- the three [total] vectors, a
         [total, D] tensor per key of `wide`, the similarity entries' [4, total] series, `w_colsum` -- and calls the entry with
         (handle, *front, [workspace, bytes,] the suffix's tail).  `workspace_for=(lengths array, nvideos)`: the device entries, whose
@@ -800,7 +873,13 @@ class MMFMIL(nn.Module):
             f32 = dict(dtype=torch.float32, device=device)
             res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
             r = {"vectors": tuple(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), "stream": C.c_void_p(stream), "out": None,
-                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0, "maps": None, "traj": None}
+                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0, "maps": None, "traj": None,
+                 "variants": None, "nvariants": len(variants)}
+            if suffix == "_variants":
+                res["logits_variants"] = torch.empty(len(variants), total, **f32)
+                res["fusion_variants"] = tuple(variants)
+                vs = _variants_struct(variants, res["logits_variants"], total)
+                r["variants"] = C.byref(vs)
             if suffix == "_trajectory":
                 steps = self.steps
                 res["logits_steps"] = torch.empty(steps + 1, total, **f32)
@@ -876,7 +955,7 @@ class MMFMIL(nn.Module):
 
     def forward_videos(self, img_rows: torch.Tensor, ev_rows: torch.Tensor, lengths, nan_to_num=True, *, row_scale=None,
                        weight_sums: bool = False, similarity: bool = False, outputs=None, attn_maps=None, row_noise=None, noise_seed=None,
-                       noise_rows=None, trajectory: bool = False) -> Dict[str, torch.Tensor]:
+                       noise_rows=None, trajectory: bool = False, fusion_variants=None) -> Dict[str, torch.Tensor]:
         """Scores of whole videos (`iefvad_forward_videos`, include/iefvad.h): `img_rows`, `ev_rows` are the videos' VALID
         feature rows concatenated in list order, [sum(lengths), D] on the device; `lengths` the snippets per video.  The
         chunker (tools.py:100-114), the conditional nan_to_num of test.py:90-95 and the `[0:len]` slicing of
@@ -907,7 +986,21 @@ class MMFMIL(nn.Module):
         [steps, sum(lengths)], as `forward` does, in packed order, valid rows only; the other three results keep their bits.  It combines
         with none of `attn_maps`, `row_scale`, `row_noise`, `similarity`, `outputs`, `weight_sums` and nan_to_num="always" (ValueError);
         model.train() raises RuntimeError.
+        `fusion_variants=True` or an iterable of names (`iefvad_forward_videos_variants`) adds `logits_variants`, [V, sum(lengths)], and
+        `fusion_variants`, the names, as `forward` does, in packed order, valid rows only; the other three results keep their bits.  It
+        combines with none of `trajectory`, `attn_maps`, `row_scale`, `row_noise`, `similarity`, `outputs`, `weight_sums` and
+        nan_to_num="always" (ValueError); compute="fp16x3", model.train() and rows that require grad raise RuntimeError.
         An evaluation entry: nothing it returns is differentiable (rows that require grad get no gradient here; use `forward`)."""
+        variants = fusion_variant_names(fusion_variants)
+        if variants:
+            asked = [n for n, on in (("trajectory=True", trajectory), ("attn_maps=", attn_maps is not None and attn_maps is not False),
+                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
+                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise)),
+                                     ("similarity=True", similarity), ("outputs=", outputs is not None), ("weight_sums=True", weight_sums),
+                                     ("nan_to_num='always'", isinstance(nan_to_num, str) and nan_to_num == "always")) if on]
+            if asked:
+                raise ValueError(f"fusion_variants= does not combine with {' / '.join(asked)}: iefvad_forward_videos_variants takes none of them")
+            self._variants_served(torch.is_grad_enabled() and (img_rows.requires_grad or ev_rows.requires_grad))
         if trajectory:
             asked = [n for n, on in (("attn_maps=", attn_maps is not None and attn_maps is not False),
                                      ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
@@ -954,6 +1047,8 @@ class MMFMIL(nn.Module):
             suffix = "_attn"
         if trajectory:
             suffix = "_trajectory"
+        if variants:
+            suffix = "_variants"
         pert = None
         if noisy:
             pert, _ = _perturb_struct(nrows, img_rows.device, row_scale, row_noise, noise_seed, noise_rows, "sum of lengths")
@@ -980,4 +1075,4 @@ class MMFMIL(nn.Module):
         elif extras:    # the scaled entry alone takes the two scale vectors, behind nan_to_num
             front += tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in scales)
         return self._rows_call("iefvad_forward_videos", suffix, device, total, front, wide=wide, weight_sums=weight_sums,
-                               workspace_for=(larr, len(lens)), attn_layers=layers)
+                               workspace_for=(larr, len(lens)), attn_layers=layers, variants=variants)

@@ -781,6 +781,41 @@ int iefvad_forward_videos_trajectory(iefvad_handle* h, const void* img_rows, con
                                      size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
                                      const iefvad_trajectory* trajectory, void* stream);
 
+/* ---- fusion ablations ------------------------------------------------------------------------------------------------
+ * One forward, and per snippet the score the model gives when the precision-weighted fusion (imf_vad.py:130-144)
+ *   w_i = f exp(-lv_i), w_e = f exp(-lv_e), den = w_i + w_e + eps, z0 = (w_i / den) mu_i + (w_e / den) mu_e
+ * is altered by one substitution, followed by the unchanged refinement (the handle's current iefvad_set_steps count) and classifier:
+ *   IEFVAD_VARIANT_FUSED  none: reproduces the call's `logits` (a self-check, and so that one result holds the whole table)
+ *   IEFVAD_VARIANT_IMAGE  w_e := 0  (the event branch removed at the fusion: z0 = w_i / (w_i + eps) mu_i + 0 mu_e)
+ *   IEFVAD_VARIANT_EVENT  w_i := 0
+ *   IEFVAD_VARIANT_EQUAL  lv_i := lv_e := 0  (both precisions equal: w_i = w_e = f)
+ * The operation order of the expression is kept, 0 mu and eps included, so NaN and inf behave as the substituted expression does.
+ *   logits[v * stride + r], v in the order of kind[0 .. count - 1], r the row of the call: b T + t (dense) or the packed row (whole
+ * videos; valid rows only, no padding is written).  Values are before the sigmoid.  `stride`: ELEMENTS between two variants, at
+ * least the call's rows.  `logits`: a device pointer, 4-byte aligned.  1 <= count <= 4, every kind at most once.
+ * Encoder and heads run once; behind the call's own tail one row kernel (iefvad_fusion_variants_kernel, csrc/variants.h) forms the
+ * variants' z0 from the pass's mu / logvar and the refinement + scorer run once more on the stacked count x rows states, with the
+ * kernels the unchanged selection rules pick for that row count.  IEFVAD_COMPUTE_F32 and IEFVAD_COMPUTE_BF16: the FUSED row has the
+ * bits of the call's logits; IEFVAD_COMPUTE_BF16X6: within the arithmetic's tolerance (the stacked set may run on the split
+ * kernels where the call's rows do not), the same bits with iefvad_set_batch_invariant.  Every other output of the call has the
+ * bits of the same call without variants.  The stacked state, its scratch and logits live behind the base workspace: use the
+ * _variants_workspace_bytes queries.  Direct launches (no hipGraph).  Refused by name before any launch: IEFVAD_COMPUTE_FP16X3
+ * (not covered: its per-chunk running-max words have no home for the stacked states), a null struct or logits pointer, a
+ * misaligned logits pointer, count outside 1..4, an unknown or repeated kind, a stride below the call's rows, a workspace smaller
+ * than the query says.  Not covered: the host-list entries and training.  Added without a change to any other entry:
+ * IEFVAD_ABI_VERSION stays. */
+enum { IEFVAD_VARIANT_FUSED = 0, IEFVAD_VARIANT_IMAGE = 1, IEFVAD_VARIANT_EVENT = 2, IEFVAD_VARIANT_EQUAL = 3 };
+typedef struct iefvad_variants { int32_t count; int32_t kind[4]; float* logits; size_t stride; } iefvad_variants;
+size_t iefvad_variants_workspace_bytes(const iefvad_handle* h, int32_t B, int32_t count);
+int iefvad_forward_variants(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                            size_t workspace_bytes, const iefvad_outputs* out, const iefvad_variants* variants, void* stream);
+/* Mirrors iefvad_forward_videos: [count, stride] in packed order. */
+size_t iefvad_videos_variants_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t count);
+int iefvad_forward_videos_variants(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                   const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                   size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                   const iefvad_variants* variants, void* stream);
+
 /* The exact three-term bf16 split of n fp32 values (n % 4 == 0): planes[0..n) = bf16(x),
  * planes[n..2n) = bf16(x - p0), planes[2n..3n) = bf16(x - p0 - p1), round-to-nearest-even; x == p0 + p1 + p2
  * for finite x.  What iefvad_set_weights applies to every projection matrix in IEFVAD_COMPUTE_BF16X6. */
