@@ -85,6 +85,19 @@ def sharpen_qk(sd: Dict[str, torch.Tensor], factors: Sequence[float]) -> Dict[st
     return out
 
 
+def shift_logvar_bias(sd: Dict[str, torch.Tensor], image: float, event: float) -> Dict[str, torch.Tensor]:
+    """A copy of `sd` with uncertain heads: `image` / `event` added to every element of `temporal.image_logvar.bias` /
+    `temporal.event_logvar.bias`.  Nothing else changes.  With `make_state_dict`'s own weights the log-variances lie in about
+    [-2.8, 3.0], so in den = w_i + w_e + eps the epsilon (1e-8) is 5e-9 of the sum, n_i + n_e = 1 to fp32 rounding and the Student-t
+    factor cancels out of every output.  Shifts of (15.5, 17.0) bring w_i + w_e down to the size of epsilon (median 1 - (n_i + n_e)
+    0.036) with every log-variance below 21, far from the underflow of exp: the regime in which the factor and epsilon are visible."""
+    out = dict(sd)
+    for m, s in zip(MODALITIES, (image, event)):
+        key = f"temporal.{m}_logvar.bias"
+        out[key] = sd[key] + float(s)
+    return out
+
+
 def make_inputs(seed: int, B: int, T: int = 256, D: int = 768, scale: float = 0.45,
                 dtype=np.float32) -> Tuple[np.ndarray, np.ndarray]:
     """Seeded N(0, scale^2) image / event feature blocks [B,T,D] (scale ~ CLIP ViT-L/14 per-dim)."""

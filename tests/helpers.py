@@ -1,4 +1,5 @@
 """Shared test helpers: golden-case loading and oracle construction (tests may import oracle/)."""
+import functools
 import glob
 import os
 
@@ -55,6 +56,112 @@ def load_case(name):
         cfg["factors"] = tuple(float(f) for f in g["factors"])
         sd = synth.sharpen_qk(sd, cfg["factors"])
     return g, cfg, sd, img, ev
+
+
+PRECISION_CASES = ("k3_student8", "k3_student1", "k3_gauss", "k0_student5_eps", "vitb_k3_student8")
+
+
+def load_precision_case(name):
+    """A `prec_<name>.npz` fixture of tests/golden/make_golden_precision.py (the "uncertain heads" regime: the log-variance biases
+    shifted by synth.shift_logvar_bias, or epsilon raised, so that the Student-t factor and epsilon of the fusion do not cancel), as
+    `load_case` returns a forward case: (fixture, cfg, state dict, image block, event block).  cfg adds D, shift and epsilon."""
+    g = np.load(os.path.join(GOLDEN, f"prec_{name}.npz"))
+    wseed, iseed, B, L, K, nu = (int(v) for v in g["meta"])
+    cfg = dict(L=L, K=K, nu=nu, lam=float(g["lam"]), noise=str(g["noise"]), B=B, wseed=wseed, iseed=iseed, in_dtype="f32", edit="tail",
+               D=int(g["dim"]), shift=tuple(float(s) for s in g["shift"]), epsilon=float(g["epsilon"]))
+    img, ev = synth.make_inputs(iseed, B, D=cfg["D"])
+    img[B - 1, 100:] = 0
+    ev[B - 1, 100:] = 0
+    sd = synth.shift_logvar_bias(synth.make_state_dict(wseed, cfg["D"], L, K), *cfg["shift"])
+    return g, cfg, sd, img, ev
+
+
+def precision_oracle_cfg(cfg):
+    """The oracle's configuration of a `load_precision_case` cfg: `oracle_cfg` plus the case's epsilon."""
+    return orc.OracleConfig(num_layers=cfg["L"], num_heads=8, num_refinement_steps=cfg["K"], lambda_ref=cfg["lam"],
+                            noise_model=cfg["noise"], nu=cfg["nu"], epsilon=cfg["epsilon"])
+
+
+def fuse_fp64(mu_i, lv_i, mu_e, lv_e, noise, nu, eps):
+    """The four formula lines of the fusion (imf_vad.py:130-144) in fp64 on the head tensors given (any shape):
+    w_m = factor exp(-lv_m), den = w_i + w_e + eps, n_m = w_m / den, z0 = n_i mu_i + n_e mu_e, factor = (nu + 1) / nu for
+    noise "StudentT" and 1 for "Gaussian".  Returns fp64 (n_i, n_e, z0): numpy arrays for numpy heads, torch tensors on the heads'
+    device for torch heads (a B = 48 forward's 9.4 M elements per tensor are evaluated where they are)."""
+    if noise not in ("Gaussian", "StudentT"):
+        raise ValueError(noise)
+    as_numpy = not isinstance(mu_i, torch.Tensor)
+    mu_i, lv_i, mu_e, lv_e = (torch.as_tensor(t).detach().double() for t in (mu_i, lv_i, mu_e, lv_e))
+    factor = (float(nu) + 1.0) / float(nu) if noise == "StudentT" else 1.0
+    w_i, w_e = factor * torch.exp(-lv_i), factor * torch.exp(-lv_e)
+    den = w_i + w_e + float(eps)
+    n_i, n_e = w_i / den, w_e / den
+    res = (n_i, n_e, n_i * mu_i + n_e * mu_e)
+    return tuple(t.numpy() for t in res) if as_numpy else res
+
+
+def formula_errors(out, noise, nu, eps, fused=False):
+    """The reference-free layer: the largest relative distance of the returned `w_i`, `w_e` (and, with `fused`, of `fused`, which is z0
+    when no refinement step ran) from `fuse_fp64` of the RETURNED heads.  Relative to the fp64 value for the weights; for z0, whose two
+    terms may cancel, to |n_i mu_i| + |n_e mu_e| (what its roundings scale with) -- the measures `formula_floor` of the prec_*.npz
+    fixtures is recorded in.  `out`: the model's output dict or a fixture (torch on any device, or numpy).  Returns {key: error}."""
+    a = {k: torch.as_tensor(out[k]).detach().double()
+         for k in ("image_mu", "image_logvar", "event_mu", "event_logvar", "w_i", "w_e") + (("fused",) if fused else ())}
+    n_i, n_e, z0 = fuse_fp64(a["image_mu"], a["image_logvar"], a["event_mu"], a["event_logvar"], noise, nu, eps)
+    errs = {"w_i": float(((a["w_i"] - n_i).abs() / n_i).max()), "w_e": float(((a["w_e"] - n_e).abs() / n_e).max())}
+    if fused:
+        errs["fused"] = float(((a["fused"] - z0).abs() / ((n_i * a["image_mu"]).abs() + (n_e * a["event_mu"]).abs())).max())
+    return errs
+
+
+# ---- gradients in the uncertain-heads regime (tests/test_precision_cpu.py, tests/test_gpu_precision.py) -----------------------------
+PRECISION_SHIFT = (15.5, 17.0)
+PRECISION_GRAD = dict(wseed=5, bseed=77, L=2, K=2, nu=8)
+
+
+def precision_scalar(o):
+    """A scalar of the outputs whose gradients see the fusion from both sides: through `logits` (z0 and its weights), through the head
+    tensors directly, and through `fused . w_i`.  Use it in the shifted regime only: with the seeded weights w_i + w_e = 1 to rounding
+    and a gradient that cancels analytically leaves an fp32 floor of hundreds of gates on one tensor."""
+    return (o["logits"].sum() + 0.5 * (o["image_mu"] * o["event_logvar"]).sum() + 0.25 * (o["event_mu"] * o["image_logvar"]).sum()
+            + 0.125 * (o["fused"] * o["w_i"]).sum())
+
+
+def precision_grad_state(shift=PRECISION_SHIFT):
+    p = PRECISION_GRAD
+    return synth.shift_logvar_bias(synth.make_state_dict(p["wseed"], 768, p["L"], p["K"]), *shift)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_precision_grads(noise, B, dtype=torch.float64, shift=PRECISION_SHIFT, nu=PRECISION_GRAD["nu"]):
+    """{parameter name: gradient (fp64 tensor)} of `precision_scalar` by autograd through the oracle in `dtype`, on
+    synth.make_train_batch(77, B) and the PRECISION_GRAD model with its log-variance biases shifted by `shift`.  Computed once per
+    argument tuple and shared: callers leave the tensors unchanged."""
+    p = PRECISION_GRAD
+    img, ev, _, _ = synth.make_train_batch(p["bseed"], B)
+    leaves = {k: v.to(dtype).requires_grad_(True) for k, v in precision_grad_state(shift).items()}
+    cfg = orc.OracleConfig(num_layers=p["L"], num_refinement_steps=p["K"], noise_model=noise, nu=nu)
+    precision_scalar(orc.forward(leaves, torch.from_numpy(img), torch.from_numpy(ev), cfg, dtype=dtype)).backward()
+    return {k: v.grad.detach().double() for k, v in leaves.items()}
+
+
+def oracle_precision_grad_floor(noise, B, nu=PRECISION_GRAD["nu"]):
+    """(floor, tensor name): the oracle's own fp32 autograd against its fp64 autograd on `precision_scalar` in the shifted regime -- the
+    worst entry over all 46 tensors in units of the gradient gate 1e-4 |want| + 2e-6 max |want| (`grad_gates`).  The GPU gradient tests
+    gate at max(1, 3 x this figure); it is measured where the test runs, next to the fp64 gradients, so that no recorded figure can be
+    padded.  On the CPU at B = 3: 0.52 (Student-8), 0.50 (Gaussian); 0.15 / 0.16 at B = 1.  No kernel enters."""
+    units = grad_gates(oracle_precision_grads(noise, B, torch.float32, nu=nu), oracle_precision_grads(noise, B, nu=nu))
+    name = max(units, key=units.get)
+    return units[name], name
+
+
+def grad_gates(got, want):
+    """Per tensor, the worst entry of |got - want| in units of the gradient gate 1e-4 |want| + 2e-6 max |want| (tests/test_gpu_train.py)."""
+    out = {}
+    for n, w in want.items():
+        w = w.double()
+        tol = 1e-4 * w.abs() + 2e-6 * float(w.abs().max())
+        out[n] = float(((got[n].double() - w).abs() / tol).max())
+    return out
 
 
 def case_gates(g, tols, floors=("floor_big", "floor_logit", "floor_sigmoid")):
