@@ -908,26 +908,26 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     len(videos) + 1 offsets into N}}.  The host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError
     otherwise); it does not combine with `trajectory`, `similarity`, `row_outputs` or `attn_maps`."""
     on_gpu = torch.device(device).type == 'cuda'
-    from .model import fusion_variant_names
+    from .model import _row_output_keys, attn_map_layers, attn_maps_asked, fusion_variant_names
     variants = fusion_variant_names(fusion_variants)
+    want_maps = attn_maps_asked(attn_maps)
     if variants:
-        if trajectory or similarity or row_outputs is not None or (attn_maps is not None and attn_maps is not False):
+        if trajectory or similarity or row_outputs is not None or want_maps:
             raise ValueError('fusion_variants does not combine with trajectory, similarity, row_outputs or attn_maps')
-        if not hasattr(model, '_variants_served'):
+        if not hasattr(model, 'set_steps'):
             raise ValueError('fusion_variants needs a model with the fusion_variants keyword (iefvad_amd.MMFMIL)')
         if not on_gpu:
             raise ValueError('fusion_variants needs a HIP device')
     if (steps is not None or trajectory) and not hasattr(model, 'set_steps'):
         raise ValueError('steps= and trajectory=True need a model with set_steps (iefvad_amd.MMFMIL)')
     if trajectory:
-        if similarity or row_outputs is not None or (attn_maps is not None and attn_maps is not False):
+        if similarity or row_outputs is not None or want_maps:
             raise ValueError('trajectory=True does not combine with similarity, row_outputs or attn_maps')
         if not on_gpu:
             raise ValueError('trajectory=True needs a HIP device')
-    from .model import _row_output_keys, attn_map_layers
     row_keys = _row_output_keys(row_outputs)
     attn_layers = ()
-    if attn_maps is not None and attn_maps is not False:
+    if want_maps:
         if similarity or row_outputs is not None:
             raise ValueError('attn_maps does not combine with similarity or row_outputs: iefvad_forward_videos_attn returns neither')
         if not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos')) or ragged is False:
@@ -1009,37 +1009,27 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                 model.set_steps(prev_steps)
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
+        if trajectory or variants or sink.dev_rows is not None:
+            offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
+        if sink.dev_traj:
+            # the slots of every forward side by side, then the valid ones in video order (the padded route leaves gaps between the videos' slots)
+            slots = [torch.cat([t[i] for t in sink.dev_traj], dim=1) for i in range(len(sink.dev_traj[0]))]
+            if offsets[-1] != sink.total:
+                idx = torch.from_numpy(np.concatenate([np.arange(o, o + n, dtype=np.int64) for o, n in sink.spans])).to(slots[0].device)
+                slots = [t[:, idx] for t in slots]
         if trajectory:
-            # the slots of every forward side by side, then the valid ones in video order (the padded route leaves gaps)
-            valid = sum(n for _, n in sink.spans)
-            if sink.dev_traj:
-                ls, dn = (torch.cat([t[i] for t in sink.dev_traj], dim=1) for i in (0, 1))
-                if valid != sink.total:
-                    idx = torch.from_numpy(np.concatenate([np.arange(o, o + n, dtype=np.int64) for o, n in sink.spans])).to(ls.device)
-                    ls, dn = ls[:, idx], dn[:, idx]
-            else:
-                ls, dn = torch.zeros(nsteps + 1, 0, device=device), torch.zeros(nsteps, 0, device=device)
+            ls, dn = slots if sink.dev_traj else (torch.zeros(nsteps + 1, 0, device=device), torch.zeros(nsteps, 0, device=device))
             sc = torch.sigmoid(ls).contiguous()
             score_loader.last_result = {"trajectory": {
-                "scores_steps": sc.cpu().numpy(), "delta_norm": dn.cpu().numpy(), "scores_steps_device": sc,
-                "row_offsets": np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)}}
+                "scores_steps": sc.cpu().numpy(), "delta_norm": dn.cpu().numpy(), "scores_steps_device": sc, "row_offsets": offsets}}
         elif variants:
-            valid = sum(n for _, n in sink.spans)
-            if sink.dev_traj:
-                lv = torch.cat([t[0] for t in sink.dev_traj], dim=1)
-                if valid != sink.total:      # the padded route leaves gaps between the videos' slots
-                    idx = torch.from_numpy(np.concatenate([np.arange(o, o + n, dtype=np.int64) for o, n in sink.spans])).to(lv.device)
-                    lv = lv[:, idx]
-            else:
-                lv = torch.zeros(len(variants), 0, device=device)
+            lv = slots[0] if sink.dev_traj else torch.zeros(len(variants), 0, device=device)
             sc = torch.sigmoid(lv).contiguous()
-            offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
             host = sc.cpu().numpy()
             score_loader.last_result = {"variants": {
                 "names": tuple(variants), "scores": [host[:, a:b] for a, b in zip(offsets[:-1], offsets[1:])], "scores_device": sc,
                 "row_offsets": offsets}}
         elif attn_layers:
-            offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
             image, event = (v[0] if len(v) == 1 else torch.cat(v, dim=1) if v else torch.zeros(len(attn_layers), 0, maxlen, device=device)
                             for v in (sink.dev_rows["image_attn"], sink.dev_rows["event_attn"]))
             score_loader.last_result = {"attn_maps": {"image": image, "event": event, "layers": attn_layers, "row_offsets": offsets}}
@@ -1049,7 +1039,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                 # one library call (the host-list walk's usual case): its tensors as they are, no second copy
                 "row_outputs": {k: v[0] if len(v) == 1 else torch.cat(v) if v else torch.zeros(0, D, device=device)
                                 for k, v in sink.dev_rows.items()},
-                "row_offsets": np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)}
+                "row_offsets": offsets}
         return sink.finish(device, return_device)
 
 
@@ -1382,18 +1372,18 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     route or the `forward_videos` loop -- and the result dict gains "variants" (see there), "auc_variants" and "ap_variants": name ->
     the global AUC / AP of that variant's scores, by the metric tail in use (sklearn, or `iefvad_auc_ap`).  "fused" is what the call
     itself returns; nothing more is printed.  It does not combine with vis=True, `attn_maps` or `trajectory`."""
-    if fusion_variants is not None and fusion_variants is not False and \
-            (vis or trajectory or (attn_maps is not None and attn_maps is not False)):
-        raise ValueError("fusion_variants does not combine with vis=True, attn_maps or trajectory")
+    from .model import attn_maps_asked
+    want_maps = attn_maps_asked(attn_maps)
     want_variants = fusion_variants is not None and fusion_variants is not False
-    if trajectory and (vis or (attn_maps is not None and attn_maps is not False)):
+    if want_variants and (vis or trajectory or want_maps):
+        raise ValueError("fusion_variants does not combine with vis=True, attn_maps or trajectory")
+    if trajectory and (vis or want_maps):
         raise ValueError("trajectory=True does not combine with vis=True or attn_maps")
     if metric_tail not in ("host", "device"):
         raise ValueError('metric_tail must be "host" or "device"')
     if vis_route not in ("padded", "rows"):
         raise ValueError(f'vis_route must be "padded" or "rows" (got {vis_route!r})')
     vis_rows = bool(vis) and vis_route == "rows"
-    want_maps = attn_maps is not None and attn_maps is not False
     model.to(device)
     model.eval()
     if batch_chunks is None:

@@ -56,8 +56,8 @@ _ROW_ENTRIES = {
     "_full": ("_full", lambda r: (r["out"],), lambda r: (r["out"], r["stream"])),
     "_scaled": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
     "_perturbed": ("_scaled", lambda r: (r["with_colsum"],), lambda r: (*r["vectors"], r["w_colsum"], r["stream"])),
-    "_attn": ("", lambda r: (), lambda r: (*r["vectors"], r["maps"], r["stream"])),
-    "_trajectory": ("_trajectory", lambda r: (), lambda r: (*r["vectors"], r["traj"], r["stream"])),
+    "_attn": ("", lambda r: (), lambda r: (*r["vectors"], r["attn"], r["stream"])),
+    "_trajectory": ("_trajectory", lambda r: (), lambda r: (*r["vectors"], r["trajectory"], r["stream"])),
     "_variants": ("_variants", lambda r: (r["nvariants"],), lambda r: (*r["vectors"], r["variants"], r["stream"])),
 }
 
@@ -118,52 +118,207 @@ def _attn_maps_struct(image: torch.Tensor, event: torch.Tensor, layers) -> "_lib
     return m
 
 
-def _row_entry_suffix(similarity, outputs, full_entry: str, extras: bool = False):
+def attn_maps_asked(attn_maps) -> bool:
+    """Whether `attn_maps=` asks for maps at all -- the raw fact, before `attn_map_layers` parses (and may refuse) the value."""
+    return attn_maps is not None and attn_maps is not False
+
+
+def _given(pair) -> bool:      # a `row_scale` / `row_noise` pair that names at least one vector
+    return pair is not None and any(v is not None for v in pair)
+
+
+def _differentiable(a: torch.Tensor, b: torch.Tensor) -> bool:      # a call on these features has to be differentiable
+    return torch.is_grad_enabled() and (a.requires_grad or b.requires_grad)
+
+
+class _Request:
+    """What one call of `forward`, `forward_videos` or `forward_videos_host` asked for: built once from the raw keywords, each fact computed
+    once.  `maps_asked` is the raw view of `attn_maps=` and `layers` the parsed one: () until the checks parse it at its place in their order,
+    so a value that does not parse is refused there and not sooner.  `_PLAIN` is the call that asks for nothing."""
+    __slots__ = ("kind", "training", "grad", "eval_grad", "fp16x3", "bf16", "timed", "row_scale", "scaled", "attn_maps", "maps_asked", "layers", "row_noise",
+                 "noisy", "noise_seed", "noise_rows", "trajectory", "variants", "similarity", "outputs", "outputs_asked", "weight_sums", "nan_always", "extras")
+
+    def __init__(self, training=False, grad=False, compute="f32", *, timed=False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None,
+                 noise_rows=None, trajectory=False, fusion_variants=None, similarity=False, outputs=None, weight_sums=False, nan_to_num=True):
+        self.variants = fusion_variant_names(fusion_variants)      # parses, and may refuse, before anything else is looked at
+        self.training, self.grad, self.eval_grad = training, grad, grad and not training      # eval_grad: the differentiable eval route
+        self.fp16x3, self.bf16, self.timed, self.trajectory = compute == "fp16x3", compute == "bf16", timed, trajectory
+        self.attn_maps, self.maps_asked, self.layers = attn_maps, attn_maps_asked(attn_maps), ()
+        self.row_scale, self.scaled = row_scale, _given(row_scale)
+        self.row_noise, self.noisy, self.noise_seed, self.noise_rows = row_noise, _given(row_noise), noise_seed, noise_rows
+        self.similarity, self.outputs, self.outputs_asked, self.weight_sums = similarity, outputs, outputs is not None, weight_sums
+        self.nan_always = isinstance(nan_to_num, str) and nan_to_num == "always"
+        self.extras = self.nan_always or weight_sums or self.scaled or self.noisy      # the sweep's extras of the valid-row calls
+        self.kind = "plain"      # the row of `_DENSE_ENTRIES` that serves the request: `forward` names it once the checks have passed
+
+
+_PLAIN = _Request()
+
+
+def _noise_rules(noisy: bool, noise_seed, noise_rows):
+    """The seed and `noise_rows` rules of a noise request."""
+    if noisy and noise_seed is None:
+        raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
+    if noise_rows is not None and not noisy:
+        raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
+
+
+# The checks of a request, in the order they fire -- the order decides which error a caller sees, and tests/request_refusals.json pins it.
+# A step is a rule (owner, ((label, member), ...), exception, message): where the request's `owner` holds, the members that hold too are
+# refused, their labels joined into the message's {}; or a function of (model, request) that raises, or fills a fact in.
+_IN_TRAIN = (("model.train()", "training"),)
+_PARSE_LAYERS = lambda m, q: setattr(q, "layers", attn_map_layers(q.attn_maps, m.temporal.num_layers))
+_VARIANTS_SERVED = (      # where a fusion-variants request cannot be served: the fp16x3 arithmetic, training, differentiable features
+    ("variants", (("", "fp16x3"),), RuntimeError, 'fusion_variants= is not available with compute="fp16x3" (its per-chunk running-max words '
+     'have no home for the stacked states); use "f32", "bf16x6" or "bf16"'),
+    ("variants", _IN_TRAIN, RuntimeError, "fusion_variants= is an evaluation request; it is not available under {} (call model.eval() first)"),
+    ("variants", (("", "grad"),), RuntimeError, "fusion_variants= is an evaluation request: nothing it returns is differentiable, and a feature "
+     "tensor requires grad (detach the features, or call under torch.no_grad())"))
+_TRAJECTORY_IN_EVAL = ("trajectory", _IN_TRAIN, RuntimeError, "trajectory=True is an evaluation request; it is not available under {} (call model.eval() first)")
+_MAPS_SERVED = (      # where a maps request cannot be served: the bf16 arithmetic (its q | k | v are bf16 planes) and training
+    ("layers", (("", "bf16"),), RuntimeError, 'attn_maps= is not available with compute="bf16" (its q | k | v are bf16 planes in another layout); '
+     'use "f32", "bf16x6" or "fp16x3"'),
+    ("layers", _IN_TRAIN, RuntimeError, "attn_maps= is an evaluation request; it is not available under {} (call model.eval() first)"))
+_FORWARD_CHECKS = (
+    ("variants", (("timed=True", "timed"), ("trajectory=True", "trajectory"), ("attn_maps=", "maps_asked"), ("row_scale=", "scaled"), ("row_noise=", "noisy")),
+     ValueError, "fusion_variants= does not combine with {}: iefvad_forward_variants is a plain evaluation forward"),
+    *_VARIANTS_SERVED,
+    ("trajectory", (("timed=True", "timed"), ("attn_maps=", "maps_asked"), ("row_scale=", "scaled"), ("row_noise=", "noisy"), ("features that require grad", "grad")),
+     ValueError, "trajectory=True does not combine with {}: iefvad_forward_trajectory is a plain evaluation forward"),
+    _TRAJECTORY_IN_EVAL,
+    _PARSE_LAYERS,
+    lambda m, q: _noise_rules(q.noisy, q.noise_seed, q.noise_rows),
+    ("noisy", (("attn_maps=", "layers"), ("timed=True", "timed"), ("model.train()", "training"), ("features that require grad", "grad")),
+     ValueError, "row_noise= does not combine with {}: iefvad_forward_perturbed is a plain evaluation forward"),
+    ("layers", (("timed=True", "timed"), ("row_scale", "scaled")),
+     ValueError, "attn_maps= does not combine with timed=True or row_scale: iefvad_forward_attn takes neither"),
+    *_MAPS_SERVED,
+    # eval() with a feature tensor that requires grad: the reference differentiates here too, dropout simply off
+    ("eval_grad", (("attn_maps=", "layers"), ("timed=True", "timed"), ("row_scale=", "scaled")),
+     ValueError, "{} with a feature tensor that requires grad in eval(): the differentiable eval route runs the train-mode forward without "
+     "dropout, which takes none of attn_maps, timed and row_scale (detach the features, or call under torch.no_grad())"),
+)
+_SWEEP_MEMBERS = (("row_scale=", "scaled"), ("row_noise=", "noisy"), ("similarity=True", "similarity"), ("outputs=", "outputs_asked"),
+                  ("weight_sums=True", "weight_sums"), ("nan_to_num='always'", "nan_always"))
+_VIDEOS_CHECKS = (
+    ("variants", (("trajectory=True", "trajectory"), ("attn_maps=", "maps_asked")) + _SWEEP_MEMBERS,
+     ValueError, "fusion_variants= does not combine with {}: iefvad_forward_videos_variants takes none of them"),
+    *_VARIANTS_SERVED,
+    ("trajectory", (("attn_maps=", "maps_asked"),) + _SWEEP_MEMBERS,
+     ValueError, "trajectory=True does not combine with {}: iefvad_forward_videos_trajectory takes none of them"),
+    _TRAJECTORY_IN_EVAL,
+    _PARSE_LAYERS,
+    ("layers", _SWEEP_MEMBERS, ValueError, "attn_maps= does not combine with similarity=True, outputs=, row_scale, row_noise, weight_sums or "
+     "nan_to_num='always': iefvad_forward_videos_attn takes none of them"),
+    *_MAPS_SERVED,
+    ("training", _IN_TRAIN, RuntimeError, "iefvad_amd.MMFMIL.forward_videos is an evaluation entry point; call model.eval() first"),
+)
+
+
+def _check_request(model, q: _Request, checks):
+    """Walk one of the tables above; the first step that objects raises."""
+    for step in checks:
+        if callable(step):
+            step(model, q)
+        elif getattr(q, step[0]):
+            asked = [label for label, member in step[1] if getattr(q, member)]
+            if asked:
+                raise step[2](step[3].format(" / ".join(asked)))
+
+
+def _row_entry_suffix(q: _Request, full_entry: str):
     """The exclusion rules between `similarity=`, `outputs=` and the sweep's extras of the valid-row calls -> (the [rows, D] keys asked
     for, the suffix of the entry that serves the request).  `full_entry`: the full entry's name, for the message."""
-    if similarity and extras:
+    if q.similarity and q.extras:
         raise ValueError("similarity=True does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
                          "iefvad_forward_videos_scaled takes no similarity buffer")
-    wide = _row_output_keys(outputs)
-    if wide and similarity:
+    wide = _row_output_keys(q.outputs)
+    if wide and q.similarity:
         raise ValueError(f"outputs= does not combine with similarity=True: {full_entry} takes no similarity buffer "
                          "(reduce the returned rows with harness.similarity_rows)")
-    if wide and extras:
+    if wide and q.extras:
         raise ValueError("outputs= does not combine with the sweep's extras (row_scale, weight_sums, nan_to_num='always'): "
                          "iefvad_forward_videos_scaled returns no [rows, D] tensor")
-    return wide, "_scaled" if extras else "_full" if wide else "_similarity" if similarity else ""
+    return wide, "_perturbed" if q.noisy else "_variants" if q.variants else "_trajectory" if q.trajectory else "_attn" if q.layers else \
+        "_scaled" if q.extras else "_full" if wide else "_similarity" if q.similarity else ""
+
+
+def _vector_pair(name: str, pair, nrows: int, device, what: str) -> tuple:
+    """`row_scale` / `row_noise` -> the pair of None or contiguous fp32 vectors of `nrows` elements on `device` (ValueError otherwise)."""
+    pair = (None, None) if pair is None else tuple(pair)
+    if len(pair) != 2:
+        raise ValueError(f"{name} must be a pair (image vector, event vector), either may be None")
+    for v in pair:
+        if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != device or v.numel() != nrows
+                              or not v.is_contiguous()):
+            raise ValueError(f"{name} vectors must be contiguous fp32 tensors of {nrows} elements ({what}) on {device}")
+    return pair
 
 
 def _perturb_struct(nrows: int, device, row_scale, row_noise, noise_seed, noise_rows, what: str):
     """The `iefvad_perturb` of a call over `nrows` rows on `device`, and whether it carries noise.  `row_scale` / `row_noise`: None or a pair
     of contiguous fp32 device vectors of `nrows` elements (either may be None); `noise_rows`: None or a contiguous int32 device vector of
     noise ids; `noise_seed`: the generator's seed, required with `row_noise` (ValueError).  `what` names the row count in the messages."""
-    pairs = {}
-    for name, pair in (("row_scale", row_scale), ("row_noise", row_noise)):
-        pair = (None, None) if pair is None else tuple(pair)
-        if len(pair) != 2:
-            raise ValueError(f"{name} must be a pair (image vector, event vector), either may be None")
-        for v in pair:
-            if v is not None and (not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != device or v.numel() != nrows
-                                  or not v.is_contiguous()):
-                raise ValueError(f"{name} vectors must be contiguous fp32 tensors of {nrows} elements ({what}) on {device}")
-        pairs[name] = pair
-    noisy = any(v is not None for v in pairs["row_noise"])
-    if noisy and noise_seed is None:
-        raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
-    if noise_rows is not None:
-        if not noisy:
-            raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
-        if (not isinstance(noise_rows, torch.Tensor) or noise_rows.dtype != torch.int32 or noise_rows.device != device
-                or noise_rows.numel() != nrows or not noise_rows.is_contiguous()):
-            raise ValueError(f"noise_rows must be a contiguous int32 tensor of {nrows} elements ({what}) on {device}")
+    scale = _vector_pair("row_scale", row_scale, nrows, device, what)
+    amp = _vector_pair("row_noise", row_noise, nrows, device, what)
+    noisy = _given(amp)
+    _noise_rules(noisy, noise_seed, noise_rows)
+    if noise_rows is not None and (not isinstance(noise_rows, torch.Tensor) or noise_rows.dtype != torch.int32 or noise_rows.device != device
+                                   or noise_rows.numel() != nrows or not noise_rows.is_contiguous()):
+        raise ValueError(f"noise_rows must be a contiguous int32 tensor of {nrows} elements ({what}) on {device}")
     p = _lib.Perturb()
     for m in (0, 1):
-        p.scale[m] = pairs["row_scale"][m].data_ptr() if pairs["row_scale"][m] is not None else None
-        p.noise_amp[m] = pairs["row_noise"][m].data_ptr() if pairs["row_noise"][m] is not None else None
+        p.scale[m] = scale[m].data_ptr() if scale[m] is not None else None
+        p.noise_amp[m] = amp[m].data_ptr() if amp[m] is not None else None
     p.noise_row = noise_rows.data_ptr() if noise_rows is not None else None
     p.seed = (int(noise_seed) & 0xFFFFFFFFFFFFFFFF) if noise_seed is not None else 0
     return p, noisy
+
+
+# What an attn / trajectory / variants request adds to a call on either route: (the results, in the order they are returned behind the
+# others, as a function of (request, steps, shape of `logits`, shape of one per-row vector -- (B, T) dense, (total,) on valid rows --, T,
+# new fp32 tensor of a shape); the entry's argument that points at them, as a function of (request, those results, rows in all)).
+_EXTRA_RESULTS = {
+    "attn": (lambda q, steps, logits, rows, T, new: {"image_attn": new(len(q.layers), *rows, T), "event_attn": new(len(q.layers), *rows, T),
+                                                     "attn_layers": q.layers},
+             lambda q, res, n: C.byref(_attn_maps_struct(res["image_attn"], res["event_attn"], q.layers))),
+    "trajectory": (lambda q, steps, logits, rows, T, new: {"logits_steps": new(steps + 1, *logits), "delta_norm": new(steps, *rows)},
+                   lambda q, res, n: C.byref(_lib.Trajectory(res["logits_steps"].data_ptr(), res["delta_norm"].data_ptr() if len(res["delta_norm"]) else None, n))),
+    "variants": (lambda q, steps, logits, rows, T, new: {"logits_variants": new(len(q.variants), *rows), "fusion_variants": q.variants},
+                 lambda q, res, n: C.byref(_variants_struct(q.variants, res["logits_variants"], n))),
+}
+
+
+def _timed_arg(m, q, n, device):
+    st = _lib.StageTimes()
+    return (C.byref(st),), lambda: setattr(m, "last_stage_times", st.as_dict())
+
+
+def _scaled_arg(m, q, n, device):
+    for sv in q.row_scale:
+        if sv is not None and (sv.dtype != torch.float32 or sv.device != device or sv.numel() != n or not sv.is_contiguous()):
+            raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {n} elements on {device}")
+    return tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in q.row_scale), None
+
+
+# The dense entries ([B, T, D] in, `MMFMIL._dense_call`) by the kind of the request (`_Request.kind`), each with: the entry; the
+# prefix of the RuntimeError of a failed call; its workspace query and the query's arguments behind (handle, B); the index at which its
+# own argument(s) stand in the plain entry's argument list; the function of (model, request, B * T, device) that forms them and says what
+# to do after the call -- None where the kind has a row in `_EXTRA_RESULTS`, which also names the results behind OUTPUT_KEYS in the full dict.
+_DENSE_ENTRIES = {
+    "plain": ("iefvad_forward", "iefvad_forward", "iefvad_workspace_bytes", lambda q: (), 9, None),
+    "timed": ("iefvad_forward_timed", "iefvad_forward", "iefvad_workspace_bytes", lambda q: (), 9, _timed_arg),
+    "scaled": ("iefvad_forward_scaled", "iefvad_forward", "iefvad_workspace_bytes", lambda q: (), 5, _scaled_arg),
+    "perturbed": ("iefvad_forward_perturbed", "iefvad_forward_perturbed", "iefvad_workspace_bytes", lambda q: (), 5,
+                  lambda m, q, n, device: ((C.byref(_perturb_struct(n, device, q.row_scale, q.row_noise, q.noise_seed, q.noise_rows, "B*T")[0]),), None)),
+    "attn": ("iefvad_forward_attn", "iefvad_forward_attn", "iefvad_workspace_bytes", lambda q: (), 8, None),
+    "trajectory": ("iefvad_forward_trajectory", "iefvad_forward_trajectory", "iefvad_trajectory_workspace_bytes", lambda q: (), 8, None),
+    "variants": ("iefvad_forward_variants", "iefvad_forward_variants", "iefvad_variants_workspace_bytes", lambda q: (len(q.variants),), 8, None),
+}
+# what `MMFMIL(outputs=)` makes every dense call return, in the order of the returned dict: (key, its shape behind [B, T]; None = D)
+_DENSE_OUTPUTS = {"full": tuple((k, (1,) if k == "logits" else None) for k in OUTPUT_KEYS),
+                  "weights": (("logits", (1,)), ("w_i", None), ("w_e", None), ("w_i_mean", ()), ("w_e_mean", ())),
+                  "scores": (("logits", (1,)), ("w_i_mean", ()), ("w_e_mean", ()))}
 
 
 def perturb_rows(img_rows: Optional[torch.Tensor], ev_rows: Optional[torch.Tensor], *, row_scale=None, row_noise=None, noise_seed=None,
@@ -536,16 +691,18 @@ class MMFMIL(nn.Module):
             if m._handle is not None and _lib.load_library().iefvad_set_steps(m._handle, K if k is None else int(k)) != 0:
                 raise RuntimeError("iefvad_set_steps: " + _lib.last_error())
 
-    def _ensure_weights(self, device: torch.device, stream: int):
-        t = self.temporal
+    def _params(self) -> list:
         # (owner's _parameters dict, name) of every parameter, resolved once: walking the module tree on every call costs
         # more host time than the rest of a one-chunk forward's enqueue; looking the slots up each time still sees a
         # Parameter that was re-assigned
         slots = self.__dict__.get("_param_slots")
         if slots is None:
-            slots = [(m._parameters, n) for m in t.modules() for n in m._parameters if m._parameters[n] is not None]
+            slots = [(m._parameters, n) for m in self.temporal.modules() for n in m._parameters if m._parameters[n] is not None]
             self.__dict__["_param_slots"] = slots
-        params = [d[n] for d, n in slots]
+        return [d[n] for d, n in slots]
+
+    def _ensure_weights(self, device: torch.device, stream: int):
+        params = self._params()
         sig = tuple((p.data_ptr(), p._version) for p in params)
         if sig == self._weights_sig:
             return
@@ -624,6 +781,11 @@ class MMFMIL(nn.Module):
             x = x.to(torch.float)        # imf_vad.py:41-42 for fp64 / integer inputs
         return x.contiguous()
 
+    def _prepare_pair(self, img: torch.Tensor, ev: torch.Tensor) -> tuple:
+        """Both feature tensors as the library takes them: contiguous, of one supported dtype."""
+        img, ev = self._prepare_input(img), self._prepare_input(ev)
+        return (img, ev) if ev.dtype == img.dtype else (img.to(torch.float), ev.to(torch.float))
+
     def forward(self, img_visual, ev_visual, padding_mask=None, text=None, lengths=None, return_attn=False,
                 *, timed: bool = False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None, noise_rows=None,
                 trajectory: bool = False, fusion_variants=None) -> Dict[str, torch.Tensor]:
@@ -657,165 +819,74 @@ class MMFMIL(nn.Module):
         repeated name, and a combination with `timed`, `trajectory`, `attn_maps`, `row_scale` or `row_noise`, is a ValueError;
         compute="fp16x3", model.train() and a feature tensor that requires grad are RuntimeErrors."""
         self._noise_code()   # ValueError for an unsupported noise_model, as the reference raises
-        variants = fusion_variant_names(fusion_variants)
-        if variants:
-            asked = [n for n, on in (("timed=True", timed), ("trajectory=True", trajectory),
-                                     ("attn_maps=", attn_maps is not None and attn_maps is not False),
-                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
-                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise))) if on]
-            if asked:
-                raise ValueError(f"fusion_variants= does not combine with {' / '.join(asked)}: iefvad_forward_variants is a plain evaluation forward")
-            self._variants_served(torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad))
-        if trajectory:
-            grad = torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad)
-            asked = [n for n, on in (("timed=True", timed), ("attn_maps=", attn_maps is not None and attn_maps is not False),
-                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
-                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise)),
-                                     ("features that require grad", grad)) if on]
-            if asked:
-                raise ValueError(f"trajectory=True does not combine with {' / '.join(asked)}: iefvad_forward_trajectory is a plain evaluation forward")
-            if self.training:
-                raise RuntimeError("trajectory=True is an evaluation request; it is not available under model.train() (call model.eval() first)")
-        layers = attn_map_layers(attn_maps, self.temporal.num_layers)
-        noisy = row_noise is not None and any(v is not None for v in row_noise)
-        if noisy:
-            if noise_seed is None:
-                raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
-            grad = torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad)
-            asked = [n for n, on in (("attn_maps=", bool(layers)), ("timed=True", timed), ("model.train()", self.training),
-                                     ("features that require grad", grad)) if on]
-            if asked:
-                raise ValueError(f"row_noise= does not combine with {' / '.join(asked)}: iefvad_forward_perturbed is a plain evaluation forward")
-        elif noise_rows is not None:
-            raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
-        if layers:
-            if timed or (row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None)):
-                raise ValueError("attn_maps= does not combine with timed=True or row_scale: iefvad_forward_attn takes neither")
-            self._attn_maps_served("model.train()" if self.training else None)
-        if self.training:
-            return self._forward_train(img_visual, ev_visual)
-        if torch.is_grad_enabled() and (img_visual.requires_grad or ev_visual.requires_grad):
-            # eval() with a feature tensor that requires grad: the reference differentiates here too, dropout simply off
-            scaled = row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None)
-            asked = [n for n, on in (("attn_maps=", bool(layers)), ("timed=True", timed), ("row_scale=", scaled)) if on]
-            if asked:
-                raise ValueError(f"{' / '.join(asked)} with a feature tensor that requires grad in eval(): the differentiable eval route "
-                                 "runs the train-mode forward without dropout, which takes none of attn_maps, timed and row_scale "
-                                 "(detach the features, or call under torch.no_grad())")
-            return self._forward_train(img_visual, ev_visual, no_dropout=True)
+        grad = _differentiable(img_visual, ev_visual)
+        if not (grad or self.training or timed or trajectory or row_scale is not None or attn_maps is not None or row_noise is not None
+                or noise_rows is not None or fusion_variants is not None):
+            q = _PLAIN      # nothing asked for: nothing to check
+        else:
+            q = _Request(self.training, grad, self.compute, timed=timed, row_scale=row_scale, attn_maps=attn_maps, row_noise=row_noise, noise_seed=noise_seed,
+                         noise_rows=noise_rows, trajectory=trajectory, fusion_variants=fusion_variants)
+            _check_request(self, q, _FORWARD_CHECKS)
+            if q.training or q.grad:
+                return self._forward_train(img_visual, ev_visual, no_dropout=not q.training)
+            q.kind = "trajectory" if q.trajectory else "variants" if q.variants else "attn" if q.layers else "perturbed" if q.noisy else \
+                "scaled" if q.scaled else "timed" if q.timed else "plain"      # the checks have refused what no entry serves
+        return self._dense_call(q, img_visual, ev_visual, *self._check_dense_inputs(img_visual, ev_visual))
+
+    def _check_dense_inputs(self, img_visual, ev_visual) -> tuple:
+        """The device, shape and [B, T, D] against the model checks of a dense call -> (B, T, D)."""
         if not (img_visual.is_cuda and ev_visual.is_cuda):
-            raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback "
-                               "(move the inputs with .to('cuda'))")
+            raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback (move the inputs with .to('cuda'))")
         if img_visual.shape != ev_visual.shape or img_visual.dim() != 3:
-            raise ValueError(f"expected two [B, T, D] tensors of equal shape, got {tuple(img_visual.shape)} and "
-                             f"{tuple(ev_visual.shape)}")
+            raise ValueError(f"expected two [B, T, D] tensors of equal shape, got {tuple(img_visual.shape)} and {tuple(ev_visual.shape)}")
         B, T, D = img_visual.shape
         if T != self.visual_length or D != self.temporal.embed_dim:
             raise ValueError(f"expected [B, {self.visual_length}, {self.temporal.embed_dim}] inputs, got [B, {T}, {D}]")
+        return B, T, D
+
+    def _ensure_workspace(self, device, need: int) -> torch.Tensor:
+        """The workspace the caller of the library owns, grown to `need` bytes on `device`."""
+        if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
+            self._workspace = None
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
+        return self._workspace
+
+    def _dense_call(self, q: _Request, img_visual, ev_visual, B, T, D) -> Dict[str, torch.Tensor]:
+        """One dense call, the row of `_DENSE_ENTRIES` that serves `q`: sizes the workspace by the row's query, allocates the results
+        `self.outputs` names and the row's own, and calls the entry with its own argument(s) at their place."""
+        kind = q.kind
+        entry, prefix, query, query_args, at, own = _DENSE_ENTRIES[kind]
         device = img_visual.device
-        img = self._prepare_input(img_visual)
-        ev = self._prepare_input(ev_visual)
-        if ev.dtype != img.dtype:
-            img, ev = img.to(torch.float), ev.to(torch.float)
+        img, ev = self._prepare_pair(img_visual, ev_visual)
         lib = _lib.load_library()
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
             self._ensure_handle(device)
             self._ensure_weights(device, stream)
-            need = lib.iefvad_trajectory_workspace_bytes(self._handle, B) if trajectory else \
-                lib.iefvad_variants_workspace_bytes(self._handle, B, len(variants)) if variants else lib.iefvad_workspace_bytes(self._handle, B)
-            if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
-                self._workspace = None
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-            N = B * T
+            ws = self._ensure_workspace(device, getattr(lib, query)(self._handle, B, *query_args(q)))
             f32 = dict(dtype=torch.float32, device=device)
             res: Dict[str, torch.Tensor] = {}
             o = _lib.Outputs()
-            res["logits"] = torch.empty(B, T, 1, **f32)
-            o.logits = res["logits"].data_ptr()
-            if self.outputs == "full":
-                for k in OUTPUT_KEYS:
-                    if k != "logits":
-                        res[k] = torch.empty(B, T, D, **f32)
-                        setattr(o, k, res[k].data_ptr())
-            else:
-                if self.outputs == "weights":       # the sweep's set (test2.py:65-68,86-87): both weight tensors, and their row means
-                    for k in ("w_i", "w_e"):
-                        res[k] = torch.empty(B, T, D, **f32)
-                        setattr(o, k, res[k].data_ptr())
-                res["w_i_mean"] = torch.empty(B, T, **f32)
-                res["w_e_mean"] = torch.empty(B, T, **f32)
-                o.w_i_mean, o.w_e_mean = res["w_i_mean"].data_ptr(), res["w_e_mean"].data_ptr()
-            args = (self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], B,
-                    C.c_void_p(self._workspace.data_ptr()), self._workspace.numel(), C.byref(o), C.c_void_p(stream))
-            if trajectory:
-                steps = self.steps
-                ls = torch.empty(steps + 1, B, T, 1, **f32)
-                dn = torch.empty(steps, B, T, **f32)
-                traj = _lib.Trajectory(ls.data_ptr(), dn.data_ptr() if steps else None, N)
-                rc = lib.iefvad_forward_trajectory(*args[:8], C.byref(traj), args[8])
-                if rc != 0:
-                    raise RuntimeError("iefvad_forward_trajectory: " + _lib.last_error())
-                res["logits_steps"], res["delta_norm"] = ls, dn
-            elif variants:
-                res["logits_variants"] = torch.empty(len(variants), B, T, **f32)
-                res["fusion_variants"] = variants
-                vs = _variants_struct(variants, res["logits_variants"], N)
-                rc = lib.iefvad_forward_variants(*args[:8], C.byref(vs), args[8])
-                if rc != 0:
-                    raise RuntimeError("iefvad_forward_variants: " + _lib.last_error())
-            elif layers:
-                res["image_attn"] = torch.empty(len(layers), B, T, T, **f32)
-                res["event_attn"] = torch.empty(len(layers), B, T, T, **f32)
-                res["attn_layers"] = layers
-                maps = _attn_maps_struct(res["image_attn"], res["event_attn"], layers)
-                rc = lib.iefvad_forward_attn(*args[:8], C.byref(maps), args[8])
-                if rc != 0:
-                    raise RuntimeError("iefvad_forward_attn: " + _lib.last_error())
-            elif noisy:
-                pert, _ = _perturb_struct(N, device, row_scale, row_noise, noise_seed, noise_rows, "B*T")
-                rc = lib.iefvad_forward_perturbed(*args[:5], C.byref(pert), *args[5:])
-                if rc != 0:
-                    raise RuntimeError("iefvad_forward_perturbed: " + _lib.last_error())
-            elif row_scale is not None and (row_scale[0] is not None or row_scale[1] is not None):
-                sp = []
-                for sv in row_scale:
-                    if sv is not None and (sv.dtype != torch.float32 or sv.device != device or sv.numel() != N or not sv.is_contiguous()):
-                        raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {N} elements on {device}")
-                    sp.append(C.c_void_p(sv.data_ptr()) if sv is not None else None)
-                rc = lib.iefvad_forward_scaled(*args[:5], sp[0], sp[1], *args[5:])
-            elif timed:
-                st = _lib.StageTimes()
-                rc = lib.iefvad_forward_timed(*args, C.byref(st))
-                self.last_stage_times = st.as_dict()
-            else:
-                rc = lib.iefvad_forward(*args)
+            for k, tail in _DENSE_OUTPUTS[self.outputs]:      # "weights": the sweep's set (test2.py:65-68,86-87), both weight tensors and their row means
+                res[k] = torch.empty(B, T, *((D,) if tail is None else tail), **f32)
+                setattr(o, k, res[k].data_ptr())
+            call = [self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], B,
+                    C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(o), C.c_void_p(stream)]
+            extra, after = {}, None
+            if kind in _EXTRA_RESULTS:
+                extra = _EXTRA_RESULTS[kind][0](q, self.steps, (B, T, 1), (B, T), T, lambda *shape: torch.empty(shape, **f32))
+                res.update(extra)
+                call.insert(at, _EXTRA_RESULTS[kind][1](q, extra, B * T))
+            elif own is not None:
+                call[at:at], after = own(self, q, B * T, device)
+            rc = getattr(lib, entry)(*call)
+            if after is not None:
+                after()
             if rc != 0:
-                raise RuntimeError("iefvad_forward: " + _lib.last_error())
+                raise RuntimeError(prefix + ": " + _lib.last_error())
         if self.outputs == "full":
-            extra = ("image_attn", "event_attn", "attn_layers") if layers else ("logits_steps", "delta_norm") if trajectory else \
-                ("logits_variants", "fusion_variants") if variants else ()
-            return {k: res[k] for k in OUTPUT_KEYS + extra}   # the reference's key order
+            return {k: res[k] for k in (*OUTPUT_KEYS, *extra)}   # the reference's key order
         return res
-
-    def _variants_served(self, grad: bool):
-        """RuntimeError where a fusion-variants request cannot be served: the fp16x3 arithmetic, training, differentiable features."""
-        if self.compute == "fp16x3":
-            raise RuntimeError('fusion_variants= is not available with compute="fp16x3" (its per-chunk running-max words have no home for '
-                               'the stacked states); use "f32", "bf16x6" or "bf16"')
-        if self.training:
-            raise RuntimeError("fusion_variants= is an evaluation request; it is not available under model.train() (call model.eval() first)")
-        if grad:
-            raise RuntimeError("fusion_variants= is an evaluation request: nothing it returns is differentiable, and a feature tensor "
-                               "requires grad (detach the features, or call under torch.no_grad())")
-
-    def _attn_maps_served(self, mode):
-        """RuntimeError where a maps request cannot be served: the bf16 arithmetic (its q | k | v are bf16 planes) and training."""
-        if self.compute == "bf16":
-            raise RuntimeError('attn_maps= is not available with compute="bf16" (its q | k | v are bf16 planes in another layout); '
-                               'use "f32", "bf16x6" or "fp16x3"')
-        if mode:
-            raise RuntimeError(f"attn_maps= is an evaluation request; it is not available under {mode} (call model.eval() first)")
 
     def forward_videos_host(self, imgs, evs, lengths, nan_to_num: bool = True, batch_chunks: int = 128, host_threads: int = 0,
                             wire_dtype: Optional[torch.dtype] = None, similarity: bool = False, *, outputs=None) -> Dict[str, torch.Tensor]:
@@ -833,7 +904,8 @@ class MMFMIL(nn.Module):
         if self.training:
             raise RuntimeError("iefvad_amd.MMFMIL.forward_videos_host is an evaluation entry point; call model.eval() first")
         self._noise_code()
-        wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_host_full")
+        q = _Request(similarity=similarity, outputs=outputs)
+        wide, suffix = _row_entry_suffix(q, "iefvad_forward_videos_host_full")
         lens = [int(n) for n in lengths]
         if not lens or min(lens) < 1 or len(imgs) != len(lens) or len(evs) != len(lens):
             raise ValueError("imgs, evs and lengths must list the same videos, every video at least one snippet")
@@ -856,12 +928,12 @@ class MMFMIL(nn.Module):
         if device.type != "cuda":
             raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback (call model.to('cuda'))")
         front = (pi, pe, _IN_DTYPES[dt], _IN_DTYPES[wire], (C.c_int32 * n)(*lens), n, 1 if nan_to_num else 0, int(batch_chunks), int(host_threads))
-        return self._rows_call("iefvad_forward_videos_host", suffix, device, sum(lens), front, wide=wide)
+        return self._rows_call("iefvad_forward_videos_host", suffix, q, device, sum(lens), front, wide=wide)
 
-    def _rows_call(self, base, suffix, device, total, front, *, wide=(), weight_sums=False, workspace_for=None, attn_layers=(), variants=()):
+    def _rows_call(self, base, suffix, q: _Request, device, total, front, *, wide=(), workspace_for=None):
         """One valid-row call, the entry `base + suffix` (`_ROW_ENTRIES`): allocates the results -- the three [total] vectors, a
-        [total, D] tensor per key of `wide`, the similarity entries' [4, total] series, `w_colsum` -- and calls the entry with
-        (handle, *front, [workspace, bytes,] the suffix's tail).  `workspace_for=(lengths array, nvideos)`: the device entries, whose
+        [total, D] tensor per key of `wide`, the similarity entries' [4, total] series, `w_colsum`, the suffix's `_EXTRA_RESULTS` -- and calls the
+        entry with (handle, *front, [workspace, bytes,] the suffix's tail).  `workspace_for=(lengths array, nvideos)`: the device entries, whose
         workspace the caller owns; it is sized by the suffix's query."""
         lib, name = _lib.load_library(), base + suffix
         query, query_tail, tail = _ROW_ENTRIES[suffix]
@@ -873,26 +945,12 @@ class MMFMIL(nn.Module):
             f32 = dict(dtype=torch.float32, device=device)
             res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
             r = {"vectors": tuple(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), "stream": C.c_void_p(stream), "out": None,
-                 "similarity": None, "w_colsum": None, "with_colsum": 1 if weight_sums else 0, "maps": None, "traj": None,
-                 "variants": None, "nvariants": len(variants)}
-            if suffix == "_variants":
-                res["logits_variants"] = torch.empty(len(variants), total, **f32)
-                res["fusion_variants"] = tuple(variants)
-                vs = _variants_struct(variants, res["logits_variants"], total)
-                r["variants"] = C.byref(vs)
-            if suffix == "_trajectory":
-                steps = self.steps
-                res["logits_steps"] = torch.empty(steps + 1, total, **f32)
-                res["delta_norm"] = torch.empty(steps, total, **f32)
-                traj = _lib.Trajectory(res["logits_steps"].data_ptr(), res["delta_norm"].data_ptr() if steps else None, total)
-                r["traj"] = C.byref(traj)
-            if suffix == "_attn":
-                T = self.visual_length
-                res["image_attn"] = torch.empty(len(attn_layers), total, T, **f32)
-                res["event_attn"] = torch.empty(len(attn_layers), total, T, **f32)
-                res["attn_layers"] = tuple(attn_layers)
-                maps = _attn_maps_struct(res["image_attn"], res["event_attn"], attn_layers)
-                r["maps"] = C.byref(maps)
+                 "similarity": None, "w_colsum": None, "with_colsum": 1 if q.weight_sums else 0, "attn": None, "trajectory": None,
+                 "variants": None, "nvariants": len(q.variants)}
+            if suffix[1:] in _EXTRA_RESULTS:
+                extra = _EXTRA_RESULTS[suffix[1:]][0](q, self.steps, (total,), (total,), self.visual_length, lambda *shape: torch.empty(shape, **f32))
+                res.update(extra)
+                r[suffix[1:]] = _EXTRA_RESULTS[suffix[1:]][1](q, extra, total)
             if suffix == "_full":
                 o = _lib.Outputs()
                 for k in res:
@@ -904,16 +962,13 @@ class MMFMIL(nn.Module):
             if suffix == "_similarity":
                 res["similarity"] = torch.empty(4, total, **f32)
                 r["similarity"] = C.c_void_p(res["similarity"].data_ptr())
-            if weight_sums:
+            if q.weight_sums:
                 res["w_colsum"] = torch.empty(2, D, dtype=torch.float64, device=device)
                 r["w_colsum"] = C.c_void_p(res["w_colsum"].data_ptr())
             front = (self._handle, *front)
             if workspace_for is not None:
-                need = getattr(lib, f"iefvad_videos{query}_workspace_bytes")(self._handle, *workspace_for, *query_tail(r))
-                if self._workspace is None or self._workspace.device != device or self._workspace.numel() < need:
-                    self._workspace = None
-                    self._workspace = torch.empty(need, dtype=torch.uint8, device=device)
-                front += (C.c_void_p(self._workspace.data_ptr()), self._workspace.numel())
+                ws = self._ensure_workspace(device, getattr(lib, f"iefvad_videos{query}_workspace_bytes")(self._handle, *workspace_for, *query_tail(r)))
+                front += (C.c_void_p(ws.data_ptr()), ws.numel())
             rc = getattr(lib, name)(*front, *tail(r))
         if rc != 0:
             raise RuntimeError(name + ": " + _lib.last_error())
@@ -932,20 +987,8 @@ class MMFMIL(nn.Module):
         if self.temporal.embed_dim != 768:
             raise RuntimeError(f"iefvad_amd.MMFMIL trains at D=768 only (this model has D={self.temporal.embed_dim}: "
                                "the D=512 path is the f32 evaluation forward)")
-        if not (img_visual.is_cuda and ev_visual.is_cuda):
-            raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback "
-                               "(move the inputs with .to('cuda'))")
-        if img_visual.shape != ev_visual.shape or img_visual.dim() != 3:
-            raise ValueError(f"expected two [B, T, D] tensors of equal shape, got {tuple(img_visual.shape)} and "
-                             f"{tuple(ev_visual.shape)}")
-        B, T, D = img_visual.shape
-        if T != self.visual_length or D != self.temporal.embed_dim:
-            raise ValueError(f"expected [B, {self.visual_length}, {self.temporal.embed_dim}] inputs, got [B, {T}, {D}]")
-        slots = self.__dict__.get("_param_slots")
-        if slots is None:
-            slots = [(m._parameters, n) for m in self.temporal.modules() for n in m._parameters if m._parameters[n] is not None]
-            self.__dict__["_param_slots"] = slots
-        params = [d[n] for d, n in slots]
+        self._check_dense_inputs(img_visual, ev_visual)
+        params = self._params()
         # a feature tensor that requires grad is an input of the node as it is (its dtype, its strides: the widening and the
         # contiguous copy happen inside the node, so the gradient lands on the caller's tensor); the others are detached
         img_in = img_visual if img_visual.requires_grad else img_visual.detach()
@@ -991,72 +1034,29 @@ class MMFMIL(nn.Module):
         combines with none of `trajectory`, `attn_maps`, `row_scale`, `row_noise`, `similarity`, `outputs`, `weight_sums` and
         nan_to_num="always" (ValueError); compute="fp16x3", model.train() and rows that require grad raise RuntimeError.
         An evaluation entry: nothing it returns is differentiable (rows that require grad get no gradient here; use `forward`)."""
-        variants = fusion_variant_names(fusion_variants)
-        if variants:
-            asked = [n for n, on in (("trajectory=True", trajectory), ("attn_maps=", attn_maps is not None and attn_maps is not False),
-                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
-                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise)),
-                                     ("similarity=True", similarity), ("outputs=", outputs is not None), ("weight_sums=True", weight_sums),
-                                     ("nan_to_num='always'", isinstance(nan_to_num, str) and nan_to_num == "always")) if on]
-            if asked:
-                raise ValueError(f"fusion_variants= does not combine with {' / '.join(asked)}: iefvad_forward_videos_variants takes none of them")
-            self._variants_served(torch.is_grad_enabled() and (img_rows.requires_grad or ev_rows.requires_grad))
-        if trajectory:
-            asked = [n for n, on in (("attn_maps=", attn_maps is not None and attn_maps is not False),
-                                     ("row_scale=", row_scale is not None and any(v is not None for v in row_scale)),
-                                     ("row_noise=", row_noise is not None and any(v is not None for v in row_noise)),
-                                     ("similarity=True", similarity), ("outputs=", outputs is not None), ("weight_sums=True", weight_sums),
-                                     ("nan_to_num='always'", isinstance(nan_to_num, str) and nan_to_num == "always")) if on]
-            if asked:
-                raise ValueError(f"trajectory=True does not combine with {' / '.join(asked)}: iefvad_forward_videos_trajectory takes none of them")
-            if self.training:
-                raise RuntimeError("trajectory=True is an evaluation request; it is not available under model.train() (call model.eval() first)")
-        layers = attn_map_layers(attn_maps, self.temporal.num_layers)
-        if layers:
-            if similarity or outputs is not None or weight_sums or nan_to_num == "always" or \
-                    (row_scale is not None and any(sv is not None for sv in row_scale)) or \
-                    (row_noise is not None and any(sv is not None for sv in row_noise)):
-                raise ValueError("attn_maps= does not combine with similarity=True, outputs=, row_scale, row_noise, weight_sums or nan_to_num='always': "
-                                 "iefvad_forward_videos_attn takes none of them")
-            self._attn_maps_served("model.train()" if self.training else None)
-        if self.training:
-            raise RuntimeError("iefvad_amd.MMFMIL.forward_videos is an evaluation entry point; call model.eval() first")
-        self._noise_code()
-        if isinstance(nan_to_num, str):
-            if nan_to_num != "always":
-                raise ValueError(f"nan_to_num must be True, False or 'always' (got {nan_to_num!r})")
-            nan_mode = 2
+        if not (self.training or row_scale is not None or weight_sums or similarity or outputs is not None or attn_maps is not None
+                or row_noise is not None or noise_rows is not None or trajectory or fusion_variants is not None or isinstance(nan_to_num, str)):
+            q = _PLAIN      # nothing asked for: nothing to check
         else:
-            nan_mode = 1 if nan_to_num else 0
-        scales = (None, None) if row_scale is None else tuple(row_scale)
-        if len(scales) != 2:
-            raise ValueError("row_scale must be a pair (image vector, event vector), either may be None")
-        nrows = sum(int(n) for n in lengths)
-        for sv in scales:
-            if sv is not None and (not isinstance(sv, torch.Tensor) or sv.dtype != torch.float32 or sv.device != img_rows.device
-                                   or sv.numel() != nrows or not sv.is_contiguous()):
-                raise ValueError(f"row_scale vectors must be contiguous fp32 tensors of {nrows} elements (sum of lengths) on {img_rows.device}")
-        noisy = row_noise is not None and any(v is not None for v in row_noise)
-        if noisy and noise_seed is None:
-            raise ValueError("row_noise needs noise_seed: the noise is a pure function of (seed, modality, noise id, column)")
-        if noise_rows is not None and not noisy:
-            raise ValueError("noise_rows without row_noise: the noise ids name rows of a noise request")
-        extras = nan_mode == 2 or weight_sums or scales[0] is not None or scales[1] is not None or noisy
-        wide, suffix = _row_entry_suffix(similarity, outputs, "iefvad_forward_videos_full", extras)
-        if layers:
-            suffix = "_attn"
-        if trajectory:
-            suffix = "_trajectory"
-        if variants:
-            suffix = "_variants"
-        pert = None
-        if noisy:
-            pert, _ = _perturb_struct(nrows, img_rows.device, row_scale, row_noise, noise_seed, noise_rows, "sum of lengths")
-            suffix = "_perturbed"
-        if not (img_rows.is_cuda and ev_rows.is_cuda):
-            raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
+            q = _Request(self.training, _differentiable(img_rows, ev_rows), self.compute, row_scale=row_scale, attn_maps=attn_maps, row_noise=row_noise,
+                         noise_seed=noise_seed, noise_rows=noise_rows, trajectory=trajectory, fusion_variants=fusion_variants,
+                         similarity=similarity, outputs=outputs, weight_sums=weight_sums, nan_to_num=nan_to_num)
+            _check_request(self, q, _VIDEOS_CHECKS)
+        self._noise_code()
+        if isinstance(nan_to_num, str) and not q.nan_always:
+            raise ValueError(f"nan_to_num must be True, False or 'always' (got {nan_to_num!r})")
+        nan_mode = 2 if q.nan_always else 1 if nan_to_num else 0
         lens = [int(n) for n in lengths]
         total = sum(lens)
+        scales, wide, suffix, pert = (None, None), (), "", None
+        if q is not _PLAIN:
+            scales = _vector_pair("row_scale", row_scale, total, img_rows.device, "sum of lengths")
+            _noise_rules(q.noisy, noise_seed, noise_rows)
+            wide, suffix = _row_entry_suffix(q, "iefvad_forward_videos_full")
+            if q.noisy:
+                pert, _ = _perturb_struct(total, img_rows.device, row_scale, row_noise, noise_seed, noise_rows, "sum of lengths")
+        if not (img_rows.is_cuda and ev_rows.is_cuda):
+            raise RuntimeError("iefvad_amd.MMFMIL runs on a HIP device only; there is no CPU fallback")
         D = self.temporal.embed_dim
         if img_rows.shape != ev_rows.shape or img_rows.dim() != 2 or tuple(img_rows.shape) != (total, D):
             raise ValueError(f"expected two [{total}, {D}] tensors (sum of lengths x D), got {tuple(img_rows.shape)} and "
@@ -1064,15 +1064,11 @@ class MMFMIL(nn.Module):
         if not lens or min(lens) < 1:
             raise ValueError("every video needs at least one snippet")
         device = img_rows.device
-        img = self._prepare_input(img_rows)
-        ev = self._prepare_input(ev_rows)
-        if ev.dtype != img.dtype:
-            img, ev = img.to(torch.float), ev.to(torch.float)
+        img, ev = self._prepare_pair(img_rows, ev_rows)
         larr = (C.c_int32 * len(lens))(*lens)
         front = (C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), nan_mode)
         if pert is not None:      # the perturbed entry: one struct in the place of the two scale vectors
             front += (C.byref(pert),)
-        elif extras:    # the scaled entry alone takes the two scale vectors, behind nan_to_num
+        elif suffix == "_scaled":    # the scaled entry alone takes the two scale vectors, behind nan_to_num
             front += tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in scales)
-        return self._rows_call("iefvad_forward_videos", suffix, device, total, front, wide=wide, weight_sums=weight_sums,
-                               workspace_for=(larr, len(lens)), attn_layers=layers, variants=variants)
+        return self._rows_call("iefvad_forward_videos", suffix, q, device, total, front, wide=wide, workspace_for=(larr, len(lens)))
