@@ -47,6 +47,7 @@
 #include "similarity.h"
 #include "trajectory.h"
 #include "variants.h"
+#include "samples.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -1036,6 +1037,29 @@ struct VarOut {
 };
 static size_t variants_bytes(size_t pass_chunks, int D, int count) { return (size_t)count * pass_chunks * IEF_T * (2 * (size_t)D + 1) * sizeof(float); }
 
+// The score samples a call asked for (include/iefvad.h, csrc/samples.h): the [count, stride] logits and the per-snippet mean / standard
+// deviation of the scores of the whole CALL; a pass writes columns row0 + packed row of the pass.  ids: the snippet ids at the pass's
+// first packed row (nullable: row0 + packed row).  ws: the workspace of a group of IEF_MAX_VARIANTS stacked states (variants_bytes),
+// behind everything else; set by the entry.
+struct SampleOut {
+    int count;
+    unsigned long long seed;
+    float scale;
+    const int* ids;
+    float* logits;
+    float* mean;
+    float* stdev;
+    long long stride, row0;
+    float* ws;
+    bool any() const { return logits != nullptr; }
+    SampleOut at(long long rows) const {
+        SampleOut o = *this;
+        if (ids) o.ids += rows;
+        o.row0 += rows;
+        return o;
+    }
+};
+
 enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 struct VideosOut {
     float* logits;                   // [rows] each
@@ -1053,6 +1077,7 @@ struct VideosOut {
     // iefvad_rows_out_wide_kernel copies the valid rows out (pass_rows_out).
     float* wide[ROWS_OUT_WIDE_MAX];
     AttnMaps attn;                   // iefvad_forward_videos_attn: the packed [rows, 256] maps, written inside the encoder (pass_encoder_layer)
+    SampleOut smp;                   // iefvad_forward_videos_samples: the score samples; keeps its bases and takes its column from row0
     VarOut var;                      // iefvad_forward_videos_variants: the ablations' logits; keeps its base and takes its column from row0
     TrajOut traj;                    // iefvad_forward_videos_trajectory: the per-step series; like the similarity series it keeps its base and takes its column from row0
     long long row0;                  // packed row of the call's list (the host entries: of the whole list) that this view's first row is
@@ -1073,6 +1098,7 @@ struct VideosOut {
         o.attn = attn.at(rows);
         o.traj.row0 += rows;
         o.var.row0 += rows;
+        o.smp = smp.at(rows);
         o.row0 += rows;
         return o;
     }
@@ -1372,9 +1398,9 @@ static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass*
 // entries) or reduces it to the similarity series (fused and both mu) before it ends -- then it stays in the workspace alias of
 // pass_buffers.  Kernel selection does not look at these.
 struct TailKeep { bool fused, mu_i, mu_e, lv_i, lv_e; };
-static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg, const VarOut* vo) {
+static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg, bool heads) {
     auto rows = [&](int t, bool in_series) { return rg && (rg->out.wide[t] || (in_series && rg->out.similarity)); };
-    const bool heads = vo != nullptr;         // the ablations re-form z0 from all four head tensors (pass_variants)
+    // heads: the ablations / the score samples re-form z0 from all four head tensors (pass_variants, pass_samples)
     return TailKeep{out->fused || rows(kWideFused, true), out->image_mu || rows(kWideMuI, true) || heads, out->event_mu || rows(kWideMuE, true) || heads,
                     out->image_logvar || rows(kWideLvI, false) || heads, out->event_logvar || rows(kWideLvE, false) || heads};
 }
@@ -1404,7 +1430,7 @@ static int pass_refine_score(iefvad_handle* h, PassBuffers& b, const RaggedPass*
 // (iefvad_set_steps): blocks 0 .. K - 1 run.  `tj` (nullable): the pass records its trajectory -- a probe launch behind the fusion and
 // behind every step; the state must then pass through HBM between steps, so the bf16 arithmetic takes its launch-per-projection
 // route (bit-identical to the chain kernel) and the folded bf16x6 tail forms z_K as a pass that keeps `fused` does.
-static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, const TrajOut* tj, const VarOut* vo,
+static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out, const RaggedPass* rg, const TrajOut* tj, bool keep_heads,
                      hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
@@ -1417,7 +1443,7 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     px.use_split = b.tail_split;
 
     const bool chain = b.chain && !tj;
-    const TailKeep keep = tail_keep(out, rg, vo);
+    const TailKeep keep = tail_keep(out, rg, keep_heads);
     const bool keep_fused = keep.fused || tj;
     // 2 + 3 in one kernel (b.heads_rows): the four head tensors are stored only if the caller asked for them.
     if (b.heads_rows) {
@@ -1564,24 +1590,40 @@ static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPas
     return 0;
 }
 
+// What the fusion ablations and the score samples share: V states of the pass's row set stacked as ONE row set of V x rows rows in
+// `ws` (the state [V, rows, D], its h scratch at V R D floats, the [V, rows] logits at 2 V R D: variants_bytes), with the kernels
+// plan_tail names for that row count (bf16: one chain launch where the rule says chain; bf16x6 on the split kernels: a scores-only
+// tail with the folded scorer; f32: the fp32 tilings, bit-identical to each other) ...
+static PassBuffers stacked_buffers(const iefvad_handle* h, const PassBuffers& b, float* ws, int V) {
+    const size_t n = (size_t)V * b.R * h->D;
+    PassBuffers s = b;
+    s.rows = V * b.rows;
+    s.z = ws;
+    s.hbuf = ws + n;
+    s.hb = (bf16_t*)s.hbuf; s.zb = s.hb + (size_t)V * b.rows * h->D;
+    s.logits = ws + 2 * n;
+    static_cast<TailFlags&>(s) = plan_tail(h->policy, h->cfg.compute, s.rows, h->steps, b.splitmb, b.compacted, h->heads_stream != nullptr,
+                                           h->chain_stream != nullptr);
+    return s;
+}
+// ... and, behind steps 4 - 5 on the stacked set, the valid rows' logits to rows 0 .. V - 1 of a [V, stride] result at `dst`
+static int pass_stacked_out(const PassBuffers& b, const PassBuffers& s, const RaggedPass* rg, int V, float* dst, long long stride, long long row0,
+                            hipStream_t stream, Timer& tm) {
+    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
+    const int valid_rows = rg ? rg->valid_rows : b.rows;
+    const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
+    return launch(tm, ST_SCORER, iefvad_variants_out_kernel, dim3(nslabs, V), dim3(256), 0, stream, (const float*)s.logits, b.rows, chunks, valid_rows, dst,
+                  stride, row0);
+}
+
 // 7. the fusion ablations of a pass (variants.h), behind its own results: the variants' z0 from the kept mu / logvar of the row set,
-// stacked as ONE row set of count x rows rows behind the workspace, then steps 4 - 5 on it with the kernels plan_tail names for that
-// row count (bf16: one chain launch where the rule says chain; bf16x6 on the split kernels: a scores-only tail with the folded
-// scorer; f32: the fp32 tilings, bit-identical to each other), then the valid rows' logits to the call's [count, stride] result.
+// stacked behind the workspace, then steps 4 - 5 on it, then the valid rows' logits to the call's [count, stride] result.
 static int pass_variants(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const VarOut& vo, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const bool d512 = h->D == IEF_D512;
     const int V = vo.count, rows = b.rows;
-    const size_t n = (size_t)V * b.R * h->D;
-    PassBuffers s = b;
-    s.rows = V * rows;
-    s.z = vo.ws;
-    s.hbuf = vo.ws + n;
-    s.hb = (bf16_t*)s.hbuf; s.zb = s.hb + (size_t)V * rows * h->D;
-    s.logits = vo.ws + 2 * n;
-    static_cast<TailFlags&>(s) = plan_tail(h->policy, c.compute, s.rows, h->steps, b.splitmb, b.compacted, h->heads_stream != nullptr,
-                                           h->chain_stream != nullptr);
+    PassBuffers s = stacked_buffers(h, b, vo.ws, V);
     VariantArgs va;
     memset(&va, 0, sizeof(va));
     va.mu_i = b.mu_i; va.lv_i = b.lv_i; va.mu_e = b.mu_e; va.lv_e = b.lv_e;
@@ -1594,11 +1636,44 @@ static int pass_variants(iefvad_handle* h, const PassBuffers& b, const RaggedPas
             return launch(tm, ST_FUSION, iefvad_fusion_variants_kernel<decltype(w)::value>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, va);
         })) return rc;
     if (int rc = pass_refine_score(h, s, rg, nullptr, s.chain, false, stream, tm)) return rc;
+    return pass_stacked_out(b, s, rg, V, vo.logits, vo.stride, vo.row0, stream, tm);
+}
+
+// 7'. the score samples of a pass (samples.h), behind its own results: groups of up to IEF_MAX_VARIANTS samples, each the sampled z0
+// of the row set stacked in the group's workspace, steps 4 - 5 on it and the valid rows' logits to rows s0 .. of the call's
+// [count, stride] result; behind the last group the per-snippet mean and standard deviation of the scores from those rows.
+static unsigned long long sample_seed(unsigned long long seed, int s) { return seed + (unsigned long long)s * 0x9E3779B97F4A7C15ull; }
+static int pass_samples(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const SampleOut& so, hipStream_t stream, Timer& tm) {
+    const iefvad_config& c = h->cfg;
+    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
+    const bool d512 = h->D == IEF_D512;
     const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
-    const int valid_rows = rg ? rg->valid_rows : rows;
+    const int valid_rows = rg ? rg->valid_rows : b.rows;
     const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
-    return launch(tm, ST_SCORER, iefvad_variants_out_kernel, dim3(nslabs, V), dim3(256), 0, stream, (const float*)s.logits, rows, chunks, valid_rows, vo.logits,
-                  vo.stride, vo.row0);
+    for (int s0 = 0; s0 < so.count; s0 += IEF_MAX_VARIANTS) {
+        const int G = so.count - s0 < IEF_MAX_VARIANTS ? so.count - s0 : IEF_MAX_VARIANTS;
+        PassBuffers s = stacked_buffers(h, b, so.ws, G);
+        SampleArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.mu_i = b.mu_i; sa.lv_i = b.lv_i; sa.mu_e = b.mu_e; sa.lv_e = b.lv_e;
+        sa.z = s.z;
+        sa.zb = (bf && !s.chain) ? s.zb : nullptr;
+        sa.chunks = chunks; sa.ids = so.ids; sa.row0 = so.row0;
+        sa.nrows = b.rows; sa.valid_rows = valid_rows;
+        sa.used_rows = (chunks && b.enc_rows_mode) ? rg->enc_used_rows : b.rows;
+        sa.chunk_rows = b.enc_rows_mode ? 0 : IEF_T;
+        sa.count = G;
+        for (int g = 0; g < G; ++g) sa.seed[g] = sample_seed(so.seed, s0 + g);
+        sa.factor = precision_factor(c); sa.eps = c.epsilon; sa.scale = so.scale;
+        const dim3 grid(chunks ? b.nb + 1 : (b.rows + 255) / 256, SAMPLE_SLICES);
+        if (int rc = dispatch_d(d512, [&](auto w) {
+                return launch(tm, ST_FUSION, iefvad_sample_states_kernel<decltype(w)::value>, grid, dim3(256), 0, stream, sa);
+            })) return rc;
+        if (int rc = pass_refine_score(h, s, rg, nullptr, s.chain, false, stream, tm)) return rc;
+        if (int rc = pass_stacked_out(b, s, rg, G, so.logits + (long long)s0 * so.stride, so.stride, so.row0, stream, tm)) return rc;
+    }
+    return launch(tm, ST_SCORER, iefvad_samples_reduce_kernel, dim3(nslabs), dim3(256), 0, stream, (const float*)so.logits, so.stride, so.count, chunks,
+                  valid_rows, so.row0, so.mean, so.stdev);
 }
 
 // One micro-batch of `nb` chunks.  Dense (rg == nullptr): `in` holds the pass's [nb, 256, 768] blocks, `scale` their per-row scales
@@ -1607,24 +1682,27 @@ static int pass_variants(iefvad_handle* h, const PassBuffers& b, const RaggedPas
 // must be all-null, `scale` kNoScale: rg->out carries the packed scales).
 static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
                         const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr,
-                        const RowNoise* nz = nullptr, const TrajOut* tj = nullptr, const VarOut* vo = nullptr) {
+                        const RowNoise* nz = nullptr, const TrajOut* tj = nullptr, const VarOut* vo = nullptr, const SampleOut* so = nullptr) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
     if (rg) maps = &rg->out.attn;                 // a whole-video pass: the maps at the pass's first packed row
     if (rg) tj = rg->out.traj.any() ? &rg->out.traj : nullptr;
     if (rg) vo = rg->out.var.any() ? &rg->out.var : nullptr;
+    if (rg) so = rg->out.smp.any() ? &rg->out.smp : nullptr;
     if (int rc = pass_load_inputs(h, b, in, scale, nz ? *nz : RowNoise{}, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
         if (int rc = pass_encoder_layer(h, b, l, rg, maps, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
-    if (int rc = pass_tail(h, b, out, rg, tj, vo, stream, tm)) return rc;
+    if (int rc = pass_tail(h, b, out, rg, tj, vo || so, stream, tm)) return rc;
     if (rg)
         if (int rc = pass_rows_out(h, b, rg, stream, tm)) return rc;
-    return vo ? pass_variants(h, b, rg, *vo, stream, tm) : 0;
+    if (vo)
+        if (int rc = pass_variants(h, b, rg, *vo, stream, tm)) return rc;
+    return so ? pass_samples(h, b, rg, *so, stream, tm) : 0;
 }
 
 static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
                         const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr, const RowNoise* nz = nullptr,
-                        const TrajOut* tj = nullptr, const VarOut* vo = nullptr) {
+                        const TrajOut* tj = nullptr, const VarOut* vo = nullptr, const SampleOut* so = nullptr) {
     const void* const img = in.img;
     const void* const ev = in.ev;
     const int32_t in_dtype = in.in_dtype;
@@ -1648,8 +1726,9 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
         pass_tj.row0 = (long long)row0;
         VarOut pass_vo = vo ? *vo : VarOut{};
         pass_vo.row0 = (long long)row0;
+        const SampleOut pass_so = so ? so->at((long long)row0) : SampleOut{};
         if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr, &pass_nz,
-                                  tj ? &pass_tj : nullptr, vo ? &pass_vo : nullptr))
+                                  tj ? &pass_tj : nullptr, vo ? &pass_vo : nullptr, so ? &pass_so : nullptr))
             return rc;
     }
     return 0;
@@ -2702,6 +2781,67 @@ extern "C" int iefvad_forward_videos_variants(iefvad_handle* h, const void* img_
     if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
     VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
     if (int rc = variants_args(who, h, variants, rows, &out.var)) return rc;
+    Timer tm;
+    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the score samples (include/iefvad.h, csrc/samples.h)
+// ------------------------------------------------------------------------------------------------
+// The checks of a samples request that need no device
+static int samples_args(const char* who, const iefvad_handle* h, const iefvad_samples* p, long long rows, SampleOut* so) {
+    if (h->cfg.compute == IEFVAD_COMPUTE_FP16X3) return fail("%s: compute = FP16X3 is not supported (IEFVAD_COMPUTE_FP16X3 has no score samples)", who);
+    if (!p) return fail("%s: null samples", who);
+    if (p->samples < 1 || p->samples > IEF_MAX_SAMPLES) return fail("%s: samples %d outside 1..%d", who, p->samples, IEF_MAX_SAMPLES);
+    if (!(p->scale >= 0.f) || p->scale > 3.40282347e38f) return fail("%s: scale must be finite and >= 0 (got %g)", who, (double)p->scale);
+    if (!p->logits_samples) return fail("%s: null logits_samples", who);
+    if (!p->score_mean) return fail("%s: null score_mean", who);
+    if (!p->score_std) return fail("%s: null score_std", who);
+    if (((uintptr_t)p->logits_samples | (uintptr_t)p->score_mean | (uintptr_t)p->score_std | (uintptr_t)p->sample_rows) & 3)
+        return fail("%s: logits_samples, score_mean, score_std and sample_rows must be 4-byte aligned", who);
+    if ((long long)p->stride < rows) return fail("%s: stride %zu is less than the call's %lld rows", who, p->stride, rows);
+    *so = SampleOut{};
+    so->count = p->samples; so->seed = p->seed; so->scale = p->scale; so->ids = p->sample_rows;
+    so->logits = p->logits_samples; so->mean = p->score_mean; so->stdev = p->score_std; so->stride = (long long)p->stride;
+    return 0;
+}
+
+extern "C" size_t iefvad_samples_workspace_bytes(const iefvad_handle* h, int32_t B) {
+    return iefvad_variants_workspace_bytes(h, B, IEF_MAX_VARIANTS);       // one group of stacked states, whatever the sample count
+}
+
+extern "C" int iefvad_forward_samples(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                                      size_t workspace_bytes, const iefvad_outputs* out, const iefvad_samples* samples, void* stream) {
+    static const char* const who = "iefvad_forward_samples";
+    if (!h) return fail("%s: null handle", who);
+    if (!img || !ev || !out) return fail("%s: null argument", who);
+    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
+    SampleOut so;
+    if (int rc = samples_args(who, h, samples, (long long)B * IEF_T, &so)) return rc;
+    const size_t need = iefvad_samples_workspace_bytes(h, B);
+    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    so.ws = (float*)((char*)workspace + iefvad_workspace_bytes(h, B));
+    Timer tm;      // direct launches: the results' pointers are per call, a cached graph would pin their addresses
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, nullptr, nullptr, nullptr,
+                        &so);
+}
+
+extern "C" size_t iefvad_videos_samples_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
+    return videos_workspace_bytes(h, lengths, nvideos, false, false, false, IEF_MAX_VARIANTS);
+}
+
+extern "C" int iefvad_forward_videos_samples(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                             const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                             size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                             const iefvad_samples* samples, void* stream) {
+    static const char* const who = "iefvad_forward_videos_samples";
+    if (!h) return fail("%s: null handle", who);
+    if (!lengths) return fail("%s: null argument", who);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    long long rows, chunks;
+    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    if (int rc = samples_args(who, h, samples, rows, &out.smp)) return rc;
     Timer tm;
     return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
 }

@@ -161,7 +161,8 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
     const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
     const size_t extra = videos_extra_bytes(h, total_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
     const size_t traj_bytes = out.traj.any() ? videos_traj_bytes(h, total_chunks) : 0;
-    const size_t need = base + extra + traj_bytes + (out.var.any() ? variants_bytes(videos_pass_chunks(h, total_chunks), h->D, out.var.count) : 0);
+    const size_t var_bytes = out.var.any() ? variants_bytes(videos_pass_chunks(h, total_chunks), h->D, out.var.count) : 0;
+    const size_t need = base + extra + traj_bytes + var_bytes + (out.smp.any() ? variants_bytes(videos_pass_chunks(h, total_chunks), h->D, IEF_MAX_VARIANTS) : 0);
     if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
     if (((uintptr_t)workspace & 15) || ((uintptr_t)in.img & 15) || ((uintptr_t)in.ev & 15)) return fail("%s: buffers must be 16-byte aligned", who);
 
@@ -249,6 +250,7 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
         rg.out.nan_mode = nan_mode;
         if (out.traj.any()) rg.out.traj.z_prev = (float*)((char*)workspace + base + extra);
         if (out.var.any()) rg.out.var.ws = (float*)((char*)workspace + base + extra + traj_bytes);      // the stacked states of the ablations, behind everything else
+        if (out.smp.any()) rg.out.smp.ws = (float*)((char*)workspace + base + extra + traj_bytes + var_bytes);     // one group of stacked sample states
         rc = forward_pass(h, in.at((size_t)row0, h->D), kNoScale, nb, 0, workspace, &none, &rg, stream, tm);
         row0 += vrows;
     }

@@ -13,6 +13,7 @@ from __future__ import annotations
 import concurrent.futures
 import contextlib
 import csv
+import math
 import os
 from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -691,7 +692,7 @@ def _lane_stream(stream):
 
 
 def _score_padded(models, stagers, streams, loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                  similarity=False, trajectory=False, variants=()):
+                  similarity=False, trajectory=False, variants=(), samples=None):
     """Padded route (the only one on the CPU): `model(img, ev, ...)` on zero-padded chunks, one forward per video
     (batch_chunks <= 0) or per batch, which closes as soon as it holds `batch_chunks` chunks; forwards round-robin over the lanes.
     `_unpack_item` has applied the NaN rule in each tensor's own dtype; a mixed batch is widened while it is staged.
@@ -705,9 +706,19 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
             else:
                 img = torch.cat([p[0].to(dt) for p in pend], dim=0).to(device)
                 ev = torch.cat([p[1].to(dt) for p in pend], dim=0).to(device)
-            out = models[k](img, ev, None, None, None, **(dict(trajectory=True) if trajectory else dict(fusion_variants=variants) if variants else {}))
+            if samples is not None:      # snippet ids: the snippet's index among the valid snippets of the whole list (0 on pad rows)
+                ids = torch.zeros(sum(p[0].shape[0] for p in pend) * maxlen, dtype=torch.int32)
+                slot = 0
+                for ci, _, n in pend:
+                    ids[slot:slot + n] = torch.arange(seen[0], seen[0] + n, dtype=torch.int32)
+                    slot, seen[0] = slot + ci.shape[0] * maxlen, seen[0] + n
+                out = models[k].forward_samples(img, ev, samples[0], samples[1], scale=samples[2], sample_rows=ids.to(device))
+            else:
+                out = models[k](img, ev, None, None, None, **(dict(trajectory=True) if trajectory else dict(fusion_variants=variants) if variants else {}))
             logits = out['logits'].reshape(-1)
             traj = None
+            if samples is not None:
+                traj = (out['logits_samples'].reshape(samples[0], -1), torch.stack([out['score_mean'].reshape(-1), out['score_std'].reshape(-1)]))
             if trajectory:
                 ls = out['logits_steps']
                 traj = (ls.reshape(ls.shape[0], -1), out['delta_norm'].reshape(ls.shape[0] - 1, -1))
@@ -728,6 +739,7 @@ def _score_padded(models, stagers, streams, loader, sink, maxlen, device, datase
                 sim = similarity_rows(out['fused'], out['image_mu'], out['event_mu'], torch.from_numpy(index))
             sink.add(logits.float(), wi.float(), we.float(), lens, stride, sim, traj=traj)
 
+    seen = [0]      # valid snippets of the videos already sent
     pend, pend_chunks, nsent = [], 0, 0
     for item in loader:
         img, ev, cls, n = _unpack_item(item, maxlen, dataset, label_map)
@@ -748,7 +760,7 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
 
 
 def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=(),
-                     attn_layers=(), trajectory=False, variants=()):
+                     attn_layers=(), trajectory=False, variants=(), samples=None):
     """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
     while this thread sends batch k and enqueues its forward; batches complete in order.
@@ -767,14 +779,21 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
         staged = fut.result()
         with _lane_stream(streams[k]):
             img, ev = stagers[k].send(staged)
-            out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
+            if samples is not None:      # snippet ids: the snippet's index among the valid snippets of the whole list
+                ids = torch.arange(seen[0], seen[0] + sum(lens), dtype=torch.int32, device=img.device)
+                seen[0] += sum(lens)
+                out = models[k].forward_videos_samples(img, ev, lens, samples[0], samples[1], scale=samples[2], nan_to_num=True, sample_rows=ids)
+            else:
+                out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
         sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out,
-                 traj=(out['logits_steps'], out['delta_norm']) if trajectory else (out['logits_variants'],) if variants else None)
+                 traj=(out['logits_steps'], out['delta_norm']) if trajectory else (out['logits_variants'],) if variants else
+                 (out['logits_samples'], torch.stack([out['score_mean'], out['score_std']])) if samples is not None else None)
 
     sim_kw = dict(similarity=True) if similarity else dict(outputs=row_outputs) if row_outputs else \
         dict(attn_maps=attn_layers) if attn_layers else dict(trajectory=True) if trajectory else \
         dict(fusion_variants=variants) if variants else {}
 
+    seen = [0]      # valid snippets of the batches already sent (batches complete in order)
     stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=1)
     inflight = []                                   # batches handed to the worker and not sent yet: ONE after every turn of the loop
     pend, pend_chunks, nstaged = [], 0, 0
@@ -838,7 +857,8 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                  label_map=None, batch_chunks: int = 0, skip_empty_chunks: bool = True, lanes: int = 1,
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
                  return_device: bool = False, similarity=False, row_outputs=None, attn_maps=None, steps: Optional[int] = None,
-                 trajectory: bool = False, fusion_variants=None):
+                 trajectory: bool = False, fusion_variants=None, score_samples: Optional[int] = None, sample_seed: Optional[int] = None,
+                 sample_scale: float = 1.0):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -906,11 +926,31 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     {"names": the names in the order asked for; "scores": per video a [V, snippets] float32 array, the sigmoid of the variants' logits;
     "scores_device": ONE [V, N] device tensor of the N valid snippets, the videos in list order; "row_offsets": int64 array of
     len(videos) + 1 offsets into N}}.  The host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError
-    otherwise); it does not combine with `trajectory`, `similarity`, `row_outputs` or `attn_maps`."""
+    otherwise); it does not combine with `trajectory`, `similarity`, `row_outputs` or `attn_maps`.
+    `score_samples=S` with `sample_seed=` (and `sample_scale=`, default 1; the per-video / padded route and the `forward_videos` loop; HIP
+    device): every forward is `MMFMIL.forward_samples` / `forward_videos_samples` -- S Monte Carlo draws of every snippet's score from the
+    heads' own Gaussians (this package's own semantics; the reference never samples).  The snippet id of a draw is the snippet's index
+    among the valid snippets of the whole list, so a snippet's samples do not depend on the route or on `batch_chunks`.  The returned
+    tuple does not change; `score_loader.last_result` becomes {"samples": {"scores_mean", "scores_std": per video a [snippets] float32
+    array, mean and population standard deviation of the S scores, formed on the device; "logits_samples_device": ONE [S, N] device
+    tensor of the N valid snippets, the videos in list order (apply the sigmoid); "row_offsets": int64 array of len(videos) + 1 offsets
+    into N}}.  The host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError otherwise); it combines
+    with none of the other extras (`steps`, `trajectory`, `fusion_variants`, `similarity`, `row_outputs`, `attn_maps`)."""
     on_gpu = torch.device(device).type == 'cuda'
     from .model import _row_output_keys, attn_map_layers, attn_maps_asked, fusion_variant_names
     variants = fusion_variant_names(fusion_variants)
     want_maps = attn_maps_asked(attn_maps)
+    samples = None
+    if score_samples is not None:
+        if steps is not None or trajectory or variants or similarity or row_outputs is not None or want_maps:
+            raise ValueError('score_samples does not combine with steps, trajectory, fusion_variants, similarity, row_outputs or attn_maps')
+        if not hasattr(model, 'forward_samples'):
+            raise ValueError('score_samples needs a model with forward_samples (iefvad_amd.MMFMIL)')
+        if not on_gpu:
+            raise ValueError('score_samples needs a HIP device')
+        if sample_seed is None:
+            raise ValueError('score_samples needs sample_seed=: the draws are a pure function of the seed')
+        samples = (score_samples, sample_seed, sample_scale)
     if variants:
         if trajectory or similarity or row_outputs is not None or want_maps:
             raise ValueError('fusion_variants does not combine with trajectory, similarity, row_outputs or attn_maps')
@@ -969,6 +1009,9 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     if variants and use_list:
         raise ValueError('fusion_variants is not served by the host-list walk (iefvad_forward_videos_host has no variants entry): '
                          'pass host_list=False for the forward_videos loop')
+    if samples is not None and use_list:
+        raise ValueError('score_samples is not served by the host-list walk (iefvad_forward_videos_host has no samples entry): '
+                         'pass host_list=False for the forward_videos loop')
     # staging buffers are pinned allocations: they live with the lane (model object) across calls, not with the call
     stagers = [None] * nl
     for k, m in enumerate(models if on_gpu else ()):
@@ -985,7 +1028,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
         sink.dev_rows = {k: [] for k in row_keys}
     if attn_layers:
         sink.dev_rows = {"image_attn": [], "event_attn": []}
-    if trajectory or variants:
+    if trajectory or variants or samples is not None:
         sink.dev_traj = []
     with torch.no_grad():
         for s in streams if nl > 1 else ():
@@ -999,17 +1042,17 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                                  row_keys)
             elif ragged:
                 _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys,
-                                 attn_layers, trajectory, variants)
+                                 attn_layers, trajectory, variants, samples)
             else:
                 _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
-                              bool(similarity), trajectory, variants)
+                              bool(similarity), trajectory, variants, samples)
             nsteps = getattr(model, 'steps', 0)
         finally:
             if steps is not None:
                 model.set_steps(prev_steps)
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
-        if trajectory or variants or sink.dev_rows is not None:
+        if trajectory or variants or samples is not None or sink.dev_rows is not None:
             offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
         if sink.dev_traj:
             # the slots of every forward side by side, then the valid ones in video order (the padded route leaves gaps between the videos' slots)
@@ -1029,6 +1072,13 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
             score_loader.last_result = {"variants": {
                 "names": tuple(variants), "scores": [host[:, a:b] for a, b in zip(offsets[:-1], offsets[1:])], "scores_device": sc,
                 "row_offsets": offsets}}
+        elif samples is not None:
+            ls, ms = slots if sink.dev_traj else (torch.zeros(samples[0], 0, device=device), torch.zeros(2, 0, device=device))
+            host = ms.cpu().numpy()
+            score_loader.last_result = {"samples": {
+                "scores_mean": [host[0, a:b] for a, b in zip(offsets[:-1], offsets[1:])],
+                "scores_std": [host[1, a:b] for a, b in zip(offsets[:-1], offsets[1:])],
+                "logits_samples_device": ls.contiguous(), "row_offsets": offsets}}
         elif attn_layers:
             image, event = (v[0] if len(v) == 1 else torch.cat(v, dim=1) if v else torch.zeros(len(attn_layers), 0, maxlen, device=device)
                             for v in (sink.dev_rows["image_attn"], sink.dev_rows["event_attn"]))
@@ -1346,7 +1396,7 @@ def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
               batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None, steps=None, trajectory=False,
-              fusion_variants=None):
+              fusion_variants=None, score_samples=None, sample_seed=None):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
@@ -1371,9 +1421,15 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     `fusion_variants` (True or names): one walk gives the fusion ablation table -- `score_loader(fusion_variants=...)` on the per-video
     route or the `forward_videos` loop -- and the result dict gains "variants" (see there), "auc_variants" and "ap_variants": name ->
     the global AUC / AP of that variant's scores, by the metric tail in use (sklearn, or `iefvad_auc_ap`).  "fused" is what the call
-    itself returns; nothing more is printed.  It does not combine with vis=True, `attn_maps` or `trajectory`."""
+    itself returns; nothing more is printed.  It does not combine with vis=True, `attn_maps` or `trajectory`.
+    `score_samples=S` with `sample_seed=`: one walk gives S Monte Carlo draws of every score from the heads' own Gaussians --
+    `score_loader(score_samples=...)` on the per-video route or the `forward_videos` loop -- and the result dict gains "samples" (see
+    there), "auc_samples" / "ap_samples" (S floats each: the global AUC / AP of sample s's scores) and "auc_mean_score" / "ap_mean_score"
+    (those of the per-snippet mean score), by the metric tail in use; nothing more is printed.  It combines with none of the other extras."""
     from .model import attn_maps_asked
     want_maps = attn_maps_asked(attn_maps)
+    if score_samples is not None and (vis or trajectory or want_maps or steps is not None or (fusion_variants is not None and fusion_variants is not False)):
+        raise ValueError("score_samples does not combine with vis=True, attn_maps, steps, trajectory or fusion_variants")
     want_variants = fusion_variants is not None and fusion_variants is not False
     if want_variants and (vis or trajectory or want_maps):
         raise ValueError("fusion_variants does not combine with vis=True, attn_maps or trajectory")
@@ -1402,7 +1458,8 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
                        return_device=metric_tail == "device", similarity="rows" if vis_rows else bool(vis),
                        **(dict(attn_maps=attn_maps) if want_maps else {}), **(dict(steps=steps) if steps is not None else {}),
                        **(dict(trajectory=True, host_list=False) if trajectory else {}),
-                       **(dict(fusion_variants=fusion_variants, host_list=False) if want_variants else {}))
+                       **(dict(fusion_variants=fusion_variants, host_list=False) if want_variants else {}),
+                       **(dict(score_samples=score_samples, sample_seed=sample_seed, host_list=False) if score_samples is not None else {}))
     scores, classes, wi, we = got[:4]
     if metric_tail == "device":
         res = evaluate_scores_device((got[4], [len(s) for s in scores]), classes, gt, args.dataset, verbose=True, normal_keys=normal_keys,
@@ -1432,6 +1489,18 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
             pairs = [(roc_auc_score(gt, np.repeat(row.tolist(), 16)), average_precision_score(gt, np.repeat(row.tolist(), 16))) for row in rows]
         last["auc_variants"] = {n: p[0] for n, p in zip(va["names"], pairs)}
         last["ap_variants"] = {n: p[1] for n, p in zip(va["names"], pairs)}
+    if score_samples is not None:
+        sm = last["samples"] = score_loader.last_result["samples"]
+        mean_host = np.concatenate(sm["scores_mean"]) if sm["scores_mean"] else np.zeros(0, np.float32)
+        if metric_tail == "device":
+            dev = sm["logits_samples_device"]
+            pairs = [device_auc_ap(row, gt) for row in torch.sigmoid(dev)] + [device_auc_ap(torch.from_numpy(mean_host).to(dev.device), gt)]
+        else:       # the calls of evaluate_scores (test.py:158-159) on each sample's scores, then on the mean score
+            from sklearn.metrics import average_precision_score, roc_auc_score
+            rows = list(torch.sigmoid(sm["logits_samples_device"]).cpu().numpy()) + [mean_host]
+            pairs = [(roc_auc_score(gt, np.repeat(row.tolist(), 16)), average_precision_score(gt, np.repeat(row.tolist(), 16))) for row in rows]
+        last["auc_samples"], last["ap_samples"] = [p[0] for p in pairs[:-1]], [p[1] for p in pairs[:-1]]
+        last["auc_mean_score"], last["ap_mean_score"] = pairs[-1]
     if vis:
         last["similarity"] = got[-1]
         last["vis_files"] = draw_vis(vis_series(last, gt, vis_flavour), os.path.join('vis', str(args.exp_name)),      # test.py:59-62
@@ -1443,7 +1512,7 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
          batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded",
-         *, attn_maps=None, steps=None, trajectory=False, fusion_variants=None):
+         *, attn_maps=None, steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
@@ -1457,29 +1526,31 @@ def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, 
     `steps=` / `trajectory=True` (keyword-only, here and in `ucf_test` / `xd_test`): evaluate with the first `steps` refinement blocks
     only / add the per-step scores, update norms and "auc_steps", "ap_steps" to `last_result` from the one walk (`_run_test`).
     `fusion_variants=` (keyword-only, here and in `ucf_test` / `xd_test`): True or names; adds the fusion ablations' scores ("variants")
-    and "auc_variants", "ap_variants" (name -> float) to `last_result` from the one walk (`_run_test`)."""
+    and "auc_variants", "ap_variants" (name -> float) to `last_result` from the one walk (`_run_test`).
+    `score_samples=S`, `sample_seed=` (keyword-only, here and in `ucf_test` / `xd_test`): adds the Monte Carlo score samples ("samples"),
+    "auc_samples" / "ap_samples" (S floats each) and "auc_mean_score" / "ap_mean_score" to `last_result` from the one walk (`_run_test`)."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
                                       False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route, attn_maps=attn_maps, steps=steps,
-                                      trajectory=trajectory, fusion_variants=fusion_variants)
+                                      trajectory=trajectory, fusion_variants=fusion_variants, score_samples=score_samples, sample_seed=sample_seed)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
              batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
-             steps=None, trajectory=False, fusion_variants=None):
+             steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
                                           ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route, attn_maps, steps,
-                                          trajectory, fusion_variants)
+                                          trajectory, fusion_variants, score_samples, sample_seed)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
-            steps=None, trajectory=False, fusion_variants=None):
+            steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -1488,7 +1559,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
                                          ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps, steps, trajectory,
-                                         fusion_variants)
+                                         fusion_variants, score_samples, sample_seed)
     test.last_result = xd_test.last_result
     return ret
 
@@ -1610,6 +1681,34 @@ def perturb_rows_host(x: torch.Tensor, scale, amp, seed, modality: int, ids) -> 
         eps = torch.from_numpy(gaussian_rows(seed, modality, ids.numpy(), x.shape[-1]))
         x = torch.where((amp != 0)[:, None], (x.float() + amp[:, None] * eps).to(x.dtype), x)
     return x
+
+
+SAMPLE_SEED_STEP = 0x9E3779B97F4A7C15      # csrc/iefvad.hip, sample_seed
+
+
+def sample_seed(seed: int, s: int) -> int:
+    """The generator's seed of score sample `s` of a call seeded `seed` (include/iefvad.h, `iefvad_samples`): seed + s * 0x9E3779B97F4A7C15
+    mod 2^64, the one definition the library and this host model share."""
+    return (int(seed) + int(s) * SAMPLE_SEED_STEP) & 0xFFFFFFFFFFFFFFFF
+
+
+def sample_states_host(mu_i, lv_i, mu_e, lv_e, seed: int, s: int, ids, factor: float, eps: float, scale: float = 1.0) -> torch.Tensor:
+    """Host model (torch, fp64) of the sampled fused state z0_s of `MMFMIL.forward_samples` (csrc/samples.h): [rows, D] head tensors and
+    the rows' snippet ids -> [rows, D] float64.  Noise = `gaussian_rows(sample_seed(seed, s), m, ids, D)`, sd_m = scale exp(0.5 lv_m) /
+    sqrt(factor), mu~_m = mu_m + noise sd_m, and the fusion of the sampled means under the call's own precisions w_m = factor exp(-lv_m)
+    with the reference's expression (imf_vad.py:130-144); `factor` the Student-t factor (nu + 1) / nu or 1, `eps` the fusion's epsilon."""
+    mu_i, lv_i, mu_e, lv_e = (torch.as_tensor(np.asarray(t)).double() for t in (mu_i, lv_i, mu_e, lv_e))
+    D = mu_i.shape[-1]
+    ids = np.asarray(ids).reshape(-1)
+    shape = mu_i.shape
+    noise = [torch.from_numpy(gaussian_rows(sample_seed(seed, s), m, ids, D)).double().reshape(shape) for m in (0, 1)]
+    root = math.sqrt(factor)
+    mt_i = mu_i + noise[0] * (scale * torch.exp(0.5 * lv_i) / root)
+    mt_e = mu_e + noise[1] * (scale * torch.exp(0.5 * lv_e) / root)
+    w_i = factor * torch.exp(-lv_i)
+    w_e = factor * torch.exp(-lv_e)
+    den = w_i + w_e + eps
+    return (w_i / den) * mt_i + (w_e / den) * mt_e
 
 
 class SweepResult(tuple):

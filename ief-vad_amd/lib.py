@@ -40,7 +40,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_train_backward_inputs", "iefvad_forward_perturbed", "iefvad_forward_videos_perturbed", "iefvad_perturb_rows",
            "iefvad_set_steps", "iefvad_trajectory_workspace_bytes", "iefvad_forward_trajectory", "iefvad_videos_trajectory_workspace_bytes",
            "iefvad_forward_videos_trajectory", "iefvad_variants_workspace_bytes", "iefvad_forward_variants",
-           "iefvad_videos_variants_workspace_bytes", "iefvad_forward_videos_variants"]
+           "iefvad_videos_variants_workspace_bytes", "iefvad_forward_videos_variants", "iefvad_samples_workspace_bytes",
+           "iefvad_forward_samples", "iefvad_videos_samples_workspace_bytes", "iefvad_forward_videos_samples"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -105,6 +106,16 @@ VARIANT_NAMES = ("fused", "image", "event", "equal")      # IEFVAD_VARIANT_FUSED
 class Variants(C.Structure):
     """iefvad_variants (include/iefvad.h): `count` kinds (indices into VARIANT_NAMES) and the device fp32 [count, stride] logits."""
     _fields_ = [("count", C.c_int32), ("kind", C.c_int32 * 4), ("logits", _fp), ("stride", C.c_size_t)]
+
+
+MAX_SAMPLES = 64      # IEF_MAX_SAMPLES (csrc/samples.h)
+
+
+class Samples(C.Structure):
+    """iefvad_samples (include/iefvad.h): S, the generator's seed, the spread's scale, device snippet ids (0 = the call's row index) and
+    the device fp32 results [S, stride], [rows], [rows]."""
+    _fields_ = [("samples", C.c_int32), ("seed", C.c_uint64), ("scale", C.c_float), ("sample_rows", _fp), ("logits_samples", _fp),
+                ("stride", C.c_size_t), ("score_mean", _fp), ("score_std", _fp)]
 
 
 class Perturb(C.Structure):
@@ -325,6 +336,15 @@ def load_library() -> C.CDLL:
     lib.iefvad_videos_variants_workspace_bytes.restype = C.c_size_t
     lib.iefvad_forward_videos_variants.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(Variants), C.c_void_p]
     lib.iefvad_forward_videos_variants.restype = C.c_int
+    # the score-sample entries: `const iefvad_samples*` in front of the stream; the queries take the plain queries' arguments
+    lib.iefvad_samples_workspace_bytes.argtypes = [C.c_void_p, C.c_int32]
+    lib.iefvad_samples_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_samples.argtypes = lib.iefvad_forward.argtypes[:8] + [C.POINTER(Samples), C.c_void_p]
+    lib.iefvad_forward_samples.restype = C.c_int
+    lib.iefvad_videos_samples_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+    lib.iefvad_videos_samples_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_videos_samples.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(Samples), C.c_void_p]
+    lib.iefvad_forward_videos_samples.restype = C.c_int
     lib.iefvad_split_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.iefvad_split_bf16x3.restype = C.c_int
     lib.iefvad_split_bf16x3_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -571,6 +571,12 @@ class MMFMIL(nn.Module):
                    and unchanged ("fused" = `logits`) -- encoder and heads run once, the refinement and classifier once more on the
                    stacked variants.  Every other result keeps its bits.
 
+    The uncertainty of the score itself (not in the reference, which never samples the heads' Gaussians):
+      forward_samples(img, ev, samples, seed) / forward_videos_samples(img_rows, ev_rows, lengths, samples, seed)  methods of their
+                   own: the plain call's results with unchanged bits plus `logits_samples` (S Monte Carlo draws of every snippet's
+                   logit, the means sampled from N(mu_m, scale^2 / w_m) and fused under the call's own precisions), `score_mean` and
+                   `score_std` -- encoder and heads run once, the refinement and classifier once per group of four samples.
+
     Without any keyword (the reference's behaviour, imf_vad.py:40-44,109-161 being an ordinary nn.Module):
       gradients of the features  a feature tensor with `requires_grad=True` receives its `.grad` from `loss.backward()`, in its own dtype
                    and shape, in train() and in eval() alike -- an adapter or a learned projection upstream of the model trains, and
@@ -1072,3 +1078,115 @@ class MMFMIL(nn.Module):
         elif suffix == "_scaled":    # the scaled entry alone takes the two scale vectors, behind nan_to_num
             front += tuple(C.c_void_p(sv.data_ptr()) if sv is not None else None for sv in scales)
         return self._rows_call("iefvad_forward_videos", suffix, q, device, total, front, wide=wide, workspace_for=(larr, len(lens)))
+
+    # ------------------------------------------------------------------ score samples
+    def _samples_request(self, who: str, feats, samples, seed, scale) -> tuple:
+        """The checks of a score-samples call that need no device -> (S, seed mod 2^64, scale)."""
+        if self.training:
+            raise RuntimeError(f"iefvad_amd.MMFMIL.{who} is an evaluation entry point; it is not available under model.train() (call model.eval() first)")
+        if _differentiable(*feats):
+            raise RuntimeError(f"iefvad_amd.MMFMIL.{who} is an evaluation entry point: nothing it returns is differentiable, and a feature tensor "
+                               "that requires grad would get no gradient (detach it)")
+        if self.compute == "fp16x3":
+            raise RuntimeError(f'{who} is not available with compute="fp16x3" (its per-chunk running-max words have no home for the stacked '
+                               'sample states); use "f32", "bf16x6" or "bf16"')
+        self._noise_code()
+        if isinstance(samples, bool) or not isinstance(samples, int) or not 1 <= samples <= _lib.MAX_SAMPLES:
+            raise ValueError(f"samples must be an int in 1..{_lib.MAX_SAMPLES} (got {samples!r})")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an int (got {seed!r})")
+        scale = float(scale)
+        if not (math.isfinite(scale) and scale >= 0.0):
+            raise ValueError(f"scale must be finite and >= 0 (got {scale!r})")
+        if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in feats):
+            raise RuntimeError(f"iefvad_amd.MMFMIL.{who} runs on a HIP device only; there is no CPU fallback (move the inputs with .to('cuda'); "
+                               "harness.sample_states_host is the host model of the sampled states)")
+        return samples, seed & 0xFFFFFFFFFFFFFFFF, scale
+
+    @staticmethod
+    def _samples_struct(S, seed, scale, sample_rows, res, stride) -> "_lib.Samples":
+        return _lib.Samples(S, seed, scale, sample_rows.data_ptr() if sample_rows is not None else None, res["logits_samples"].data_ptr(), stride,
+                            res["score_mean"].data_ptr(), res["score_std"].data_ptr())
+
+    def forward_samples(self, img_visual, ev_visual, samples: int, seed: int, *, scale: float = 1.0, sample_rows=None) -> Dict[str, torch.Tensor]:
+        """One forward and `samples` (1..64) Monte Carlo draws of every snippet's score from the heads' own Gaussians
+        (`iefvad_forward_samples`, include/iefvad.h).  The reference never samples; these semantics are this package's own ("parity
+        unpinned", as for `row_noise`).  For sample s, modality m, snippet id r and column c: eps = the standard normal of
+        `harness.gaussian_rows(harness.sample_seed(seed, s), m, ids, D)`, sd_m = scale exp(0.5 lv_m) / sqrt(f) (f the Student-t factor: the
+        variance the fusion itself assigns to m), mu~_m = mu_m + eps sd_m, z0_s = the fusion of the sampled means under the call's own
+        precisions, then the `self.steps` refinement steps and the classifier (`harness.sample_states_host` is the host model of z0_s).
+        The snippet id is `sample_rows[b*T + t]` (a contiguous int32 DEVICE vector of B*T ids) or b*T + t, so a snippet keeps its draws
+        whatever else is in the batch.  Returns what the plain call returns, with unchanged bits, plus `logits_samples` [S, B, T] fp32
+        (apply the sigmoid), `score_mean` and `score_std` [B, T]: mean and population standard deviation (ddof = 0) of the S scores,
+        formed on the device.  Encoder and heads run once.  model.train(), features that require grad and compute="fp16x3" raise
+        RuntimeError, as do host tensors; samples outside 1..64, a negative or non-finite scale raise ValueError.  It takes none of
+        `forward`'s keyword extras."""
+        S, seed, scale = self._samples_request("forward_samples", (img_visual, ev_visual), samples, seed, scale)
+        B, T, D = self._check_dense_inputs(img_visual, ev_visual)
+        device = img_visual.device
+        if sample_rows is not None and (not isinstance(sample_rows, torch.Tensor) or sample_rows.dtype != torch.int32 or sample_rows.device != device
+                                        or sample_rows.numel() != B * T or not sample_rows.is_contiguous()):
+            raise ValueError(f"sample_rows must be a contiguous int32 tensor of {B * T} elements (B*T) on {device}")
+        img, ev = self._prepare_pair(img_visual, ev_visual)
+        lib = _lib.load_library()
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._ensure_handle(device)
+            self._ensure_weights(device, stream)
+            ws = self._ensure_workspace(device, lib.iefvad_samples_workspace_bytes(self._handle, B))
+            f32 = dict(dtype=torch.float32, device=device)
+            res: Dict[str, torch.Tensor] = {}
+            o = _lib.Outputs()
+            for k, tail in _DENSE_OUTPUTS[self.outputs]:
+                res[k] = torch.empty(B, T, *((D,) if tail is None else tail), **f32)
+                setattr(o, k, res[k].data_ptr())
+            extra = {"logits_samples": torch.empty(S, B, T, **f32), "score_mean": torch.empty(B, T, **f32), "score_std": torch.empty(B, T, **f32)}
+            sm = self._samples_struct(S, seed, scale, sample_rows, extra, B * T)
+            rc = lib.iefvad_forward_samples(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], B,
+                                            C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(o), C.byref(sm), C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("iefvad_forward_samples: " + _lib.last_error())
+        if self.outputs == "full":
+            return {**{k: res[k] for k in OUTPUT_KEYS}, **extra}
+        return {**res, **extra}
+
+    def forward_videos_samples(self, img_rows, ev_rows, lengths, samples: int, seed: int, *, scale: float = 1.0,
+                               nan_to_num: bool = True, sample_rows=None) -> Dict[str, torch.Tensor]:
+        """`forward_samples` on whole videos (`iefvad_forward_videos_samples`): the valid rows [sum(lengths), D] and the lengths as
+        `forward_videos` takes them.  Returns `logits`, `w_i_mean`, `w_e_mean` with the bits of `forward_videos`, plus `logits_samples`
+        [S, sum(lengths)], `score_mean` and `score_std` [sum(lengths)], in packed order, valid rows only.  The snippet id is the packed row
+        of the call, in whatever micro-batch pass it falls -- the draws of the dense call on the padded chunks with `sample_rows` = packed
+        row -- or `sample_rows[r]` (a contiguous int32 DEVICE vector of sum(lengths) ids).  The refusals are `forward_samples`'s."""
+        S, seed, scale = self._samples_request("forward_videos_samples", (img_rows, ev_rows), samples, seed, scale)
+        if not isinstance(nan_to_num, bool):
+            raise ValueError(f"nan_to_num must be True or False (got {nan_to_num!r})")
+        lens = [int(n) for n in lengths]
+        total = sum(lens)
+        D = self.temporal.embed_dim
+        if img_rows.shape != ev_rows.shape or img_rows.dim() != 2 or tuple(img_rows.shape) != (total, D):
+            raise ValueError(f"expected two [{total}, {D}] tensors (sum of lengths x D), got {tuple(img_rows.shape)} and {tuple(ev_rows.shape)}")
+        if not lens or min(lens) < 1:
+            raise ValueError("every video needs at least one snippet")
+        device = img_rows.device
+        if sample_rows is not None and (not isinstance(sample_rows, torch.Tensor) or sample_rows.dtype != torch.int32 or sample_rows.device != device
+                                        or sample_rows.numel() != total or not sample_rows.is_contiguous()):
+            raise ValueError(f"sample_rows must be a contiguous int32 tensor of {total} elements (sum of lengths) on {device}")
+        img, ev = self._prepare_pair(img_rows, ev_rows)
+        larr = (C.c_int32 * len(lens))(*lens)
+        lib = _lib.load_library()
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._ensure_handle(device)
+            self._ensure_weights(device, stream)
+            ws = self._ensure_workspace(device, lib.iefvad_videos_samples_workspace_bytes(self._handle, larr, len(lens)))
+            f32 = dict(dtype=torch.float32, device=device)
+            res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
+            res.update(logits_samples=torch.empty(S, total, **f32), score_mean=torch.empty(total, **f32), score_std=torch.empty(total, **f32))
+            sm = self._samples_struct(S, seed, scale, sample_rows, res, total)
+            rc = lib.iefvad_forward_videos_samples(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr,
+                                                   len(lens), 1 if nan_to_num else 0, C.c_void_p(ws.data_ptr()), ws.numel(),
+                                                   *(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), C.byref(sm),
+                                                   C.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("iefvad_forward_videos_samples: " + _lib.last_error())
+        return res

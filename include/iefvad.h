@@ -816,6 +816,56 @@ int iefvad_forward_videos_variants(iefvad_handle* h, const void* img_rows, const
                                    size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
                                    const iefvad_variants* variants, void* stream);
 
+/* ---- score samples ---------------------------------------------------------------------------------------------------
+ * One forward, and per snippet S scores drawn from the model's own predictive spread: the heads predict a mean and a log-variance
+ * per modality, and the fusion (imf_vad.py:130-144) collapses each Gaussian to its mean.  Here the means are sampled instead.  The
+ * reference never samples, so these semantics are this library's own ("parity unpinned", as for the row noise above).  For sample
+ * s = 0 .. samples - 1, modality m (0 image, 1 event), snippet id r, column c:
+ *   seed_s = seed + s * 0x9E3779B97F4A7C15 (mod 2^64)
+ *   eps    = the standard normal of the row noise (iefvad_perturb) for (seed_s, r, m, c)
+ *   sd_m   = scale * exp(0.5 lv_m) / sqrt(f)        f: the Student-t factor (nu + 1) / nu, 1 for the Gaussian likelihood; so
+ *                                                   sd_m^2 = scale^2 / w_m, the variance the fusion itself assigns to modality m
+ *   mu~_m  = mu_m + eps * sd_m
+ *   z0_s   = (w_i / den) mu~_i + (w_e / den) mu~_e  with the call's own w_i, w_e, den = w_i + w_e + epsilon
+ * followed by the unchanged refinement (the handle's current iefvad_set_steps count) and classifier.  Literal fp32, no clamps: inf
+ * and NaN behave as the expression does.  scale = 0 reproduces the call's logits in every sample (within the arithmetic's tolerance).
+ * The snippet id is the one the row noise uses: sample_rows[row] (a DEVICE int32 vector over the call's rows, nullable), else the row
+ * of the call -- b T + t (dense), the packed row (whole videos).  A snippet with the same id gets the same draws on either route, in
+ * any batch composition and in any micro-batch pass.
+ *   logits_samples[s * stride + row]   before the sigmoid; `stride`: ELEMENTS between two samples, at least the call's rows
+ *   score_mean[row], score_std[row]    mean and population standard deviation (ddof = 0) over s of sigmoid(logits_samples[s]):
+ *                                      formed on the device in fp32, samples in index order, two passes, no atomics -- the same call
+ *                                      gives the same bits
+ * All three are device fp32 pointers, 4-byte aligned; on the whole-video entry only valid rows are written.
+ * Encoder and heads run once.  Behind the call's own tail, per group of up to 4 samples, one row kernel
+ * (iefvad_sample_states_kernel, csrc/samples.h) forms the group's z0 from the pass's mu / logvar and the refinement + scorer run once
+ * more on the stacked states with the kernels the unchanged selection rules pick for that row count; iefvad_samples_reduce_kernel
+ * follows the last group.  Every other output of the call has the bits of the same call without samples.  One group's stacked state,
+ * scratch and logits live behind the base workspace: use the _samples_workspace_bytes queries (they do not depend on S).  Direct
+ * launches (no hipGraph).  Refused by name before any launch: IEFVAD_COMPUTE_FP16X3 (its per-chunk running-max words have no home for
+ * the stacked states), a null struct, samples outside 1..64, a negative or non-finite scale, a null or misaligned result pointer, a
+ * stride below the call's rows, a workspace smaller than the query says.  Not covered: the host-list entries and training.  Added
+ * without a change to any other entry: IEFVAD_ABI_VERSION stays. */
+typedef struct iefvad_samples {
+    int32_t samples;                /* S, 1..64 */
+    uint64_t seed;
+    float scale;                    /* >= 0, finite; 1 = the heads' own spread */
+    const int32_t* sample_rows;     /* device, nullable */
+    float* logits_samples;          /* device [S, stride] */
+    size_t stride;
+    float* score_mean;              /* device [rows] */
+    float* score_std;               /* device [rows] */
+} iefvad_samples;
+size_t iefvad_samples_workspace_bytes(const iefvad_handle* h, int32_t B);
+int iefvad_forward_samples(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                           size_t workspace_bytes, const iefvad_outputs* out, const iefvad_samples* samples, void* stream);
+/* Mirrors iefvad_forward_videos: [S, stride] and the two vectors in packed order. */
+size_t iefvad_videos_samples_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos);
+int iefvad_forward_videos_samples(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                  const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, void* workspace,
+                                  size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                  const iefvad_samples* samples, void* stream);
+
 /* The exact three-term bf16 split of n fp32 values (n % 4 == 0): planes[0..n) = bf16(x),
  * planes[n..2n) = bf16(x - p0), planes[2n..3n) = bf16(x - p0 - p1), round-to-nearest-even; x == p0 + p1 + p2
  * for finite x.  What iefvad_set_weights applies to every projection matrix in IEFVAD_COMPUTE_BF16X6. */
