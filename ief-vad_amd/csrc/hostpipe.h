@@ -181,7 +181,7 @@ static int forward_videos_host_impl(iefvad_handle* h, const HostRowsIn& in, cons
             }
         p.slot_bytes = cap;
     }
-    const size_t need_ws = iefvad_workspace_bytes(h, (int32_t)max_chunks) + videos_extra_bytes(h, max_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
+    const size_t need_ws = videos_tail(h, max_chunks, out.wants()).total;
     if (p.workspace_bytes < need_ws) {
         HIP_TRY(hipDeviceSynchronize());                   // a forward of an earlier call may still use the old workspaces
         p.workspace_bytes = 0;

@@ -25,6 +25,7 @@
 #include "attention_split.h"
 #include "common.h"
 #include "launch_rules.h"
+#include "workspace_tail.h"
 #include "gather.h"
 #include "gemm_f32.h"
 #include "gemm_bf16.h"
@@ -988,12 +989,7 @@ struct RowsIn {
         return RowsIn{(const char*)img + o, (const char*)ev + o, in_dtype};
     }
 };
-static const float* const kNoScale[2] = {nullptr, nullptr};      // per-row input scales: only the two scaled entries carry them
 
-// Where the results of a whole-video call go: one record per call, filled by the entry (csrc/videos.h, csrc/hostpipe.h); it is defined
-// here because a pass (RaggedPass, below) holds the view of it at its own first packed row.  `at` is the one place where row offsets
-// are added: it advances the vectors and the [rows, D] tensors; the series keeps its base pointer and takes its column from row0, which
-// `at` advances by the same rows.  Everything is nullable except logits.
 // The head-averaged attention maps a call asked for (include/iefvad.h, csrc/attention_maps.h): [rows, 256] fp32 per modality and layer,
 // null where not asked for.  `at` moves every map to a later first row.
 struct AttnMaps {
@@ -1015,18 +1011,23 @@ struct AttnMaps {
 
 // The refinement trajectory a call asked for (include/iefvad.h, csrc/trajectory.h): the [steps + 1, stride] logits and the
 // [steps, stride] update norms of the whole CALL, either nullable; a pass writes columns row0 + packed row of the pass.  z_prev: the
-// pass's second state buffer ([R, D] floats behind the base workspace), set by the entry.
+// pass's second state buffer (workspace_tail.h), set by Extras::place.
 struct TrajOut {
     float* logits_steps;
     float* delta_norm;
     long long stride, row0;
     float* z_prev;
     bool any() const { return logits_steps || delta_norm; }
+    TrajOut at(long long rows) const {
+        TrajOut o = *this;
+        o.row0 += rows;
+        return o;
+    }
 };
 
 // The fusion ablations a call asked for (include/iefvad.h, csrc/variants.h): the [count, stride] logits of the whole CALL; a pass writes
 // columns row0 + packed row of the pass.  ws: the stacked state [count, R, D], its h scratch of the same size and the [count, R]
-// logits of a pass (variants_bytes), behind everything else of the workspace; set by the entry.
+// logits of a pass (workspace_tail.h), set by Extras::place.
 struct VarOut {
     int count;
     int kind[IEF_MAX_VARIANTS];
@@ -1034,13 +1035,17 @@ struct VarOut {
     long long stride, row0;
     float* ws;
     bool any() const { return logits != nullptr; }
+    VarOut at(long long rows) const {
+        VarOut o = *this;
+        o.row0 += rows;
+        return o;
+    }
 };
-static size_t variants_bytes(size_t pass_chunks, int D, int count) { return (size_t)count * pass_chunks * IEF_T * (2 * (size_t)D + 1) * sizeof(float); }
 
 // The score samples a call asked for (include/iefvad.h, csrc/samples.h): the [count, stride] logits and the per-snippet mean / standard
 // deviation of the scores of the whole CALL; a pass writes columns row0 + packed row of the pass.  ids: the snippet ids at the pass's
-// first packed row (nullable: row0 + packed row).  ws: the workspace of a group of IEF_MAX_VARIANTS stacked states (variants_bytes),
-// behind everything else; set by the entry.
+// first packed row (nullable: row0 + packed row).  ws: the workspace of a group of IEF_MAX_VARIANTS stacked states (workspace_tail.h),
+// set by Extras::place.
 struct SampleOut {
     int count;
     unsigned long long seed;
@@ -1060,13 +1065,62 @@ struct SampleOut {
     }
 };
 
+// What a call asks for beyond its base outputs, on either route: filled by the entry, value-initialised = nothing.  `at` is the one place
+// that moves it to a later first row of the call (the series keep their base pointers and take their column from row0); `place` the
+// one place that gives the members their homes behind the base workspace (workspace_tail.h, which carries its own copies of two sizes).
+static_assert(kTailChunkRows == IEF_T && kTailSampleGroup == IEF_MAX_VARIANTS, "workspace_tail.h is out of step with common.h / variants.h");
+struct Extras {
+    const float* scale[2];           // the scaled / perturbed entries: per-row input scales (image, event), [rows] each
+    RowNoise noise;                  // the perturbed entries: per-row noise amplitudes, ids and seed (common.h)
+    AttnMaps attn;                   // the attn entries: [rows, 256] maps, written inside the encoder (pass_encoder_layer)
+    TrajOut traj;                    // the trajectory entries
+    VarOut var;                      // the variants entries
+    SampleOut smp;                   // the samples entries
+    bool keep_heads() const { return var.any() || smp.any(); }      // both re-form z0 from all four head tensors
+    TailWants wants() const { return TailWants{false, false, traj.any(), var.any() ? var.count : 0, smp.any()}; }
+    Extras at(long long rows) const {
+        Extras o = *this;
+        for (int m = 0; m < 2; ++m)
+            if (scale[m]) o.scale[m] += rows;
+        o.noise = noise.at(rows);        // ids default to the row of the CALL
+        o.attn = attn.at(rows);
+        o.traj = traj.at(rows);
+        o.var = var.at(rows);
+        o.smp = smp.at(rows);
+        return o;
+    }
+    void place(void* workspace, const WorkspaceTail& t) {
+        if (traj.any()) traj.z_prev = (float*)((char*)workspace + t.z_prev);
+        if (var.any()) var.ws = (float*)((char*)workspace + t.var);
+        if (smp.any()) smp.ws = (float*)((char*)workspace + t.smp);
+    }
+};
+
+// The row perturbation of a call as the kernels take it (common.h): the caller's amplitudes, ids and seed at row 0 of the call
+static RowNoise row_noise(const iefvad_perturb& p) {
+    RowNoise nz = {};
+    nz.amp[0] = p.noise_amp[0]; nz.amp[1] = p.noise_amp[1];
+    nz.id = p.noise_row;
+    nz.seed = p.seed;
+    return nz;
+}
+// ... and with its scales, as the record of a call that asks for nothing else
+static Extras perturb_extras(const iefvad_perturb& p) {
+    Extras x = {};
+    x.scale[0] = p.scale[0]; x.scale[1] = p.scale[1];
+    x.noise = row_noise(p);
+    return x;
+}
+
+// Where the results of a whole-video call go: one record per call, filled by the entry (csrc/videos.h, csrc/hostpipe.h); it is defined
+// here because a pass (RaggedPass, below) holds the view of it at its own first packed row.  `at` is the one place where row offsets
+// are added: it advances the vectors, the [rows, D] tensors and the extras; the series keeps its base pointer and takes its column
+// from row0, which `at` advances by the same rows.  Everything is nullable except logits.
 enum { kWideFused = 0, kWideMuI, kWideMuE, kWideLvI, kWideLvE, kWideWi, kWideWe };
 struct VideosOut {
     float* logits;                   // [rows] each
     float* w_i_mean;
     float* w_e_mean;
-    const float* scale[2];           // iefvad_forward_videos_scaled: per-row input scales (image, event), [rows] each
-    RowNoise noise;                  // iefvad_forward_videos_perturbed: per-row noise amplitudes, ids and seed (common.h); all null otherwise
     double* w_colsum;                // iefvad_forward_videos_scaled: [2, D], the call's column sums of w_i / w_e over its valid rows
     // the similarity entries: the [4, sim_stride] series; packed row r of this view is column row0 + r.  With it the tail keeps fused
     // (= z_K) and both mu of its row set (tail_keep).
@@ -1076,29 +1130,25 @@ struct VideosOut {
     // tensors of its row set (mu / lv / z in the workspace aliases of pass_buffers, the weights in w_rows) and
     // iefvad_rows_out_wide_kernel copies the valid rows out (pass_rows_out).
     float* wide[ROWS_OUT_WIDE_MAX];
-    AttnMaps attn;                   // iefvad_forward_videos_attn: the packed [rows, 256] maps, written inside the encoder (pass_encoder_layer)
-    SampleOut smp;                   // iefvad_forward_videos_samples: the score samples; keeps its bases and takes its column from row0
-    VarOut var;                      // iefvad_forward_videos_variants: the ablations' logits; keeps its base and takes its column from row0
-    TrajOut traj;                    // iefvad_forward_videos_trajectory: the per-step series; like the similarity series it keeps its base and takes its column from row0
+    Extras x;                        // the scaled, perturbed, attn, trajectory, variants and samples entries: what they add, in packed rows
     long long row0;                  // packed row of the call's list (the host entries: of the whole list) that this view's first row is
     int nan_mode;                    // 0 = rows as they are, 1 = the per-video rule of test.py:90-95, 2 = every video and modality (test2.py:59-60)
     bool sweep_codes;                // the scaled entry: nan_mode outside 0..2 is refused (the other entries read any non-zero value as 1)
 
     bool wants_w_rows() const { return w_colsum || wide[kWideWi] || wide[kWideWe]; }      // the fusion stage must store its weights
+    TailWants wants() const {
+        TailWants w = x.wants();
+        w.w_rows = wants_w_rows(); w.colsum = w_colsum != nullptr;
+        return w;
+    }
     VideosOut at(long long rows, int D) const {
         VideosOut o = *this;
         o.logits += rows;
         if (w_i_mean) o.w_i_mean += rows;
         if (w_e_mean) o.w_e_mean += rows;
-        for (int m = 0; m < 2; ++m)
-            if (scale[m]) o.scale[m] += rows;
-        o.noise = noise.at(rows);
         for (int t = 0; t < ROWS_OUT_WIDE_MAX; ++t)
             if (wide[t]) o.wide[t] += rows * D;
-        o.attn = attn.at(rows);
-        o.traj.row0 += rows;
-        o.var.row0 += rows;
-        o.smp = smp.at(rows);
+        o.x = x.at(rows);
         o.row0 += rows;
         return o;
     }
@@ -1201,8 +1251,7 @@ static ProjCtx proj_ctx(const iefvad_handle* h, const PassBuffers& b, hipStream_
 }
 
 // 0. inputs: `.to(torch.float)` (imf_vad.py:41-42) into b.cur; bf16 mode also gets the bf16 operand copy (b.need_xb0)
-static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, const float* const scale[2], const RowNoise& nz,
-                            const RaggedPass* rg, hipStream_t stream, Timer& tm) {
+static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, const Extras& x, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     const size_t D = h->D, n = b.R * D;
     const void* const pi = in.img;
     const void* const pe = in.ev;
@@ -1222,10 +1271,9 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
         }
         // (the NaN flags of ALL the call's videos are already set: forward_videos_impl scans every pass's chunks before the
         // first pass runs, because test.py:90-95 decides per whole video and a video may straddle passes)
-        const VideosOut& o = rg->out;
-        const int nan_all = o.nan_mode == 2;
-        const bool scaled = o.scale[0] || o.scale[1] || nan_all;
-        const bool noisy = o.noise.any();       // an amplitude vector selects the noise instantiation; every other call launches what it always has
+        const int nan_all = rg->out.nan_mode == 2;
+        const bool scaled = x.scale[0] || x.scale[1] || nan_all;
+        const bool noisy = x.noise.any();       // an amplitude vector selects the noise instantiation; every other call launches what it always has
         if (int rc = dispatch_in(in_dtype, d512, [&](auto t, auto w) {
                 using T = typename decltype(t)::type;
                 constexpr int W = decltype(w)::value;
@@ -1233,16 +1281,16 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
                 const int nrows = b.enc_rows_mode ? 0 : IEF_T;
                 if (noisy)
                     return launch(tm, ST_CAST, iefvad_scatter_rows_kernel<T, W, true, RowNoise>, grid, dim3(256), 0, stream, (const T*)pi, (const T*)pe,
-                                  rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0], o.scale[1], nan_all, o.noise);
+                                  rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, x.scale[0], x.scale[1], nan_all, x.noise);
                 return launch(tm, ST_CAST, scaled ? iefvad_scatter_rows_kernel<T, W, true> : iefvad_scatter_rows_kernel<T, W, false>, grid, dim3(256), 0,
-                              stream, (const T*)pi, (const T*)pe, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, o.scale[0], o.scale[1],
+                              stream, (const T*)pi, (const T*)pe, rg->d_chunks, rg->d_flags, b.xin[0], b.xin[1], b0p, b1p, nrows, x.scale[0], x.scale[1],
                               nan_all);
             })) return rc;
-    } else if (scale[0] || scale[1] || nz.any()) {
+    } else if (x.scale[0] || x.scale[1] || x.noise.any()) {
         // iefvad_forward_scaled / _perturbed: the rows pass through the cast kernel whatever their type, scaled and perturbed on the way (rowops.h)
         hipEvent_t e = tm.begin(ST_CAST);
         const int rc = dispatch_in(in_dtype, d512, [&](auto t, auto w) {
-            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, scale[0], scale[1], nz, stream);
+            return launch_cast_scaled<typename decltype(t)::type, decltype(w)::value>(pi, pe, b.xin[0], b.xin[1], b0p, b1p, n, x.scale[0], x.scale[1], x.noise, stream);
         });
         tm.end(e);
         if (rc) return rc;
@@ -1273,7 +1321,7 @@ static int pass_load_inputs(iefvad_handle* h, PassBuffers& b, const RowsIn& in, 
 }
 
 // 1. one layer of the temporal encoder (imf_vad.py:113-123): in_proj, attention, out_proj + residual, LayerNorm; b.cur moves to its output
-static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const RaggedPass* rg, const AttnMaps* maps, hipStream_t stream, Timer& tm) {
+static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const RaggedPass* rg, const AttnMaps& maps, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
     const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const int D = h->D, L = c.num_layers, rows = b.rows, nb = b.nb;
@@ -1314,13 +1362,13 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
         if (int rc = launch(tm, ST_ATT, kernel, dim3(IEF_H, 2, 2 * nb), dim3(256), b.splitmb ? ATS_LDS_BYTES : 0, stream, aa)) return rc;
     }
 
-    if (maps && (maps->p[0][l] || maps->p[1][l])) {
+    if (maps.p[0][l] || maps.p[1][l]) {
         // the layer's head-averaged attention weights, from q | k | v while they are alive (attention_maps.h).  The entries refuse
         // the bf16 arithmetic, whose q | k | v are bf16 planes in another layout.
         if (bf) return fail("attention maps: compute = BF16 is not supported");
         AttnMapArgs ma;
         memset(&ma, 0, sizeof(ma));
-        for (int m = 0; m < 2; ++m) { ma.qkv[m] = b.qkv[m]; ma.out[m] = maps->p[m][l]; }
+        for (int m = 0; m < 2; ++m) { ma.qkv[m] = b.qkv[m]; ma.out[m] = maps.p[m][l]; }
         ma.nchunks = nb;
         ma.chunks = rg ? rg->d_chunks : nullptr;
         void (*const kernel)(AttnMapArgs) = d512 ? (enc_chunks ? iefvad_attention_maps_kernel<true, 64> : iefvad_attention_maps_kernel<false, 64>)
@@ -1405,6 +1453,15 @@ static TailKeep tail_keep(const iefvad_outputs* out, const RaggedPass* rg, bool 
                     out->image_logvar || rows(kWideLvI, false) || heads, out->event_logvar || rows(kWideLvE, false) || heads};
 }
 
+// The rows of a pass that carry results, as the kernels behind the tail take them: the chunk table on the row-compressed / whole-chunk
+// set (one slab per chunk), or no table on a dense or a compacted set, which is in packed order already (256-row slabs of it).
+struct RowSet { const RaggedChunk* chunks; int valid_rows, nslabs; };
+static RowSet row_set(const PassBuffers& b, const RaggedPass* rg) {
+    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
+    const int valid_rows = rg ? rg->valid_rows : b.rows;
+    return RowSet{chunks, valid_rows, chunks ? b.nb : (valid_rows + 255) / 256};
+}
+
 // The probe of state z_k of a trajectory pass (trajectory.h): k = 0 behind the fusion, k = j + 1 behind step j.  `copy_logits`: entry k
 // is the pass's logits, already in b.logits (the folded scorer).
 static int pass_step_probe(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const TrajOut& tj, int k, int steps, bool copy_logits,
@@ -1413,9 +1470,9 @@ static int pass_step_probe(iefvad_handle* h, const PassBuffers& b, const RaggedP
     float* const dn = (tj.delta_norm && k > 0) ? tj.delta_norm + (long long)(k - 1) * tj.stride : nullptr;
     const int store_prev = tj.delta_norm && k < steps;
     if (!lo && !dn && !store_prev) return 0;
-    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
-    const int valid_rows = rg ? rg->valid_rows : b.rows;
-    const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
+    const RowSet rs = row_set(b, rg);
+    const RaggedChunk* const chunks = rs.chunks;
+    const int valid_rows = rs.valid_rows, nslabs = rs.nslabs;
     return dispatch_d(h->D == IEF_D512, [&](auto w) {
         return launch(tm, ST_SCORER, iefvad_step_probe_kernel<decltype(w)::value>, dim3(nslabs, TRAJ_SLICES), dim3(256), 0, stream, (const float*)b.z, tj.z_prev,
                       (const float*)h->cls_w, (const float*)h->cls_b, copy_logits ? (const float*)b.logits : (const float*)nullptr, chunks, valid_rows, lo, dn,
@@ -1423,8 +1480,65 @@ static int pass_step_probe(iefvad_handle* h, const PassBuffers& b, const RaggedP
     });
 }
 
+// 4 - 5 of the tail on the state b.z of b.rows rows (scratch b.hbuf / b.hb / b.zb, partial sums in the y region, logits to b.logits),
+// with the kernels b's TailFlags name: the call's own tail (pass_tail), and once more the stacked states of its fusion ablations
+// and score samples (pass_stacked).  chain: the bf16 chain kernel takes steps and scorer; keep_fused: z_K is wanted, not the logits alone.
 static int pass_refine_score(iefvad_handle* h, PassBuffers& b, const RaggedPass* rg, const TrajOut* tj, bool chain, bool keep_fused, hipStream_t stream,
-                             Timer& tm);
+                             Timer& tm) {
+    const iefvad_config& c = h->cfg;
+    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
+    const int D = h->D, K = h->steps, rows = b.rows;
+    const bool d512 = h->D == IEF_D512;
+    const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
+    float* const z = b.z;
+    ProjCtx px = proj_ctx(h, b, stream, tm);
+    px.use_split = b.tail_split;
+    const bool fold = b.fold;
+    const float* const score_fold = score_fold_of(h, K);
+
+    if (chain)
+        if (int rc = launch_refine_chain(h, z, keep_fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
+
+    // bf16x6 on the split kernels: the last step's second projection is folded into the scorer,
+    //   logits = c . z_K + b_c = c . z_{K-1} + v . h + s0     (v, s0: iefvad_set_weights; rowops.h),
+    // v . h taken in the epilogue of the last step's FIRST projection (EPI_BIAS_RELU_DOT: six partial sums per row, into the y
+    // region, dead since the last LayerNorm).  Without `fused` in the outputs (and no similarity reduction behind the pass:
+    // keep_fused) that projection stores no h and the last W2 launch does not run; with it, h is stored and z_K is formed as always,
+    // after the scorer has read z_{K-1} (EPI_REFINE updates z in place) -- so the logits of both output sets are the same bits.
+    float* const fold_part = b.ybuf[0];
+
+    // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
+    for (int k = 0; k < K && !chain; ++k) {
+        const bool dot = fold && k == K - 1;
+        Proj p = Proj::of(EPI_BIAS_RELU, D, D, h->ref1[k]);
+        p.A32[0] = z; p.A16[0] = b.zb; p.amaxA[0] = b.am_z(k); p.amaxC[0] = b.am_h(k);
+        p.C[0] = bf ? nullptr : b.hbuf; p.Cb[0] = bf ? b.hb : nullptr;
+        if (dot) {
+            p.epi = EPI_BIAS_RELU_DOT; p.R[0] = score_fold; p.C2[0] = fold_part;
+            if (!keep_fused) p.C[0] = nullptr;
+        }
+        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
+        if (dot) {
+            if (int rc = launch(tm, ST_SCORER, iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>, row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
+                                score_fold, b.logits, rows)) return rc;
+            if (!keep_fused) break;
+        }
+        p = Proj::of(EPI_REFINE, D, D, h->ref2[k]);
+        p.alpha = c.lambda_ref;
+        p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
+        p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
+        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
+        if (tj)
+            if (int rc = pass_step_probe(h, b, rg, *tj, k + 1, K, dot, stream, tm)) return rc;
+    }
+
+    // 5. scorer (imf_vad.py:150)
+    if (!chain && !fold)
+        return dispatch_d(d512, [&](auto w) {
+            return launch(tm, ST_SCORER, iefvad_scorer_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, z, h->cls_w, h->cls_b, b.logits, rows);
+        });
+    return 0;
+}
 
 // 2 - 5. everything behind the encoder, row-wise: heads, fusion, refinement, scorer.  K is the handle's current step count
 // (iefvad_set_steps): blocks 0 .. K - 1 run.  `tj` (nullable): the pass records its trajectory -- a probe launch behind the fusion and
@@ -1488,74 +1602,14 @@ static int pass_tail(iefvad_handle* h, PassBuffers& b, const iefvad_outputs* out
     return pass_refine_score(h, b, rg, tj, chain, keep_fused, stream, tm);
 }
 
-// 4 - 5 of the tail on the state b.z of b.rows rows (scratch b.hbuf / b.hb / b.zb, partial sums in the y region, logits to b.logits),
-// with the kernels b's TailFlags name: the call's own tail (pass_tail), and once more the stacked states of its fusion ablations
-// (pass_variants).  chain: the bf16 chain kernel takes steps and scorer; keep_fused: z_K is wanted, not the logits alone.
-static int pass_refine_score(iefvad_handle* h, PassBuffers& b, const RaggedPass* rg, const TrajOut* tj, bool chain, bool keep_fused, hipStream_t stream,
-                             Timer& tm) {
-    const iefvad_config& c = h->cfg;
-    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
-    const int D = h->D, K = h->steps, rows = b.rows;
-    const bool d512 = h->D == IEF_D512;
-    const dim3 row_grid((rows + ROW_WAVES - 1) / ROW_WAVES);
-    float* const z = b.z;
-    ProjCtx px = proj_ctx(h, b, stream, tm);
-    px.use_split = b.tail_split;
-    const bool fold = b.fold;
-    const float* const score_fold = score_fold_of(h, K);
-
-    if (chain)
-        if (int rc = launch_refine_chain(h, z, keep_fused ? z : nullptr, b.logits, rows, stream, tm)) return rc;
-
-    // bf16x6 on the split kernels: the last step's second projection is folded into the scorer,
-    //   logits = c . z_K + b_c = c . z_{K-1} + v . h + s0     (v, s0: iefvad_set_weights; rowops.h),
-    // v . h taken in the epilogue of the last step's FIRST projection (EPI_BIAS_RELU_DOT: six partial sums per row, into the y
-    // region, dead since the last LayerNorm).  Without `fused` in the outputs (and no similarity reduction behind the pass:
-    // keep_fused) that projection stores no h and the last W2 launch does not run; with it, h is stored and z_K is formed as always,
-    // after the scorer has read z_{K-1} (EPI_REFINE updates z in place) -- so the logits of both output sets are the same bits.
-    float* const fold_part = b.ybuf[0];
-
-    // 4. K refinement steps z <- z - lambda * (W2 relu(W1 z + b1) + b2) (imf_vad.py:146-149); the state z stays fp32
-    for (int k = 0; k < K && !chain; ++k) {
-        const bool dot = fold && k == K - 1;
-        Proj p = Proj::of(EPI_BIAS_RELU, D, D, h->ref1[k]);
-        p.A32[0] = z; p.A16[0] = b.zb; p.amaxA[0] = b.am_z(k); p.amaxC[0] = b.am_h(k);
-        p.C[0] = bf ? nullptr : b.hbuf; p.Cb[0] = bf ? b.hb : nullptr;
-        if (dot) {
-            p.epi = EPI_BIAS_RELU_DOT; p.R[0] = score_fold; p.C2[0] = fold_part;
-            if (!keep_fused) p.C[0] = nullptr;
-        }
-        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
-        if (dot) {
-            if (int rc = launch(tm, ST_SCORER, iefvad_scorer_fold_kernel<IEF_D, IEF_D / kSplitBN>, row_grid, dim3(256), 0, stream, z, h->cls_w, fold_part,
-                                score_fold, b.logits, rows)) return rc;
-            if (!keep_fused) break;
-        }
-        p = Proj::of(EPI_REFINE, D, D, h->ref2[k]);
-        p.alpha = c.lambda_ref;
-        p.A32[0] = b.hbuf; p.A16[0] = b.hb; p.amaxA[0] = b.am_h(k); p.amaxC[0] = b.am_z(k + 1);
-        p.C[0] = z; p.R[0] = z; p.Cb[0] = (bf && k + 1 < K) ? b.zb : nullptr;
-        if (int rc = launch_proj(px, p, ST_REFINE)) return rc;
-        if (tj)
-            if (int rc = pass_step_probe(h, b, rg, *tj, k + 1, K, dot, stream, tm)) return rc;
-    }
-
-    // 5. scorer (imf_vad.py:150)
-    if (!chain && !fold)
-        return dispatch_d(d512, [&](auto w) {
-            return launch(tm, ST_SCORER, iefvad_scorer_kernel<decltype(w)::value>, row_grid, dim3(256), 0, stream, z, h->cls_w, h->cls_b, b.logits, rows);
-        });
-    return 0;
-}
-
 // 6. a ragged pass: the valid rows' results -> the caller's packed vectors and tensors (test.py:119-121: logits1[0:len_cur]), from
-// where the tail left them.  The row set is the chunk table on the row-compressed / whole-chunk set; a compacted set is already in
-// packed order (256-row slabs of it, no table).
+// where the tail left them, by the pass's row set (row_set).
 static int pass_rows_out(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     const VideosOut& o = rg->out;
     const bool d512 = h->D == IEF_D512;
-    const RaggedChunk* const chunks = b.compacted ? nullptr : rg->d_chunks;
-    const int valid_rows = rg->valid_rows, nslabs = b.compacted ? (valid_rows + 255) / 256 : b.nb;
+    const RowSet rs = row_set(b, rg);
+    const RaggedChunk* const chunks = rs.chunks;
+    const int valid_rows = rs.valid_rows, nslabs = rs.nslabs;
     if (int rc = launch(tm, ST_SCORER, iefvad_rows_out_kernel, dim3(nslabs), dim3(256), 0, stream, b.logits, b.wim_out, b.wem_out, o.logits, o.w_i_mean,
                         o.w_e_mean, chunks, valid_rows)) return rc;
     if (o.similarity)      // the four series of the pass's valid rows from z_K / mu_i / mu_e (similarity.h)
@@ -1609,34 +1663,42 @@ static PassBuffers stacked_buffers(const iefvad_handle* h, const PassBuffers& b,
 // ... and, behind steps 4 - 5 on the stacked set, the valid rows' logits to rows 0 .. V - 1 of a [V, stride] result at `dst`
 static int pass_stacked_out(const PassBuffers& b, const PassBuffers& s, const RaggedPass* rg, int V, float* dst, long long stride, long long row0,
                             hipStream_t stream, Timer& tm) {
-    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
-    const int valid_rows = rg ? rg->valid_rows : b.rows;
-    const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
+    const RowSet rs = row_set(b, rg);
+    const RaggedChunk* const chunks = rs.chunks;
+    const int valid_rows = rs.valid_rows, nslabs = rs.nslabs;
     return launch(tm, ST_SCORER, iefvad_variants_out_kernel, dim3(nslabs, V), dim3(256), 0, stream, (const float*)s.logits, b.rows, chunks, valid_rows, dst,
                   stride, row0);
+}
+// The four steps on V stacked states: their buffers in `ws`, `fill(s, zb)` writes the V z0 (zb: the bf16 copy, null where the tail
+// does not read it), steps 4 - 5, the valid rows' logits to `dst`
+template <typename Fill>
+static int pass_stacked(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, float* ws, int V, float* dst, long long stride, long long row0,
+                        hipStream_t stream, Timer& tm, Fill&& fill) {
+    PassBuffers s = stacked_buffers(h, b, ws, V);
+    if (int rc = fill(s, (h->cfg.compute == IEFVAD_COMPUTE_BF16 && !s.chain) ? s.zb : nullptr)) return rc;
+    if (int rc = pass_refine_score(h, s, rg, nullptr, s.chain, false, stream, tm)) return rc;
+    return pass_stacked_out(b, s, rg, V, dst, stride, row0, stream, tm);
 }
 
 // 7. the fusion ablations of a pass (variants.h), behind its own results: the variants' z0 from the kept mu / logvar of the row set,
 // stacked behind the workspace, then steps 4 - 5 on it, then the valid rows' logits to the call's [count, stride] result.
 static int pass_variants(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const VarOut& vo, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
-    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const bool d512 = h->D == IEF_D512;
     const int V = vo.count, rows = b.rows;
-    PassBuffers s = stacked_buffers(h, b, vo.ws, V);
-    VariantArgs va;
-    memset(&va, 0, sizeof(va));
-    va.mu_i = b.mu_i; va.lv_i = b.lv_i; va.mu_e = b.mu_e; va.lv_e = b.lv_e;
-    va.z = s.z;
-    va.zb = (bf && !s.chain) ? s.zb : nullptr;
-    va.nrows = rows; va.count = V;
-    for (int v = 0; v < V; ++v) va.kind[v] = vo.kind[v];
-    va.factor = precision_factor(c); va.eps = c.epsilon;
-    if (int rc = dispatch_d(d512, [&](auto w) {
+    return pass_stacked(h, b, rg, vo.ws, V, vo.logits, vo.stride, vo.row0, stream, tm, [&](const PassBuffers& s, bf16_t* zb) {
+        VariantArgs va;
+        memset(&va, 0, sizeof(va));
+        va.mu_i = b.mu_i; va.lv_i = b.lv_i; va.mu_e = b.mu_e; va.lv_e = b.lv_e;
+        va.z = s.z;
+        va.zb = zb;
+        va.nrows = rows; va.count = V;
+        for (int v = 0; v < V; ++v) va.kind[v] = vo.kind[v];
+        va.factor = precision_factor(c); va.eps = c.epsilon;
+        return dispatch_d(d512, [&](auto w) {
             return launch(tm, ST_FUSION, iefvad_fusion_variants_kernel<decltype(w)::value>, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, va);
-        })) return rc;
-    if (int rc = pass_refine_score(h, s, rg, nullptr, s.chain, false, stream, tm)) return rc;
-    return pass_stacked_out(b, s, rg, V, vo.logits, vo.stride, vo.row0, stream, tm);
+        });
+    });
 }
 
 // 7'. the score samples of a pass (samples.h), behind its own results: groups of up to IEF_MAX_VARIANTS samples, each the sampled z0
@@ -1645,64 +1707,66 @@ static int pass_variants(iefvad_handle* h, const PassBuffers& b, const RaggedPas
 static unsigned long long sample_seed(unsigned long long seed, int s) { return seed + (unsigned long long)s * 0x9E3779B97F4A7C15ull; }
 static int pass_samples(iefvad_handle* h, const PassBuffers& b, const RaggedPass* rg, const SampleOut& so, hipStream_t stream, Timer& tm) {
     const iefvad_config& c = h->cfg;
-    const bool bf = (c.compute == IEFVAD_COMPUTE_BF16);
     const bool d512 = h->D == IEF_D512;
-    const RaggedChunk* const chunks = (rg && !b.compacted) ? rg->d_chunks : nullptr;
-    const int valid_rows = rg ? rg->valid_rows : b.rows;
-    const int nslabs = chunks ? b.nb : (valid_rows + 255) / 256;
+    const RowSet rs = row_set(b, rg);
+    const RaggedChunk* const chunks = rs.chunks;
+    const int valid_rows = rs.valid_rows, nslabs = rs.nslabs;
     for (int s0 = 0; s0 < so.count; s0 += IEF_MAX_VARIANTS) {
         const int G = so.count - s0 < IEF_MAX_VARIANTS ? so.count - s0 : IEF_MAX_VARIANTS;
-        PassBuffers s = stacked_buffers(h, b, so.ws, G);
-        SampleArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.mu_i = b.mu_i; sa.lv_i = b.lv_i; sa.mu_e = b.mu_e; sa.lv_e = b.lv_e;
-        sa.z = s.z;
-        sa.zb = (bf && !s.chain) ? s.zb : nullptr;
-        sa.chunks = chunks; sa.ids = so.ids; sa.row0 = so.row0;
-        sa.nrows = b.rows; sa.valid_rows = valid_rows;
-        sa.used_rows = (chunks && b.enc_rows_mode) ? rg->enc_used_rows : b.rows;
-        sa.chunk_rows = b.enc_rows_mode ? 0 : IEF_T;
-        sa.count = G;
-        for (int g = 0; g < G; ++g) sa.seed[g] = sample_seed(so.seed, s0 + g);
-        sa.factor = precision_factor(c); sa.eps = c.epsilon; sa.scale = so.scale;
-        const dim3 grid(chunks ? b.nb + 1 : (b.rows + 255) / 256, SAMPLE_SLICES);
-        if (int rc = dispatch_d(d512, [&](auto w) {
-                return launch(tm, ST_FUSION, iefvad_sample_states_kernel<decltype(w)::value>, grid, dim3(256), 0, stream, sa);
+        if (int rc = pass_stacked(h, b, rg, so.ws, G, so.logits + (long long)s0 * so.stride, so.stride, so.row0, stream, tm, [&](const PassBuffers& s, bf16_t* zb) {
+                SampleArgs sa;
+                memset(&sa, 0, sizeof(sa));
+                sa.mu_i = b.mu_i; sa.lv_i = b.lv_i; sa.mu_e = b.mu_e; sa.lv_e = b.lv_e;
+                sa.z = s.z;
+                sa.zb = zb;
+                sa.chunks = chunks; sa.ids = so.ids; sa.row0 = so.row0;
+                sa.nrows = b.rows; sa.valid_rows = valid_rows;
+                sa.used_rows = (chunks && b.enc_rows_mode) ? rg->enc_used_rows : b.rows;
+                sa.chunk_rows = b.enc_rows_mode ? 0 : IEF_T;
+                sa.count = G;
+                for (int g = 0; g < G; ++g) sa.seed[g] = sample_seed(so.seed, s0 + g);
+                sa.factor = precision_factor(c); sa.eps = c.epsilon; sa.scale = so.scale;
+                const dim3 grid(chunks ? b.nb + 1 : (b.rows + 255) / 256, SAMPLE_SLICES);
+                return dispatch_d(d512, [&](auto w) {
+                    return launch(tm, ST_FUSION, iefvad_sample_states_kernel<decltype(w)::value>, grid, dim3(256), 0, stream, sa);
+                });
             })) return rc;
-        if (int rc = pass_refine_score(h, s, rg, nullptr, s.chain, false, stream, tm)) return rc;
-        if (int rc = pass_stacked_out(b, s, rg, G, so.logits + (long long)s0 * so.stride, so.stride, so.row0, stream, tm)) return rc;
     }
     return launch(tm, ST_SCORER, iefvad_samples_reduce_kernel, dim3(nslabs), dim3(256), 0, stream, (const float*)so.logits, so.stride, so.count, chunks,
                   valid_rows, so.row0, so.mean, so.stdev);
 }
 
-// One micro-batch of `nb` chunks.  Dense (rg == nullptr): `in` holds the pass's [nb, 256, 768] blocks, `scale` their per-row scales
-// (kNoScale but for iefvad_forward_scaled), results go to `out` at row offset row0.  Ragged: `in` holds the pass's packed rows, the
+// One micro-batch of `nb` chunks; `x`: what the call asks for beyond its base outputs, at the pass's first row.  Dense (rg == nullptr):
+// `in` holds the pass's [nb, 256, 768] blocks, results go to `out` at row offset row0.  Ragged: `in` holds the pass's packed rows, the
 // chunks are built from them on the device, everything behind the encoder runs on the valid rows only, results go to rg->out (`out`
-// must be all-null, `scale` kNoScale: rg->out carries the packed scales).
-static int forward_pass(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int nb, size_t row0, void* workspace,
-                        const iefvad_outputs* out, const RaggedPass* rg, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr,
-                        const RowNoise* nz = nullptr, const TrajOut* tj = nullptr, const VarOut* vo = nullptr, const SampleOut* so = nullptr) {
+// must be all-null, `x` is rg->out.x).
+static int forward_pass(iefvad_handle* h, const RowsIn& in, const Extras& x, int nb, size_t row0, void* workspace, const iefvad_outputs* out,
+                        const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     PassBuffers b = pass_buffers(h, nb, row0, workspace, out, rg);
-    if (rg) maps = &rg->out.attn;                 // a whole-video pass: the maps at the pass's first packed row
-    if (rg) tj = rg->out.traj.any() ? &rg->out.traj : nullptr;
-    if (rg) vo = rg->out.var.any() ? &rg->out.var : nullptr;
-    if (rg) so = rg->out.smp.any() ? &rg->out.smp : nullptr;
-    if (int rc = pass_load_inputs(h, b, in, scale, nz ? *nz : RowNoise{}, rg, stream, tm)) return rc;
+    if (int rc = pass_load_inputs(h, b, in, x, rg, stream, tm)) return rc;
     for (int l = 0; l < h->cfg.num_layers; ++l)
-        if (int rc = pass_encoder_layer(h, b, l, rg, maps, stream, tm)) return rc;
+        if (int rc = pass_encoder_layer(h, b, l, rg, x.attn, stream, tm)) return rc;
     if (int rc = pass_compact_rows(h, b, rg, stream, tm)) return rc;
-    if (int rc = pass_tail(h, b, out, rg, tj, vo || so, stream, tm)) return rc;
+    if (int rc = pass_tail(h, b, out, rg, x.traj.any() ? &x.traj : nullptr, x.keep_heads(), stream, tm)) return rc;
     if (rg)
         if (int rc = pass_rows_out(h, b, rg, stream, tm)) return rc;
-    if (vo)
-        if (int rc = pass_variants(h, b, rg, *vo, stream, tm)) return rc;
-    return so ? pass_samples(h, b, rg, *so, stream, tm) : 0;
+    if (x.var.any())
+        if (int rc = pass_variants(h, b, rg, x.var, stream, tm)) return rc;
+    return x.smp.any() ? pass_samples(h, b, rg, x.smp, stream, tm) : 0;
 }
 
-static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const scale[2], int32_t B, void* workspace, size_t workspace_bytes,
-                        const iefvad_outputs* out, hipStream_t stream, Timer& tm, const AttnMaps* maps = nullptr, const RowNoise* nz = nullptr,
-                        const TrajOut* tj = nullptr, const VarOut* vo = nullptr, const SampleOut* so = nullptr) {
+// the layout behind the base workspace of a dense call of B chunks
+static WorkspaceTail dense_tail(const iefvad_handle* h, int32_t B, const TailWants& w) {
+    const int mb = micro_batch(h);
+    return workspace_tail(iefvad_workspace_bytes(h, B), (size_t)(B < mb ? B : mb), h->D, w);
+}
+// the public workspace queries of the dense entries with an extra: 0 for arguments no call would accept
+static size_t dense_workspace_bytes(const iefvad_handle* h, int32_t B, const TailWants& w) {
+    return iefvad_workspace_bytes(h, B) ? dense_tail(h, B, w).total : 0;
+}
+
+static int forward_impl(iefvad_handle* h, const RowsIn& in, const Extras& x, int32_t B, void* workspace, size_t workspace_bytes,
+                        const iefvad_outputs* out, hipStream_t stream, Timer& tm) {
     const void* const img = in.img;
     const void* const ev = in.ev;
     const int32_t in_dtype = in.in_dtype;
@@ -1711,25 +1775,18 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const float* const s
     if (B <= 0) return fail("iefvad_forward: B must be positive (got %d)", B);
     if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16)
         return fail("iefvad_forward: unknown in_dtype %d", in_dtype);
-    if (!workspace || workspace_bytes < iefvad_workspace_bytes(h, B))
-        return fail("iefvad_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, iefvad_workspace_bytes(h, B));
+    const WorkspaceTail tail = dense_tail(h, B, x.wants());
+    if (!workspace || workspace_bytes < tail.total)
+        return fail("iefvad_forward: workspace too small (%zu < %zu bytes)", workspace_bytes, tail.total);
     if (((uintptr_t)workspace & 15) || ((uintptr_t)img & 15) || ((uintptr_t)ev & 15))
         return fail("iefvad_forward: buffers must be 16-byte aligned");
+    Extras call = x;
+    call.place(workspace, tail);
     const int mb = micro_batch(h);
     for (int b0 = 0; b0 < B; b0 += mb) {
         const int nb = (B - b0 < mb) ? (B - b0) : mb;
         const size_t row0 = (size_t)b0 * IEF_T;
-        const float* const pass_scale[2] = {scale[0] ? scale[0] + row0 : nullptr, scale[1] ? scale[1] + row0 : nullptr};
-        const AttnMaps pass_maps = maps ? maps->at((long long)row0) : AttnMaps();
-        const RowNoise pass_nz = nz ? nz->at((long long)row0) : RowNoise{};       // ids default to the row of the CALL: b T + t
-        TrajOut pass_tj = tj ? *tj : TrajOut{};
-        pass_tj.row0 = (long long)row0;
-        VarOut pass_vo = vo ? *vo : VarOut{};
-        pass_vo.row0 = (long long)row0;
-        const SampleOut pass_so = so ? so->at((long long)row0) : SampleOut{};
-        if (int rc = forward_pass(h, in.at(row0, h->D), pass_scale, nb, row0, workspace, out, nullptr, stream, tm, maps ? &pass_maps : nullptr, &pass_nz,
-                                  tj ? &pass_tj : nullptr, vo ? &pass_vo : nullptr, so ? &pass_so : nullptr))
-            return rc;
+        if (int rc = forward_pass(h, in.at(row0, h->D), call.at((long long)row0), nb, row0, workspace, out, nullptr, stream, tm)) return rc;
     }
     return 0;
 }
@@ -1838,7 +1895,7 @@ static int forward_graphed(iefvad_handle* h, const void* img, const void* ev, in
             gc.disabled = true;
             return -1;
         }
-        const int rc = forward_impl(h, RowsIn{s_img, s_ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, &so, gc.cap_stream, tm);
+        const int rc = forward_impl(h, RowsIn{s_img, s_ev, in_dtype}, Extras{}, B, workspace, workspace_bytes, &so, gc.cap_stream, tm);
         hipGraph_t graph = nullptr;
         const hipError_t ce = hipStreamEndCapture(gc.cap_stream, &graph);      // always end the capture, also after a failed launch
         if (rc) {
@@ -1885,7 +1942,7 @@ extern "C" int iefvad_forward(iefvad_handle* h, const void* img, const void* ev,
         }
     }
     Timer tm;      // everything else, and every invalid argument (reported by forward_impl), takes the direct path
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, Extras{}, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
 }
 
 // The checks of a maps request that need no device: something is asked for, only at layers the model has, 16-byte aligned, and
@@ -1913,20 +1970,12 @@ static int attn_maps_args(const char* who, const iefvad_handle* h, const iefvad_
 
 extern "C" int iefvad_forward_attn(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
                                    size_t workspace_bytes, const iefvad_outputs* out, const iefvad_attn_maps* maps, void* stream) {
-    AttnMaps am;
-    if (int rc = attn_maps_args("iefvad_forward_attn", h, maps, &am)) return rc;
+    Extras x = {};
+    if (int rc = attn_maps_args("iefvad_forward_attn", h, maps, &x.attn)) return rc;
     Timer tm;      // direct launches: the map pointers are per call, a cached graph would pin their addresses
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, &am);
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, x, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
 }
 
-// The row perturbation of a call as the kernels take it (common.h): the caller's amplitudes, ids and seed at row 0 of the call
-static RowNoise row_noise(const iefvad_perturb& p) {
-    RowNoise nz = {};
-    nz.amp[0] = p.noise_amp[0]; nz.amp[1] = p.noise_amp[1];
-    nz.id = p.noise_row;
-    nz.seed = p.seed;
-    return nz;
-}
 static int perturb_aligned(const char* who, const iefvad_perturb& p) {
     if (((uintptr_t)p.noise_amp[0] | (uintptr_t)p.noise_amp[1] | (uintptr_t)p.noise_row) & 3)
         return fail("%s: noise amplitude and noise row vectors must be 4-byte aligned", who);
@@ -1938,10 +1987,10 @@ extern "C" int iefvad_forward_perturbed(iefvad_handle* h, const void* img, const
     if (!h) return fail("iefvad_forward_perturbed: null argument");
     if (!p) return fail("iefvad_forward_perturbed: null perturbation");
     if (int rc = perturb_aligned("iefvad_forward_perturbed", *p)) return rc;
-    const RowNoise nz = row_noise(*p);
-    if (!p->scale[0] && !p->scale[1] && !nz.any()) return iefvad_forward(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream);
+    const Extras x = perturb_extras(*p);
+    if (!x.scale[0] && !x.scale[1] && !x.noise.any()) return iefvad_forward(h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream);
     Timer tm;      // direct launches: vectors and seed are per call, a cached graph would pin them
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, p->scale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, &nz);
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, x, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
 }
 
 extern "C" int iefvad_forward_scaled(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, const float* img_row_scale,
@@ -1991,7 +2040,7 @@ extern "C" int iefvad_forward_timed(iefvad_handle* h, const void* img, const voi
     hipEvent_t t0 = pool.take(), t1 = pool.take();
     if (!t0 || !t1) return fail("iefvad_forward_timed: hipEventCreate: %s", hipGetErrorString(pool.err));
     HIP_TRY(hipEventRecord(t0, stream));
-    int rc = forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, stream, tm);
+    int rc = forward_impl(h, RowsIn{img, ev, in_dtype}, Extras{}, B, workspace, workspace_bytes, out, stream, tm);
     (void)hipEventRecord(t1, stream);
     hipError_t se = hipStreamSynchronize(stream);
     if (rc) return rc;
@@ -2670,8 +2719,42 @@ extern "C" int iefvad_set_steps(iefvad_handle* h, int32_t steps) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// the refinement trajectory (include/iefvad.h, csrc/trajectory.h)
+// the entries that add one extra to a forward: trajectory, fusion ablations, score samples (include/iefvad.h)
 // ------------------------------------------------------------------------------------------------
+// A dense entry: its null and B checks, `args(x, rows of the call)` -- the extra's own checks, into the record --, its workspace check
+// under its own name, then the forward.  Direct launches: the results' pointers are per call, a cached graph would pin their addresses.
+template <typename Args>
+static int forward_extra(const char* who, iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
+                         size_t workspace_bytes, const iefvad_outputs* out, void* stream, Args&& args) {
+    if (!h) return fail("%s: null handle", who);
+    if (!img || !ev || !out) return fail("%s: null argument", who);
+    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
+    Extras x = {};
+    if (int rc = args(x, (long long)B * IEF_T)) return rc;
+    const size_t need = dense_workspace_bytes(h, B, x.wants());
+    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    Timer tm;
+    return forward_impl(h, RowsIn{img, ev, in_dtype}, x, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm);
+}
+// A whole-video entry: the same, on the call's packed rows; forward_videos_impl makes the remaining checks
+template <typename Args>
+static int forward_videos_extra(const char* who, iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype, const int32_t* lengths,
+                                int32_t nvideos, int32_t nan_to_num, void* workspace, size_t workspace_bytes, float* logits, float* w_i_mean,
+                                float* w_e_mean, void* stream, Args&& args) {
+    if (!h) return fail("%s: null handle", who);
+    if (!lengths) return fail("%s: null argument", who);
+    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
+    long long rows, chunks;
+    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
+    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
+    if (int rc = args(out.x, rows)) return rc;
+    Timer tm;
+    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+}
+static TailWants want_traj() { TailWants w = {}; w.traj = true; return w; }
+static TailWants want_variants(int count) { TailWants w = {}; w.variants = count; return w; }
+static TailWants want_samples() { TailWants w = {}; w.samples = true; return w; }
+
 // The checks of a trajectory request that need no device: something is asked for, 4-byte aligned, a stride that holds the call's rows
 static int trajectory_args(const char* who, const iefvad_trajectory* t, long long rows, TrajOut* tj) {
     if (!t) return fail("%s: null trajectory", who);
@@ -2682,26 +2765,16 @@ static int trajectory_args(const char* who, const iefvad_trajectory* t, long lon
     return 0;
 }
 
-extern "C" size_t iefvad_trajectory_workspace_bytes(const iefvad_handle* h, int32_t B) {
-    const size_t base = iefvad_workspace_bytes(h, B);
-    if (!base) return 0;
-    const int mb = micro_batch(h);
-    return base + (size_t)(B < mb ? B : mb) * IEF_T * h->D * sizeof(float);
+extern "C" size_t iefvad_trajectory_workspace_bytes(const iefvad_handle* h, int32_t B) { return dense_workspace_bytes(h, B, want_traj()); }
+extern "C" size_t iefvad_videos_trajectory_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
+    return videos_workspace_bytes(h, lengths, nvideos, want_traj());
 }
 
 extern "C" int iefvad_forward_trajectory(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
                                          size_t workspace_bytes, const iefvad_outputs* out, const iefvad_trajectory* trajectory, void* stream) {
     static const char* const who = "iefvad_forward_trajectory";
-    if (!h) return fail("%s: null handle", who);
-    if (!img || !ev || !out) return fail("%s: null argument", who);
-    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
-    TrajOut tj;
-    if (int rc = trajectory_args(who, trajectory, (long long)B * IEF_T, &tj)) return rc;
-    const size_t need = iefvad_trajectory_workspace_bytes(h, B);
-    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    tj.z_prev = (float*)((char*)workspace + iefvad_workspace_bytes(h, B));
-    Timer tm;      // direct launches: the series' pointers are per call, a cached graph would pin their addresses
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, nullptr, &tj);
+    return forward_extra(who, h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream,
+                         [&](Extras& x, long long rows) { return trajectory_args(who, trajectory, rows, &x.traj); });
 }
 
 extern "C" int iefvad_forward_videos_trajectory(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
@@ -2709,20 +2782,10 @@ extern "C" int iefvad_forward_videos_trajectory(iefvad_handle* h, const void* im
                                                 size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
                                                 const iefvad_trajectory* trajectory, void* stream) {
     static const char* const who = "iefvad_forward_videos_trajectory";
-    if (!h) return fail("%s: null handle", who);
-    if (!lengths) return fail("%s: null argument", who);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    long long rows, chunks;
-    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
-    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
-    if (int rc = trajectory_args(who, trajectory, rows, &out.traj)) return rc;
-    Timer tm;
-    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+    return forward_videos_extra(who, h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean, w_e_mean,
+                                stream, [&](Extras& x, long long rows) { return trajectory_args(who, trajectory, rows, &x.traj); });
 }
 
-// ------------------------------------------------------------------------------------------------
-// the fusion ablations (include/iefvad.h, csrc/variants.h)
-// ------------------------------------------------------------------------------------------------
 // The checks of a variants request that need no device
 static int variants_args(const char* who, const iefvad_handle* h, const iefvad_variants* v, long long rows, VarOut* vo) {
     if (h->cfg.compute == IEFVAD_COMPUTE_FP16X3) return fail("%s: compute = FP16X3 is not supported (IEFVAD_COMPUTE_FP16X3 has no fusion variants)", who);
@@ -2742,31 +2805,19 @@ static int variants_args(const char* who, const iefvad_handle* h, const iefvad_v
     return 0;
 }
 
+static bool variants_count_ok(int32_t count) { return count >= 1 && count <= IEF_MAX_VARIANTS; }
 extern "C" size_t iefvad_variants_workspace_bytes(const iefvad_handle* h, int32_t B, int32_t count) {
-    const size_t base = iefvad_workspace_bytes(h, B);
-    if (!base || count < 1 || count > IEF_MAX_VARIANTS) return 0;
-    const int mb = micro_batch(h);
-    return base + variants_bytes((size_t)(B < mb ? B : mb), h->D, count);
+    return variants_count_ok(count) ? dense_workspace_bytes(h, B, want_variants(count)) : 0;
+}
+extern "C" size_t iefvad_videos_variants_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t count) {
+    return variants_count_ok(count) ? videos_workspace_bytes(h, lengths, nvideos, want_variants(count)) : 0;
 }
 
 extern "C" int iefvad_forward_variants(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
                                        size_t workspace_bytes, const iefvad_outputs* out, const iefvad_variants* variants, void* stream) {
     static const char* const who = "iefvad_forward_variants";
-    if (!h) return fail("%s: null handle", who);
-    if (!img || !ev || !out) return fail("%s: null argument", who);
-    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
-    VarOut vo;
-    if (int rc = variants_args(who, h, variants, (long long)B * IEF_T, &vo)) return rc;
-    const size_t need = iefvad_variants_workspace_bytes(h, B, vo.count);
-    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    vo.ws = (float*)((char*)workspace + iefvad_workspace_bytes(h, B));
-    Timer tm;      // direct launches: the result's pointer is per call, a cached graph would pin its address
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, nullptr, nullptr, &vo);
-}
-
-extern "C" size_t iefvad_videos_variants_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t count) {
-    if (count < 1 || count > IEF_MAX_VARIANTS) return 0;
-    return videos_workspace_bytes(h, lengths, nvideos, false, false, false, count);
+    return forward_extra(who, h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream,
+                         [&](Extras& x, long long rows) { return variants_args(who, h, variants, rows, &x.var); });
 }
 
 extern "C" int iefvad_forward_videos_variants(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
@@ -2774,20 +2825,10 @@ extern "C" int iefvad_forward_videos_variants(iefvad_handle* h, const void* img_
                                               size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
                                               const iefvad_variants* variants, void* stream) {
     static const char* const who = "iefvad_forward_videos_variants";
-    if (!h) return fail("%s: null handle", who);
-    if (!lengths) return fail("%s: null argument", who);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    long long rows, chunks;
-    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
-    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
-    if (int rc = variants_args(who, h, variants, rows, &out.var)) return rc;
-    Timer tm;
-    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+    return forward_videos_extra(who, h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean, w_e_mean,
+                                stream, [&](Extras& x, long long rows) { return variants_args(who, h, variants, rows, &x.var); });
 }
 
-// ------------------------------------------------------------------------------------------------
-// the score samples (include/iefvad.h, csrc/samples.h)
-// ------------------------------------------------------------------------------------------------
 // The checks of a samples request that need no device
 static int samples_args(const char* who, const iefvad_handle* h, const iefvad_samples* p, long long rows, SampleOut* so) {
     if (h->cfg.compute == IEFVAD_COMPUTE_FP16X3) return fail("%s: compute = FP16X3 is not supported (IEFVAD_COMPUTE_FP16X3 has no score samples)", who);
@@ -2806,28 +2847,17 @@ static int samples_args(const char* who, const iefvad_handle* h, const iefvad_sa
     return 0;
 }
 
-extern "C" size_t iefvad_samples_workspace_bytes(const iefvad_handle* h, int32_t B) {
-    return iefvad_variants_workspace_bytes(h, B, IEF_MAX_VARIANTS);       // one group of stacked states, whatever the sample count
+// one group of stacked states, whatever the sample count
+extern "C" size_t iefvad_samples_workspace_bytes(const iefvad_handle* h, int32_t B) { return dense_workspace_bytes(h, B, want_samples()); }
+extern "C" size_t iefvad_videos_samples_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
+    return videos_workspace_bytes(h, lengths, nvideos, want_samples());
 }
 
 extern "C" int iefvad_forward_samples(iefvad_handle* h, const void* img, const void* ev, int32_t in_dtype, int32_t B, void* workspace,
                                       size_t workspace_bytes, const iefvad_outputs* out, const iefvad_samples* samples, void* stream) {
     static const char* const who = "iefvad_forward_samples";
-    if (!h) return fail("%s: null handle", who);
-    if (!img || !ev || !out) return fail("%s: null argument", who);
-    if (B <= 0) return fail("%s: B must be positive (got %d)", who, B);
-    SampleOut so;
-    if (int rc = samples_args(who, h, samples, (long long)B * IEF_T, &so)) return rc;
-    const size_t need = iefvad_samples_workspace_bytes(h, B);
-    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
-    so.ws = (float*)((char*)workspace + iefvad_workspace_bytes(h, B));
-    Timer tm;      // direct launches: the results' pointers are per call, a cached graph would pin their addresses
-    return forward_impl(h, RowsIn{img, ev, in_dtype}, kNoScale, B, workspace, workspace_bytes, out, (hipStream_t)stream, tm, nullptr, nullptr, nullptr, nullptr,
-                        &so);
-}
-
-extern "C" size_t iefvad_videos_samples_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
-    return videos_workspace_bytes(h, lengths, nvideos, false, false, false, IEF_MAX_VARIANTS);
+    return forward_extra(who, h, img, ev, in_dtype, B, workspace, workspace_bytes, out, stream,
+                         [&](Extras& x, long long rows) { return samples_args(who, h, samples, rows, &x.smp); });
 }
 
 extern "C" int iefvad_forward_videos_samples(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
@@ -2835,13 +2865,6 @@ extern "C" int iefvad_forward_videos_samples(iefvad_handle* h, const void* img_r
                                              size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
                                              const iefvad_samples* samples, void* stream) {
     static const char* const who = "iefvad_forward_videos_samples";
-    if (!h) return fail("%s: null handle", who);
-    if (!lengths) return fail("%s: null argument", who);
-    if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
-    long long rows, chunks;
-    if (int rc = videos_layout(lengths, nvideos, &rows, &chunks, who)) return rc;
-    VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
-    if (int rc = samples_args(who, h, samples, rows, &out.smp)) return rc;
-    Timer tm;
-    return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
+    return forward_videos_extra(who, h, img_rows, ev_rows, in_dtype, lengths, nvideos, nan_to_num, workspace, workspace_bytes, logits, w_i_mean, w_e_mean,
+                                stream, [&](Extras& x, long long rows) { return samples_args(who, h, samples, rows, &x.smp); });
 }

@@ -69,42 +69,31 @@ static int videos_layout(const int32_t* lengths, int32_t nvideos, long long* tot
     return 0;
 }
 
-// What lies behind the base workspace of a call of `chunks` chunks.  With w_colsum or a wide w_i / w_e the fusion stage stores the
-// weights of the pass's row set, and they need a home: no region of the base workspace is dead in every arithmetic while the tail runs
-// (bf16 mode keeps its A operand in the att region, mu / lv / z / h fill the qkv region, y holds the row-mean and scorer partial
-// sums).  So: [2, R, D] floats (`w_rows`), then the [nb, 2, D] double slab partials of the column sums (`colsum`); nb = chunks of a
-// pass, R = nb * 256.
+// What lies behind the base workspace of a call of `chunks` chunks, sized for a pass of it (workspace_tail.h)
 static size_t videos_pass_chunks(const iefvad_handle* h, long long chunks) { return (size_t)(chunks < micro_batch(h) ? chunks : micro_batch(h)); }
-static size_t videos_extra_bytes(const iefvad_handle* h, long long chunks, bool w_rows, bool colsum) {
-    const size_t nb = videos_pass_chunks(h, chunks);
-    return (w_rows || colsum ? 2 * nb * IEF_T * (size_t)h->D * sizeof(float) : 0) + (colsum ? nb * 2 * (size_t)h->D * sizeof(double) : 0);
+static WorkspaceTail videos_tail(const iefvad_handle* h, long long chunks, const TailWants& w) {
+    return workspace_tail(iefvad_workspace_bytes(h, (int32_t)chunks), videos_pass_chunks(h, chunks), h->D, w);
 }
 
-// the second state buffer of a trajectory pass (trajectory.h): [R, D] floats behind everything else
-static size_t videos_traj_bytes(const iefvad_handle* h, long long chunks) { return videos_pass_chunks(h, chunks) * IEF_T * (size_t)h->D * sizeof(float); }
-
 // the public workspace queries: 0 for arguments no call would accept
-static size_t videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, bool w_rows, bool colsum, bool traj = false,
-                                     int variants = 0) {
+static size_t videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, const TailWants& w) {
     if (!h || !lengths || nvideos <= 0) return 0;
     long long rows, chunks;
     if (videos_layout(lengths, nvideos, &rows, &chunks) || chunks > 0x7fffffffLL) return 0;
-    const size_t base = iefvad_workspace_bytes(h, (int32_t)chunks);
-    return base ? base + videos_extra_bytes(h, chunks, w_rows, colsum) + (traj ? videos_traj_bytes(h, chunks) : 0) +
-                      (variants ? variants_bytes(videos_pass_chunks(h, chunks), h->D, variants) : 0)
-                : 0;
-}
-extern "C" size_t iefvad_videos_trajectory_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
-    return videos_workspace_bytes(h, lengths, nvideos, false, false, true);
+    return iefvad_workspace_bytes(h, (int32_t)chunks) ? videos_tail(h, chunks, w).total : 0;
 }
 extern "C" size_t iefvad_videos_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos) {
-    return videos_workspace_bytes(h, lengths, nvideos, false, false);
+    return videos_workspace_bytes(h, lengths, nvideos, TailWants{});
 }
 extern "C" size_t iefvad_videos_scaled_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, int32_t with_colsum) {
-    return videos_workspace_bytes(h, lengths, nvideos, false, with_colsum != 0);
+    TailWants w = {};
+    w.colsum = with_colsum != 0;
+    return videos_workspace_bytes(h, lengths, nvideos, w);
 }
 extern "C" size_t iefvad_videos_full_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, const iefvad_outputs* out) {
-    return videos_workspace_bytes(h, lengths, nvideos, out && (out->w_i || out->w_e), false);
+    TailWants w = {};
+    w.w_rows = out && (out->w_i || out->w_e);
+    return videos_workspace_bytes(h, lengths, nvideos, w);
 }
 
 // The checks of a whole-video call that look at neither the handle nor the rows; none makes a HIP call.  forward_videos_impl and
@@ -117,8 +106,8 @@ static int videos_args(const char* who, const VideosOut& out, int32_t in_dtype, 
     if (in_dtype != IEFVAD_IN_F32 && in_dtype != IEFVAD_IN_F16 && in_dtype != IEFVAD_IN_BF16) return fail("%s: unknown in_dtype %d", who, in_dtype);
     if (nvideos <= 0) return fail("%s: nvideos must be positive (got %d)", who, nvideos);
     if ((uintptr_t)out.w_colsum & 7) return fail("%s: w_colsum must be 8-byte aligned", who);
-    if (((uintptr_t)out.scale[0] | (uintptr_t)out.scale[1]) & 3) return fail("%s: row scale vectors must be 4-byte aligned", who);
-    if (((uintptr_t)out.noise.amp[0] | (uintptr_t)out.noise.amp[1] | (uintptr_t)out.noise.id) & 3)
+    if (((uintptr_t)out.x.scale[0] | (uintptr_t)out.x.scale[1]) & 3) return fail("%s: row scale vectors must be 4-byte aligned", who);
+    if (((uintptr_t)out.x.noise.amp[0] | (uintptr_t)out.x.noise.amp[1] | (uintptr_t)out.x.noise.id) & 3)
         return fail("%s: noise amplitude and noise row vectors must be 4-byte aligned", who);
     return 0;
 }
@@ -158,12 +147,8 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
     long long total_rows, total_chunks;
     if (int rc = videos_layout(lengths, nvideos, &total_rows, &total_chunks, who)) return rc;
     if (total_chunks > 0x7fffffffLL / IEF_T) return fail("%s: too many chunks", who);
-    const size_t base = iefvad_workspace_bytes(h, (int32_t)total_chunks);
-    const size_t extra = videos_extra_bytes(h, total_chunks, out.wants_w_rows(), out.w_colsum != nullptr);
-    const size_t traj_bytes = out.traj.any() ? videos_traj_bytes(h, total_chunks) : 0;
-    const size_t var_bytes = out.var.any() ? variants_bytes(videos_pass_chunks(h, total_chunks), h->D, out.var.count) : 0;
-    const size_t need = base + extra + traj_bytes + var_bytes + (out.smp.any() ? variants_bytes(videos_pass_chunks(h, total_chunks), h->D, IEF_MAX_VARIANTS) : 0);
-    if (!workspace || workspace_bytes < need) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, need);
+    const WorkspaceTail tail = videos_tail(h, total_chunks, out.wants());
+    if (!workspace || workspace_bytes < tail.total) return fail("%s: workspace too small (%zu < %zu bytes)", who, workspace_bytes, tail.total);
     if (((uintptr_t)workspace & 15) || ((uintptr_t)in.img & 15) || ((uintptr_t)in.ev & 15)) return fail("%s: buffers must be 16-byte aligned", who);
 
     // ---- metadata: the chunk table of the whole call (src_row relative to its pass, filled below) + the flag words
@@ -225,12 +210,15 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
     RaggedPass rg;
     memset(&rg, 0, sizeof(rg));
     rg.d_flags = dflags;
-    if (out.wants_w_rows()) {         // the homes behind the base workspace, the same for every pass (videos_extra_bytes)
-        const size_t per = videos_pass_chunks(h, total_chunks) * IEF_T * h->D;
-        rg.w_rows[0] = (float*)((char*)workspace + base);
-        rg.w_rows[1] = rg.w_rows[0] + per;
-        if (out.w_colsum) rg.colsum_part = (double*)(rg.w_rows[1] + per);
+    // the homes behind the base workspace, the same for every pass
+    if (out.wants_w_rows()) {
+        rg.w_rows[0] = (float*)((char*)workspace + tail.w_rows);
+        rg.w_rows[1] = rg.w_rows[0] + videos_pass_chunks(h, total_chunks) * IEF_T * h->D;
+        if (out.w_colsum) rg.colsum_part = (double*)((char*)workspace + tail.colsum);
     }
+    VideosOut call = out;
+    call.nan_mode = nan_mode;
+    call.x.place(workspace, tail);
     iefvad_outputs none;
     memset(&none, 0, sizeof(none));
     long long row0 = 0;
@@ -246,12 +234,8 @@ static int forward_videos_impl(iefvad_handle* h, const RowsIn& in, const int32_t
             rg.enc_rows = (rg.enc_used_rows + IEF_T - 1) / IEF_T * IEF_T;        // <= nb * 256
         }
         rg.first_pass = c0 == 0;
-        rg.out = out.at(row0, h->D);          // pass-relative, like src_row
-        rg.out.nan_mode = nan_mode;
-        if (out.traj.any()) rg.out.traj.z_prev = (float*)((char*)workspace + base + extra);
-        if (out.var.any()) rg.out.var.ws = (float*)((char*)workspace + base + extra + traj_bytes);      // the stacked states of the ablations, behind everything else
-        if (out.smp.any()) rg.out.smp.ws = (float*)((char*)workspace + base + extra + traj_bytes + var_bytes);     // one group of stacked sample states
-        rc = forward_pass(h, in.at((size_t)row0, h->D), kNoScale, nb, 0, workspace, &none, &rg, stream, tm);
+        rg.out = call.at(row0, h->D);         // pass-relative, like src_row
+        rc = forward_pass(h, in.at((size_t)row0, h->D), rg.out.x, nb, 0, workspace, &none, &rg, stream, tm);
         row0 += vrows;
     }
     (void)hipEventRecord(mr.done[slot], stream);       // the slot's buffers are free once everything enqueued above has run
@@ -274,7 +258,7 @@ extern "C" int iefvad_forward_videos_attn(iefvad_handle* h, const void* img_rows
     static const char* const who = "iefvad_forward_videos_attn";
     Timer tm;
     VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
-    if (int rc = attn_maps_args(who, h, maps, &out.attn)) return rc;
+    if (int rc = attn_maps_args(who, h, maps, &out.x.attn)) return rc;
     return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);
 }
 
@@ -284,10 +268,7 @@ static int forward_videos_perturbed(const char* who, iefvad_handle* h, const voi
                                     size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean, double* w_colsum, void* stream) {
     Timer tm;
     VideosOut out = videos_out(logits, w_i_mean, w_e_mean, nan_to_num);
-    out.scale[0] = p.scale[0]; out.scale[1] = p.scale[1];
-    out.noise.amp[0] = p.noise_amp[0]; out.noise.amp[1] = p.noise_amp[1];
-    out.noise.id = p.noise_row;
-    out.noise.seed = p.seed;
+    out.x = perturb_extras(p);
     out.w_colsum = w_colsum;
     out.sweep_codes = true;
     return forward_videos_impl(h, RowsIn{img_rows, ev_rows, in_dtype}, lengths, nvideos, workspace, workspace_bytes, out, (hipStream_t)stream, tm, who);

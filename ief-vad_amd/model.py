@@ -136,7 +136,7 @@ class _Request:
     once.  `maps_asked` is the raw view of `attn_maps=` and `layers` the parsed one: () until the checks parse it at its place in their order,
     so a value that does not parse is refused there and not sooner.  `_PLAIN` is the call that asks for nothing."""
     __slots__ = ("kind", "training", "grad", "eval_grad", "fp16x3", "bf16", "timed", "row_scale", "scaled", "attn_maps", "maps_asked", "layers", "row_noise",
-                 "noisy", "noise_seed", "noise_rows", "trajectory", "variants", "similarity", "outputs", "outputs_asked", "weight_sums", "nan_always", "extras")
+                 "noisy", "noise_seed", "noise_rows", "trajectory", "variants", "samples", "similarity", "outputs", "outputs_asked", "weight_sums", "nan_always", "extras")
 
     def __init__(self, training=False, grad=False, compute="f32", *, timed=False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None,
                  noise_rows=None, trajectory=False, fusion_variants=None, similarity=False, outputs=None, weight_sums=False, nan_to_num=True):
@@ -149,6 +149,7 @@ class _Request:
         self.similarity, self.outputs, self.outputs_asked, self.weight_sums = similarity, outputs, outputs is not None, weight_sums
         self.nan_always = isinstance(nan_to_num, str) and nan_to_num == "always"
         self.extras = self.nan_always or weight_sums or self.scaled or self.noisy      # the sweep's extras of the valid-row calls
+        self.samples = None      # `forward_samples` / `forward_videos_samples`: (S, seed, scale, sample_rows)
         self.kind = "plain"      # the row of `_DENSE_ENTRIES` that serves the request: `forward` names it once the checks have passed
 
 
@@ -275,7 +276,12 @@ def _perturb_struct(nrows: int, device, row_scale, row_noise, noise_seed, noise_
     return p, noisy
 
 
-# What an attn / trajectory / variants request adds to a call on either route: (the results, in the order they are returned behind the
+def _samples_struct(S, seed, scale, sample_rows, res, stride) -> "_lib.Samples":
+    return _lib.Samples(S, seed, scale, sample_rows.data_ptr() if sample_rows is not None else None, res["logits_samples"].data_ptr(), stride,
+                        res["score_mean"].data_ptr(), res["score_std"].data_ptr())
+
+
+# What an attn / trajectory / variants / samples request adds to a call on either route: (the results, in the order they are returned behind the
 # others, as a function of (request, steps, shape of `logits`, shape of one per-row vector -- (B, T) dense, (total,) on valid rows --, T,
 # new fp32 tensor of a shape); the entry's argument that points at them, as a function of (request, those results, rows in all)).
 _EXTRA_RESULTS = {
@@ -286,6 +292,8 @@ _EXTRA_RESULTS = {
                    lambda q, res, n: C.byref(_lib.Trajectory(res["logits_steps"].data_ptr(), res["delta_norm"].data_ptr() if len(res["delta_norm"]) else None, n))),
     "variants": (lambda q, steps, logits, rows, T, new: {"logits_variants": new(len(q.variants), *rows), "fusion_variants": q.variants},
                  lambda q, res, n: C.byref(_variants_struct(q.variants, res["logits_variants"], n))),
+    "samples": (lambda q, steps, logits, rows, T, new: {"logits_samples": new(q.samples[0], *rows), "score_mean": new(*rows), "score_std": new(*rows)},
+                lambda q, res, n: C.byref(_samples_struct(*q.samples, res, n))),
 }
 
 
@@ -315,6 +323,18 @@ _DENSE_ENTRIES = {
     "trajectory": ("iefvad_forward_trajectory", "iefvad_forward_trajectory", "iefvad_trajectory_workspace_bytes", lambda q: (), 8, None),
     "variants": ("iefvad_forward_variants", "iefvad_forward_variants", "iefvad_variants_workspace_bytes", lambda q: (len(q.variants),), 8, None),
 }
+# The samples entries, one row in the form of each table above.  They stand beside the tables, which list exactly the kinds a request of
+# `forward` / `forward_videos` can reach: `forward_samples` / `forward_videos_samples` name these rows and `_entry_row` finds them.
+_SAMPLES_ENTRIES = {
+    "samples": ("iefvad_forward_samples", "iefvad_forward_samples", "iefvad_samples_workspace_bytes", lambda q: (), 8, None),
+    "_samples": ("_samples", lambda r: (), lambda r: (*r["vectors"], r["samples"], r["stream"])),
+}
+
+
+def _entry_row(table: dict, key: str) -> tuple:
+    return table[key] if key in table else _SAMPLES_ENTRIES[key]
+
+
 # what `MMFMIL(outputs=)` makes every dense call return, in the order of the returned dict: (key, its shape behind [B, T]; None = D)
 _DENSE_OUTPUTS = {"full": tuple((k, (1,) if k == "logits" else None) for k in OUTPUT_KEYS),
                   "weights": (("logits", (1,)), ("w_i", None), ("w_e", None), ("w_i_mean", ()), ("w_e_mean", ())),
@@ -861,7 +881,7 @@ class MMFMIL(nn.Module):
         """One dense call, the row of `_DENSE_ENTRIES` that serves `q`: sizes the workspace by the row's query, allocates the results
         `self.outputs` names and the row's own, and calls the entry with its own argument(s) at their place."""
         kind = q.kind
-        entry, prefix, query, query_args, at, own = _DENSE_ENTRIES[kind]
+        entry, prefix, query, query_args, at, own = _entry_row(_DENSE_ENTRIES, kind)
         device = img_visual.device
         img, ev = self._prepare_pair(img_visual, ev_visual)
         lib = _lib.load_library()
@@ -942,7 +962,7 @@ class MMFMIL(nn.Module):
         entry with (handle, *front, [workspace, bytes,] the suffix's tail).  `workspace_for=(lengths array, nvideos)`: the device entries, whose
         workspace the caller owns; it is sized by the suffix's query."""
         lib, name = _lib.load_library(), base + suffix
-        query, query_tail, tail = _ROW_ENTRIES[suffix]
+        query, query_tail, tail = _entry_row(_ROW_ENTRIES, suffix)
         D = self.temporal.embed_dim
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream(device).cuda_stream
@@ -952,7 +972,7 @@ class MMFMIL(nn.Module):
             res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
             r = {"vectors": tuple(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), "stream": C.c_void_p(stream), "out": None,
                  "similarity": None, "w_colsum": None, "with_colsum": 1 if q.weight_sums else 0, "attn": None, "trajectory": None,
-                 "variants": None, "nvariants": len(q.variants)}
+                 "variants": None, "nvariants": len(q.variants), "samples": None}
             if suffix[1:] in _EXTRA_RESULTS:
                 extra = _EXTRA_RESULTS[suffix[1:]][0](q, self.steps, (total,), (total,), self.visual_length, lambda *shape: torch.empty(shape, **f32))
                 res.update(extra)
@@ -1103,11 +1123,6 @@ class MMFMIL(nn.Module):
                                "harness.sample_states_host is the host model of the sampled states)")
         return samples, seed & 0xFFFFFFFFFFFFFFFF, scale
 
-    @staticmethod
-    def _samples_struct(S, seed, scale, sample_rows, res, stride) -> "_lib.Samples":
-        return _lib.Samples(S, seed, scale, sample_rows.data_ptr() if sample_rows is not None else None, res["logits_samples"].data_ptr(), stride,
-                            res["score_mean"].data_ptr(), res["score_std"].data_ptr())
-
     def forward_samples(self, img_visual, ev_visual, samples: int, seed: int, *, scale: float = 1.0, sample_rows=None) -> Dict[str, torch.Tensor]:
         """One forward and `samples` (1..64) Monte Carlo draws of every snippet's score from the heads' own Gaussians
         (`iefvad_forward_samples`, include/iefvad.h).  The reference never samples; these semantics are this package's own ("parity
@@ -1127,28 +1142,9 @@ class MMFMIL(nn.Module):
         if sample_rows is not None and (not isinstance(sample_rows, torch.Tensor) or sample_rows.dtype != torch.int32 or sample_rows.device != device
                                         or sample_rows.numel() != B * T or not sample_rows.is_contiguous()):
             raise ValueError(f"sample_rows must be a contiguous int32 tensor of {B * T} elements (B*T) on {device}")
-        img, ev = self._prepare_pair(img_visual, ev_visual)
-        lib = _lib.load_library()
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            self._ensure_handle(device)
-            self._ensure_weights(device, stream)
-            ws = self._ensure_workspace(device, lib.iefvad_samples_workspace_bytes(self._handle, B))
-            f32 = dict(dtype=torch.float32, device=device)
-            res: Dict[str, torch.Tensor] = {}
-            o = _lib.Outputs()
-            for k, tail in _DENSE_OUTPUTS[self.outputs]:
-                res[k] = torch.empty(B, T, *((D,) if tail is None else tail), **f32)
-                setattr(o, k, res[k].data_ptr())
-            extra = {"logits_samples": torch.empty(S, B, T, **f32), "score_mean": torch.empty(B, T, **f32), "score_std": torch.empty(B, T, **f32)}
-            sm = self._samples_struct(S, seed, scale, sample_rows, extra, B * T)
-            rc = lib.iefvad_forward_samples(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], B,
-                                            C.c_void_p(ws.data_ptr()), ws.numel(), C.byref(o), C.byref(sm), C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("iefvad_forward_samples: " + _lib.last_error())
-        if self.outputs == "full":
-            return {**{k: res[k] for k in OUTPUT_KEYS}, **extra}
-        return {**res, **extra}
+        q = _Request()
+        q.kind, q.samples = "samples", (S, seed, scale, sample_rows)
+        return self._dense_call(q, img_visual, ev_visual, B, T, D)
 
     def forward_videos_samples(self, img_rows, ev_rows, lengths, samples: int, seed: int, *, scale: float = 1.0,
                                nan_to_num: bool = True, sample_rows=None) -> Dict[str, torch.Tensor]:
@@ -1173,20 +1169,7 @@ class MMFMIL(nn.Module):
             raise ValueError(f"sample_rows must be a contiguous int32 tensor of {total} elements (sum of lengths) on {device}")
         img, ev = self._prepare_pair(img_rows, ev_rows)
         larr = (C.c_int32 * len(lens))(*lens)
-        lib = _lib.load_library()
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            self._ensure_handle(device)
-            self._ensure_weights(device, stream)
-            ws = self._ensure_workspace(device, lib.iefvad_videos_samples_workspace_bytes(self._handle, larr, len(lens)))
-            f32 = dict(dtype=torch.float32, device=device)
-            res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
-            res.update(logits_samples=torch.empty(S, total, **f32), score_mean=torch.empty(total, **f32), score_std=torch.empty(total, **f32))
-            sm = self._samples_struct(S, seed, scale, sample_rows, res, total)
-            rc = lib.iefvad_forward_videos_samples(self._handle, C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr,
-                                                   len(lens), 1 if nan_to_num else 0, C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                   *(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), C.byref(sm),
-                                                   C.c_void_p(stream))
-        if rc != 0:
-            raise RuntimeError("iefvad_forward_videos_samples: " + _lib.last_error())
-        return res
+        q = _Request()
+        q.samples = (S, seed, scale, sample_rows)
+        front = (C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), 1 if nan_to_num else 0)
+        return self._rows_call("iefvad_forward_videos", "_samples", q, device, total, front, workspace_for=(larr, len(lens)))
