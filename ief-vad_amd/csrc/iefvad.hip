@@ -1158,13 +1158,17 @@ struct VideosOut {
 struct RaggedPass {
     const RaggedChunk* d_chunks;     // device: the pass's chunks (src_row relative to the pass's first packed row)
     const int* d_flags;              // device: NaN flag per (video, modality); nullptr unless out.nan_mode == 1
-    int valid_rows;                  // packed rows of the pass
+    int valid_rows;                  // packed rows of the pass (an online pass: its read-out rows)
     int enc_used_rows;               // rows of the compressed set that belong to chunks
     int enc_rows;                    // > 0: the encoder's row set is row-compressed (RaggedChunk, common.h) and has this many rows (a multiple of 256)
     int first_pass;                  // the pass overwrites out.w_colsum, later ones add to it
     float* w_rows[2];                // home of the pass's w_i / w_e rows ([R, D] each, behind the base workspace); set if out.wants_w_rows()
     double* colsum_part;             // [nb, 2, D] slab partials of the pass; set with out.w_colsum
     VideosOut out;                   // the call's destinations at the pass's first packed row
+    // an online pass (csrc/online.h): the chunks are overlapping trailing windows, src_row relative to the pass's source base, and
+    // only rows skip .. skip + count of window c are read out, to packed row dst of the pass (window_plan.h); nullptr otherwise
+    const OnlineRead* d_reads;
+    int read_slices;                 // workgroups per (window, modality) of the read-out gather: one per 16 rows of the pass's largest count
 };
 
 // The workspace of one micro-batch carved into its tensors, with the pass's row set and the kernel choices that depend on it
@@ -1415,7 +1419,37 @@ static int pass_encoder_layer(iefvad_handle* h, PassBuffers& b, int l, const Rag
 static int pass_compact_rows(iefvad_handle* h, PassBuffers& b, const RaggedPass* rg, hipStream_t stream, Timer& tm) {
     const bool bf = (h->cfg.compute == IEFVAD_COMPUTE_BF16);
     const size_t D = h->D;
-    if (rg && !b.enc_rows_mode && h->cfg.compute != IEFVAD_COMPUTE_FP16X3) {
+    if (rg && rg->d_reads) {
+        // an online pass, row-compressed windows or whole chunks: the windows' read-out rows are gathered in packed order and the
+        // tail runs on them alone, as on a compacted set (the entry refuses fp16x3)
+        const int mc = (rg->valid_rows + 255) / 256 * 256;        // <= b.rows: a window contributes at most its valid rows
+        const size_t tail0 = (size_t)rg->valid_rows * D, tailn = (size_t)(mc - rg->valid_rows) * D;
+        const dim3 grid(b.nb, 2, rg->read_slices);
+        const bool d512 = h->D == IEF_D512;
+        if (bf) {
+            ReadoutArgs<bf16_t> ra;
+            memset(&ra, 0, sizeof(ra));
+            for (int m = 0; m < 2; ++m) { ra.src[m] = b.xb[m]; ra.dst[m] = b.attb[m]; b.xtb[m] = b.attb[m]; }
+            ra.chunks = rg->d_chunks; ra.reads = rg->d_reads;
+            if (tailn)
+                for (int m = 0; m < 2; ++m) HIP_TRY(hipMemsetAsync(b.attb[m] + tail0, 0, tailn * sizeof(bf16_t), stream));
+            if (int rc = dispatch_d(d512, [&](auto w) {
+                    return launch(tm, ST_CAST, iefvad_readout_rows_kernel<bf16_t, decltype(w)::value>, grid, dim3(256), 0, stream, ra);
+                })) return rc;
+        } else {
+            ReadoutArgs<float> ra;
+            memset(&ra, 0, sizeof(ra));
+            for (int m = 0; m < 2; ++m) { ra.src[m] = b.xbuf[m]; ra.dst[m] = b.att[m]; b.xt[m] = b.att[m]; }
+            ra.chunks = rg->d_chunks; ra.reads = rg->d_reads;
+            if (tailn)
+                for (int m = 0; m < 2; ++m) HIP_TRY(hipMemsetAsync(b.att[m] + tail0, 0, tailn * sizeof(float), stream));
+            if (int rc = dispatch_d(d512, [&](auto w) {
+                    return launch(tm, ST_CAST, iefvad_readout_rows_kernel<float, decltype(w)::value>, grid, dim3(256), 0, stream, ra);
+                })) return rc;
+        }
+        b.rows = mc;
+        b.compacted = true;
+    } else if (rg && !b.enc_rows_mode && h->cfg.compute != IEFVAD_COMPUTE_FP16X3) {
         const int mc = (rg->valid_rows + 255) / 256 * 256;
         if (mc < b.rows) {
             CompactArgs ca;
@@ -1796,6 +1830,7 @@ static int forward_impl(iefvad_handle* h, const RowsIn& in, const Extras& x, int
 // ------------------------------------------------------------------------------------------------
 static int attn_maps_args(const char* who, const iefvad_handle* h, const iefvad_attn_maps* maps, AttnMaps* am);   // the maps entries' checks, below
 #include "videos.h"
+#include "online.h"
 
 // ------------------------------------------------------------------------------------------------
 // small batches: replay a captured hipGraph of the forward

@@ -29,6 +29,7 @@
 #include <hip/hip_bf16.h>
 #include "common.h"
 #include "rowops.h"
+#include "window_plan.h"
 
 template <typename T> struct RaggedLimits;
 template <> struct RaggedLimits<float> { static __device__ float max() { return 3.40282347e38f; } };
@@ -317,4 +318,50 @@ __global__ __launch_bounds__(256) void iefvad_colsum_finish_kernel(const double*
     double t = first ? 0.0 : out[i];
     for (int g = 0; g < COLSUM_SEGS; ++g) t += seg_sum[g][jj];
     out[i] = t;
+}
+
+// ---- the read-out rows of an online pass (iefvad_forward_videos_online, csrc/window_plan.h) behind the last LayerNorm: of window c,
+// rows enc_row + skip .. + count of the encoder's row set -> rows dst .. of the pass's packed read-out order (OnlineRead), so that the
+// row-wise tail runs on the rows that are read and on nothing else.  It takes the role iefvad_compact_rows_kernel has in the
+// dense-encoder mode.  T = float (the f32 and bf16x6 arithmetics' rows) or __bf16 (the bf16 arithmetic's operand copy); the copy is
+// of bits, in 16-byte lanes: a row is NV = D sizeof(T) / 16 of them, lane l owns l, l + 64, ...  gridDim.z workgroups per (window,
+// modality), 16-row groups dealt round-robin, one wavefront per row, four rows of the wave in flight, as in
+// iefvad_rows_out_wide_kernel; no LDS, no atomics.  Rows outside [skip, skip + count) are never read.
+template <typename T>
+struct ReadoutArgs {
+    const T* src[2];        // the encoder's row set of the last layer, per modality
+    T* dst[2];
+    const RaggedChunk* chunks;
+    const OnlineRead* reads;
+};
+template <typename T, int D>
+__global__ __launch_bounds__(256) void iefvad_readout_rows_kernel(ReadoutArgs<T> a) {
+    constexpr int NV = D * (int)sizeof(T) / 16, NJ = (NV + 63) / 64;
+    static_assert(D * sizeof(T) % 16 == 0, "rows are whole 16-byte lanes");
+    const RaggedChunk c = a.chunks[blockIdx.x];
+    const OnlineRead rd = a.reads[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const f32x4* src = (const f32x4*)(a.src[blockIdx.y] + ((size_t)c.enc_row + rd.skip) * D) + lane;
+    f32x4* dst = (f32x4*)(a.dst[blockIdx.y] + (size_t)rd.dst * D) + lane;
+    const int nr = rd.count;
+    for (int r0 = wave + 16 * blockIdx.z; r0 < nr; r0 += 16 * gridDim.z) {
+        f32x4 v[4][NJ];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = r0 + 4 * u;
+            if (r < nr) {
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+                    if (lane + 64 * j < NV) v[u][j] = src[(size_t)r * NV + 64 * j];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int r = r0 + 4 * u;
+            if (r >= nr) break;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (lane + 64 * j < NV) dst[(size_t)r * NV + 64 * j] = v[u][j];
+        }
+    }
 }

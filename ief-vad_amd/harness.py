@@ -449,6 +449,19 @@ def _has_nan(t: torch.Tensor) -> bool:
     return bool(torch.isnan(s)) and bool(torch.isnan(t).any())
 
 
+def online_windows(n: int, stride: int, history: int = 256) -> List[Tuple[int, int, int]]:
+    """The trailing windows of a video of `n` snippets as `MMFMIL.forward_videos_online` evaluates them (csrc/window_plan.h): a list of
+    (start, end, read0), one per window j = 1 .. ceil(n / stride) with end = min(j stride, n), start = max(0, end - history), read0 =
+    (j - 1) stride.  Window j holds rows [start, end) of the video and zero rows behind them; only snippets [read0, end) are read out
+    of it, rows read0 - start .. of the window.  1 <= stride <= history <= 256 (ValueError otherwise)."""
+    from .model import online_params
+    stride, history = online_params(stride, history)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError(f"a video needs at least one snippet (got {n!r})")
+    ends = [min(j * stride, int(n)) for j in range(1, (int(n) + stride - 1) // stride + 1)]
+    return [(max(0, e - history), e, j * stride) for j, e in enumerate(ends)]
+
+
 def video_chunks(n: int, T: int) -> int:
     # chunks of a video of n rows without the loader's all-zero chunk: the rule of `video_chunks` in csrc/iefvad.hip
     return n // T + (1 if n % T else 0) if n >= T else 1
@@ -760,8 +773,8 @@ _NEEDS_FULL = ('similarity=True reads the forward\'s fused, image_mu and event_m
 
 
 def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, label_map, batch_chunks, similarity=False, row_outputs=(),
-                     attn_layers=(), trajectory=False, variants=(), samples=None):
-    """Valid-row loop around `MMFMIL.forward_videos`: a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
+                     attn_layers=(), trajectory=False, variants=(), samples=None, online=None):
+    """Valid-row loop around `MMFMIL.forward_videos` (`online=(stride, history)`: around `MMFMIL.forward_videos_online`): a batch closes as soon as its videos make up `batch_chunks` chunks; batches go
     round-robin over the lanes.  The staging copy of batch k + 1 (host threads inside the library, no GIL) runs on a worker thread
     while this thread sends batch k and enqueues its forward; batches complete in order.
     `similarity`: every forward also returns its [4, n] block of series (`forward_videos(similarity=True)`) for the sink.
@@ -783,6 +796,8 @@ def _score_rows_loop(models, stagers, streams, loader, sink, maxlen, dataset, la
                 ids = torch.arange(seen[0], seen[0] + sum(lens), dtype=torch.int32, device=img.device)
                 seen[0] += sum(lens)
                 out = models[k].forward_videos_samples(img, ev, lens, samples[0], samples[1], scale=samples[2], nan_to_num=True, sample_rows=ids)
+            elif online is not None:
+                out = models[k].forward_videos_online(img, ev, lens, online[0], history=online[1], nan_to_num=True)
             else:
                 out = models[k].forward_videos(img, ev, lens, nan_to_num=True, **sim_kw)
         sink.add(out['logits'], out['w_i_mean'], out['w_e_mean'], lens, sim=out.get('similarity'), rows=out,
@@ -858,7 +873,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                  ragged: Optional[bool] = None, host_list: bool = True, host_list_bytes: int = 1 << 30, wire_bf16: bool = False,
                  return_device: bool = False, similarity=False, row_outputs=None, attn_maps=None, steps: Optional[int] = None,
                  trajectory: bool = False, fusion_variants=None, score_samples: Optional[int] = None, sample_seed: Optional[int] = None,
-                 sample_scale: float = 1.0):
+                 sample_scale: float = 1.0, online_stride: Optional[int] = None, online_history: int = 256):
     """Per-video sigmoid scores and mean fusion weights, in loader order.
 
     batch_chunks == 0: one forward per video with B = that video's chunk count -- the reference's call
@@ -935,12 +950,31 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
     array, mean and population standard deviation of the S scores, formed on the device; "logits_samples_device": ONE [S, N] device
     tensor of the N valid snippets, the videos in list order (apply the sigmoid); "row_offsets": int64 array of len(videos) + 1 offsets
     into N}}.  The host-list walk does not take it: on the valid-row routes pass host_list=False (ValueError otherwise); it combines
-    with none of the other extras (`steps`, `trajectory`, `fusion_variants`, `similarity`, `row_outputs`, `attn_maps`)."""
+    with none of the other extras (`steps`, `trajectory`, `fusion_variants`, `similarity`, `row_outputs`, `attn_maps`).
+    `online_stride=s` (and `online_history=`, default 256; the `forward_videos` loop; HIP device): every call is
+    `MMFMIL.forward_videos_online` -- each video evaluated over trailing windows (`online_windows`), so that a snippet's score depends
+    on fewer than s snippets after it (this package's own semantics; the reference evaluates offline; the NaN rule stays per whole
+    video).  The returned tuple holds the online scores and weight means; `score_loader.last_result` becomes {"online": {"scores": per
+    video a [snippets] float32 array; "scores_device": ONE [N] device tensor of the N valid snippets, the videos in list order;
+    "row_offsets": int64 array of len(videos) + 1 offsets into N; "stride", "history"}}.  The host-list walk does not take it: pass
+    host_list=False (ValueError otherwise); it combines with none of the other extras."""
     on_gpu = torch.device(device).type == 'cuda'
-    from .model import _row_output_keys, attn_map_layers, attn_maps_asked, fusion_variant_names
+    from .model import _row_output_keys, attn_map_layers, attn_maps_asked, fusion_variant_names, online_params
     variants = fusion_variant_names(fusion_variants)
     want_maps = attn_maps_asked(attn_maps)
     samples = None
+    online = None
+    if online_stride is not None:
+        online = online_params(online_stride, online_history)
+        if steps is not None or trajectory or variants or similarity or row_outputs is not None or want_maps or score_samples is not None:
+            raise ValueError('online_stride does not combine with steps, trajectory, fusion_variants, score_samples, similarity, row_outputs or attn_maps')
+        if host_list:
+            raise ValueError('online_stride is not served by the host-list walk (iefvad_forward_videos_host has no online entry): '
+                             'pass host_list=False for the forward_videos_online loop')
+        if not (on_gpu and batch_chunks > 0 and hasattr(model, 'forward_videos_online')) or ragged is False:
+            raise ValueError('online_stride takes the forward_videos_online loop: it needs a HIP device, batch_chunks > 0 and a model with '
+                             'forward_videos_online (and not ragged=False)')
+        ragged = True
     if score_samples is not None:
         if steps is not None or trajectory or variants or similarity or row_outputs is not None or want_maps:
             raise ValueError('score_samples does not combine with steps, trajectory, fusion_variants, similarity, row_outputs or attn_maps')
@@ -1042,7 +1076,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                                  row_keys)
             elif ragged:
                 _score_rows_loop(models, stagers, streams, test_loader, sink, maxlen, dataset, label_map, batch_chunks, sim_rows, row_keys,
-                                 attn_layers, trajectory, variants, samples)
+                                 attn_layers, trajectory, variants, samples, online)
             else:
                 _score_padded(models, stagers, streams, test_loader, sink, maxlen, device, dataset, label_map, batch_chunks, skip_empty_chunks,
                               bool(similarity), trajectory, variants, samples)
@@ -1052,7 +1086,7 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                 model.set_steps(prev_steps)
         for s in streams if nl > 1 else ():
             torch.cuda.current_stream(device).wait_stream(s)
-        if trajectory or variants or samples is not None or sink.dev_rows is not None:
+        if trajectory or variants or samples is not None or sink.dev_rows is not None or online is not None:
             offsets = np.concatenate([[0], np.cumsum([n for _, n in sink.spans])]).astype(np.int64)
         if sink.dev_traj:
             # the slots of every forward side by side, then the valid ones in video order (the padded route leaves gaps between the videos' slots)
@@ -1090,6 +1124,11 @@ def score_loader(model: Callable, test_loader: Iterable, maxlen: int, device, da
                 "row_outputs": {k: v[0] if len(v) == 1 else torch.cat(v) if v else torch.zeros(0, D, device=device)
                                 for k, v in sink.dev_rows.items()},
                 "row_offsets": offsets}
+        if online is not None:
+            res = sink.finish(device, True)
+            score_loader.last_result = {"online": {"scores": res[0], "scores_device": res[4], "row_offsets": offsets, "stride": online[0],
+                                                   "history": online[1]}}
+            return res if return_device else res[:4]
         return sink.finish(device, return_device)
 
 
@@ -1396,7 +1435,7 @@ def draw_vis(series: Dict[str, Dict[str, object]], directory: str, dpi: float = 
 
 def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys, total_samples, log,
               batch_chunks, lanes, metric_tail="host", vis_flavour="test", vis_route="padded", attn_maps=None, steps=None, trajectory=False,
-              fusion_variants=None, score_samples=None, sample_seed=None):
+              fusion_variants=None, score_samples=None, sample_seed=None, online_stride=None, online_history=256):
     """The body the three `test()` functions of the reference share (test.py:57-212): model.to / eval, the per-video
     loop, the metric tail, the prints.  What differs between the files is passed in: the Ano-AUC filter, the
     "Total Samples" suffix of ucf_test.py:173-174 and the `wandb.log` calls (ucf_test.py:158-162,175-178 /
@@ -1425,8 +1464,15 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
     `score_samples=S` with `sample_seed=`: one walk gives S Monte Carlo draws of every score from the heads' own Gaussians --
     `score_loader(score_samples=...)` on the per-video route or the `forward_videos` loop -- and the result dict gains "samples" (see
     there), "auc_samples" / "ap_samples" (S floats each: the global AUC / AP of sample s's scores) and "auc_mean_score" / "ap_mean_score"
-    (those of the per-snippet mean score), by the metric tail in use; nothing more is printed.  It combines with none of the other extras."""
-    from .model import attn_maps_asked
+    (those of the per-snippet mean score), by the metric tail in use; nothing more is printed.  It combines with none of the other extras.
+    `online_stride=s` (with `online_history=`, default 256): IN ADDITION to the evaluation above, a second walk over the loader --
+    `score_loader(online_stride=s, host_list=False)`, 64 chunks per call with `batch_chunks` unset or 0 -- scores every video over
+    trailing windows (`MMFMIL.forward_videos_online`); the result dict gains "online" (see there), "auc_online" and "ap_online": the
+    global AUC / AP of the online scores, by the metric tail in use (sklearn, or `iefvad_auc_ap`).  Nothing more is printed; the
+    returned values and every other key are those of the same call without it.  The loader must be iterable twice."""
+    from .model import attn_maps_asked, online_params
+    if online_stride is not None:
+        online_params(online_stride, online_history)
     want_maps = attn_maps_asked(attn_maps)
     if score_samples is not None and (vis or trajectory or want_maps or steps is not None or (fusion_variants is not None and fusion_variants is not False)):
         raise ValueError("score_samples does not combine with vis=True, attn_maps, steps, trajectory or fusion_variants")
@@ -1501,6 +1547,16 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
             pairs = [(roc_auc_score(gt, np.repeat(row.tolist(), 16)), average_precision_score(gt, np.repeat(row.tolist(), 16))) for row in rows]
         last["auc_samples"], last["ap_samples"] = [p[0] for p in pairs[:-1]], [p[1] for p in pairs[:-1]]
         last["auc_mean_score"], last["ap_mean_score"] = pairs[-1]
+    if online_stride is not None:
+        score_loader(model, test_loader, maxlen, device, args.dataset, label_map, batch_chunks if batch_chunks > 0 else 64, host_list=False,
+                     online_stride=online_stride, online_history=online_history)
+        on = last["online"] = score_loader.last_result["online"]
+        if metric_tail == "device":
+            last["auc_online"], last["ap_online"] = device_auc_ap(on["scores_device"], gt)
+        else:       # the calls of evaluate_scores (test.py:158-159) on the online scores
+            from sklearn.metrics import average_precision_score, roc_auc_score
+            flat = np.repeat(np.concatenate(on["scores"]).tolist() if on["scores"] else [], 16)
+            last["auc_online"], last["ap_online"] = roc_auc_score(gt, flat), average_precision_score(gt, flat)
     if vis:
         last["similarity"] = got[-1]
         last["vis_files"] = draw_vis(vis_series(last, gt, vis_flavour), os.path.join('vis', str(args.exp_name)),      # test.py:59-62
@@ -1512,7 +1568,8 @@ def _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis
 
 def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, label_map=None,
          batch_chunks: Optional[int] = None, normal_keys=('Normal',), lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded",
-         *, attn_maps=None, steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None):
+         *, attn_maps=None, steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None, online_stride=None,
+         online_history=256):
     """Counterpart of ROOT `test.py`'s `test()` (test.py:46-56; call site test.py:380-390): same positional order
     (..., device, attn, vis), Ano-AUC over every class but 'Normal' (test.py:336).  `label_map` is keyword-only in
     spirit: root test.py reads a global for the xd remap (test.py:81).  Returns (ROC1, AP1), or
@@ -1528,29 +1585,32 @@ def test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, 
     `fusion_variants=` (keyword-only, here and in `ucf_test` / `xd_test`): True or names; adds the fusion ablations' scores ("variants")
     and "auc_variants", "ap_variants" (name -> float) to `last_result` from the one walk (`_run_test`).
     `score_samples=S`, `sample_seed=` (keyword-only, here and in `ucf_test` / `xd_test`): adds the Monte Carlo score samples ("samples"),
-    "auc_samples" / "ap_samples" (S floats each) and "auc_mean_score" / "ap_mean_score" to `last_result` from the one walk (`_run_test`)."""
+    "auc_samples" / "ap_samples" (S floats each) and "auc_mean_score" / "ap_mean_score" to `last_result` from the one walk (`_run_test`).
+    `online_stride=s`, `online_history=` (keyword-only, here and in `ucf_test` / `xd_test`): a second walk scores every video over
+    trailing windows (`MMFMIL.forward_videos_online`) and adds "online", "auc_online" and "ap_online" to `last_result` (`_run_test`)."""
     ret, test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, label_map, attn, vis, normal_keys,
                                       False, None, batch_chunks, lanes, metric_tail, vis_route=vis_route, attn_maps=attn_maps, steps=steps,
-                                      trajectory=trajectory, fusion_variants=fusion_variants, score_samples=score_samples, sample_seed=sample_seed)
+                                      trajectory=trajectory, fusion_variants=fusion_variants, score_samples=score_samples, sample_seed=sample_seed,
+                                      online_stride=online_stride, online_history=online_history)
     return ret
 
 
 def ucf_test(args, model, test_loader, maxlen, prompt_text, gt, device, attn=False, vis=False, *, log=None,
              batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
-             steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None):
+             steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None, online_stride=None, online_history=256):
     """Drop-in for `train/ucf_test.py`'s `test` (ucf_test.py:16-26; call site ucf_train.py:130-139): positional order
     (..., device, attn, vis); Ano-AUC excludes BOTH 'Normal' and 'normal' (ucf_test.py:340); the per-class lines carry
     "Total Samples" (ucf_test.py:173-174).  `log` (e.g. `wandb.log`) receives the dicts the reference logs."""
     ret, ucf_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, None, attn, vis,
                                           ('Normal', 'normal'), True, log, batch_chunks, lanes, metric_tail, "ucf_test", vis_route, attn_maps, steps,
-                                          trajectory, fusion_variants, score_samples, sample_seed)
+                                          trajectory, fusion_variants, score_samples, sample_seed, online_stride, online_history)
     test.last_result = ucf_test.last_result
     return ret
 
 
 def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map, vis=False, attn=False, *, log=None,
             batch_chunks: Optional[int] = None, lanes: int = 1, metric_tail: str = "host", vis_route: str = "padded", attn_maps=None,
-            steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None):
+            steps=None, trajectory=False, fusion_variants=None, score_samples=None, sample_seed=None, online_stride=None, online_history=256):
     """Drop-in for `train/xd_test.py`'s `test` (xd_test.py:15-26; call site xd_train.py:102-112): `label_map` is the
     8th positional, then (vis, attn) -- the reverse of ucf_test's order; every video's class is
     `label_map[cls.split('-')[0]]` whatever args.dataset says (xd_test.py:68, unconditional); Ano-AUC excludes
@@ -1559,7 +1619,7 @@ def xd_test(args, model, test_loader, maxlen, prompt_text, gt, device, label_map
         raise TypeError("xd_test: label_map is required (xd_test.py:68 indexes it for every video)")
     ret, xd_test.last_result = _run_test(args, model, test_loader, maxlen, gt, device, _AlwaysRemap(label_map), attn, vis,
                                          ('normal',), False, log, batch_chunks, lanes, metric_tail, "xd_test", vis_route, attn_maps, steps, trajectory,
-                                         fusion_variants, score_samples, sample_seed)
+                                         fusion_variants, score_samples, sample_seed, online_stride, online_history)
     test.last_result = xd_test.last_result
     return ret
 

@@ -41,7 +41,8 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_set_steps", "iefvad_trajectory_workspace_bytes", "iefvad_forward_trajectory", "iefvad_videos_trajectory_workspace_bytes",
            "iefvad_forward_videos_trajectory", "iefvad_variants_workspace_bytes", "iefvad_forward_variants",
            "iefvad_videos_variants_workspace_bytes", "iefvad_forward_videos_variants", "iefvad_samples_workspace_bytes",
-           "iefvad_forward_samples", "iefvad_videos_samples_workspace_bytes", "iefvad_forward_videos_samples"]
+           "iefvad_forward_samples", "iefvad_videos_samples_workspace_bytes", "iefvad_forward_videos_samples",
+           "iefvad_videos_online_workspace_bytes", "iefvad_forward_videos_online"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -116,6 +117,14 @@ class Samples(C.Structure):
     the device fp32 results [S, stride], [rows], [rows]."""
     _fields_ = [("samples", C.c_int32), ("seed", C.c_uint64), ("scale", C.c_float), ("sample_rows", _fp), ("logits_samples", _fp),
                 ("stride", C.c_size_t), ("score_mean", _fp), ("score_std", _fp)]
+
+
+ONLINE_MAX_HISTORY = 256      # kWindowRows (csrc/window_plan.h): a window is one chunk
+
+
+class Online(C.Structure):
+    """iefvad_online (include/iefvad.h): the trailing windows' stride and history, 1 <= stride <= history <= 256."""
+    _fields_ = [("stride", C.c_int32), ("history", C.c_int32)]
 
 
 class Perturb(C.Structure):
@@ -345,6 +354,11 @@ def load_library() -> C.CDLL:
     lib.iefvad_videos_samples_workspace_bytes.restype = C.c_size_t
     lib.iefvad_forward_videos_samples.argtypes = lib.iefvad_forward_videos.argtypes[:12] + [C.POINTER(Samples), C.c_void_p]
     lib.iefvad_forward_videos_samples.restype = C.c_int
+    # the online entry: `const iefvad_online*` behind nan_to_num, and behind the plain query's arguments
+    lib.iefvad_videos_online_workspace_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.POINTER(Online)]
+    lib.iefvad_videos_online_workspace_bytes.restype = C.c_size_t
+    lib.iefvad_forward_videos_online.argtypes = lib.iefvad_forward_videos.argtypes[:7] + [C.POINTER(Online)] + lib.iefvad_forward_videos.argtypes[7:]
+    lib.iefvad_forward_videos_online.restype = C.c_int
     lib.iefvad_split_bf16x3.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.iefvad_split_bf16x3.restype = C.c_int
     lib.iefvad_split_bf16x3_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]

@@ -136,7 +136,7 @@ class _Request:
     once.  `maps_asked` is the raw view of `attn_maps=` and `layers` the parsed one: () until the checks parse it at its place in their order,
     so a value that does not parse is refused there and not sooner.  `_PLAIN` is the call that asks for nothing."""
     __slots__ = ("kind", "training", "grad", "eval_grad", "fp16x3", "bf16", "timed", "row_scale", "scaled", "attn_maps", "maps_asked", "layers", "row_noise",
-                 "noisy", "noise_seed", "noise_rows", "trajectory", "variants", "samples", "similarity", "outputs", "outputs_asked", "weight_sums", "nan_always", "extras")
+                 "noisy", "noise_seed", "noise_rows", "trajectory", "variants", "samples", "similarity", "outputs", "outputs_asked", "weight_sums", "nan_always", "extras", "online")
 
     def __init__(self, training=False, grad=False, compute="f32", *, timed=False, row_scale=None, attn_maps=None, row_noise=None, noise_seed=None,
                  noise_rows=None, trajectory=False, fusion_variants=None, similarity=False, outputs=None, weight_sums=False, nan_to_num=True):
@@ -150,6 +150,7 @@ class _Request:
         self.nan_always = isinstance(nan_to_num, str) and nan_to_num == "always"
         self.extras = self.nan_always or weight_sums or self.scaled or self.noisy      # the sweep's extras of the valid-row calls
         self.samples = None      # `forward_samples` / `forward_videos_samples`: (S, seed, scale, sample_rows)
+        self.online = None       # `forward_videos_online`: the call's `lib.Online`
         self.kind = "plain"      # the row of `_DENSE_ENTRIES` that serves the request: `forward` names it once the checks have passed
 
 
@@ -331,8 +332,25 @@ _SAMPLES_ENTRIES = {
 }
 
 
+# The online entry, a sibling in the same way: `forward_videos_online` names the row.  Its `iefvad_online` stands behind nan_to_num in the
+# call's front arguments and behind (handle, lengths, nvideos) in the query's.
+_ONLINE_ENTRIES = {
+    "_online": ("_online", lambda r: (r["online"],), lambda r: (*r["vectors"], r["stream"])),
+}
+
+
 def _entry_row(table: dict, key: str) -> tuple:
-    return table[key] if key in table else _SAMPLES_ENTRIES[key]
+    return table[key] if key in table else _SAMPLES_ENTRIES[key] if key in _SAMPLES_ENTRIES else _ONLINE_ENTRIES[key]
+
+
+def online_params(stride, history=_lib.ONLINE_MAX_HISTORY) -> tuple:
+    """The (stride, history) of an online call, checked: ints with 1 <= stride <= history <= 256 (ValueError otherwise)."""
+    for name, v in (("stride", stride), ("history", history)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an int (got {v!r})")
+    if not 1 <= stride <= history <= _lib.ONLINE_MAX_HISTORY:
+        raise ValueError(f"1 <= stride <= history <= {_lib.ONLINE_MAX_HISTORY} required (got stride={stride}, history={history})")
+    return stride, history
 
 
 # what `MMFMIL(outputs=)` makes every dense call return, in the order of the returned dict: (key, its shape behind [B, T]; None = D)
@@ -972,7 +990,8 @@ class MMFMIL(nn.Module):
             res = {k: torch.empty(total, **f32) for k in ("logits", "w_i_mean", "w_e_mean")}
             r = {"vectors": tuple(C.c_void_p(res[k].data_ptr()) for k in ("logits", "w_i_mean", "w_e_mean")), "stream": C.c_void_p(stream), "out": None,
                  "similarity": None, "w_colsum": None, "with_colsum": 1 if q.weight_sums else 0, "attn": None, "trajectory": None,
-                 "variants": None, "nvariants": len(q.variants), "samples": None}
+                 "variants": None, "nvariants": len(q.variants), "samples": None,
+                 "online": C.byref(q.online) if q.online is not None else None}
             if suffix[1:] in _EXTRA_RESULTS:
                 extra = _EXTRA_RESULTS[suffix[1:]][0](q, self.steps, (total,), (total,), self.visual_length, lambda *shape: torch.empty(shape, **f32))
                 res.update(extra)
@@ -1173,3 +1192,50 @@ class MMFMIL(nn.Module):
         q.samples = (S, seed, scale, sample_rows)
         front = (C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), 1 if nan_to_num else 0)
         return self._rows_call("iefvad_forward_videos", "_samples", q, device, total, front, workspace_for=(larr, len(lens)))
+
+    # ------------------------------------------------------------------ online scores
+    def forward_videos_online(self, img_rows, ev_rows, lengths, stride: int, *, history: int = 256, nan_to_num: bool = True) -> Dict[str, torch.Tensor]:
+        """What the model would have said live (`iefvad_forward_videos_online`, include/iefvad.h): the valid rows [sum(lengths), D] and
+        the lengths as `forward_videos` takes them, every video evaluated over trailing windows.  With 1 <= stride <= history <= 256
+        (ValueError otherwise), a video of n snippets has windows j = 1 .. ceil(n / stride): end = min(j stride, n), start =
+        max(0, end - history), read0 = (j - 1) stride (`harness.online_windows`).  Window j is the 256-row chunk of rows [start, end) and
+        zero rows behind them; it goes through the unchanged model, and only snippets [read0, end) are read out.  Every snippet belongs to
+        exactly one window and its results depend on no snippet at or beyond that window's end: the look-ahead is below `stride`, and
+        stride=1 is strictly causal.  The reference never does this; these semantics are this package's own ("parity unpinned"), pinned
+        by the dense `forward` on host-built windows.  Returns `logits`, `w_i_mean`, `w_e_mean`, each [sum(lengths)] in packed order.
+        `nan_to_num=True` is the per-video rule of test.py:90-95, decided over the WHOLE video as everywhere: a NaN anywhere in a video
+        changes how all its windows are loaded, so this one rule is not causal.  The encoder runs once per window; heads, fusion,
+        refinement and scorer run on the read-out rows only.  model.train(), features that require grad, host tensors and
+        compute="fp16x3" raise RuntimeError.  It takes none of `forward_videos`'s keyword extras."""
+        stride, history = online_params(stride, history)
+        if not isinstance(nan_to_num, bool):
+            raise ValueError(f"nan_to_num must be True or False (got {nan_to_num!r})")
+        if not (isinstance(img_rows, torch.Tensor) and isinstance(ev_rows, torch.Tensor)):
+            raise ValueError("img_rows and ev_rows must be tensors")
+        lens = [int(n) for n in lengths]
+        total = sum(lens)
+        D = self.temporal.embed_dim
+        if img_rows.shape != ev_rows.shape or img_rows.dim() != 2 or tuple(img_rows.shape) != (total, D):
+            raise ValueError(f"expected two [{total}, {D}] tensors (sum of lengths x D), got {tuple(img_rows.shape)} and {tuple(ev_rows.shape)}")
+        if not lens or min(lens) < 1:
+            raise ValueError("every video needs at least one snippet")
+        who = "iefvad_amd.MMFMIL.forward_videos_online"
+        if self.training:
+            raise RuntimeError(f"{who} is an evaluation entry point; it is not available under model.train() (call model.eval() first)")
+        if _differentiable(img_rows, ev_rows):
+            raise RuntimeError(f"{who} is an evaluation entry point: nothing it returns is differentiable, and a feature tensor that requires "
+                               "grad would get no gradient (detach it)")
+        if self.compute == "fp16x3":
+            raise RuntimeError('forward_videos_online is not available with compute="fp16x3" (its operand scales are per chunk and its tail '
+                               'keeps whole chunks); use "f32", "bf16x6" or "bf16"')
+        self._noise_code()
+        if not (img_rows.is_cuda and ev_rows.is_cuda):
+            raise RuntimeError(f"{who} runs on a HIP device only; there is no CPU fallback (move the inputs with .to('cuda'); "
+                               "harness.online_windows is the host model of the windows)")
+        device = img_rows.device
+        img, ev = self._prepare_pair(img_rows, ev_rows)
+        larr = (C.c_int32 * len(lens))(*lens)
+        q = _Request()
+        q.online = _lib.Online(stride, history)
+        front = (C.c_void_p(img.data_ptr()), C.c_void_p(ev.data_ptr()), _IN_DTYPES[img.dtype], larr, len(lens), 1 if nan_to_num else 0, C.byref(q.online))
+        return self._rows_call("iefvad_forward_videos", "_online", q, device, total, front, workspace_for=(larr, len(lens)))

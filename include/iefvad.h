@@ -866,6 +866,38 @@ int iefvad_forward_videos_samples(iefvad_handle* h, const void* img_rows, const 
                                   size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
                                   const iefvad_samples* samples, void* stream);
 
+/* ---- online scores: trailing-window evaluation -------------------------------------------------------------------
+ * iefvad_forward_videos and the reference's test() cut a video at fixed multiples of 256 snippets, and the temporal encoder attends
+ * over the whole chunk (imf_vad.py:115, unmasked): the score of snippet t may depend on up to 255 FUTURE snippets.  This entry answers
+ * what the model would have said live with a look-ahead below `stride` snippets.  The reference never does this, so these semantics
+ * are this library's own ("parity unpinned", as for the row noise and the score samples); iefvad_forward on host-built windows pins
+ * them exactly.  With 1 <= stride <= history <= 256, a video of n snippets has windows j = 1 .. ceil(n / stride):
+ *   end_j = min(j stride, n)      start_j = max(0, end_j - history)      read0_j = (j - 1) stride
+ * Window j is a 256-row chunk: rows [start_j, end_j) of the video, then zero rows (the chunker's convention for a short video).  It
+ * goes through the unchanged model, and only snippets [read0_j, end_j) -- rows read0_j - start_j .. of the window -- are read out.
+ * Every snippet belongs to exactly one window; its results depend on no snippet at or beyond end_j, so stride = 1 is strictly causal.
+ * n = 300, stride = 128, history = 256: (start, end, read0) = (0,128,0) (0,256,128) (44,300,256).
+ * nan_to_num (any non-zero value) is the per-video rule of iefvad_forward_videos, decided over the WHOLE video, once per video: a
+ * NaN anywhere in a video changes how its earlier windows are loaded.  That one rule is NOT causal.
+ * Arguments and results are those of iefvad_forward_videos: packed valid rows in, logits / w_i_mean / w_e_mean [sum(lengths)] out
+ * (the latter two nullable).  The call's windows run in passes of at most micro_batch windows (csrc/window_plan.h); the encoder runs
+ * on row-compressed windows (whole chunks with IEFVAD_DENSE_ENCODER=1); behind the last LayerNorm iefvad_readout_rows_kernel gathers
+ * the read-out rows, and heads, fusion, refinement and scorer run on those alone, with the kernels the unchanged selection rules pick
+ * for that row count.  Only the encoder's cost grows with the number of windows.  stride = history = 256 on videos whose lengths
+ * are <= 256 or multiples of 256 builds the chunks of iefvad_forward_videos.
+ * Refused by name before any launch: IEFVAD_COMPUTE_FP16X3 (its operand scales are per chunk and its tail keeps whole chunks), null
+ * parameters, stride or history out of range, a workspace smaller than iefvad_videos_online_workspace_bytes says (0 for arguments no
+ * call would accept).  Direct launches (no hipGraph).  Added without a change to any other entry: IEFVAD_ABI_VERSION stays. */
+typedef struct iefvad_online {
+    int32_t stride;                 /* 1..history: snippets read out per window; the look-ahead is below it */
+    int32_t history;                /* stride..256: snippets a window holds at most */
+} iefvad_online;
+size_t iefvad_videos_online_workspace_bytes(const iefvad_handle* h, const int32_t* lengths, int32_t nvideos, const iefvad_online* online);
+int iefvad_forward_videos_online(iefvad_handle* h, const void* img_rows, const void* ev_rows, int32_t in_dtype,
+                                 const int32_t* lengths, int32_t nvideos, int32_t nan_to_num, const iefvad_online* online,
+                                 void* workspace, size_t workspace_bytes, float* logits, float* w_i_mean, float* w_e_mean,
+                                 void* stream);
+
 /* The exact three-term bf16 split of n fp32 values (n % 4 == 0): planes[0..n) = bf16(x),
  * planes[n..2n) = bf16(x - p0), planes[2n..3n) = bf16(x - p0 - p1), round-to-nearest-even; x == p0 + p1 + p2
  * for finite x.  What iefvad_set_weights applies to every projection matrix in IEFVAD_COMPUTE_BF16X6. */
