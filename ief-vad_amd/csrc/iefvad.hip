@@ -2727,6 +2727,110 @@ extern "C" int iefvad_gemm_split_small_unit(const iefvad_gemm_split_io* io, int3
     return launch_gemm_split_small(g, nz, (hipStream_t)stream, tm, ST_QKV);
 }
 
+// One kernel of the backward pass on the caller's buffers (include/iefvad.h), through train.h's own launch helpers
+extern "C" int iefvad_backward_unit(int32_t kind, const void* args, size_t args_bytes, void* stream_) {
+    static const char* const who = "iefvad_backward_unit";
+    if (!args) return fail("%s: null argument", who);
+    hipStream_t stream = (hipStream_t)stream_;
+    auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+    auto sized = [&](size_t want) { return args_bytes == want ? 0 : fail("%s: kind %d takes an argument block of %zu bytes (got %zu)", who, kind, want, args_bytes); };
+    switch (kind) {
+    case IEFVAD_BWD_BGEMM: {
+        if (int rc = sized(sizeof(iefvad_bwd_bgemm))) return rc;
+        const iefvad_bwd_bgemm& u = *(const iefvad_bwd_bgemm*)args;
+        if (!u.A || !u.B || !u.C) return fail("%s: BGEMM needs A, B and C", who);
+        if (!al(u.A) || !al(u.B) || ((u.a1 | u.a2 | u.b1 | u.b2) & 3)) return fail("%s: BGEMM reads A and B 16 bytes at a time: pointers and batch strides must be aligned", who);
+        if (u.act < 0 || u.act > 2) return fail("%s: BGEMM act = %d (0, 1 or 2)", who, u.act);
+        BgemmArgs a;
+        memset(&a, 0, sizeof(a));
+        a.A = u.A; a.B = u.B; a.C = u.C; a.R = u.R; a.G = u.G; a.bias = u.bias;
+        a.M = u.M; a.N = u.N; a.K = u.K; a.lda = u.lda; a.ldb = u.ldb; a.ldc = u.ldc;
+        a.a1 = u.a1; a.a2 = u.a2; a.b1 = u.b1; a.b2 = u.b2; a.c1 = u.c1; a.c2 = u.c2;
+        a.nz2 = u.nz2; a.alpha = u.alpha; a.act = u.act; a.a_drop = u.a_drop;
+        return launch_bgemm(a, u.akc != 0, u.bkc != 0, u.nz, stream);
+    }
+    case IEFVAD_BWD_SPLIT_TN: {
+        if (int rc = sized(sizeof(iefvad_bwd_split_tn))) return rc;
+        const iefvad_bwd_split_tn& u = *(const iefvad_bwd_split_tn*)args;
+        if (!u.dY || !u.X || !u.part || !u.dW || (u.colsum_part && !u.db)) return fail("%s: SPLIT_TN needs dY, X, part and dW (and db with colsum_part)", who);
+        if (!al(u.dY) || !al(u.X) || !al(u.part) || !al(u.colsum_part)) return fail("%s: SPLIT_TN operands must be 16-byte aligned", who);
+        if (u.rows <= 0 || u.rows % TN_BK || u.n_out <= 0 || u.n_out % 128)
+            return fail("%s: SPLIT_TN rows = %d must be a multiple of %d and n_out = %d of 128", who, u.rows, TN_BK, u.n_out);
+        const int nk_total = u.rows / TN_BK;
+        if (u.slices < 1 || u.slices > nk_total / 8) return fail("%s: SPLIT_TN slices = %d outside 1..%d (eight 16-row tiles per slice at least)", who, u.slices, nk_total / 8);
+        hipError_t e = raise_lds_limit((const void*)iefvad_gemm_split_tn256_kernel);
+        if (e != hipSuccess) return fail("%s: %s", who, hipGetErrorString(e));
+        return launch_dw_split_tn(u.dY, u.X, u.rows, u.n_out, u.slices, u.part, u.colsum_part, u.n_out, u.alpha, u.dW, nullptr, u.db, nullptr, stream);
+    }
+    case IEFVAD_BWD_SOFTMAX_DROPOUT: {
+        if (int rc = sized(sizeof(iefvad_bwd_softmax_dropout))) return rc;
+        const iefvad_bwd_softmax_dropout& u = *(const iefvad_bwd_softmax_dropout*)args;
+        if (!u.S || !al(u.S) || u.rows <= 0) return fail("%s: SOFTMAX_DROPOUT needs S, 16-byte aligned, and rows > 0", who);
+        SoftmaxDropArgs a;
+        a.S = u.S; a.drop = u.drop ? 1 : 0; a.keep = u.keep; a.seed = u.seed; a.p = u.p; a.rows = u.rows;
+        return launch_softmax_dropout(a, stream);
+    }
+    case IEFVAD_BWD_SOFTMAX_BWD: {
+        if (int rc = sized(sizeof(iefvad_bwd_softmax_bwd))) return rc;
+        const iefvad_bwd_softmax_bwd& u = *(const iefvad_bwd_softmax_bwd*)args;
+        if (!u.Ps || !u.dPd || !al(u.Ps) || !al(u.dPd) || u.rows <= 0) return fail("%s: SOFTMAX_BWD needs Ps and dPd, 16-byte aligned, and rows > 0", who);
+        return launch_softmax_bwd(u.Ps, u.scale, u.dPd, u.rows, stream);
+    }
+    case IEFVAD_BWD_COLSUM: {
+        if (int rc = sized(sizeof(iefvad_bwd_colsum))) return rc;
+        const iefvad_bwd_colsum& u = *(const iefvad_bwd_colsum*)args;
+        if (!u.Y || !u.part || u.rows <= 0 || u.ncols <= 0 || u.ld < u.ncols) return fail("%s: COLSUM needs Y and part, rows > 0 and 0 < ncols <= ld", who);
+        return launch_colsum(u.Y, u.ld, u.rows, u.ncols, u.part, stream);
+    }
+    case IEFVAD_BWD_REDUCE_PARTS:
+    case IEFVAD_BWD_REDUCE_PARTS_MULTI: {
+        if (int rc = sized(sizeof(iefvad_bwd_reduce))) return rc;
+        const iefvad_bwd_reduce& u = *(const iefvad_bwd_reduce*)args;
+        if (u.count < 1 || u.count > 5) return fail("%s: REDUCE_PARTS count = %d (1..5)", who, u.count);
+        for (int j = 0; j < u.count; ++j)
+            if (!u.part[j] || u.nparts[j] < 1) return fail("%s: REDUCE_PARTS job %d needs part and nparts >= 1", who, j);
+        if (kind == IEFVAD_BWD_REDUCE_PARTS) return reduce_parts(u.part[0], (size_t)u.stride[0], u.nparts[0], (size_t)u.n[0], u.out[0], u.alpha[0], stream);
+        ReduceBatch rb;
+        for (int j = 0; j < u.count; ++j) rb.add(u.part[j], (size_t)u.stride[j], u.nparts[j], (size_t)u.n[j], u.out[j], u.alpha[j]);
+        return rb.launch(stream);
+    }
+    case IEFVAD_BWD_SCORER: {
+        if (int rc = sized(sizeof(iefvad_bwd_scorer))) return rc;
+        const iefvad_bwd_scorer& u = *(const iefvad_bwd_scorer*)args;
+        if (!u.z || !u.w || !u.g || !u.part_w || !u.part_b || u.rows <= 0) return fail("%s: SCORER needs z, w, g, part_w, part_b and rows > 0", who);
+        if (!al(u.z) || !al(u.w) || !al(u.g) || !al(u.dfused)) return fail("%s: SCORER operands must be 16-byte aligned", who);
+        ScorerBwdArgs a;
+        a.dlogit = u.dlogit; a.dfused = u.dfused; a.z = u.z; a.w = u.w; a.g = u.g; a.part_w = u.part_w; a.part_b = u.part_b; a.rows = u.rows;
+        return launch_scorer_bwd(a, stream);
+    }
+    case IEFVAD_BWD_FUSION: {
+        if (int rc = sized(sizeof(iefvad_bwd_fusion))) return rc;
+        const iefvad_bwd_fusion& u = *(const iefvad_bwd_fusion*)args;
+        if (!u.mu_i || !u.lv_i || !u.mu_e || !u.lv_e || !u.gz || !u.dh_i || !u.dh_e || u.rows <= 0)
+            return fail("%s: FUSION needs mu, logvar of both modalities, gz, dh_i, dh_e and rows > 0", who);
+        for (const void* p : {(const void*)u.mu_i, (const void*)u.lv_i, (const void*)u.mu_e, (const void*)u.lv_e, (const void*)u.gz, (const void*)u.d_mu_i,
+                              (const void*)u.d_lv_i, (const void*)u.d_mu_e, (const void*)u.d_lv_e, (const void*)u.dh_i, (const void*)u.dh_e})
+            if (!al(p)) return fail("%s: FUSION operands must be 16-byte aligned", who);
+        FusionBwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.mu_i = u.mu_i; a.lv_i = u.lv_i; a.mu_e = u.mu_e; a.lv_e = u.lv_e; a.gz = u.gz;
+        a.d_mu_i = u.d_mu_i; a.d_lv_i = u.d_lv_i; a.d_mu_e = u.d_mu_e; a.d_lv_e = u.d_lv_e; a.d_n_i = u.d_n_i; a.d_n_e = u.d_n_e;
+        a.dh_i = u.dh_i; a.dh_e = u.dh_e; a.rows = u.rows; a.factor = u.factor; a.eps = u.eps;
+        return launch_fusion_bwd(a, stream);
+    }
+    case IEFVAD_BWD_LAYERNORM: {
+        if (int rc = sized(sizeof(iefvad_bwd_layernorm))) return rc;
+        const iefvad_bwd_layernorm& u = *(const iefvad_bwd_layernorm*)args;
+        if (!u.x || !u.dy || !u.g || !u.dx || !u.part_g || !u.part_b || u.rows <= 0) return fail("%s: LAYERNORM needs x, dy, g, dx, part_g, part_b and rows > 0", who);
+        if (!al(u.x) || !al(u.dy) || !al(u.g) || !al(u.dx)) return fail("%s: LAYERNORM operands must be 16-byte aligned", who);
+        LnBwdArgs a;
+        a.x = u.x; a.dy = u.dy; a.g = u.g; a.dx = u.dx; a.part_g = u.part_g; a.part_b = u.part_b; a.rows = u.rows; a.eps = u.eps;
+        return launch_layernorm_bwd(a, stream);
+    }
+    }
+    return fail("%s: unknown kind %d", who, kind);
+}
+
 // Batch-invariant mode (include/iefvad.h): flips LaunchPolicy::split_always.  The cached hipGraphs hold the other mode's launches, so
 // they go (after the device has finished with their staging buffers).  train.h never reads the flag: training keeps its own rule.
 extern "C" int iefvad_set_batch_invariant(iefvad_handle* h, int on) {

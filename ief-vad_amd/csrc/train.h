@@ -243,6 +243,31 @@ struct ReduceBatch {
     }
 };
 
+// The launches of the row kernels of backward.h, each with the grid its kernel is written for: train_forward / train_backward below and
+// the unit entry iefvad_backward_unit (include/iefvad.h) launch through these, so a unit test runs the launch the training step runs.
+static int bwd_row_blocks(int rows) { return (rows + BWD_ROWS_PER_BLOCK - 1) / BWD_ROWS_PER_BLOCK; }      // scorer / LayerNorm backward
+static int colsum_blocks(int rows) { return (rows + kColsumRows - 1) / kColsumRows; }
+static int launch_softmax_dropout(const SoftmaxDropArgs& a, hipStream_t stream) {
+    return launch(iefvad_softmax_dropout_kernel, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, stream, a);
+}
+static int launch_softmax_bwd(const float* Ps, float scale, float* dPd, long long rows, hipStream_t stream) {
+    return launch(iefvad_softmax_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, Ps, scale, dPd, rows);
+}
+// part[colsum_blocks(rows)][ncols]: column sums of Y [rows, ld] per block of kColsumRows rows
+static int launch_colsum(const float* Y, int ld, int rows, int ncols, float* part, hipStream_t stream) {
+    const dim3 grid((ncols + 255) / 256, colsum_blocks(rows));
+    return launch(iefvad_colsum_kernel, grid, dim3(256), 0, stream, Y, ld, rows, ncols, kColsumRows, part);
+}
+static int launch_scorer_bwd(const ScorerBwdArgs& a, hipStream_t stream) {
+    return launch(iefvad_scorer_bwd_kernel, dim3(bwd_row_blocks(a.rows)), dim3(256), 0, stream, a);
+}
+static int launch_fusion_bwd(const FusionBwdArgs& a, hipStream_t stream) {
+    return launch(iefvad_fusion_bwd_kernel, dim3((a.rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, a);
+}
+static int launch_layernorm_bwd(const LnBwdArgs& a, hipStream_t stream) {
+    return launch(iefvad_layernorm_bwd_kernel, dim3(bwd_row_blocks(a.rows)), dim3(256), 0, stream, a);
+}
+
 // The parameter gradients of one Linear y = x W^T + b with W = w->w [w->N, 768]: dW = alpha * dY^T X and db = alpha * column sums of dY
 // over the rows; null destinations are frozen parameters.  dW2 / db2 (nullable) receive rows / columns [n_split, w->N) as tensors of
 // their own (the stacked mu | logvar heads).
@@ -251,6 +276,34 @@ struct LinearGrads {
     float *dW, *db; float *dW2 = nullptr, *db2 = nullptr; int n_split = 0;
     int n_first() const { return n_split > 0 ? n_split : w->N; }      // outputs of dW / db; the rest, if any, are dW2's / db2's
 };
+
+// dW (and db) of one Linear on the split TN kernel (gemm_split_tn.h): `slices` ragged row slices write their partial products
+// part[slices][n_out][768] (and, colsum != null, their partial column sums of dY colsum[slices][n_out]); ONE launch of the fixed-order
+// reduction behind them adds the weight partials (both halves of a stacked product, split at output n1) and the bias partials.
+// rows % 16 == 0, n_out % 128 == 0, 1 <= slices <= rows / 16 / 8.  Shared by launch_dw and iefvad_backward_unit.
+static int launch_dw_split_tn(const float* dY, const float* X, int rows, int n_out, int slices, float* part, float* colsum, int n1, float alpha,
+                              float* dW, float* dW2, float* db, float* db2, hipStream_t stream) {
+    const size_t per = (size_t)n_out * IEF_D;
+    TnArgs t;
+    memset(&t, 0, sizeof(t));
+    t.A = dY; t.B = X; t.C = part; t.M = n_out; t.N = IEF_D; t.lda = n_out; t.ldb = IEF_D; t.ldc = IEF_D;
+    t.nk_total = rows / TN_BK;
+    t.slices = slices;
+    t.tiles_n = IEF_D / 256;
+    // the bias gradient of the same Linear (column sums of dY) rides along in the first column block's workgroups
+    t.colsum = colsum;
+    if (int rc = launch(iefvad_gemm_split_tn256_kernel, dim3((unsigned)((n_out / 128) * t.tiles_n * slices)), dim3(256), TN_LDS_BYTES_OF(4), stream, t))
+        return rc;
+    // one launch reduces the weight partials (both halves of a stacked product) and the bias partials that rode along
+    ReduceBatch rb;
+    rb.add(part, per, slices, (size_t)n1 * IEF_D, dW, alpha);
+    if (dW2) rb.add(part + (size_t)n1 * IEF_D, per, slices, (size_t)(n_out - n1) * IEF_D, dW2, alpha);
+    if (colsum) {
+        rb.add(colsum, (size_t)n_out, slices, (size_t)n1, db, alpha);
+        if (db2) rb.add(colsum + n1, (size_t)n_out, slices, (size_t)(n_out - n1), db2, alpha);
+    }
+    return rb.launch(stream);
+}
 
 // dW by split-K with fixed-order reduction.  `db_done`: the bias sums rode along (the split TN kernel, room in cpart) and are reduced too.
 static int launch_dw(const BwdCtx& x, const LinearGrads& g, bool& db_done) {
@@ -265,31 +318,15 @@ static int launch_dw(const BwdCtx& x, const LinearGrads& g, bool& db_done) {
         // bf16x6 handles: the same partial products on the bf16 matrix pipe (gemm_split_tn.h), the same fixed-order reduction behind them:
         // the 128 x 256 block (64 x 128 per wave, two workgroups per CU) over as many RAGGED row slices as fill the chip's workgroup slots
         // once (at most the slices the scratch was sized for)
-        TnArgs t;
-        memset(&t, 0, sizeof(t));
-        t.A = g.dY; t.B = g.X; t.C = x.part; t.M = n_out; t.N = IEF_D; t.lda = n_out; t.ldb = IEF_D; t.ldc = IEF_D;
-        t.nk_total = rows / TN_BK;
+        const int nk_total = rows / TN_BK;
         const int tiles = (n_out / 128) * (IEF_D / 256);
         int slices = (2 * g_num_cus) / tiles;
-        if (slices > t.nk_total / 8) slices = t.nk_total / 8;
+        if (slices > nk_total / 8) slices = nk_total / 8;
         if (slices > splits) slices = splits;          // the scratch (part, cpart) holds `splits` partial results
         if (slices < 1) slices = 1;
-        t.slices = slices;
-        t.tiles_n = IEF_D / 256;
-        // the bias gradient of the same Linear (column sums of dY) rides along in the first column block's workgroups
+        // the bias gradient of the same Linear (column sums of dY) rides along where cpart has room for it
         db_done = (g.db || g.db2) && (size_t)slices * n_out <= x.cpart_floats;
-        t.colsum = db_done ? x.cpart : nullptr;
-        if (int rc = launch(iefvad_gemm_split_tn256_kernel, dim3((unsigned)((n_out / 128) * t.tiles_n * slices)), dim3(256), TN_LDS_BYTES_OF(4), x.stream, t))
-            return rc;
-        // one launch reduces the weight partials (both halves of a stacked product) and the bias partials that rode along
-        ReduceBatch rb;
-        rb.add(x.part, per, slices, (size_t)n1 * IEF_D, g.dW, g.alpha);
-        if (g.dW2) rb.add(x.part + (size_t)n1 * IEF_D, per, slices, (size_t)(n_out - n1) * IEF_D, g.dW2, g.alpha);
-        if (db_done) {
-            rb.add(x.cpart, (size_t)n_out, slices, (size_t)n1, g.db, g.alpha);
-            if (g.db2) rb.add(x.cpart + n1, (size_t)n_out, slices, (size_t)(n_out - n1), g.db2, g.alpha);
-        }
-        return rb.launch(x.stream);
+        return launch_dw_split_tn(g.dY, g.X, rows, n_out, slices, x.part, db_done ? x.cpart : nullptr, n1, g.alpha, g.dW, g.dW2, g.db, g.db2, x.stream);
     }
     BgemmArgs a;
     memset(&a, 0, sizeof(a));
@@ -305,9 +342,8 @@ static int launch_dw(const BwdCtx& x, const LinearGrads& g, bool& db_done) {
 static int launch_db(const BwdCtx& x, const LinearGrads& g) {
     if (!g.db && !g.db2) return 0;
     const int ncols = g.w->N, n1 = g.n_first();
-    const int nblk = (x.rows + kColsumRows - 1) / kColsumRows;
-    const dim3 grid((ncols + 255) / 256, nblk);
-    if (int rc = launch(iefvad_colsum_kernel, grid, dim3(256), 0, x.stream, g.dY, ncols, x.rows, ncols, kColsumRows, x.cpart)) return rc;
+    const int nblk = colsum_blocks(x.rows);
+    if (int rc = launch_colsum(g.dY, ncols, x.rows, ncols, x.cpart, x.stream)) return rc;
     if (int rc = reduce_parts(x.cpart, (size_t)ncols, nblk, (size_t)n1, g.db, g.alpha, x.stream)) return rc;
     return reduce_parts(x.cpart + n1, (size_t)ncols, nblk, (size_t)(ncols - n1), g.db2, g.alpha, x.stream);
 }
@@ -501,7 +537,7 @@ extern "C" int iefvad_train_forward(iefvad_handle* h, const void* img, const voi
             SoftmaxDropArgs sa;
             sa.S = P; sa.drop = drop ? 1 : 0; sa.keep = keep; sa.seed = seed; sa.p = pdrop;
             sa.rows = (long long)B * IEF_H * IEF_T;
-            if (int rc = launch(iefvad_softmax_dropout_kernel, dim3((unsigned)((sa.rows + 3) / 4)), dim3(256), 0, stream, sa)) return rc;
+            if (int rc = launch_softmax_dropout(sa, stream)) return rc;
             // attention output = dropout(P) v: dropout(P) from the sign-carrying tensor, in the A tile's staging
             const float a_drop = drop ? (float)(1.0 / (1.0 - (double)pdrop)) : 0.f;
             if (int rc = head_product(head_rows(att), probs(P), true, v_of(qkv), false, IEF_T, IEF_DH, IEF_T, 1.f, a_drop, B, stream)) return rc;
@@ -574,7 +610,7 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
     const TrainLayout t = train_layout(L, K, B);
     float* ws = (float*)train_ws;
     const int rows = B * IEF_T;
-    const int nblk = (rows + BWD_ROWS_PER_BLOCK - 1) / BWD_ROWS_PER_BLOCK;
+    const int nblk = bwd_row_blocks(rows);
     const float qscale = 1.0f / sqrtf((float)IEF_DH);
     float* rpart = ws + t.rpart;
     float* g = ws + t.g;
@@ -588,7 +624,7 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
         ScorerBwdArgs sa;
         sa.dlogit = dout->logits; sa.dfused = dout->fused; sa.z = rec->zK; sa.w = h->cls_w; sa.g = g;
         sa.part_w = rpart; sa.part_b = rpart + (size_t)nblk * IEF_D; sa.rows = rows;
-        if (int rc = launch(iefvad_scorer_bwd_kernel, dim3(nblk), dim3(256), 0, stream, sa)) return rc;
+        if (int rc = launch_scorer_bwd(sa, stream)) return rc;
         ReduceBatch rb;
         rb.add(rpart, (size_t)IEF_D, nblk, (size_t)IEF_D, dw->cls_w, 1.f);
         rb.add(rpart + (size_t)nblk * IEF_D, (size_t)1, nblk, (size_t)1, dw->cls_b, 1.f);
@@ -615,7 +651,7 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
         fa.d_n_i = dout->w_i; fa.d_n_e = dout->w_e;
         fa.dh_i = ws + t.dh[0]; fa.dh_e = ws + t.dh[1];
         fa.rows = rows; fa.factor = precision_factor(c); fa.eps = c.epsilon;
-        if (int rc = launch(iefvad_fusion_bwd_kernel, dim3((rows + ROW_WAVES - 1) / ROW_WAVES), dim3(256), 0, stream, fa)) return rc;
+        if (int rc = launch_fusion_bwd(fa, stream)) return rc;
     }
     for (int m = 0; m < 2; ++m) {
         const float* dhm = ws + t.dh[m];
@@ -628,7 +664,7 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
         auto ln_bwd = [&](const float* x, const float* gamma, float* dgamma, float* dbeta) -> int {
             LnBwdArgs la;
             la.x = x; la.dy = gx; la.g = gamma; la.dx = gx; la.part_g = rpart; la.part_b = rpart + (size_t)nblk * IEF_D; la.rows = rows; la.eps = 1e-5f;
-            if (int rc = launch(iefvad_layernorm_bwd_kernel, dim3(nblk), dim3(256), 0, stream, la)) return rc;
+            if (int rc = launch_layernorm_bwd(la, stream)) return rc;
             ReduceBatch rb;
             rb.add(rpart, (size_t)IEF_D, nblk, (size_t)IEF_D, dgamma, 1.f);
             rb.add(rpart + (size_t)nblk * IEF_D, (size_t)IEF_D, nblk, (size_t)IEF_D, dbeta, 1.f);
@@ -676,7 +712,7 @@ static int train_backward(iefvad_handle* h, int32_t B, void* train_ws, size_t tr
             if (!ds_fused) {
                 // d S = Pd .* d Pd - P rowsum(Pd .* d Pd)
                 const long long srows = (long long)B * IEF_H * IEF_T;
-                if (int rc = launch(iefvad_softmax_bwd_kernel, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, stream, P, drop_scale, dP, srows)) return rc;
+                if (int rc = launch_softmax_bwd(P, drop_scale, dP, srows, stream)) return rc;
                 // d q (before the 1/sqrt(96) scale) = qscale * d S k  (ds_fused: done by the same launch, on the d S in its registers)
                 if (int rc = head_product(q_of(dqkv), probs(dP), true, k_of(qkv), false, IEF_T, IEF_DH, IEF_T, qscale, 0.f, B, stream)) return rc;
             }

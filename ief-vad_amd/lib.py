@@ -42,7 +42,7 @@ SYMBOLS = ["iefvad_abi_version", "iefvad_create", "iefvad_create_ex", "iefvad_se
            "iefvad_forward_videos_trajectory", "iefvad_variants_workspace_bytes", "iefvad_forward_variants",
            "iefvad_videos_variants_workspace_bytes", "iefvad_forward_videos_variants", "iefvad_samples_workspace_bytes",
            "iefvad_forward_samples", "iefvad_videos_samples_workspace_bytes", "iefvad_forward_videos_samples",
-           "iefvad_videos_online_workspace_bytes", "iefvad_forward_videos_online"]
+           "iefvad_videos_online_workspace_bytes", "iefvad_forward_videos_online", "iefvad_backward_unit"]
 COMM_ID_BYTES = 128
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -171,6 +171,66 @@ class GemmSplitIO(C.Structure):
 
 (SPLIT_EPI_BIAS, SPLIT_EPI_QKV, SPLIT_EPI_BIAS_RELU, SPLIT_EPI_BIAS_RESID, SPLIT_EPI_REFINE, SPLIT_EPI_HEADS,
  SPLIT_EPI_BIAS_RELU_DOT) = range(7)
+
+
+(BWD_BGEMM, BWD_SPLIT_TN, BWD_SOFTMAX_DROPOUT, BWD_SOFTMAX_BWD, BWD_COLSUM, BWD_REDUCE_PARTS, BWD_REDUCE_PARTS_MULTI, BWD_SCORER, BWD_FUSION,
+ BWD_LAYERNORM) = range(10)
+
+
+class BwdBgemm(C.Structure):
+    """iefvad_bwd_bgemm (include/iefvad.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("A", "B", "C", "R", "G", "bias")] + [(n, C.c_int64) for n in ("a1", "a2", "b1", "b2", "c1", "c2")] +
+                [(n, C.c_int32) for n in ("M", "N", "K", "lda", "ldb", "ldc", "nz", "nz2", "akc", "bkc", "act")] +
+                [("alpha", C.c_float), ("a_drop", C.c_float)])
+
+
+class BwdSplitTn(C.Structure):
+    """iefvad_bwd_split_tn (include/iefvad.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("dY", "X", "part", "dW", "colsum_part", "db")] +
+                [("rows", C.c_int32), ("n_out", C.c_int32), ("slices", C.c_int32), ("alpha", C.c_float)])
+
+
+class BwdSoftmaxDropout(C.Structure):
+    """iefvad_bwd_softmax_dropout (include/iefvad.h)."""
+    _fields_ = [("S", C.c_void_p), ("keep", C.c_void_p), ("seed", C.c_uint64), ("rows", C.c_int64), ("drop", C.c_int32), ("p", C.c_float)]
+
+
+class BwdSoftmaxBwd(C.Structure):
+    """iefvad_bwd_softmax_bwd (include/iefvad.h)."""
+    _fields_ = [("Ps", C.c_void_p), ("dPd", C.c_void_p), ("rows", C.c_int64), ("scale", C.c_float)]
+
+
+class BwdColsum(C.Structure):
+    """iefvad_bwd_colsum (include/iefvad.h)."""
+    _fields_ = [("Y", C.c_void_p), ("part", C.c_void_p), ("ld", C.c_int32), ("rows", C.c_int32), ("ncols", C.c_int32)]
+
+
+class BwdReduce(C.Structure):
+    """iefvad_bwd_reduce (include/iefvad.h)."""
+    _fields_ = [("part", C.c_void_p * 5), ("out", C.c_void_p * 5), ("stride", C.c_uint64 * 5), ("n", C.c_uint64 * 5), ("nparts", C.c_int32 * 5),
+                ("alpha", C.c_float * 5), ("count", C.c_int32)]
+
+
+class BwdScorer(C.Structure):
+    """iefvad_bwd_scorer (include/iefvad.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("dlogit", "dfused", "z", "w", "g", "part_w", "part_b")] + [("rows", C.c_int32)]
+
+
+class BwdFusion(C.Structure):
+    """iefvad_bwd_fusion (include/iefvad.h)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("mu_i", "lv_i", "mu_e", "lv_e", "gz", "d_mu_i", "d_lv_i", "d_mu_e", "d_lv_e", "d_n_i", "d_n_e", "dh_i", "dh_e")] +
+                [("rows", C.c_int32), ("factor", C.c_float), ("eps", C.c_float)])
+
+
+class BwdLayernorm(C.Structure):
+    """iefvad_bwd_layernorm (include/iefvad.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("x", "dy", "g", "dx", "part_g", "part_b")] + [("rows", C.c_int32), ("eps", C.c_float)]
+
+
+# the argument block of every kind of iefvad_backward_unit
+BWD_ARGS = {BWD_BGEMM: BwdBgemm, BWD_SPLIT_TN: BwdSplitTn, BWD_SOFTMAX_DROPOUT: BwdSoftmaxDropout, BWD_SOFTMAX_BWD: BwdSoftmaxBwd,
+            BWD_COLSUM: BwdColsum, BWD_REDUCE_PARTS: BwdReduce, BWD_REDUCE_PARTS_MULTI: BwdReduce, BWD_SCORER: BwdScorer, BWD_FUSION: BwdFusion,
+            BWD_LAYERNORM: BwdLayernorm}
 
 
 class ResblockWeights(C.Structure):
@@ -323,6 +383,8 @@ def load_library() -> C.CDLL:
     lib.iefvad_gemm_split_small_unit.restype = C.c_int
     lib.iefvad_gemm_split_small_launches.argtypes = []
     lib.iefvad_gemm_split_small_launches.restype = C.c_uint64
+    lib.iefvad_backward_unit.argtypes = [C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.iefvad_backward_unit.restype = C.c_int
     lib.iefvad_set_batch_invariant.argtypes = [C.c_void_p, C.c_int]
     lib.iefvad_set_batch_invariant.restype = C.c_int
     lib.iefvad_set_steps.argtypes = [C.c_void_p, C.c_int32]

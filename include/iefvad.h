@@ -735,6 +735,82 @@ int iefvad_gemm_split_small_unit(const iefvad_gemm_split_io* io, int32_t M, int3
                                  int32_t qcols, float alpha, int32_t nz, void* stream);
 uint64_t iefvad_gemm_split_small_launches(void);
 
+/* ---- unit entry for the kernels of the training step's backward pass (per-kernel parity tests) --------------------------
+ * Launches ONE kernel of csrc/backward.h (or the split TN product of csrc/gemm_split_tn.h with its reduction) through the launch
+ * helper iefvad_train_forward / iefvad_train_backward use, on caller-supplied DEVICE buffers: the kernel symbol and the grid are
+ * the training step's.  No handle.  `args` points to the kind's argument block below, `args_bytes` is its sizeof (checked).  The
+ * entry checks shapes as the helpers do and nothing about buffer sizes: the caller owns every extent named below.  Floats
+ * throughout; 16-byte aligned pointers unless said otherwise.  Enqueued on `stream`.
+ *   IEFVAD_BWD_BGEMM               iefvad_bwd_bgemm: C[z][i, j] = act(alpha * sum_k A(i, k) B(j, k) + bias[j] + R[z][i, j]), zeroed where
+ *                                  G[z][i, j] <= 0; akc != 0: A(i, k) = A[i * lda + k], else A[k * lda + i]; bkc likewise; batch
+ *                                  z = z1 * nz2 + z2 < nz at operand offsets z1 * x1 + z2 * x2; a_drop != 0: A carries a dropout mask
+ *                                  in its sign bits, A(i, k) = sign ? 0 : stored * a_drop; act 0 none, 1 QuickGELU, 2 ELU.
+ *                                  M % 128 == 0, N % 128 == 0 or N % 96 == 0, K % 16 == 0, lda and ldb multiples of 4.
+ *   IEFVAD_BWD_SPLIT_TN            iefvad_bwd_split_tn: part[z] = dY[rows of slice z]^T X[rows of slice z] for `slices` ragged row
+ *                                  slices (slice z owns the 16-row tiles [z nk / slices, (z + 1) nk / slices), nk = rows / 16),
+ *                                  dW = alpha * sum_z part[z]; with colsum_part: colsum_part[z] = column sums of dY over slice z and
+ *                                  db = alpha * their sum.  dY [rows, n_out], X [rows, 768], part [slices, n_out, 768], dW [n_out, 768],
+ *                                  colsum_part [slices, n_out], db [n_out].  rows % 16 == 0, n_out % 128 == 0, 1 <= slices <= nk / 8.
+ *   IEFVAD_BWD_SOFTMAX_DROPOUT     iefvad_bwd_softmax_dropout: S [rows, 256] scores in, sign-carrying probabilities out; drop != 0:
+ *                                  element idx is dropped (sign set) where keep[idx] == 0, or without keep where the library's
+ *                                  generator draws below p for (seed, idx)
+ *   IEFVAD_BWD_SOFTMAX_BWD         iefvad_bwd_softmax_bwd: dPd [rows, 256] <- Pd .* dPd - |Ps| rowsum(Pd .* dPd), Pd = sign ? 0 : Ps * scale
+ *   IEFVAD_BWD_COLSUM              iefvad_bwd_colsum: part[b][j] = sum of Y[r, j] over rows [128 b, 128 b + 128) below `rows`;
+ *                                  Y [rows, ld], part [ceil(rows / 128), ncols]; any alignment
+ *   IEFVAD_BWD_REDUCE_PARTS        iefvad_bwd_reduce, job 0 alone: out[i] = alpha * sum_p part[p * stride + i], i < n; any alignment
+ *   IEFVAD_BWD_REDUCE_PARTS_MULTI  iefvad_bwd_reduce: jobs 0 .. count - 1 in ONE launch (a fifth job is ignored, as a null `out` is)
+ *   IEFVAD_BWD_SCORER              iefvad_bwd_scorer: g = dlogit w (+ dfused) [rows, 768]; part_w [ceil(rows / 32), 768] and part_b
+ *                                  [ceil(rows / 32)]: per 32-row block, the sums of dlogit * z and of dlogit
+ *   IEFVAD_BWD_FUSION              iefvad_bwd_fusion: the precision-weighted fusion's backward; dh_i, dh_e [rows, 1536] = d mu | d logvar
+ *   IEFVAD_BWD_LAYERNORM           iefvad_bwd_layernorm: dx [rows, 768] (may be dy), part_g and part_b [ceil(rows / 32), 768]
+ * Added without a change to any other entry: IEFVAD_ABI_VERSION stays. */
+#define IEFVAD_BWD_BGEMM 0
+#define IEFVAD_BWD_SPLIT_TN 1
+#define IEFVAD_BWD_SOFTMAX_DROPOUT 2
+#define IEFVAD_BWD_SOFTMAX_BWD 3
+#define IEFVAD_BWD_COLSUM 4
+#define IEFVAD_BWD_REDUCE_PARTS 5
+#define IEFVAD_BWD_REDUCE_PARTS_MULTI 6
+#define IEFVAD_BWD_SCORER 7
+#define IEFVAD_BWD_FUSION 8
+#define IEFVAD_BWD_LAYERNORM 9
+typedef struct iefvad_bwd_bgemm {
+    const float* A; const float* B; float* C; const float* R; const float* G; const float* bias;
+    int64_t a1, a2, b1, b2, c1, c2;
+    int32_t M, N, K, lda, ldb, ldc, nz, nz2, akc, bkc, act;
+    float alpha, a_drop;
+} iefvad_bwd_bgemm;
+typedef struct iefvad_bwd_split_tn {
+    const float* dY; const float* X; float* part; float* dW; float* colsum_part; float* db;
+    int32_t rows, n_out, slices;
+    float alpha;
+} iefvad_bwd_split_tn;
+typedef struct iefvad_bwd_softmax_dropout {
+    float* S; const uint8_t* keep; uint64_t seed; int64_t rows; int32_t drop; float p;
+} iefvad_bwd_softmax_dropout;
+typedef struct iefvad_bwd_softmax_bwd {
+    const float* Ps; float* dPd; int64_t rows; float scale;
+} iefvad_bwd_softmax_bwd;
+typedef struct iefvad_bwd_colsum {
+    const float* Y; float* part; int32_t ld, rows, ncols;
+} iefvad_bwd_colsum;
+typedef struct iefvad_bwd_reduce {
+    const float* part[5]; float* out[5]; uint64_t stride[5]; uint64_t n[5]; int32_t nparts[5]; float alpha[5]; int32_t count;
+} iefvad_bwd_reduce;
+typedef struct iefvad_bwd_scorer {
+    const float* dlogit; const float* dfused; const float* z; const float* w; float* g; float* part_w; float* part_b; int32_t rows;
+} iefvad_bwd_scorer;
+typedef struct iefvad_bwd_fusion {
+    const float* mu_i; const float* lv_i; const float* mu_e; const float* lv_e; const float* gz;
+    const float* d_mu_i; const float* d_lv_i; const float* d_mu_e; const float* d_lv_e; const float* d_n_i; const float* d_n_e;
+    float* dh_i; float* dh_e;
+    int32_t rows; float factor, eps;
+} iefvad_bwd_fusion;
+typedef struct iefvad_bwd_layernorm {
+    const float* x; const float* dy; const float* g; float* dx; float* part_g; float* part_b; int32_t rows; float eps;
+} iefvad_bwd_layernorm;
+int iefvad_backward_unit(int32_t kind, const void* args, size_t args_bytes, void* stream);
+
 /* Batch-invariant mode of an IEFVAD_COMPUTE_BF16X6 handle (on != 0; off is the default).  By default a bf16x6 handle runs a
  * micro-batch's projections and attention in the split arithmetic only from 6 chunks on and in the f32 arithmetic below, so a
  * video's results differ at the 1e-7 level with what else is in the launch.  In this mode every projection and every attention of

@@ -48,6 +48,46 @@ def test_struct_layout_matches_c_compiler(tmp_path):
     assert got == want
 
 
+def test_backward_unit_argument_blocks_match_the_header_and_refusals_need_no_gpu(lib, tmp_path):
+    """iefvad_backward_unit: every kind's ctypes argument block has the size and the last-field offset a C compiler gives the header's
+    struct, and what the entry refuses -- a null block, an unknown kind, a block of the wrong size, shapes the launch helpers cannot
+    run -- comes back as a return code with a message before any HIP call."""
+    names = ["bgemm", "split_tn", "softmax_dropout", "softmax_bwd", "colsum", "reduce", "scorer", "fusion", "layernorm"]
+    last = ["a_drop", "alpha", "p", "scale", "ncols", "count", "rows", "eps", "eps"]
+    types = [L.BwdBgemm, L.BwdSplitTn, L.BwdSoftmaxDropout, L.BwdSoftmaxBwd, L.BwdColsum, L.BwdReduce, L.BwdScorer, L.BwdFusion, L.BwdLayernorm]
+    src = tmp_path / "bwd.c"
+    body = "".join(f'printf("%zu %zu\\n", sizeof(iefvad_bwd_{n}), offsetof(iefvad_bwd_{n}, {f}));' for n, f in zip(names, last))
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "iefvad.h"\nint main(){' + body + 'return 0;}\n')
+    exe = tmp_path / "bwd"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    want = [v for t, f in zip(types, last) for v in (C.sizeof(t), getattr(t, f).offset)]
+    assert got == want
+    assert set(L.BWD_ARGS.values()) == set(types) and sorted(L.BWD_ARGS) == list(range(10))
+    assert lib.iefvad_backward_unit.restype is C.c_int
+    a = L.BwdBgemm()
+    assert lib.iefvad_backward_unit(L.BWD_BGEMM, None, 0, None) != 0 and L.last_error().startswith("iefvad_backward_unit:") and "null" in L.last_error()
+    assert lib.iefvad_backward_unit(10, C.byref(a), C.sizeof(a), None) != 0 and "unknown kind 10" in L.last_error()
+    assert lib.iefvad_backward_unit(L.BWD_BGEMM, C.byref(a), C.sizeof(a) - 4, None) != 0 and "argument block" in L.last_error()
+    assert lib.iefvad_backward_unit(L.BWD_BGEMM, C.byref(a), C.sizeof(a), None) != 0 and "needs A, B and C" in L.last_error()
+    a.A = a.B = a.C = 4096      # never dereferenced: the shape is refused first
+    a.M, a.N, a.K, a.lda, a.ldb, a.ldc, a.nz, a.nz2, a.alpha = 100, 128, 16, 16, 16, 128, 1, 1, 1.0
+    assert lib.iefvad_backward_unit(L.BWD_BGEMM, C.byref(a), C.sizeof(a), None) != 0 and "bgemm: shape M=100" in L.last_error()
+    a.M, a.lda = 128, 18
+    assert lib.iefvad_backward_unit(L.BWD_BGEMM, C.byref(a), C.sizeof(a), None) != 0 and "multiples of 4" in L.last_error()
+    t = L.BwdSplitTn()
+    t.dY = t.X = t.part = t.dW = 4096
+    for rows, n_out, slices, frag in [(120, 128, 1, "multiple of 16"), (128, 192, 1, "of 128"), (128, 128, 0, "outside 1..1"), (128, 128, 2, "outside 1..1"),
+                                      (1168, 768, 10, "outside 1..9")]:
+        t.rows, t.n_out, t.slices = rows, n_out, slices
+        assert lib.iefvad_backward_unit(L.BWD_SPLIT_TN, C.byref(t), C.sizeof(t), None) != 0 and frag in L.last_error(), (rows, n_out, slices, L.last_error())
+    r = L.BwdReduce()
+    assert lib.iefvad_backward_unit(L.BWD_REDUCE_PARTS_MULTI, C.byref(r), C.sizeof(r), None) != 0 and "count = 0" in L.last_error()
+    for kind in (L.BWD_SOFTMAX_DROPOUT, L.BWD_SOFTMAX_BWD, L.BWD_COLSUM, L.BWD_SCORER, L.BWD_FUSION, L.BWD_LAYERNORM):
+        z = L.BWD_ARGS[kind]()
+        assert lib.iefvad_backward_unit(kind, C.byref(z), C.sizeof(z), None) != 0 and "needs" in L.last_error(), kind
+
+
 def test_create_rejects_bad_config_without_touching_the_gpu(lib):
     h = C.c_void_p()
     base = dict(abi_version=L.ABI_VERSION, embed_dim=768, seq_len=256, num_heads=8, num_layers=2, num_steps=10,
