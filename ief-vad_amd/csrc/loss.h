@@ -106,6 +106,13 @@ __global__ __launch_bounds__(256) void iefvad_loss_rows_kernel(LossRowArgs a) {
     }
 }
 
+// F.binary_cross_entropy's clamp of a logarithm at -100, NaN kept: fmaxf(NaN, -100) is -100, which turned the NaN score of a video
+// (a length <= 0, a k beyond T, a NaN logit in its prefix) into a finite classification loss
+__device__ __forceinline__ float bce_log(float x) {
+    const float l = logf(x);
+    return l < -100.f ? -100.f : l;
+}
+
 // ONE workgroup: fixed-order sums of the partials -> out[8] = classification, reg, cos, norm, kl, kl_image, kl_event, total
 struct LossFinishArgs {
     const float* inst;           // [B] instance scores
@@ -121,7 +128,7 @@ __global__ __launch_bounds__(256) void iefvad_loss_finish_kernel(LossFinishArgs 
     double acc[5] = {0, 0, 0, 0, 0};
     for (int v = t; v < a.B; v += 256) {
         const float p = a.inst[v], y = a.targets[v];
-        const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.0f - p), -100.f);      // F.binary_cross_entropy's clamp
+        const float lp = bce_log(p), lq = bce_log(1.0f - p);
         acc[0] += (double)(-(y * lp + (1.0f - y) * lq));
     }
     // eight rows requested ahead, added in row order (the order of the one-row-at-a-time loop: same bits; that loop was 128 dependent
@@ -224,6 +231,9 @@ __global__ __launch_bounds__(256) void iefvad_loss_rows_grad_kernel(LossRowGradA
     }
     // F.normalize (x / max(|x|, 1e-12)) then F.cosine_similarity (each factor / max(its norm, 1e-8)), differentiated WITH their
     // clamp branches, so that a zero row gets what autograd gives it (a 1e20-scale value: meaningless, but the same)
+    // Not covered: a nonzero row whose norm is below 1e-19.  Its squares are fp32 subnormals, and in the second clamp's branch
+    // (hi <= 1e-8) this formula differs from torch's fp64 autograd by 1.3e-2 relative there (tests/test_gpu_loss_units.py leaves
+    // such rows out; the heads' rows have norms of order 1 to 10).
     const float rni = sqrtf(wave_sum(sii)), rne = sqrtf(wave_sum(see));
     const float ni = fmaxf(rni, 1e-12f), ne = fmaxf(rne, 1e-12f);
     const float hi = rni / ni, he = rne / ne;                       // norms of the normalised rows: 1, or |x| 1e12 below the clamp
@@ -270,7 +280,7 @@ __global__ __launch_bounds__(256) void iefvad_loss_rows_grad_kernel(LossRowGradA
 
 // ---- optimiser step: torch.optim.AdamW as the trainers construct it (/root/reference/train/ucf_train.py:28, xd_train.py:25:
 // lr from the arguments, betas (0.9, 0.999), eps 1e-8, weight_decay 0.01, no amsgrad), single-tensor form, torch's operation order:
-//   p *= 1 - lr wd;  m = lerp(m, g, 1 - b1);  v = b2 v + (1 - b2) g g;  p += -(lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
+//   p *= 1 - lr wd;  m = lerp(m, g, 1 - b1);  v = b2 v + ((1 - b2) g) g;  p += -(lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps))
 // Every scalar (1 - lr wd, 1 - b1, 1 - b2, lr / (1 - b1^t), sqrt(1 - b2^t)) is formed on the HOST in double and rounded to fp32
 // once, as torch forms them in Python floats before they meet the fp32 tensors (1.0f - 0.999f would be 0.00099998713, torch
 // multiplies by fp32(0.001) = 0.0010000000475).
@@ -285,7 +295,8 @@ __global__ __launch_bounds__(256) void iefvad_adamw_kernel(AdamWArgs a) {
         float p = a.p[i];
         p = p * a.decay;                                                           // mul_(1 - lr * weight_decay)
         const float m = a.m[i] + a.w1 * (g - a.m[i]);                              // lerp_(grad, 1 - beta1)
-        const float v = a.beta2 * a.v[i] + a.w2 * (g * g);                         // mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+        const float v = a.beta2 * a.v[i] + (a.w2 * g) * g;                         // mul_(beta2).addcmul_(grad, grad, value = 1 - beta2):
+                                                                                   // addcmul forms (value grad) grad, finite up to |g| 1.8e20
         const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
         a.m[i] = m;
         a.v[i] = v;
@@ -317,7 +328,7 @@ __global__ __launch_bounds__(256) void iefvad_adamw_multi_kernel(AdamWMultiArgs 
         float p = t.param[i];
         p = p * a.decay;
         const float m = t.exp_avg[i] + a.w1 * (g - t.exp_avg[i]);
-        const float v = a.beta2 * t.exp_avg_sq[i] + a.w2 * (g * g);
+        const float v = a.beta2 * t.exp_avg_sq[i] + (a.w2 * g) * g;
         const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
         t.exp_avg[i] = m;
         t.exp_avg_sq[i] = v;

@@ -329,7 +329,10 @@ int iefvad_forward_videos_attn(iefvad_handle* h, const void* img_rows, const voi
  *   out[7] total = classification + lambda_reg * reg + lambda_kl * kl   (1, 1 in ucf_train.py:100-102; 0.01, 0.01 in xd_train.py:73-75)
  * logits [B, T]; the four 768-d tensors [B*T, 768]; lengths int32 [B] and targets fp32 [B] (1 = abnormal, i.e.
  * 1 - labels[:, 0], loss.py:20) on the DEVICE; out: 8 fp32 on the device.  T must be 256.  Deterministic (no atomics).
- * `workspace`: iefvad_loss_workspace_bytes(B, T) device bytes, 16-byte aligned.
+ * `workspace`: iefvad_loss_workspace_bytes(B, T) device bytes, 16-byte aligned.  Layout, readable once the call's work on the
+ * stream is done: fp32 part[B*T][4] (per row: 1 - cos, | ||mu_i|| - ||mu_e|| |, and the row sums of 1 + l - mu^2 - exp(l) for the
+ * image and the event modality; left unwritten when the four 768-d pointers are NULL), then fp32 inst[B] (per video the top-k mean
+ * of the sigmoid scores; NaN for a length <= 0 or a k beyond the 256 snippets).  out[] is the fixed-order sum of exactly these.
  * The four 768-d pointers may all be NULL: then only out[0] (and out[7] = out[0]) is computed -- CLAS2 alone.
  * iefvad_loss_backward: the gradients of grad_scale * total with respect to logits [B, T] and the four 768-d tensors (what
  * `loss.backward()` hands to the model's outputs in /root/reference/train/ucf_train.py:103): CLAS2 through torch's BCE

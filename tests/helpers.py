@@ -260,3 +260,41 @@ def with_nan(vids, video, row, col):
     vids = [(v[0].copy(), v[1].copy()) for v in vids]
     vids[video][0][row, col] = float("nan")
     return vids
+
+
+# ---- reference-side floors for single-kernel tests (tests/test_gpu_backward_units.py, tests/test_gpu_loss_units.py) ------------------
+FLOOR_FACTOR = 3                                 # ARITHMETIC.md: gates sit at 3 x their reference-side floor
+RATIOS = {}                                     # kernel -> (floor, worst measured ratio), printed by each test
+
+
+class FloorGate:
+    """Row-kernel gate.  Every case of a test adds its result, the fp64 value and the fp32 CPU evaluation of the same formula under the
+    name of the kernel output; check() takes, per output, the fp32 evaluation's worst error over the test's own inputs as the floor and
+    holds every case of the kernel to FLOOR_FACTOR x that floor."""
+
+    def __init__(self):
+        self.cases = {}
+
+    def add(self, kind, tag, got, want64, f32):
+        want64 = np.asarray(want64, np.float64)
+        err = np.abs(np.asarray(got, np.float64) - want64)
+        err = float(err.max()) if not np.isnan(err).any() else float("nan")
+        self.cases.setdefault(kind, []).append((tag, err, float(np.abs(np.asarray(f32, np.float64) - want64).max())))
+
+    def check(self):
+        for kind, cases in self.cases.items():
+            floor = max(c[2] for c in cases)
+            worst = max(cases, key=lambda c: (c[1] != c[1], c[1]))
+            ratio = worst[1] / floor if floor > 0 else (0.0 if worst[1] == 0 else float("inf"))
+            print(f"{kind}: fp32 floor {floor:.3e}  kernel worst {worst[1]:.3e} at {worst[0]}  ratio {ratio:.2f}  ({len(cases)} cases)")
+            RATIOS[kind] = (floor, ratio)
+        for kind, cases in self.cases.items():
+            floor = RATIOS[kind][0]
+            for tag, err, _ in cases:
+                assert err <= FLOOR_FACTOR * floor, (kind, tag, err, floor)
+
+
+def seq_sum32(x, axis=0):
+    """Plain sequential fp32 sum (numpy's cumulative sum adds in index order in the array's own type)."""
+    x = np.asarray(x, np.float32)
+    return np.take(np.cumsum(x, axis=axis, dtype=np.float32), -1, axis=axis)

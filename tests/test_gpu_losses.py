@@ -1,6 +1,10 @@
 """f-4 loss head (`iefvad_loss_forward` / `iefvad_loss_backward`, csrc/loss.h; `iefvad_amd.losses`) against the reference-generated
 fixture tests/golden/loss_terms.npz (the reference's CLAS2, train/loss.py:18-30, and the trainers' torch calls,
-train/ucf_train.py:75-98) and against the fp64 oracle on other inputs.  Tolerance 1e-6 on every term."""
+train/ucf_train.py:75-98) and against the fp64 oracle on other inputs.  Tolerance 1e-6 on every term.
+
+These are end-to-end checks of the eight scalars and of sampled gradient entries.  The kernels behind them are tested one at a time, on
+whole tensors (the per-row partials and per-video scores in the workspace included) and at their edges, against fp64 with
+reference-side floors in tests/test_gpu_loss_units.py."""
 import os
 
 import numpy as np
